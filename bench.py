@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the MOM6 dynamical-core hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one baroclinic time step (DT) of the model on the synthetic global C-grid named in
@@ -12,7 +12,9 @@ and every DT_THERM/DT-th step advect_tracer (src/core/MOM.F90:1438) and the ALE 
 ALE_remap_tracers, ALE_remap_set_h_vel, ALE_remap_velocities).  The state
 evolves: every step starts from the previous step's u, v, h, T, S.  Every operator of the reference's dynamic step on this configuration is
 the library's own (nothing is prescribed or set to zero).  The state is resident in HBM before
-the timed region.  Rank 0 prints ONE JSON line; `components_ms_per_call` times each operator on its own.
+the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, spins up, warms up, times K steps and prints it;
+--full adds the figures that need runs of their own (`roofline`, `barotropic_subcycle`, `pressure_force_fp64`,
+`components_ms_per_call`: each operator on its own, the lateral parameterisations, `cpu_baseline`).
 """
 import argparse
 import json
@@ -82,9 +84,40 @@ def parse():
     ap.add_argument("--workload", default="om4_025", help="om4_025 | benchmark | double_gyre | NIxNJxNK")
     ap.add_argument("--scheme", default=SCHEME)
     ap.add_argument("--spinup", type=int, default=None, help="untimed steps before the warm-up (default: SPINUP)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: HIP events on the dominant kernels in the timed window (roofline, barotropic subcycle, "
+                         "pressure force), the streaming bandwidth and launch floor, per-operator timings, the lateral parameterisations "
+                         "and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no streaming bandwidth and no per-operator timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last step returned (u, v, h, T, S, the passive tracers, uh, vh, "
+                         "uhtr, vhtr, eta_av) as DIR/<name>.npy in float64; arrays of more than 2^19 elements as a fixed, "
+                         "seeded sample of that many")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 19      # elements per dumped array at most: 12 arrays x 4 MiB in float64
+DUMP_SEED = 20261016
+
+
+def dump_outputs(M, out_dir, suffix=""):
+    """What a caller of the timed path receives after its last step, as float64 .npy files.  An array with more than DUMP_SAMPLE elements
+    is written as the elements at DUMP_SAMPLE positions drawn (sorted, with repeats removed) from a generator seeded with DUMP_SEED: the same
+    positions for the same shape in every run, so two builds can be compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"u": M.u, "v": M.v, "h": M.h, "T": M.T, "S": M.S, "uh": M.uh, "vh": M.vh, "uhtr": M.uhtr, "vhtr": M.vhtr,
+              "eta_av": M.eta_av}
+    for q, t in enumerate(M.passive):
+        arrays[f"tracer{q + 2}"] = t
+    M.dg.sync()
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), flat.to(torch.float64).cpu().numpy())
 
 
 def attach_exchange(dom, dg, device, exchange):
@@ -759,30 +792,32 @@ def main():
     M.dg.sync()
     health_w = M.health()
     barrier()
-    M.dg.kernel_timing(True)            # HIP events around the dominant kernel's launches, on the library's stream
-    if exchange == "rccl":
-        dom.exchange_timing(True)       # HIP events around every group pass, on the library's communication stream
+    if a.full:
+        M.dg.kernel_timing(True)            # HIP events around the dominant kernel's launches, on the library's stream
+        if exchange == "rccl":
+            dom.exchange_timing(True)       # HIP events around every group pass, on the library's communication stream
     t0 = time.perf_counter()
     for n in range(a.steps):
         M.step()
     M.dg.sync()
     barrier()
     elapsed = time.perf_counter() - t0
-    ktime = M.dg.kernel_timing(False)
+    ktime = M.dg.kernel_timing(False) if a.full else None
     exch = None
     if dist is not None:
         on = "cuda" if backend == "nccl" else "cpu"
         t = torch.tensor([elapsed], device=on, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        if exchange == "rccl":          # per rank: milliseconds per step inside group passes (pack, send / recv, unpack), passes per step
-            ms, npass = dom.exchange_timing(False)
-            mine = torch.tensor([ms / a.steps, npass / a.steps], device=on, dtype=torch.float64)
-            every = [torch.zeros_like(mine) for _ in range(world)]
-            dist.all_gather(every, mine)
-            exch = {"kind": "native RCCL send/recv on the library's communication stream (mom6hip_domain_init_rccl)",
-                    "ms_per_step_per_rank": [round(float(e[0]), 3) for e in every],
-                    "group_passes_per_step": float(every[0][1])}
+        if exchange == "rccl":
+            exch = {"kind": "native RCCL send/recv on the library's communication stream (mom6hip_domain_init_rccl)"}
+            if a.full:      # per rank: milliseconds per step inside group passes (pack, send / recv, unpack), passes per step
+                ms, npass = dom.exchange_timing(False)
+                mine = torch.tensor([ms / a.steps, npass / a.steps], device=on, dtype=torch.float64)
+                every = [torch.zeros_like(mine) for _ in range(world)]
+                dist.all_gather(every, mine)
+                exch.update({"ms_per_step_per_rank": [round(float(e[0]), 3) for e in every],
+                             "group_passes_per_step": float(every[0][1])})
         else:
             exch = {"kind": f"torch.distributed callbacks ({backend})"}
     health = M.health()
@@ -850,10 +885,12 @@ def main():
             "overlap_stats": list(M.dg.overlap_stats()),
         },
     }
+    if a.dump_outputs:
+        dump_outputs(M, a.dump_outputs, "" if world == 1 else f"_rank{rank}")
     # what the device delivers to plain streaming kernels on THIS box (a = b, a = b + s*c over 4 GiB arrays), next to the nominal
     # peak the fractions are quoted against (report both)
     measured_bw = None
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         import ctypes as C
         from mom6_amd._lib import check, lib
         cp, tr = C.c_double(0.0), C.c_double(0.0)
@@ -862,7 +899,7 @@ def main():
         check(L.mom6hip_stream_bandwidth(M.dg.handle, 4 << 30, 10, C.byref(cp), C.byref(tr)), "mom6hip_stream_bandwidth")
         measured_bw = {"copy_GBs": cp.value, "triad_GBs": tr.value, "bytes_per_array": 4 << 30, "launches": 10}
     bt_floor = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         nodes = M.dg.bt_graph_nodes()
         if nodes > 0:
             pts = (NI + 2 * 4) * (NJ + 2 * 4)
@@ -876,7 +913,7 @@ def main():
     # events around its launches inside the timed region.  Algorithmic bytes per cell and launch:
     # read v, visc_rem_v, h (24 B), write vh (8 B) [+ v_cor (8 B) with vhbt] [+ h_v (8 B) with BT_cont] -> 40 / 48 / 40 B
     # for the three calls of a step.
-    if rank == 0:
+    if rank == 0 and a.full:
         ms_y, n_y = ktime[1]
         ms_x, n_x = ktime[0]
         if n_y > 0:
@@ -909,7 +946,7 @@ def main():
                 "frac_of_measured_triad": None if not measured_bw else alg / (avg_ms * 1e-3) / 1e9 / measured_bw["triad_GBs"],
             }
 
-    if rank == 0:
+    if rank == 0 and a.full:
         # microseconds per barotropic time step against the launch floor.  HIP events around the replay of the
         # subcycle's hipGraph (barotropic.hip), inside the timed region; 4 kernels + the x-halo wraps per barotropic step.
         ms_bt, n_bt = ktime[2]
@@ -942,7 +979,7 @@ def main():
                 pass
             out["pressure_force_fp64"] = fp64
 
-    if world == 1 and not a.no_roofline:
+    if world == 1 and a.full and not a.no_roofline:
         # per-operator device time on a stationary synthetic state, HIP events on the stream the library launches on
         # (the null stream, which is also torch's current stream here)
         S = Components(grid, dom, device, a.scheme)
@@ -1033,7 +1070,7 @@ def main():
             k: {"GBs": bb / (m * 1e-3) / 1e9, "frac": bb / (m * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms": m} for k, (bb, m) in cand.items()}
         S.dg.close()
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(grid, a.scheme, cells, spa)
 
     if rank == 0:
