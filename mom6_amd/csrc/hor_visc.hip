@@ -4,6 +4,7 @@
 // horizontal_viscosity is a chain of four 2-D stencils per layer (velocities -> strains -> Laplacian of the velocity ->
 // stresses -> accelerations), every layer independent.  hv_fused_kernel does the chain for one tile of one layer with the
 // intermediates (the reference's 2-D work arrays sh_xx, sh_xy, Del2u, Del2v, str_xx, str_xy, h_u, h_v) in LDS: see there.
+// hv_chunk_kernel does it for the production options over a chunk of layers, with a point's metrics in registers.
 // The products hor_visc_init keeps in the control structure (dx2h = dxT*dxT, DX_dyT = dxT*IdyT, Idx2dyCu ...) are single
 // multiplications of grid metrics and are evaluated in place (the same bits as the stored arrays).
 // Algorithmic traffic: read u, v, h, write diffu, diffv = 40 B per cell.
@@ -327,9 +328,10 @@ struct HVFArgs {
 };
 
 
-// CFG = HV_GENERIC: the options are read from the argument; otherwise they are the bits of CFG at compile time (the
-// production set -- biharmonic Smagorinsky with the better bounds -- is instantiated: the branches and the static arrays it
-// does not use are gone, which is what lets the remaining base pointers stay in scalar registers).
+// CFG = HV_GENERIC: the options are read from the argument; otherwise they are the bits of CFG at compile time (the branches
+// and the static arrays a set does not use are gone, which is what lets the remaining base pointers stay in scalar registers).
+// Only HV_GENERIC is launched: the production set -- biharmonic Smagorinsky with the better bounds, HV_BIH_SMAG -- runs in
+// hv_chunk_kernel below.
 constexpr unsigned HV_GENERIC = ~0u;
 constexpr unsigned HV_BIH_SMAG = (1u << F_BIHARMONIC) | (1u << F_SMAG_AH) | (1u << F_BOUND_KH) | (1u << F_BETTER_BOUND_KH) | (1u << F_BOUND_AH) |
                                  (1u << F_BETTER_BOUND_AH) | (1u << F_LAND_MASK);
@@ -656,6 +658,194 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
 #undef END_POINTS
 }
 
+// ---- the production set, layer-chunked --------------------------------------------------------------------------------
+// hv_fused_kernel<HV_BIH_SMAG> reads, for every layer, the ~30 k-independent planes of its 68 x 20 frame from L2: ~400 KB per
+// block, 47 GB per call at 1440x1080x75, which is what bounded it.  hv_chunk_kernel does the same chain for the same options
+// with ONE frame point per thread (a W x H frame = a (W-4) x (H-4) tile, W*H threads) and works through HV_KCH consecutive layers
+// of its tile: the 28 metrics and coefficients a point uses AT ITSELF are loaded into registers once per block.
+//
+// Neighbour metrics are never read.  Every read of a metric at a neighbour in hv_fused_kernel is a product with a value at that
+// same neighbour, which the neighbour forms for itself and leaves in LDS (IEEE multiplication is commutative and exact to the
+// bit, and the build does not contract: every value is the same operation on the same operands).  The pairs:
+//   strains      IdyCu*u (-1,0) and IdxCv*v (0,-1) in the tension; v*IdyCv (1,0) and u*IdxCu (0,1) in the shear; mask2dT*h (1,0),
+//                (0,1) in the face thicknesses                                                             -> planes P_*
+//   Del2u/Del2v  dy2h*sh_xx (1,0), dx2q*sh_xy (0,-1), dy2q*sh_xy (-1,0), dx2h*sh_xx (0,1)                  -> S_D2H_XX ... S_D2Q_XY
+//   stresses     IdyCu*Del2u (-1,0), IdxCv*Del2v (0,-1), Del2v*IdyCv (1,0), Del2u*IdxCu (0,1)              -> planes P_* (reused)
+//   diffu/diffv  dy2h*str_xx (1,0), dx2q*str_xy (0,-1), dy2q*str_xy (-1,0), dx2h*str_xx (0,1)              -> S_D2H_XX ... (reused)
+// and the squares sh_xx^2, sh_xy^2 of Shear_mag and the thicknesses h_u, h_v are left in LDS in the same way.  Only the western
+// column (li = 0) and the southern row (lj = 0) of the frame need a product from outside it (u at I-1, v at J-1 of the tension):
+// they form it themselves, with IdyCu (-1,0) / IdxCv (0,-1) in two more registers.
+//
+// Per layer: 4 stages, 4 barriers.  Plane lifetimes let the stress products reuse the strain products and the Del2 products reuse
+// the velocity products (13 planes of W*H doubles); the next layer's u, v, h are loaded while this layer is computed.
+#ifndef HV_KCH_DEF
+#define HV_KCH_DEF 15
+#endif
+constexpr int HV_KCH = HV_KCH_DEF;      // layers a block works through with the metrics of its points in registers
+#ifndef HV_CW_DEF
+#define HV_CW_DEF 64
+#endif
+#ifndef HV_CH_DEF
+#define HV_CH_DEF 16
+#endif
+constexpr int HV_CW = HV_CW_DEF, HV_CH = HV_CH_DEF;      // the frame of hv_chunk_kernel (the tile is 4 points narrower and lower)
+
+template <int W, int H>
+__global__ __launch_bounds__(W * H) void hv_chunk_kernel(HVFArgs A, int ntx, int ntiles, int nch) {
+  constexpr int NP = W * H, TI = W - 4, TJ = H - 4;
+  static_assert(13 * NP * 8 <= 160 * 1024, "hv_chunk_kernel: the frame's planes do not fit in LDS");
+  enum { P_MH, P_YU, P_XU, P_XV, P_YV, NPP };      // (P_MH first: no plane read at (-1, 0) or (0, -1) is the first)
+  enum { S_D2H_XX, S_D2H_XX2, S_D2Q_XY, S_D2Q_XY2, S_XX2, S_XY2, S_HU, S_HV, NSP };
+  // P_YU..P_YV: IdyCu*u, IdxCu*u, IdxCv*v, IdyCv*v, then IdyCu*Del2u, IdxCu*Del2u, IdxCv*Del2v, IdyCv*Del2v;  P_MH: mask2dT*h
+  // S_D2H_XX, S_D2H_XX2, S_D2Q_XY, S_D2Q_XY2: dy2h*sh_xx, dx2h*sh_xx, dx2q*sh_xy, dy2q*sh_xy, then the same with str_xx, str_xy
+  __shared__ double sp[NPP][NP], ss[NSP][NP];
+  const int L = blockIdx.x, m = L >> 3;
+  const int c = m % nch, tile = (m / nch) * 8 + (L & 7);      // the chunks of one tile on one XCD, back to back
+  if (tile >= ntiles) return;
+  const int k0 = c * HV_KCH, k1 = min(k0 + HV_KCH, A.nk);
+  const int i0 = A.isc + (tile % ntx) * TI, j0 = A.jsc + (tile / ntx) * TJ;
+  const int ib = i0 - 2, jb = j0 - 2;
+  const int is = i0, ie = min(i0 + TI - 1, A.iec), js = j0, je = min(j0 + TJ - 1, A.jec);
+  const int Isq = is - 1, Ieq = ie, Jsq = js - 1, Jeq = je;
+  const double h_neglect = A.h_neglect, h_neglect3 = h_neglect * h_neglect * h_neglect;
+  const unsigned RQ = (unsigned)(A.nih + 1) * 8u, RH = (unsigned)A.nih * 8u;
+  const char *pk = A.pk;
+  const unsigned PB = A.plane_bytes;
+
+  const int lo = threadIdx.x, lj = lo / W, li = lo - lj * W;
+  const int i = ib + li, j = jb + lj, I = i, J = j;
+  const bool live = i <= ie + 2 && j <= je + 2;      // the frame's points past the data of a partial tile are never read
+  const unsigned cj = (unsigned)(j - A.jsd), ci = (unsigned)(i - A.isd);
+  const unsigned bq = ((cj + 1u) * (unsigned)(A.nih + 1) + ci + 1u) * 8u;
+  const unsigned bh = (cj * (unsigned)A.nih + ci) * 8u;
+  const unsigned bu = (cj * (unsigned)(A.nih + 1) + ci + 1u) * 8u;
+  const unsigned bv = ((cj + 1u) * (unsigned)A.nih + ci) * 8u;
+#define LD(b, off) (*(const double *)((const char *)(b) + (off)))
+#define GM(mp) (live ? LD(pk + (size_t)(mp) * PB, bq) : 0.0)
+#define SH(a) (live ? LD(A.s.a, bh) : 0.0)
+#define SQ(a) (live ? LD(A.s.a, bq) : 0.0)
+  // the point's own metrics and coefficients, for the whole chunk
+  const double dx2h = GM(P_DX2H), dy2h = GM(P_DY2H), DX_dyT = GM(P_DXDYT), DY_dxT = GM(P_DYDXT), maskT = GM(P_MASKT);
+  const double dx2q = GM(P_DX2Q), dy2q = GM(P_DY2Q), DX_dyBu = GM(P_DXDYBU), DY_dxBu = GM(P_DYDXBU), maskBu = GM(P_MASKBU);
+  const double IdxCu = GM(P_IDXCU), IdyCu = GM(P_IDYCU), IareaCu = GM(P_IAREACU), Idx2dyCu = GM(P_IDX2DYCU), Idxdy2u = GM(P_IDXDY2U);
+  const double IdxCv = GM(P_IDXCV), IdyCv = GM(P_IDYCV), IareaCv = GM(P_IAREACV), Idx2dyCv = GM(P_IDX2DYCV), Idxdy2v = GM(P_IDXDY2V);
+  const double Ah_bg_xx = SH(Ah_bg_xx), Biharm_xx = SH(Biharm_const_xx), Ah_Max_xx = SH(Ah_Max_xx), red_xx = SH(reduction_xx);
+  const double Ah_bg_xy = SQ(Ah_bg_xy), Biharm_xy = SQ(Biharm_const_xy), Ah_Max_xy = SQ(Ah_Max_xy), red_xy = SQ(reduction_xy);
+  // the products from outside the frame: IdyCu at (I-1, j) for the western column, IdxCv at (i, J-1) for the southern row
+  const bool west = live && li == 0, south = live && lj == 0;
+  const double IdyCu_w = west ? LD(pk + (size_t)P_IDYCU * PB, bq - 8u) : 0.0;
+  const double IdxCv_s = south ? LD(pk + (size_t)P_IDXCV * PB, bq - RQ) : 0.0;
+#undef GM
+#undef SH
+#undef SQ
+  const size_t nU = (size_t)(A.nih + 1) * A.njh, nV = (size_t)A.nih * (A.njh + 1), nH = (size_t)A.nih * A.njh;
+  double un = 0.0, vn = 0.0, hn = 0.0, uwn = 0.0, vsn = 0.0;      // the next layer's fields
+  auto fetch = [&](int k) {
+    const char *u_k = (const char *)(A.u + nU * k), *v_k = (const char *)(A.v + nV * k), *h_k = (const char *)(A.h + nH * k);
+    if (live) { un = LD(u_k, bu); vn = LD(v_k, bv); hn = LD(h_k, bh); }
+    if (west) uwn = LD(u_k, bu - 8u);
+    if (south) vsn = LD(v_k, bv - RH);
+  };
+  fetch(k0);
+  const int Iw = (i0 == A.isc) ? is - 1 : is, Js = (j0 == A.jsc) ? js - 1 : js;
+#define PX(a, di, dj) sp[a][lo + (dj) * W + (di)]
+#define SX(a, di, dj) ss[a][lo + (dj) * W + (di)]
+  for (int k = k0; k < k1; k++) {
+    const double u = un, v = vn, h = hn, uw = uwn, vs = vsn;
+    if (k + 1 < k1) fetch(k + 1);
+    // ---- the velocity products and the masked thickness ----
+    const double yu = IdyCu * u, xu = IdxCu * u, xv = IdxCv * v, yv = IdyCv * v, mh = maskT * h;
+    PX(P_YU, 0, 0) = yu; PX(P_XU, 0, 0) = xu; PX(P_XV, 0, 0) = xv; PX(P_YV, 0, 0) = yv; PX(P_MH, 0, 0) = mh;
+    __syncthreads();
+
+    // ---- strains and the thicknesses at velocity points :693-765 ----
+    double sxx = 0.0, sxy = 0.0, hu = 0.0, hv = 0.0;
+    if (j >= Jsq - 1 && j <= Jeq + 2 && i >= Isq - 1 && i <= Ieq + 2) {      // horizontal tension
+      const double dudx = DY_dxT * (yu - (li == 0 ? IdyCu_w * uw : PX(P_YU, -1, 0)));
+      const double dvdy = DX_dyT * (xv - (lj == 0 ? IdxCv_s * vs : PX(P_XV, 0, -1)));
+      sxx = dudx - dvdy;
+    }
+    if (J >= js - 2 && J <= Jeq + 1 && I >= is - 2 && I <= Ieq + 1) {      // shearing strain
+      const double dvdx = DY_dxBu * (PX(P_YV, 1, 0) - yv);
+      const double dudy = DX_dyBu * (PX(P_XU, 0, 1) - xu);
+      sxy = maskBu * (dvdx + dudy);
+    }
+    if (j >= js - 1 && j <= je + 1 && I >= is - 2 && I <= ie + 1) hu = 0.5 * (mh + PX(P_MH, 1, 0));
+    if (J >= js - 2 && J <= je + 1 && i >= is - 1 && i <= ie + 1) hv = 0.5 * (mh + PX(P_MH, 0, 1));
+    const double sxx2 = sxx * sxx, sxy2 = sxy * sxy;
+    SX(S_D2H_XX, 0, 0) = dy2h * sxx; SX(S_D2H_XX2, 0, 0) = dx2h * sxx; SX(S_D2Q_XY, 0, 0) = dx2q * sxy; SX(S_D2Q_XY2, 0, 0) = dy2q * sxy;
+    SX(S_XX2, 0, 0) = sxx2; SX(S_XY2, 0, 0) = sxy2; SX(S_HU, 0, 0) = hu; SX(S_HV, 0, 0) = hv;
+    __syncthreads();
+
+    // ---- the Laplacian of the velocity :882-891 ----
+    double d2u = 0.0, d2v = 0.0;
+    if (j >= js - 1 && j <= Jeq + 1 && I >= Isq - 1 && I <= Ieq + 1)
+      d2u = Idxdy2u * (SX(S_D2H_XX, 1, 0) - SX(S_D2H_XX, 0, 0)) + Idx2dyCu * (SX(S_D2Q_XY, 0, 0) - SX(S_D2Q_XY, 0, -1));
+    if (J >= Jsq - 1 && J <= Jeq + 1 && i >= is - 1 && i <= Ieq + 1)
+      d2v = Idxdy2v * (SX(S_D2Q_XY2, 0, 0) - SX(S_D2Q_XY2, -1, 0)) - Idx2dyCv * (SX(S_D2H_XX2, 0, 1) - SX(S_D2H_XX2, 0, 0));
+    const double yd2u = IdyCu * d2u, xd2u = d2u * IdxCu, xd2v = IdxCv * d2v, yd2v = d2v * IdyCv;
+    PX(P_YU, 0, 0) = yd2u; PX(P_XU, 0, 0) = xd2u; PX(P_XV, 0, 0) = xd2v; PX(P_YV, 0, 0) = yd2v;
+    __syncthreads();
+
+    // ---- viscosities and layer-integrated stresses :1056-1741 (biharmonic Smagorinsky, better bounds, land mask) ----
+    double r_xx = 0.0, r_xy = 0.0;
+    if (j >= Jsq && j <= Jeq + 1 && i >= Isq && i <= Ieq + 1) {      // h point
+      const double sh_xx_sq = sxx2;
+      const double sh_xy_sq = 0.25 * ((SX(S_XY2, -1, -1) + sxy2) + (SX(S_XY2, -1, 0) + SX(S_XY2, 0, -1)));
+      const double Shear_mag = sqrt(sh_xx_sq + sh_xy_sq);
+      const double h_min = min4(hu, SX(S_HU, -1, 0), hv, SX(S_HV, 0, -1));
+      const double hrat_min = min2(1.0, h_min / (h + h_neglect));
+      const double visc_bound_rem = 1.0;
+      double A_ = Ah_bg_xx;
+      const double AhSm = Biharm_xx * Shear_mag;
+      A_ = max2(A_, AhSm);
+      A_ = min2(A_, visc_bound_rem * hrat_min * Ah_Max_xx);
+      const double d_del2u = yd2u - PX(P_YU, -1, 0);
+      const double d_del2v = xd2v - PX(P_XV, 0, -1);
+      const double d_str = A_ * (DY_dxT * d_del2u - DX_dyT * d_del2v);
+      const double str = 0.0 + d_str;
+      r_xx = str * (h * red_xx);
+    }
+    if (J >= js - 1 && J <= Jeq && I >= is - 1 && I <= Ieq) {      // q point
+      const double sh_xy_sq = sxy2;
+      const double sh_xx_sq = 0.25 * ((sxx2 + SX(S_XX2, 1, 1)) + (SX(S_XX2, 0, 1) + SX(S_XX2, 1, 0)));
+      const double Shear_mag = sqrt(sh_xy_sq + sh_xx_sq);
+      const double hu0 = hu, hu1 = SX(S_HU, 0, 1);
+      const double hv0 = hv, hv1 = SX(S_HV, 1, 0);
+      const double h2uq = 4.0 * (hu0 * hu1);
+      const double h2vq = 4.0 * (hv0 * hv1);
+      const double hq = (2.0 * (h2uq * h2vq)) / (h_neglect3 + (h2uq + h2vq) * ((hu0 + hu1) + (hv0 + hv1)));
+      const double h_min = min4(hu0, hu1, hv0, hv1);
+      const double hrat_min = min2(1.0, h_min / (hq + h_neglect));
+      const double visc_bound_rem = 1.0;
+      double A_ = Ah_bg_xy;
+      const double AhSm = Biharm_xy * Shear_mag;
+      A_ = max2(A_, AhSm);
+      A_ = min2(A_, visc_bound_rem * hrat_min * Ah_Max_xy);
+      const double dDel2vdx = DY_dxBu * (PX(P_YV, 1, 0) - yd2v);
+      const double dDel2udy = DX_dyBu * (PX(P_XU, 0, 1) - xd2u);
+      const double d_str = A_ * (dDel2vdx + dDel2udy);
+      const double str = 0.0 + d_str;
+      r_xy = str * (hq * maskBu * red_xy);
+    }
+    // (the strain products are dead: their planes take the stress products)
+    SX(S_D2H_XX, 0, 0) = dy2h * r_xx; SX(S_D2H_XX2, 0, 0) = dx2h * r_xx; SX(S_D2Q_XY, 0, 0) = dx2q * r_xy; SX(S_D2Q_XY2, 0, 0) = dy2q * r_xy;
+    __syncthreads();
+
+    // ---- diffu, diffv :1744-1770 ----
+    if (j >= js && j <= je && I >= Iw && I <= ie)
+      *(double *)((char *)(A.diffu + nU * k) + bu) =
+          ((IdyCu * (SX(S_D2H_XX, 0, 0) - SX(S_D2H_XX, 1, 0)) + IdxCu * (SX(S_D2Q_XY, 0, -1) - SX(S_D2Q_XY, 0, 0))) * IareaCu) / (hu + h_neglect);
+    if (i >= is && i <= ie && J >= Js && J <= je)
+      *(double *)((char *)(A.diffv + nV * k) + bv) =
+          ((IdyCv * (SX(S_D2Q_XY2, -1, 0) - SX(S_D2Q_XY2, 0, 0)) - IdxCv * (SX(S_D2H_XX2, 0, 0) - SX(S_D2H_XX2, 0, 1))) * IareaCv) / (hv + h_neglect);
+    // (no barrier: the next layer's first stage writes only sp, which nobody reads after the stresses' barrier)
+  }
+#undef PX
+#undef SX
+#undef LD
+}
+
 // MEKE%mom_src (:1783-1800, :1833-1889 with MEKE%backscatter_Ro_c = 0): the frictional work of each layer from its layer-integrated
 // stresses, summed over the layers in order.  One lane per column.
 __global__ __launch_bounds__(256) void hv_frictwork_kernel(m6::GridDev g, const double *__restrict__ u, const double *__restrict__ v,
@@ -799,11 +989,20 @@ int horizontal_viscosity_dev(mom6hip_ctx_t *ctx, const mom6hip_hor_visc_cs_t *cs
     hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(NT), 0, ctx->stream, A, ntx, ntiles);
     return 0;
   };
-  // (tiles of 64x8, 64x12, 32x16, 128x8 points and blocks of 256 / 1024 threads all ran within 5% of this one: the kernel is
-  // bound by the L2 -> L1 traffic of the metric planes, which every block reads for its tile -- profiles/r02_hor_visc.txt)
   int rc;
-  if (A.flags.bits == HV_BIH_SMAG && !meke && !ob) rc = launch(hv_fused_kernel<HV_BIH_SMAG, 64, 16, 512, 4>, 64, 16, 512);
-  else rc = launch(hv_fused_kernel<HV_GENERIC, 64, 16, 512, 4>, 64, 16, 512);
+  if (A.flags.bits == HV_BIH_SMAG && !meke && !ob) {
+    // the production set: one block per (tile, chunk of HV_KCH layers), the chunks of a tile back to back on one XCD
+    constexpr int TI = HV_CW - 4, TJ = HV_CH - 4;
+    const int ntx = (ni + TI - 1) / TI, nty = (nj + TJ - 1) / TJ, ntiles = ntx * nty, nch = (g.nk + HV_KCH - 1) / HV_KCH;
+    const long nblocks = (long)((ntiles + 7) / 8) * 8 * nch;
+    rc = nblocks >= (1L << 31);
+    if (!rc) hipLaunchKernelGGL((hv_chunk_kernel<HV_CW, HV_CH>), dim3((unsigned)nblocks), dim3(HV_CW * HV_CH), 0, ctx->stream, A, ntx, ntiles, nch);
+  } else {
+    // everything else (OBC maps, MEKE Ku / Au and str_*_out, the Laplacian, options at run time) one layer per block
+    // (tiles of 64x8, 64x12, 32x16, 128x8 points and blocks of 256 / 1024 threads all ran within 5% of this one: the kernel is
+    // bound by the L2 -> L1 traffic of the metric planes, which every block reads for its tile -- profiles/r02_hor_visc.txt)
+    rc = launch(hv_fused_kernel<HV_GENERIC, 64, 16, 512, 4>, 64, 16, 512);
+  }
   M6_REQUIRE(rc == 0, "horizontal_viscosity: the grid is too large for one launch");
   if (cs->MEKE_mom_src)
     hipLaunchKernelGGL(hv_frictwork_kernel, dim3((ni + 255) / 256, nj), dim3(256), 0, ctx->stream, g, u, v, A.str_xx_out, A.str_xy_out,
