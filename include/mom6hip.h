@@ -1031,8 +1031,10 @@ int mom6hip_set_viscous_ml(mom6hip_ctx_t *ctx, const mom6hip_set_visc_cs_t *cs, 
  * the two entry points that have none.
  * DIFFUSE_ML_TO_INTERIOR (unsupported[2]) is taken by mom6hip_tracer_hordiff_epipycnal with its own control structure (round 4),
  * and refused by the entry points that have none.
- * Not provided (refused by name, any nonzero `unsupported`): USE_HORIZONTAL_BOUNDARY_DIFFUSION,
- * KHTR_USE_EBT_STRUCT, offline khdt arrays, the df_x / df_y flux diagnostics.
+ * USE_HORIZONTAL_BOUNDARY_DIFFUSION (unsupported[1]) is taken by mom6hip_tracer_hordiff_hbd with its own control structure, and
+ * refused by the entry points that have none.
+ * Not provided (refused by name, any nonzero `unsupported`): KHTR_USE_EBT_STRUCT, offline khdt arrays, the df_x / df_y flux
+ * diagnostics.
  */
 typedef struct mom6hip_tracer_hor_diff_cs {
   double KhTr;             /* KHTR [L2 T-1] (0: tracer_hordiff returns at once unless use_variable_mixing) */
@@ -1139,6 +1141,37 @@ int mom6hip_tracer_hordiff_epipycnal(mom6hip_ctx_t *ctx, const mom6hip_tracer_ho
                                      const mom6hip_hordiff_fields_t *fields, const double *h, const mom6hip_eos_t *eos, double dt,
                                      double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S,
                                      int32_t memspace, mom6hip_hordiff_stats_t *stats);
+
+/*
+ * hbd_CS, src/tracer/MOM_hor_bnd_diffusion.F90:40-70, as set by hor_bnd_diffusion_init (:79-158): horizontal boundary diffusion of the
+ * tracers inside the surface boundary layer visc%h_ML (fields->h_ML).  Provided: the HBD grid of every wet face (hbd_grid, the merged
+ * interfaces of both columns and both boundary-layer depths), fluxes_layer_method with HBD_LINEAR_TRANSITION, APPLY_LIMITER and
+ * APPLY_LIMITER_REMAP, and HBD_REMAPPING_SCHEME PCM, PLM (the default), PPM_H4, PPM_IH4 or PPM_CW, each with or without
+ * HBD_BOUNDARY_EXTRAP.  Not provided (refused by name): any other scheme, HBD_DEBUG, the hbd_* diagnostics, and more than 128 layers
+ * (the reference has no such bound: a face's columns are walked from private arrays of a fixed size).
+ */
+typedef struct mom6hip_hor_bnd_diffusion_cs {
+  int32_t linear;          /* HBD_LINEAR_TRANSITION (0) */
+  int32_t limiter;         /* APPLY_LIMITER (1) */
+  int32_t limiter_remap;   /* APPLY_LIMITER_REMAP (0) */
+  int32_t boundary_extrap; /* HBD_BOUNDARY_EXTRAP (0) */
+  int32_t remap_scheme;    /* HBD_REMAPPING_SCHEME as MOM6HIP_REMAP_* (MOM6HIP_REMAP_PLM) */
+  int32_t debug;           /* HBD_DEBUG (0; refused if set) */
+  int32_t diagnostics;     /* a registered hbd_* diagnostic (0; refused if set) */
+  int32_t initialized;
+  int32_t reserved[8];
+} mom6hip_hor_bnd_diffusion_cs_t;
+
+/* tracer_hordiff with cs->unsupported[1] (CS%use_hor_bnd_diffusion) set: a group pass of the tracers and then num_itts calls of
+ * hor_bnd_diffusion (MOM_tracer_hor_diff.F90:408-472) with a group pass before every call after the first -- fields->h_ML is visc%h_ML,
+ * the boundary-layer depth, with a valid halo of 1 -- followed by the neutral branch (cs->unsupported[0], with nd, eos, p_surf, idx_T and
+ * idx_S as mom6hip_tracer_hordiff_neutral takes them) or the along-layer diffusion, as the other entry points do.  stats->halo_updates
+ * counts the passes of the HBD calls too.  hbd may be NULL when cs->unsupported[1] is 0.  HBD with DIFFUSE_ML_TO_INTERIOR is refused as
+ * the reference refuses it (:1735). */
+int mom6hip_tracer_hordiff_hbd(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hor_bnd_diffusion_cs_t *hbd,
+                               const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_hordiff_fields_t *fields, const double *h,
+                               const mom6hip_eos_t *eos, const double *p_surf, double dt, double *const *tr, const double *conc_underflow,
+                               int32_t ntr, int32_t idx_T, int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats);
 
 /* ---- MOM_hor_visc ----------------------------------------------------------------------------- */
 

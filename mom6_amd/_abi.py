@@ -182,6 +182,17 @@ class EpipycnalCS(C.Structure):
                 ("nk_rho_varies", C.c_int32), ("answer_date", C.c_int32), ("limit_bug", C.c_int32), ("reserved1", C.c_int32 * 4)]
 
 
+class HorBndDiffusionCS(C.Structure):
+    """mom6hip_hor_bnd_diffusion_cs_t (include/mom6hip.h)."""
+    _fields_ = [("linear", C.c_int32), ("limiter", C.c_int32), ("limiter_remap", C.c_int32), ("boundary_extrap", C.c_int32),
+                ("remap_scheme", C.c_int32), ("debug", C.c_int32), ("diagnostics", C.c_int32), ("initialized", C.c_int32),
+                ("reserved", C.c_int32 * 8)]
+
+
+# HBD_REMAPPING_SCHEME values mom6hip_tracer_hordiff_hbd provides
+HBD_REMAPPING_SCHEMES = ("PCM", "PLM", "PPM_H4", "PPM_IH4", "PPM_CW")
+
+
 OBC_NONE, OBC_DIRECTION_N, OBC_DIRECTION_S, OBC_DIRECTION_E, OBC_DIRECTION_W = 0, 100, 200, 300, 400
 
 

@@ -169,12 +169,15 @@ int epipycnal_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_epipycnal_cs_
 int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_eos_t *eos, const double *h,
                    const double *p_surf, const double *h_ML, const double *khdt_x, const double *khdt_y, int num_itts, double I_numitts,
                    const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S, int *halo_updates);
+int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_cs_t *hbd, const double *h, const double *h_ML,
+               const double *khdt_x, const double *khdt_y, int num_itts, double I_numitts, const std::vector<double *> &d_tr,
+               const std::vector<double> &cu, int *halo_updates);
 }
 
 static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
                         const mom6hip_epipycnal_cs_t *epi, const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos,
                         const double *p_surf, double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
-                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats);
+                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_hor_bnd_diffusion_cs_t *hbd = nullptr);
 
 extern "C" int mom6hip_tracer_hordiff_neutral(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
                                               const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, const double *p_surf,
@@ -195,17 +198,31 @@ extern "C" int mom6hip_tracer_hordiff_epipycnal(mom6hip_ctx_t *ctx, const mom6hi
   return hordiff_impl(ctx, cs, nullptr, cs->unsupported[2] ? epi : nullptr, F, h, eos, nullptr, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, stats);
 }
 
+extern "C" int mom6hip_tracer_hordiff_hbd(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hor_bnd_diffusion_cs_t *hbd,
+                                          const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_hordiff_fields_t *F, const double *h,
+                                          const mom6hip_eos_t *eos, const double *p_surf, double dt, double *const *tr,
+                                          const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S, int32_t memspace,
+                                          mom6hip_hordiff_stats_t *stats) {
+  M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
+  M6_REQUIRE(!(cs->unsupported[1] && cs->unsupported[2]),
+             "MOM_tracer_hor_diff: USE_HORIZONTAL_BOUNDARY_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!");      // :1735
+  M6_REQUIRE(!cs->unsupported[2], "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR is not provided by this entry point (mom6hip_tracer_hordiff_epipycnal takes it)");
+  M6_REQUIRE(!cs->unsupported[1] || hbd != nullptr, "tracer_hordiff: USE_HORIZONTAL_BOUNDARY_DIFFUSION needs its control structure (mom6hip_hor_bnd_diffusion_cs_t)");
+  return hordiff_impl(ctx, cs, nd, nullptr, F, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, stats, hbd);
+}
+
 static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
                         const mom6hip_epipycnal_cs_t *epi, const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos,
                         const double *p_surf, double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
-                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats) {
+                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_hor_bnd_diffusion_cs_t *hbd) {
   static const char *names[8] = {"USE_NEUTRAL_DIFFUSION", "USE_HORIZONTAL_BOUNDARY_DIFFUSION", "DIFFUSE_ML_TO_INTERIOR",
                                  "(free)", "(free)", "KHTR_USE_EBT_STRUCT", "offline khdt (do_online = false)",
                                  "the df_x / df_y flux diagnostics"};
   M6_REQUIRE(ctx != nullptr, "MOM_tracer_hor_diff: register_tracer must be called before tracer_hordiff.");
   M6_REQUIRE(cs != nullptr && h != nullptr, "tracer_hordiff: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "tracer_hordiff: bad memspace");
-  for (int q = 1; q < 8; q++) M6_REQUIRE(q == 2 || !cs->unsupported[q], "tracer_hordiff: %s is not provided by libmom6hip", names[q]);
+  // hbd: the call came through mom6hip_tracer_hordiff_hbd, which takes USE_HORIZONTAL_BOUNDARY_DIFFUSION
+  for (int q = 1; q < 8; q++) M6_REQUIRE(q == 2 || (q == 1 && hbd) || !cs->unsupported[q], "tracer_hordiff: %s is not provided by libmom6hip", names[q]);
   M6_REQUIRE(!cs->unsupported[2] || epi != nullptr, "tracer_hordiff: %s is not provided by this entry point", names[2]);
   const bool use_neutral = cs->unsupported[0] != 0;      // CS%use_neutral_diffusion
   if (stats) { stats->num_itts = 0; stats->halo_updates = 0; stats->max_CFL = 0.0; }
@@ -288,6 +305,11 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   std::vector<double *> pf(d_tr);
   std::vector<int32_t> ppos(ntr, MOM6HIP_POS_H), pnk(ntr, g.nk);
   int halo_updates = 0;
+  if (hbd && cs->unsupported[1]) {      // :408-472, before the neutral or the along-layer branch
+    const double *d_hbl = (F && F->h_ML) ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
+    M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
+    if (int rc = m6::hbd_branch(ctx, st, hbd, A.h, d_hbl, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, &halo_updates)) return rc;
+  }
   if (use_neutral) {      // :474-534
     const double *d_ps = p_surf ? st.in(p_surf, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
     const double *d_hml = (nd && nd->interior_only && F && F->h_ML) ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;

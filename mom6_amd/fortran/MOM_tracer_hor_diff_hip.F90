@@ -20,7 +20,9 @@ use mom6hip_c_api
 use mom6hip_MOM_glue,          only : mom6hip_shared_context, mom6hip_read_topology, mom6hip_fatal_if
 use mom6hip_MOM_glue,          only : mom6hip_read_resident, mom6hip_resident, mom6hip_mirror, mom6hip_read_eos
 use MOM_cpu_clock,             only : cpu_clock_id, cpu_clock_begin, cpu_clock_end, CLOCK_MODULE
-use MOM_diabatic_driver,       only : diabatic_CS
+use MOM_CVMix_KPP,             only : KPP_CS
+use MOM_diabatic_driver,       only : diabatic_CS, extract_diabatic_member
+use MOM_energetic_PBL,         only : energetic_PBL_CS
 use MOM_diag_mediator,         only : diag_ctrl, time_type
 use MOM_EOS,                   only : EOS_type
 use MOM_error_handler,         only : MOM_error, FATAL, WARNING
@@ -53,6 +55,7 @@ type, public :: tracer_hor_diff_CS ; private
   logical :: recalc_neutral_surf  !< If true, recalculate the neutral surfaces if CFL has been exceeded
   type(mom6hip_neutral_diffusion_cs_t) :: nd   !< neutral_diffusion_CS as the library reads it
   type(mom6hip_epipycnal_cs_t) :: epi          !< the parameters of tracer_epipycnal_ML_diff as the library reads them
+  type(mom6hip_hor_bnd_diffusion_cs_t) :: hbd  !< hbd_CS (USE_HORIZONTAL_BOUNDARY_DIFFUSION) as the library reads it
   type(mom6hip_eos_t) :: eos                   !< the equation of state tracer_hor_diff_init was given
   type(diag_ctrl), pointer :: diag => NULL()
 end type tracer_hor_diff_CS
@@ -101,6 +104,10 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
 
   allocate(tr(Reg%ntr), cu(Reg%ntr))
   do m=1,Reg%ntr
+    if (CS%use_hor_bnd_diffusion .and. (Reg%Tr(m)%id_hbdxy_cont > 0 .or. Reg%Tr(m)%id_hbdxy_cont_2d > 0 .or. &
+        Reg%Tr(m)%id_hbdxy_conc > 0 .or. Reg%Tr(m)%id_hbd_dfx > 0 .or. Reg%Tr(m)%id_hbd_dfy > 0 .or. Reg%Tr(m)%id_hbd_dfx_2d > 0 .or. &
+        Reg%Tr(m)%id_hbd_dfy_2d > 0)) call MOM_error(FATAL, "tracer_hordiff (HIP): the hbd_* diagnostics of tracer "// &
+        trim(Reg%Tr(m)%name)//" are not provided by the GPU path.")
     if (associated(Reg%Tr(m)%df_x) .or. associated(Reg%Tr(m)%df_y) .or. associated(Reg%Tr(m)%df2d_x) .or. &
         associated(Reg%Tr(m)%df2d_y)) call MOM_error(FATAL, "tracer_hordiff (HIP): the diffusive flux diagnostics of tracer "// &
         trim(Reg%Tr(m)%name)//" are not provided by the GPU path.")
@@ -138,6 +145,11 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
     endif
     CS%nd%H_to_RZ = GV%H_to_RZ ; CS%nd%recalc_neutral_surf = merge(1, 0, CS%recalc_neutral_surf)
   endif
+  if (CS%use_hor_bnd_diffusion) then      ! :408-472, hor_bnd_diffusion :217-221
+    ccs%unsupported(2) = 1
+    if (.not.associated(visc%h_ML)) call MOM_error(FATAL, "hor_bnd_diffusion requires that visc%h_ML is associated.")
+    fld%h_ML = c_loc(visc%h_ML)
+  endif
   if (CS%Diffuse_ML_interior) then      ! :544-550, :613-620: tv%T and tv%S are registered tracers, found by association
     ccs%unsupported(3) = 1
     if (.not.(associated(tv%T) .and. associated(tv%S))) call MOM_error(FATAL, &
@@ -163,6 +175,10 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
       rc = mom6hip_tracer_hordiff_epipycnal(ctx, ccs, CS%epi, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
                                             CS%eos, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
                                             int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats)
+    elseif (CS%use_hor_bnd_diffusion) then
+      rc = mom6hip_tracer_hordiff_hbd(ctx, ccs, CS%hbd, CS%nd, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
+                                      CS%eos, p_surf, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
+                                      int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats)
     else
     rc = mom6hip_tracer_hordiff_neutral(ctx, ccs, CS%nd, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
                                         CS%eos, p_surf, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
@@ -171,6 +187,9 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   elseif (CS%Diffuse_ML_interior) then
     rc = mom6hip_tracer_hordiff_epipycnal(mom6hip_shared_context(G, GV), ccs, CS%epi, fld, c_loc(h), CS%eos, dt, tr, c_loc(cu), &
                                           int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats)
+  elseif (CS%use_hor_bnd_diffusion) then
+    rc = mom6hip_tracer_hordiff_hbd(mom6hip_shared_context(G, GV), ccs, CS%hbd, CS%nd, fld, c_loc(h), CS%eos, p_surf, dt, tr, c_loc(cu), &
+                                    int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats)
   else
     rc = mom6hip_tracer_hordiff_neutral(mom6hip_shared_context(G, GV), ccs, CS%nd, fld, c_loc(h), CS%eos, p_surf, dt, tr, c_loc(cu), &
                                         int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats)
@@ -278,12 +297,57 @@ subroutine tracer_hor_diff_init(Time, G, GV, US, param_file, diag, EOS, diabatic
   endif
   if (CS%use_neutral_diffusion .and. CS%Diffuse_ML_interior) call MOM_error(FATAL, "MOM_tracer_hor_diff: "// &
        "USE_NEUTRAL_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!")
-  call get_param(param_file, mdl, "USE_HORIZONTAL_BOUNDARY_DIFFUSION", CS%use_hor_bnd_diffusion, default=.false.)
-  call refuse(CS%use_hor_bnd_diffusion, "USE_HORIZONTAL_BOUNDARY_DIFFUSION")
+  call hor_bnd_diffusion_init()
+  if (CS%use_hor_bnd_diffusion .and. CS%Diffuse_ML_interior) call MOM_error(FATAL, "MOM_tracer_hor_diff: "// &
+       "USE_HORIZONTAL_BOUNDARY_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!")
   call mom6hip_read_topology(param_file)
   call mom6hip_read_resident(param_file)
   id_clock_diffuse = cpu_clock_id('(Ocean diffuse tracer)', grain=CLOCK_MODULE)
 contains
+  !> hor_bnd_diffusion_init (src/tracer/MOM_hor_bnd_diffusion.F90:79-158): its parameters, names and defaults
+  subroutine hor_bnd_diffusion_init()
+    character(len=40) :: hbd_mdl = "MOM_hor_bnd_diffusion"
+    character(len=80) :: string
+    type(KPP_CS), pointer :: KPP_CSp => NULL()
+    type(energetic_PBL_CS), pointer :: ePBL_CSp => NULL()
+    logical :: debug
+    call get_param(param_file, hbd_mdl, "USE_HORIZONTAL_BOUNDARY_DIFFUSION", CS%use_hor_bnd_diffusion, &
+                   "If true, enables the horizonal boundary tracer's diffusion module.", default=.false.)
+    if (.not.CS%use_hor_bnd_diffusion) return
+    if (associated(diabatic_CSp)) then
+      call extract_diabatic_member(diabatic_CSp, KPP_CSp=KPP_CSp)
+      call extract_diabatic_member(diabatic_CSp, energetic_PBL_CSp=ePBL_CSp)
+    endif
+    if (.not.associated(ePBL_CSp) .and. .not.associated(KPP_CSp)) call MOM_error(FATAL, &
+      "Horizontal boundary diffusion is true, but no valid boundary layer scheme was found")
+    call get_param(param_file, hbd_mdl, "HBD_LINEAR_TRANSITION", flag, &
+                   "If True, apply a linear transition at the base/top of the boundary. \n"//&
+                   "The flux will be fully applied at k=k_min and zero at k=k_max.", default=.false.)
+    CS%hbd%linear = merge(1, 0, flag)
+    call get_param(param_file, hbd_mdl, "APPLY_LIMITER", flag, "If True, apply a flux limiter in the native grid.", default=.true.)
+    CS%hbd%limiter = merge(1, 0, flag)
+    call get_param(param_file, hbd_mdl, "APPLY_LIMITER_REMAP", flag, "If True, apply a flux limiter in the remapped grid.", &
+                   default=.false.)
+    CS%hbd%limiter_remap = merge(1, 0, flag)
+    call get_param(param_file, hbd_mdl, "HBD_BOUNDARY_EXTRAP", flag, "Use boundary extrapolation in HBD code", default=.false.)
+    CS%hbd%boundary_extrap = merge(1, 0, flag)
+    call get_param(param_file, hbd_mdl, "HBD_REMAPPING_SCHEME", string, &
+                   "This sets the reconstruction scheme used for vertical remapping for all variables.", default="PLM")
+    select case (trim(string))
+      case ("PCM") ; CS%hbd%remap_scheme = MOM6HIP_REMAP_PCM
+      case ("PLM") ; CS%hbd%remap_scheme = MOM6HIP_REMAP_PLM
+      case ("PPM_H4") ; CS%hbd%remap_scheme = MOM6HIP_REMAP_PPM_H4
+      case ("PPM_IH4") ; CS%hbd%remap_scheme = MOM6HIP_REMAP_PPM_IH4
+      case ("PPM_CW") ; CS%hbd%remap_scheme = MOM6HIP_REMAP_PPM_CW
+      case default ; call refuse(.true., "HBD_REMAPPING_SCHEME = "//trim(string))
+    end select
+    call get_param(param_file, hbd_mdl, "DEBUG", debug, default=.false., do_not_log=.true.)
+    call get_param(param_file, hbd_mdl, "HBD_DEBUG", flag, "If true, write out verbose debugging data in the HBD module.", &
+                   default=debug)
+    call refuse(flag, "HBD_DEBUG")
+    CS%hbd%initialized = 1
+  end subroutine hor_bnd_diffusion_init
+
   subroutine refuse(on, name)
     logical,          intent(in) :: on
     character(len=*), intent(in) :: name

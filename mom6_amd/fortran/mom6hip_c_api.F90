@@ -192,6 +192,13 @@ type, bind(c) :: mom6hip_neutral_diffusion_cs_t
   integer(c_int32_t) :: unsupported(8) = 0
 end type mom6hip_neutral_diffusion_cs_t
 
+!> mom6hip_hor_bnd_diffusion_cs_t (hbd_CS, src/tracer/MOM_hor_bnd_diffusion.F90:40), as hor_bnd_diffusion_init leaves it
+type, bind(c) :: mom6hip_hor_bnd_diffusion_cs_t
+  integer(c_int32_t) :: linear = 0, limiter = 1, limiter_remap = 0, boundary_extrap = 0
+  integer(c_int32_t) :: remap_scheme = MOM6HIP_REMAP_PLM, debug = 0, diagnostics = 0, initialized = 0
+  integer(c_int32_t) :: reserved(8) = 0
+end type mom6hip_hor_bnd_diffusion_cs_t
+
 !> mom6hip_obc_segment_t / mom6hip_obc_t: what continuity_PPM reads of OBC_segment_type / ocean_OBC_type (src/core/MOM_open_boundary.F90:146, :266)
 integer(c_int32_t), parameter :: MOM6HIP_OBC_TAN_RADIATION = 1, MOM6HIP_OBC_GRAD_RADIATION = 2, MOM6HIP_OBC_TAN_NUDGED = 4, &
                                  MOM6HIP_OBC_GRAD_NUDGED = 8, MOM6HIP_OBC_TAN_OBLIQUE = 16, MOM6HIP_OBC_GRAD_OBLIQUE = 32
@@ -577,6 +584,31 @@ interface
     type(mom6hip_hordiff_stats_t), intent(out) :: stats
     integer(c_int) :: rc
   end function mom6hip_tracer_hordiff_neutral
+
+  !> tracer_hordiff with CS%use_hor_bnd_diffusion (cs%unsupported(2)): hor_bnd_diffusion on fields%h_ML, then the neutral branch
+  !! (cs%unsupported(1), with nd, eos, p_surf, idx_T, idx_S) or the along-layer diffusion
+  function mom6hip_tracer_hordiff_hbd(ctx, cs, hbd, nd, fields, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, &
+                                      stats) bind(c, name="mom6hip_tracer_hordiff_hbd") result(rc)
+    import :: c_int, c_int32_t, c_double, c_ptr, mom6hip_tracer_hor_diff_cs_t, mom6hip_hordiff_stats_t, mom6hip_hordiff_fields_t, &
+              mom6hip_neutral_diffusion_cs_t, mom6hip_eos_t, mom6hip_hor_bnd_diffusion_cs_t
+    type(c_ptr), value :: ctx, h, p_surf, conc_underflow
+    type(mom6hip_tracer_hor_diff_cs_t), intent(in) :: cs
+    type(mom6hip_hor_bnd_diffusion_cs_t), intent(in) :: hbd
+    type(mom6hip_neutral_diffusion_cs_t), intent(in) :: nd
+    type(mom6hip_hordiff_fields_t), intent(in) :: fields
+    type(mom6hip_eos_t), intent(in) :: eos
+    real(c_double), value :: dt
+    type(c_ptr), intent(in) :: tr(*)
+    integer(c_int32_t), value :: ntr, idx_T, idx_S, memspace
+    type(mom6hip_hordiff_stats_t), intent(out) :: stats
+    integer(c_int) :: rc
+  end function mom6hip_tracer_hordiff_hbd
+
+  !> sizeof(mom6hip_hor_bnd_diffusion_cs_t) as the library was compiled
+  function mom6hip_abi_sizeof_hor_bnd_diffusion_cs() bind(c, name="mom6hip_abi_sizeof_hor_bnd_diffusion_cs") result(n)
+    import :: c_int64_t
+    integer(c_int64_t) :: n
+  end function mom6hip_abi_sizeof_hor_bnd_diffusion_cs
 
   !> tracer_hordiff with CS%Diffuse_ML_interior (cs%unsupported(3)); idx_T, idx_S: the 0-based places of tv%T, tv%S in tr
   function mom6hip_tracer_hordiff_epipycnal(ctx, cs, epi, fields, h, eos, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, &

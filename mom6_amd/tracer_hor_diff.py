@@ -1,8 +1,9 @@
 """Host-side mirror of MOM_tracer_hor_diff (reference: src/tracer/MOM_tracer_hor_diff.F90): tracer_hor_diff_init (:1625) and
 tracer_hordiff (:119) -- the along-layer diffusion with a constant KHTR or the VarMix / MEKE diffusivities of :236-281, and with
 USE_NEUTRAL_DIFFUSION the continuous branch of MOM_neutral_diffusion (:474-534; mom6_amd/csrc/neutral_diffusion.hip), with
-DIFFUSE_ML_TO_INTERIOR tracer_epipycnal_ML_diff (:700; mom6_amd/csrc/epipycnal_diff.hip).  The work is done by libmom6hip
-(mom6_amd/csrc/tracer_hor_diff.hip)."""
+DIFFUSE_ML_TO_INTERIOR tracer_epipycnal_ML_diff (:700; mom6_amd/csrc/epipycnal_diff.hip), and with USE_HORIZONTAL_BOUNDARY_DIFFUSION the
+horizontal boundary diffusion of src/tracer/MOM_hor_bnd_diffusion.F90 before either branch (:408-472; mom6_amd/csrc/hor_bnd_diffusion.hip).
+The work is done by libmom6hip (mom6_amd/csrc/tracer_hor_diff.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,7 +17,10 @@ from .tracer_advect import DeviceGrid, _ptr_space
 _PARAMS = {"KHTR": "KhTr", "MAX_TR_DIFFUSION_CFL": "max_diff_CFL", "CHECK_DIFFUSIVE_CFL": "check_diffusive_CFL", "KHTR_SLOPE_CFF": "KhTr_Slope_Cff",
            "KHTR_MIN": "KhTr_min", "KHTR_MAX": "KhTr_max", "KHTR_PASSIVITY_COEFF": "KhTr_passivity_coeff", "KHTR_PASSIVITY_MIN": "KhTr_passivity_min"}
 # parameters of the reference whose branches this build does not provide: accepted at their defaults, refused otherwise
-_REFUSED = {"USE_HORIZONTAL_BOUNDARY_DIFFUSION": 1, "KHTR_USE_EBT_STRUCT": 5}
+_REFUSED = {"KHTR_USE_EBT_STRUCT": 5}
+# hor_bnd_diffusion_init (src/tracer/MOM_hor_bnd_diffusion.F90:79-158): its parameters (module MOM_hor_bnd_diffusion) and their defaults
+_HBD_PARAMS = {"HBD_LINEAR_TRANSITION": "linear", "APPLY_LIMITER": "limiter", "APPLY_LIMITER_REMAP": "limiter_remap",
+               "HBD_BOUNDARY_EXTRAP": "boundary_extrap", "HBD_DEBUG": "debug"}
 # DIFFUSE_ML_TO_INTERIOR and its parameters (:1687-1727)
 _EPI_PARAMS = {"ML_KHTR_SCALE": ("ML_KhTr_scale", float), "HOR_DIFF_ANSWER_DATE": ("answer_date", int), "HOR_DIFF_LIMIT_BUG": ("limit_bug", bool)}
 # neutral_diffusion_init (src/tracer/MOM_neutral_diffusion.F90:138): the parameters of the continuous branch, and those refused
@@ -35,8 +39,19 @@ class tracer_hor_diff_CS:
         nd.ref_pres, nd.ndiff_answer_date, nd.H_to_RZ = -1.0, 20240101, 0.0      # H_to_RZ: GV%H_to_RZ, taken from the grid at the call
         ep = self.epipycnal = _abi.EpipycnalCS()
         ep.ML_KhTr_scale, ep.answer_date, ep.limit_bug = 1.0, 20240101, 1
+        hb = self.hor_bnd_diffusion_CSp = _abi.HorBndDiffusionCS()
+        hb.limiter, hb.remap_scheme = 1, _abi.REMAP_SCHEMES["PLM"]
         for k, v in params.items():
-            if k == "DIFFUSE_ML_TO_INTERIOR":
+            if k == "USE_HORIZONTAL_BOUNDARY_DIFFUSION":
+                st.unsupported[1] = int(bool(v))      # CS%use_hor_bnd_diffusion (taken by mom6hip_tracer_hordiff_hbd)
+            elif k in _HBD_PARAMS:
+                setattr(hb, _HBD_PARAMS[k], int(bool(v)))
+            elif k == "HBD_REMAPPING_SCHEME":
+                if v not in _abi.HBD_REMAPPING_SCHEMES:
+                    raise Mom6HipError(f"hor_bnd_diffusion: HBD_REMAPPING_SCHEME = {v} is not provided by libmom6hip "
+                                       f"({', '.join(_abi.HBD_REMAPPING_SCHEMES)} are)")
+                hb.remap_scheme = _abi.REMAP_SCHEMES[v]
+            elif k == "DIFFUSE_ML_TO_INTERIOR":
                 st.unsupported[2] = int(bool(v))      # CS%Diffuse_ML_interior (taken by mom6hip_tracer_hordiff_epipycnal)
             elif k in _EPI_PARAMS:
                 setattr(ep, _EPI_PARAMS[k][0], _EPI_PARAMS[k][1](v))
@@ -60,7 +75,9 @@ class tracer_hor_diff_CS:
                 raise Mom6HipError(f"tracer_hor_diff_init: unknown parameter {k}")
         if st.unsupported[0] and st.unsupported[2]:
             raise Mom6HipError("MOM_tracer_hor_diff: USE_NEUTRAL_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!")      # :1732
-        st.initialized = 1; nd.initialized = 1
+        if st.unsupported[1] and st.unsupported[2]:
+            raise Mom6HipError("MOM_tracer_hor_diff: USE_HORIZONTAL_BOUNDARY_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!")      # :1735
+        st.initialized = 1; nd.initialized = 1; hb.initialized = 1
         self.last = None
 
 
@@ -80,6 +97,8 @@ def tracer_hordiff(h, dt, MEKE, VarMix, visc, G: DeviceGrid, CS: tracer_hor_diff
         raise Mom6HipError("MOM_tracer_hor_diff: register_tracer must be called before tracer_hordiff.")
     if do_online_flag is False or read_khdt_x is not None or read_khdt_y is not None:
         raise Mom6HipError("tracer_hordiff (HIP): offline khdt arrays are not supported on this path")
+    if CS.st.unsupported[1]:
+        return _tracer_hordiff_hbd(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow)
     if CS.st.unsupported[0]:
         return _tracer_hordiff_neutral(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow)
     if CS.st.unsupported[2]:
@@ -118,24 +137,21 @@ def _same(a, b):
     return a is b or (hasattr(a, "data_ptr") and hasattr(b, "data_ptr") and a.data_ptr() == b.data_ptr())
 
 
-def _tracer_hordiff_neutral(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow):
-    """the USE_NEUTRAL_DIFFUSION branch (:474-534): tv has T, S (two of the arrays of Reg, as in the reference where the registry
-    points at tv%T and tv%S), eqn_of_state (an _abi.EOS) and optionally p_surf -- a dict or an object; with NDIFF_INTERIOR_ONLY visc
-    has h_ML (visc%h_ML, the boundary-layer depth)."""
+def _tv_TS(tv, tr, what):
+    """(get, [idx_T, idx_S]): tv%T and tv%S among the registered tracers (the reference's registry points at them)"""
     get = (lambda n: tv.get(n)) if isinstance(tv, dict) else (lambda n: getattr(tv, n, None))
     if tv is None or get("T") is None or get("S") is None or get("eqn_of_state") is None:
-        raise Mom6HipError("tracer_hordiff: USE_NEUTRAL_DIFFUSION needs tv%T, tv%S and tv%eqn_of_state")
-    tr = list(Reg)
+        raise Mom6HipError(f"tracer_hordiff: {what} needs tv%T, tv%S and tv%eqn_of_state")
     idx = [next((m for m, t in enumerate(tr) if _same(t, get(n))), -1) for n in ("T", "S")]
     if min(idx) < 0:
         raise Mom6HipError("tracer_hordiff: tv%T and tv%S must be registered tracers (entries of Reg)")
+    return get, idx
+
+
+def _marshal(h, MEKE, VarMix, CS, tr):
+    """the arguments every entry point takes: (h pointer, the MEKE / VarMix fields, the tracer table, the memory spaces seen so far)"""
     if VarMix is not None and set(VarMix) - set(_abi.HORDIFF_FIELDS):
         raise Mom6HipError("tracer_hordiff (HIP): of VarMix only L2u/v, SN_u/v, Res_fn_h and Rd_dx_h are read")
-    L = lib()
-    L.mom6hip_tracer_hordiff_neutral.argtypes = [C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.NeutralDiffusionCS),
-                                                 C.POINTER(_abi.HorDiffFields), C.c_void_p, C.POINTER(_abi.EOS), C.c_void_p, C.c_double,
-                                                 C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                                 C.POINTER(_abi.HorDiffStats)]
     spaces = set()
     hp, s0 = _ptr_space(h); spaces.add(s0)
     F = _abi.HorDiffFields()
@@ -150,11 +166,31 @@ def _tracer_hordiff_neutral(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_unde
     ptrs = (C.c_void_p * max(len(tr), 1))()
     for m, t in enumerate(tr):
         p, s = _ptr_space(t); ptrs[m] = p; spaces.add(s)
+    return hp, F, ptrs, spaces
+
+
+def _h_ML(visc):
+    hml = None if visc is None else (visc.get("h_ML") if isinstance(visc, dict) else getattr(visc, "h_ML", None))
+    if hml is None:
+        raise Mom6HipError("hor_bnd_diffusion requires that visc%h_ML is associated.")
+    return hml
+
+
+def _tracer_hordiff_neutral(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow):
+    """the USE_NEUTRAL_DIFFUSION branch (:474-534): tv has T, S (two of the arrays of Reg, as in the reference where the registry
+    points at tv%T and tv%S), eqn_of_state (an _abi.EOS) and optionally p_surf -- a dict or an object; with NDIFF_INTERIOR_ONLY visc
+    has h_ML (visc%h_ML, the boundary-layer depth)."""
+    tr = list(Reg)
+    get, idx = _tv_TS(tv, tr, "USE_NEUTRAL_DIFFUSION")
+    L = lib()
+    L.mom6hip_tracer_hordiff_neutral.argtypes = [C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.NeutralDiffusionCS),
+                                                 C.POINTER(_abi.HorDiffFields), C.c_void_p, C.POINTER(_abi.EOS), C.c_void_p, C.c_double,
+                                                 C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.POINTER(_abi.HorDiffStats)]
+    hp, F, ptrs, spaces = _marshal(h, MEKE, VarMix, CS, tr)
+    st = CS.st
     if CS.neutral_diffusion_CSp.interior_only:
-        hml = None if visc is None else (visc.get("h_ML") if isinstance(visc, dict) else getattr(visc, "h_ML", None))
-        if hml is None:
-            raise Mom6HipError("hor_bnd_diffusion requires that visc%h_ML is associated.")
-        p, s = _ptr_space(hml); spaces.add(s); F.h_ML = p
+        p, s = _ptr_space(_h_ML(visc)); spaces.add(s); F.h_ML = p
     ps = None
     if get("p_surf") is not None:
         ps, s = _ptr_space(get("p_surf")); spaces.add(s)
@@ -168,6 +204,42 @@ def _tracer_hordiff_neutral(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_unde
     check(L.mom6hip_tracer_hordiff_neutral(G.handle, C.byref(st), C.byref(nd), C.byref(F), C.c_void_p(hp), C.byref(get("eqn_of_state")),
                                            None if ps is None else C.c_void_p(ps), float(dt), ptrs, None if cu is None else cu.ctypes.data,
                                            len(tr), idx[0], idx[1], spaces.pop(), C.byref(stats)), "tracer_hordiff")
+    CS.last = stats
+    return stats
+
+
+def _tracer_hordiff_hbd(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow):
+    """USE_HORIZONTAL_BOUNDARY_DIFFUSION (:408-472) and then the neutral branch (USE_NEUTRAL_DIFFUSION, tv as _tracer_hordiff_neutral takes
+    it) or the along-layer diffusion: visc -- a dict or an object -- has h_ML (visc%h_ML, the boundary-layer depth)."""
+    hml = _h_ML(visc)
+    tr = list(Reg)
+    st = CS.st
+    neutral = bool(st.unsupported[0])
+    idx, eos, p_surf = [0, 0], None, None
+    if neutral:
+        get, idx = _tv_TS(tv, tr, "USE_NEUTRAL_DIFFUSION")
+        eos, p_surf = get("eqn_of_state"), get("p_surf")
+    L = lib()
+    L.mom6hip_tracer_hordiff_hbd.argtypes = [C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.HorBndDiffusionCS),
+                                             C.POINTER(_abi.NeutralDiffusionCS), C.POINTER(_abi.HorDiffFields), C.c_void_p, C.POINTER(_abi.EOS),
+                                             C.c_void_p, C.c_double, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.POINTER(_abi.HorDiffStats)]
+    hp, F, ptrs, spaces = _marshal(h, MEKE, VarMix, CS, tr)
+    p, s = _ptr_space(hml); spaces.add(s); F.h_ML = p
+    ps = None
+    if p_surf is not None:
+        ps, s = _ptr_space(p_surf); spaces.add(s)
+    if len(spaces) != 1:
+        raise Mom6HipError("tracer_hordiff: h, visc%h_ML, p_surf and every tracer must be in the same memory space")
+    nd = CS.neutral_diffusion_CSp
+    if neutral and nd.H_to_RZ == 0.0:
+        nd.H_to_RZ = float(G.grid.Rho0 * G.grid.H_to_Z)      # GV%H_to_RZ, Boussinesq
+    cu = None if conc_underflow is None else np.ascontiguousarray(conc_underflow, dtype=np.float64)
+    stats = _abi.HorDiffStats()
+    check(L.mom6hip_tracer_hordiff_hbd(G.handle, C.byref(st), C.byref(CS.hor_bnd_diffusion_CSp), C.byref(nd) if neutral else None, C.byref(F),
+                                       C.c_void_p(hp), C.byref(eos) if neutral else None, None if ps is None else C.c_void_p(ps), float(dt),
+                                       ptrs, None if cu is None else cu.ctypes.data, len(tr), idx[0], idx[1], spaces.pop(), C.byref(stats)),
+          "tracer_hordiff")
     CS.last = stats
     return stats
 
