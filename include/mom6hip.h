@@ -696,6 +696,9 @@ typedef struct mom6hip_pressureforce_cs {
 int mom6hip_pressureforce_fv_bouss(mom6hip_ctx_t *ctx, const mom6hip_pressureforce_cs_t *cs, const mom6hip_eos_t *eos,
                                    const double *h, const double *T, const double *S, const double *p_atm,
                                    double *PFu, double *PFv, double *pbce, double *eta, int32_t memspace);
+/* How often the PLM branch of mom6hip_pressureforce_fv_bouss launched its generic face kernel (counts[0]) and a face kernel
+ * specialised for the call's options at compile time (counts[1]: EQN_OF_STATE = WRIGHT) on this context. */
+int mom6hip_pgf_face_launches(mom6hip_ctx_t *ctx, uint64_t *counts);
 
 /*
  * PressureForce_FV_nonBouss(h, tv, PFu, PFv, G, GV, US, CS, ALE_CSp, p_atm, pbce, eta)   src/core/MOM_PressureForce_FV.F90:89

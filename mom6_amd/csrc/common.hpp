@@ -115,6 +115,7 @@ struct mom6hip_ctx {
   m6::DevBuf hv_str;            // the layer-integrated stresses of every layer, kept for MEKE%mom_src (hor_visc.hip)
   m6::DevBuf cont_hmid;         // continuity in two phases around a pass in flight: the thicknesses after the first direction
   uint64_t overlap[4] = {0, 0, 0, 0};      // mom6hip_overlap_stats
+  uint64_t pgf_face_launches[2] = {0, 0};  // mom6hip_pgf_face_launches: pgf_face_kernel, pgf_face_kernel_t
   int cont_phase = 0;           // 0: the whole continuity; 1: what needs no halo row (before the completion); 2: the rest (after it)
   // u_bc_accel = (CAu + PFu) + diffu of the RK2 step (MOM_dynamics_split_RK2.F90:557-564, :879-886) formed by the kernel that produces the
   // later of CAu and PFu (pgf_face_kernel or coradcalc_kernel) instead of a sweep of its own: set by the stepper around that call; the

@@ -132,11 +132,15 @@ __device__ __forceinline__ double eos_density(const EosDev &E, double T, double 
   return (pressure + p0) / (lambda + al0 * (pressure + p0));
 }
 
-// density_anomaly_elem :98-129
+// density_anomaly_elem :98-129.  FORM = EOS_FORM_RUNTIME reads the form from E at run time; a MOM6HIP_EOS_* value fixes it at compile
+// time (the other forms fold away: the kernels that evaluate it many times per point get one straight-line body).  One text for both.
+constexpr int EOS_FORM_RUNTIME = -1;
+template <int FORM = EOS_FORM_RUNTIME>
 __device__ __forceinline__ double eos_density_anomaly(const EosDev &E, double T, double S, double pressure, double rho_ref) {
-  if (E.form == MOM6HIP_EOS_LINEAR) return (E.Rho_T0_S0 - rho_ref) + (E.dRho_dT * T + E.dRho_dS * S);
-  if (E.form == MOM6HIP_EOS_UNESCO) return unesco::density_anomaly(T, S, pressure, rho_ref);
-  if (is_wrightx(E.form)) return wrightx_density_anomaly(wright_coefs(E.form), T, S, pressure, rho_ref);
+  const int form = (FORM == EOS_FORM_RUNTIME) ? E.form : FORM;
+  if (form == MOM6HIP_EOS_LINEAR) return (E.Rho_T0_S0 - rho_ref) + (E.dRho_dT * T + E.dRho_dS * S);
+  if (form == MOM6HIP_EOS_UNESCO) return unesco::density_anomaly(T, S, pressure, rho_ref);
+  if (is_wrightx(form)) return wrightx_density_anomaly(wright_coefs(form), T, S, pressure, rho_ref);
   const double pa_000 = (b0 * (1.0 - a0 * rho_ref) - rho_ref * c0);
   const double al_TS = a1 * T + a2 * S;
   const double al0 = a0 + al_TS;

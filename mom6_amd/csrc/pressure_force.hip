@@ -13,6 +13,10 @@
 //                      and eta.  Writes e, T_t, T_b, S_t, S_b, dpa, intz_dpa.
 //   pgf_face_kernel    per (I,j)/(i,J) face pair: the 15+15 EOS evaluations of intx_dpa / inty_dpa and the
 //                      PFu / PFv formulas (:794-811), carrying pa, intx_pa, inty_pa down the column.
+//   pgf_face_kernel_t  the same with the equation of state (WRIGHT), the mass weighting, the u_bc_accel fusion and the surface
+//                      pressure fixed at compile time: a layer is one straight-line region in which the scheduler interleaves
+//                      the 30 evaluations (9.7 -> 7.8 ms at 1440x1080x75, profiles/r07_pgf_face.txt).  The host picks the
+//                      instantiation; a combination without one runs pgf_face_kernel.
 // Splitting at the column kernel keeps the EOS count at the reference's 35 per cell (a single fused
 // kernel would have to recompute the neighbours' vertical integrals: 45).
 #include <cmath>
@@ -199,16 +203,26 @@ __global__ __launch_bounds__(64, PGF_COL_OCC) void pgf_column_kernel(PgfArgs p) 
 }
 
 // ---- face kernel ---------------------------------------------------------------------------------
-// 15 EOS evaluations across one face between the columns at offsets oL (left/south) and oR (right/north)
-__device__ __forceinline__ double face_integral(const PgfArgs &p, long oL3, long oR3, long oL2, long oR2, double eL_K,
-                                                double eL_Kp1, double eR_K, double eR_Kp1) {
+// what the face integrals read of one column in one layer
+struct PgfColK { double e_Kp1, Tt, Tb, St, Sb, dpa; };
+constexpr int PGF_RUNTIME = -1;      // a template option read from PgfArgs at run time (pgf_face_kernel)
+
+// 15 EOS evaluations across one face between the columns L (left/south) and R (right/north), from values in registers.
+// FORM: EOS_FORM_RUNTIME or a MOM6HIP_EOS_* value; MASSW: PGF_RUNTIME (p.massw), 0 or 1.  With both fixed at compile time the
+// 15 evaluations are one straight-line region (the m and n loops unroll; the only branch, on hWght, lies ahead of them).
+template <int FORM, int MASSW, bool FENCE = false>
+__device__ __forceinline__ double face_integral_core(const PgfArgs &p, const PgfColK &L, const PgfColK &R, double bathyL, double bathyR,
+                                                     double eL_K, double eR_K) {
   const m6::GridDev &g = p.g;
   const double G_e = g.g_Earth, GxRho = G_e * p.rho_ref, rho_ref = p.rho_ref;
   const double C1_90 = 1.0 / 90.0;
+  const double eL_Kp1 = L.e_Kp1, eR_Kp1 = R.e_Kp1;
   double Ttl, Tbl, Ttr, Tbr, Stl, Sbl, Str, Sbr;
-  const double TtL = p.T_t[oL3], TtR = p.T_t[oR3], TbL = p.T_b[oL3], TbR = p.T_b[oR3];
-  const double StL = p.S_t[oL3], StR = p.S_t[oR3], SbL = p.S_b[oL3], SbR = p.S_b[oR3];
-  double hWght = (p.massw ? 1. : 0.) * max3(0., -g.bathyT[oL2] - eR_K, -g.bathyT[oR2] - eL_K);
+  const double TtL = L.Tt, TtR = R.Tt, TbL = L.Tb, TbR = R.Tb;
+  const double StL = L.St, StR = R.St, SbL = L.Sb, SbR = R.Sb;
+  const bool massw = (MASSW == PGF_RUNTIME) ? (p.massw != 0) : (MASSW != 0);
+  double hWght = 0.;      // MASSW == 0: the reference's 0 * max(...) is never > 0
+  if (MASSW != 0) hWght = (massw ? 1. : 0.) * max3(0., -bathyL - eR_K, -bathyR - eL_K);
   if (hWght > 0.) {
     const double hL = (eL_K - eL_Kp1) + g.dZ_subroundoff;
     const double hR = (eR_K - eR_Kp1) + g.dZ_subroundoff;
@@ -228,7 +242,7 @@ __device__ __forceinline__ double face_integral(const PgfArgs &p, long oL3, long
     Stl = StL; Sbl = SbL; Str = StR; Sbr = SbR;
   }
   double intz[5];
-  intz[0] = p.dpa[oL3]; intz[4] = p.dpa[oR3];
+  intz[0] = L.dpa; intz[4] = R.dpa;
 #pragma unroll
   for (int m = 2; m <= 4; m++) {
     const double w_left = 0.25 * (double)(5 - m), w_right = 1.0 - w_left;
@@ -248,11 +262,23 @@ __device__ __forceinline__ double face_integral(const PgfArgs &p, long oL3, long
         Sn = wt_t * S1 + wt_b * S5;
         Tn = wt_t * T1 + wt_b * T5;
       }
-      r[n - 1] = eos_density_anomaly(p.eos, Tn, Sn, pn, rho_ref);
+      r[n - 1] = eos_density_anomaly<FORM>(p.eos, Tn, Sn, pn, rho_ref);
     }
     intz[m - 1] = G_e * dz_x * (C1_90 * (7.0 * (r[0] + r[4]) + 32.0 * (r[1] + r[3]) + 12.0 * r[2]));
+    if (FENCE) __builtin_amdgcn_sched_barrier(0);
   }
   return C1_90 * (7.0 * (intz[0] + intz[4]) + 32.0 * (intz[1] + intz[3]) + 12.0 * intz[2]);
+}
+
+// the generic form: every option read at run time, the columns at offsets oL (left/south) and oR (right/north)
+__device__ __forceinline__ double face_integral(const PgfArgs &p, long oL3, long oR3, long oL2, long oR2, double eL_K,
+                                                double eL_Kp1, double eR_K, double eR_Kp1) {
+  PgfColK L, R;
+  L.e_Kp1 = eL_Kp1; R.e_Kp1 = eR_Kp1;
+  L.Tt = p.T_t[oL3]; R.Tt = p.T_t[oR3]; L.Tb = p.T_b[oL3]; R.Tb = p.T_b[oR3];
+  L.St = p.S_t[oL3]; R.St = p.S_t[oR3]; L.Sb = p.S_b[oL3]; R.Sb = p.S_b[oR3];
+  L.dpa = p.dpa[oL3]; R.dpa = p.dpa[oR3];
+  return face_integral_core<EOS_FORM_RUNTIME, PGF_RUNTIME>(p, L, R, p.g.bathyT[oL2], p.g.bathyT[oR2], eL_K, eR_K);
 }
 
 __global__ __launch_bounds__(64, PGF_FACE_OCC) void pgf_face_kernel(PgfArgs p) {
@@ -322,6 +348,180 @@ __global__ __launch_bounds__(64, PGF_FACE_OCC) void pgf_face_kernel(PgfArgs p) {
     pa_c = pa_c + dpa_c;
     ec_K = ec_Kp1;
   }
+}
+
+// ---- the face kernel with its options fixed at compile time ------------------------------------------------------------
+// FORM (a MOM6HIP_EOS_* value), MASSW (MASS_WEIGHT_IN_PRESSURE_GRADIENT), BC (the RK2 step's u_bc_accel: PGF_BC_OFF, _VISCOUS,
+// _INVISCID) and PATM (a surface pressure) are template parameters; mom6hip_pressureforce_fv_bouss picks the instantiation and
+// keeps pgf_face_kernel for every combination that has none.  The results are pgf_face_kernel's bit for bit; what changes is
+// the shape of the code:
+//   - both faces of a point are computed by every lane (a lane without an x or a y face, on the first row or in the first
+//     column, takes its own column as the neighbour and stores nothing), so a layer is one straight-line region: its 30 EOS
+//     evaluations, each a serial chain ending in an IEEE division, are interleaved by the scheduler instead of being run one
+//     after the other in basic blocks of their own;
+//   - array elements are addressed by 32-bit byte offsets from the uniform array pointers (pgf_ld);
+//   - optionally (PGF_FACE_PF, off by default: it measured no faster) the loads are a layer ahead: what the evaluations need
+//     first (the interface heights and the edge values of T and S of the three columns, 1) or everything (2) is loaded for layer
+//     k+1 before layer k's arithmetic.
+// Defaults as measured at 1440x1080x75 (profiles/r07_pgf_face.txt): no layer-ahead loads, 3 waves per SIMD (152 VGPRs, no scratch).
+#ifndef PGF_FACE_T_OCC
+#define PGF_FACE_T_OCC 3
+#endif
+#ifndef PGF_FACE_PF
+#define PGF_FACE_PF 0
+#endif
+#ifndef PGF_FACE_FENCE
+#define PGF_FACE_FENCE 0      // 1: no scheduling across the two faces; 2: nor across the three groups of five evaluations of a face
+#endif
+constexpr int PGF_BC_OFF = 0, PGF_BC_VISCOUS = 1, PGF_BC_INVISCID = 2;
+struct PgfColLate { double h, iz; };      // what only the PFu / PFv formulas read
+// Array elements are addressed by 32-bit byte offsets from the (uniform) array pointers: one register per column instead of a
+// 64-bit address per array and column.  The host launches this kernel only where every offset fits (pgf_face_pick).
+__device__ __forceinline__ double pgf_ld(const double *a, unsigned b) { return *(const double *)((const char *)a + b); }
+__device__ __forceinline__ void pgf_st(double *a, unsigned b, double v) { *(double *)((char *)a + b) = v; }
+__device__ __forceinline__ PgfColK pgf_load_col(const PgfArgs &p, unsigned b, unsigned plb) {
+  PgfColK c;
+  c.e_Kp1 = pgf_ld(p.e, b + plb); c.Tt = pgf_ld(p.T_t, b); c.Tb = pgf_ld(p.T_b, b); c.St = pgf_ld(p.S_t, b); c.Sb = pgf_ld(p.S_b, b);
+  c.dpa = pgf_ld(p.dpa, b);
+  return c;
+}
+__device__ __forceinline__ PgfColLate pgf_load_late(const PgfArgs &p, unsigned b) {
+  PgfColLate c;
+  c.h = pgf_ld(p.h, b); c.iz = pgf_ld(p.intz_dpa, b);
+  return c;
+}
+
+template <int FORM, bool MASSW, int BC, bool PATM>
+__global__ __launch_bounds__(64, PGF_FACE_T_OCC) void pgf_face_kernel_t(PgfArgs p) {
+  const m6::GridDev &g = p.g;
+  const int i = g.isc - 1 + blockIdx.x * 64 + threadIdx.x;      // I (x face) / i (y face)
+  const int j = g.jsc - 1 + blockIdx.y;                         // j (x face) / J (y face)
+  if (i > g.iec) return;
+  const bool do_x = (j >= g.jsc), do_y = (i >= g.isc);          // j <= jec and i <= iec by the grid size
+  if (!do_x && !do_y) return;
+  const int nz = g.nk;
+  const long oc = g.h2(i, j), oe = do_x ? oc + 1 : oc, on = do_y ? oc + g.nih : oc;
+  const long ou = g.u2(i, j), ov = g.v2(i, j);
+  // byte offsets of the layer in hand and of a plane, per staggering
+  const unsigned pl = 8u * (unsigned)(g.nih * g.njh), plU = 8u * (unsigned)((g.nih + 1) * g.njh), plV = 8u * (unsigned)(g.nih * (g.njh + 1));
+  unsigned c3 = 8u * (unsigned)oc, e3 = 8u * (unsigned)oe, n3 = 8u * (unsigned)on, u3 = 8u * (unsigned)ou, v3 = 8u * (unsigned)ov;
+  const double h_neglect = g.H_subroundoff, I_Rho0 = 1.0 / g.Rho0;
+  const double rg = p.rho_ref * g.g_Earth;
+  auto pa0 = [&](long o2) -> double {
+    double v = rg * (p.e[o2] - p.Z_ref);
+    if (PATM) v = v + p.p_atm[o2];
+    return v;
+  };
+  double pa_c = pa0(oc), pa_e = pa0(oe), pa_n = pa0(on);
+  double intx_pa = 0.5 * (pa_c + pa_e), inty_pa = 0.5 * (pa_c + pa_n);
+  const double fx = do_x ? (2.0 * I_Rho0 * g.IdxCu[ou]) : 0.0;
+  const double fy = do_y ? (2.0 * I_Rho0 * g.IdyCv[ov]) : 0.0;
+  double bathy_c = 0., bathy_e = 0., bathy_n = 0.;
+  if (MASSW) { bathy_c = g.bathyT[oc]; bathy_e = g.bathyT[oe]; bathy_n = g.bathyT[on]; }
+  double ec_K = p.e[oc], ee_K = p.e[oe], en_K = p.e[on];
+#if PGF_FACE_PF >= 1
+  PgfColK c = pgf_load_col(p, c3, pl), e = pgf_load_col(p, e3, pl), n = pgf_load_col(p, n3, pl);
+#endif
+#if PGF_FACE_PF == 2
+  PgfColLate lc = pgf_load_late(p, c3), le = pgf_load_late(p, e3), ln = pgf_load_late(p, n3);
+  double cau = 0., cav = 0., dfu = 0., dfv = 0.;
+  if (BC != PGF_BC_OFF) { cau = pgf_ld(p.bc_CAu, u3); cav = pgf_ld(p.bc_CAv, v3); }
+  if (BC == PGF_BC_VISCOUS) { dfu = pgf_ld(p.bc_diffu, u3); dfv = pgf_ld(p.bc_diffv, v3); }
+#endif
+  for (int k = 0; k < nz; k++) {
+    // the next layer's loads (the last layer loads itself again: no branch in the loop)
+    const unsigned dn = (k + 1 < nz) ? pl : 0u, dnU = (k + 1 < nz) ? plU : 0u, dnV = (k + 1 < nz) ? plV : 0u;
+    (void)dn; (void)dnU; (void)dnV;
+#if PGF_FACE_PF >= 1
+    const PgfColK c1 = pgf_load_col(p, c3 + dn, pl), e1 = pgf_load_col(p, e3 + dn, pl), n1 = pgf_load_col(p, n3 + dn, pl);
+#else
+    const PgfColK c = pgf_load_col(p, c3, pl), e = pgf_load_col(p, e3, pl), n = pgf_load_col(p, n3, pl);
+#endif
+#if PGF_FACE_PF == 2
+    const PgfColLate lc1 = pgf_load_late(p, c3 + dn), le1 = pgf_load_late(p, e3 + dn), ln1 = pgf_load_late(p, n3 + dn);
+    double cau1 = 0., cav1 = 0., dfu1 = 0., dfv1 = 0.;
+    if (BC != PGF_BC_OFF) { cau1 = pgf_ld(p.bc_CAu, u3 + dnU); cav1 = pgf_ld(p.bc_CAv, v3 + dnV); }
+    if (BC == PGF_BC_VISCOUS) { dfu1 = pgf_ld(p.bc_diffu, u3 + dnU); dfv1 = pgf_ld(p.bc_diffv, v3 + dnV); }
+#else
+    // read only by the formulas behind the evaluations: in flight while those run
+    const PgfColLate lc = pgf_load_late(p, c3), le = pgf_load_late(p, e3), ln = pgf_load_late(p, n3);
+    double cau = 0., cav = 0., dfu = 0., dfv = 0.;
+    if (BC != PGF_BC_OFF) { cau = pgf_ld(p.bc_CAu, u3); cav = pgf_ld(p.bc_CAv, v3); }
+    if (BC == PGF_BC_VISCOUS) { dfu = pgf_ld(p.bc_diffu, u3); dfv = pgf_ld(p.bc_diffv, v3); }
+#endif
+    const double intx_dpa = face_integral_core<FORM, MASSW ? 1 : 0, PGF_FACE_FENCE == 2>(p, c, e, bathy_c, bathy_e, ec_K, ee_K);
+#if PGF_FACE_FENCE
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    const double inty_dpa = face_integral_core<FORM, MASSW ? 1 : 0, PGF_FACE_FENCE == 2>(p, c, n, bathy_c, bathy_n, ec_K, en_K);
+#if PGF_FACE_FENCE
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    const double h_c = lc.h, iz_c = lc.iz, ec_Kp1 = c.e_Kp1;
+    {
+      const double ee_Kp1 = e.e_Kp1, h_e = le.h;
+      const double pfu = (((pa_c * h_c + iz_c) - (pa_e * h_e + le.iz)) +
+                          ((h_e - h_c) * intx_pa - (ee_Kp1 - ec_Kp1) * intx_dpa * g.Z_to_H)) *
+                         (fx / ((h_c + h_e) + h_neglect));
+      if (do_x) {
+        pgf_st(p.PFu, u3, pfu);
+        if (BC != PGF_BC_OFF) {
+          double a = cau + pfu;
+          if (BC == PGF_BC_INVISCID) a = (a == 0.0) ? 0.0 : a; else a = a + dfu;
+          pgf_st(p.bc_u, u3, a);
+        }
+      }
+      intx_pa = intx_pa + intx_dpa;
+      pa_e = pa_e + e.dpa;
+      ee_K = ee_Kp1;
+    }
+    {
+      const double en_Kp1 = n.e_Kp1, h_n = ln.h;
+      const double pfv = (((pa_c * h_c + iz_c) - (pa_n * h_n + ln.iz)) +
+                          ((h_n - h_c) * inty_pa - (en_Kp1 - ec_Kp1) * inty_dpa * g.Z_to_H)) *
+                         (fy / ((h_c + h_n) + h_neglect));
+      if (do_y) {
+        pgf_st(p.PFv, v3, pfv);
+        if (BC != PGF_BC_OFF) {
+          double a = cav + pfv;
+          if (BC == PGF_BC_INVISCID) a = (a == 0.0) ? 0.0 : a; else a = a + dfv;
+          pgf_st(p.bc_v, v3, a);
+        }
+      }
+      inty_pa = inty_pa + inty_dpa;
+      pa_n = pa_n + n.dpa;
+      en_K = en_Kp1;
+    }
+    pa_c = pa_c + c.dpa;
+    ec_K = ec_Kp1;
+    c3 += pl; e3 += pl; n3 += pl; u3 += plU; v3 += plV;
+#if PGF_FACE_PF >= 1
+    c = c1; e = e1; n = n1;
+#endif
+#if PGF_FACE_PF == 2
+    lc = lc1; le = le1; ln = ln1; cau = cau1; cav = cav1; dfu = dfu1; dfv = dfv1;
+#endif
+  }
+}
+
+// the instantiations of pgf_face_kernel_t: EQN_OF_STATE = WRIGHT with every combination of the other three options (the RK2 step
+// of the benchmark runs <WRIGHT, false, PGF_BC_VISCOUS or _OFF, false>); null: pgf_face_kernel
+using PgfFaceKernel = void (*)(PgfArgs);
+template <int FORM>
+PgfFaceKernel pgf_face_pick_form(bool massw, int bc, bool patm) {
+#define PGF_T(M, B) (patm ? pgf_face_kernel_t<FORM, M, B, true> : pgf_face_kernel_t<FORM, M, B, false>)
+  if (massw) return bc == PGF_BC_OFF ? PGF_T(true, PGF_BC_OFF) : bc == PGF_BC_VISCOUS ? PGF_T(true, PGF_BC_VISCOUS) : PGF_T(true, PGF_BC_INVISCID);
+  return bc == PGF_BC_OFF ? PGF_T(false, PGF_BC_OFF) : bc == PGF_BC_VISCOUS ? PGF_T(false, PGF_BC_VISCOUS) : PGF_T(false, PGF_BC_INVISCID);
+#undef PGF_T
+}
+PgfFaceKernel pgf_face_pick(const PgfArgs &a) {
+  // the 32-bit byte offsets of pgf_face_kernel_t: the largest is the last plane of e (nk+1 planes) or of a velocity-point array
+  const uint64_t planes = (uint64_t)a.g.nk + 1, pmax = (uint64_t)(a.g.nih + 1) * (uint64_t)(a.g.njh + 1);
+  if (planes * pmax * 8 >= (1ull << 32)) return nullptr;
+  if (!a.bc_u != !a.bc_v) return nullptr;
+  const int bc = !a.bc_u ? PGF_BC_OFF : a.bc_inviscid ? PGF_BC_INVISCID : PGF_BC_VISCOUS;
+  if (a.eos.form == MOM6HIP_EOS_WRIGHT) return pgf_face_pick_form<MOM6HIP_EOS_WRIGHT>(a.massw != 0, bc, a.p_atm != nullptr);
+  return nullptr;
 }
 
 // ---- ALE_PLM_edge_values (MOM_ALE.F90:1520-1579) of one 3-d scalar: the reconstruction above for a caller's own field ----
@@ -930,7 +1130,9 @@ extern "C" int mom6hip_pressureforce_fv_bouss(mom6hip_ctx_t *ctx, const mom6hip_
       f->done = true;
     }
     hipLaunchKernelGGL(pgf_column_kernel, gc, dim3(64), 0, s, a);
-    { m6::KTimer kt(ctx, MOM6HIP_KT_PGF_FACE); hipLaunchKernelGGL(pgf_face_kernel, gf, dim3(64), 0, s, a); }
+    const PgfFaceKernel face_t = pgf_face_pick(a);
+    ctx->pgf_face_launches[face_t ? 1 : 0]++;
+    { m6::KTimer kt(ctx, MOM6HIP_KT_PGF_FACE); hipLaunchKernelGGL(face_t ? face_t : pgf_face_kernel, gf, dim3(64), 0, s, a); }
   } else if (mode == PCM_LINEAR) {
     hipLaunchKernelGGL(pgf_pcm_column_kernel<PCM_LINEAR>, gc, dim3(64), 0, s, a);
     hipLaunchKernelGGL(pgf_pcm_face_kernel<PCM_LINEAR>, gf, dim3(64), 0, s, a);
@@ -943,6 +1145,12 @@ extern "C" int mom6hip_pressureforce_fv_bouss(mom6hip_ctx_t *ctx, const mom6hip_
   }
   M6_HIP(hipGetLastError());
   return st.finish();
+}
+
+extern "C" int mom6hip_pgf_face_launches(mom6hip_ctx_t *ctx, uint64_t *counts) {
+  M6_REQUIRE(ctx != nullptr && counts != nullptr, "mom6hip_pgf_face_launches: null argument");
+  counts[0] = ctx->pgf_face_launches[0]; counts[1] = ctx->pgf_face_launches[1];
+  return 0;
 }
 
 extern "C" int mom6hip_pressureforce_fv_nonbouss(mom6hip_ctx_t *ctx, const mom6hip_pressureforce_cs_t *cs,

@@ -39,6 +39,15 @@ def calculate_density(T, S, pressure, rho, EOS, G: DeviceGrid, rho_ref=None):
                                       spaces.pop()), "calculate_density")
 
 
+def pgf_face_launches(G: DeviceGrid):
+    """mom6hip_pgf_face_launches: how often PressureForce_FV_Bouss (PLM branch) launched (its generic face kernel, a face kernel
+    specialised at compile time for the call's options) on this grid's context."""
+    L = lib(); L.mom6hip_pgf_face_launches.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 2)()
+    check(L.mom6hip_pgf_face_launches(G.handle, out), "mom6hip_pgf_face_launches")
+    return int(out[0]), int(out[1])
+
+
 def PressureForce_init(grid, Rho0=None, boundary_extrap=True, useMassWghtInterp=False, Z_ref=0.0, reconstruct=True, use_ALE=True,
                        nk_rho_varies=0, P_Ref=2.0e7, Rlay=None, g_prime=None):
     """PressureForce_FV_init (MOM_PressureForce_FV.F90:921): RHO_PGF_REF, RECONSTRUCT_FOR_PRESSURE,
