@@ -1054,15 +1054,6 @@ int mom6hip_btstep_obc(mom6hip_ctx_t *ctx, mom6hip_barotropic_cs_t *cs, const do
     w.gtot_E = H(); w.gtot_W = H(); w.gtot_N = H(); w.gtot_S = H(); w.eta_src = H(); w.e_anom = H();
     w.q = (double *)q;
   }
-  // the second set of the five fields that alternate between the steps of the fused kernel (bt_step_fused_kernel)
-  double *alt_eta = nullptr, *alt_ubt = nullptr, *alt_vbt = nullptr, *alt_uhbtp = nullptr, *alt_vhbtp = nullptr;
-  {
-    char *q = (char *)st.scratch(2 * sz.u2 + 2 * sz.v2 + sz.h2);
-    M6_REQUIRE(!st.failed() && q, "btstep: staging failed");
-    M6_HIP(hipMemsetAsync(q, 0, 2 * sz.u2 + 2 * sz.v2 + sz.h2, s));
-    alt_ubt = (double *)q; alt_uhbtp = (double *)(q + sz.u2); alt_vbt = (double *)(q + 2 * sz.u2); alt_vhbtp = (double *)(q + 2 * sz.u2 + sz.v2);
-    alt_eta = (double *)(q + 2 * sz.u2 + 2 * sz.v2);
-  }
   // ---- open boundaries :770-780
   w.obc_u = w.obc_v = nullptr;
   w.ob_Cg_u = w.ob_dZ_u = w.ob_uhbt = w.ob_ubt_outer = w.ob_SSH_u = w.ubt_old = w.ubt_first = w.ubt_wtd = nullptr;
@@ -1110,6 +1101,20 @@ int mom6hip_btstep_obc(mom6hip_ctx_t *ctx, mom6hip_barotropic_cs_t *cs, const do
     double **pu[8] = {&w.ob_Cg_u, &w.ob_dZ_u, &w.ob_uhbt, &w.ob_ubt_outer, &w.ob_SSH_u, &w.ubt_old, &w.ubt_first, &w.ubt_wtd};
     double **pv[8] = {&w.ob_Cg_v, &w.ob_dZ_v, &w.ob_vhbt, &w.ob_vbt_outer, &w.ob_SSH_v, &w.vbt_old, &w.vbt_first, &w.vbt_wtd};
     for (int q = 0; q < 8; q++) { *pu[q] = (double *)(ob + q * sz.u2); *pv[q] = (double *)(ob + 8 * sz.u2 + q * sz.v2); }
+  }
+  // MOM6HIP_BT_FUSED=1: one fused kernel a step (bt_step_fused_kernel; not with open boundaries or face areas that follow eta).  Bit-exact
+  // and slower than the four kernels at every tile height measured (profiles/r05_experiments.txt section 2): not the default.  Its five
+  // alternating fields: step n reads set A (the Work arrays) when n is odd, set B when it is even.  (Read at every call: tests switch it
+  // within one process.)  Set B is reserved and zeroed only when the fused kernel runs.
+  const char *fused_env = getenv("MOM6HIP_BT_FUSED");
+  const bool fused = fused_env && atoi(fused_env) == 1 && !apply_OBCs && !nonlin_update;
+  double *alt_eta = nullptr, *alt_ubt = nullptr, *alt_vbt = nullptr, *alt_uhbtp = nullptr, *alt_vhbtp = nullptr;
+  if (fused) {
+    char *q = (char *)st.scratch(2 * sz.u2 + 2 * sz.v2 + sz.h2);
+    M6_REQUIRE(!st.failed() && q, "btstep: staging failed");
+    M6_HIP(hipMemsetAsync(q, 0, 2 * sz.u2 + 2 * sz.v2 + sz.h2, s));
+    alt_ubt = (double *)q; alt_uhbtp = (double *)(q + sz.u2); alt_vbt = (double *)(q + 2 * sz.u2); alt_vhbtp = (double *)(q + 2 * sz.u2 + sz.v2);
+    alt_eta = (double *)(q + 2 * sz.u2 + 2 * sz.v2);
   }
   // the part of set_up_BT_OBC :3234-3262, :3296-3322 for the specified segments: the external transports summed over the layers, and
   // the barotropic velocities that carry them
@@ -1526,11 +1531,7 @@ int mom6hip_btstep_obc(mom6hip_ctx_t *ctx, mom6hip_barotropic_cs_t *cs, const do
       rng[n] = {isv, iev, jsv, jev, pf};
     }
   }
-  // MOM6HIP_BT_FUSED=1: one fused kernel a step (bt_step_fused_kernel; not with open boundaries or face areas that follow eta).  Bit-exact
-  // and slower than the four kernels at every tile height measured (profiles/r05_experiments.txt section 2): not the default.  Its five
-  // alternating fields: step n reads set A (the Work arrays) when n is odd, set B when it is even.  (Read at every call: tests switch it.)
-  const char *fused_env = getenv("MOM6HIP_BT_FUSED");
-  const bool fused = fused_env && atoi(fused_env) == 1 && !apply_OBCs && !nonlin_update;
+  // the fused kernel's fields (`fused`, set above): the set step n reads
   auto eta_at = [&](int n) { return (fused && n % 2 == 0) ? alt_eta : w.eta; };        // the set step n reads (and a pass before it updates)
   auto do_pass = [&](int n) -> int {
     if (fused && n % 2 == 0) return pass({{alt_eta, PH}, {alt_ubt, PU}, {alt_vbt, PV}, {alt_uhbtp, PU}, {alt_vhbtp, PV}});

@@ -141,6 +141,8 @@ struct mom6hip_ctx {
   uint64_t obc_table_clock = 0, obc_table_builds = 0;
   m6::DevBuf vv_ntrunc;         // device counter of vertvisc_limit_vel's truncations (vert_friction.hip)
   bool vv_ntrunc_ready = false;
+  m6::DevBuf vv_kvml[2];        // the KV_ML_INVZ2 profile at the u and v interfaces, handed from the first vertvisc call of a step to the
+  const void *vv_kvml_h = nullptr;      // later ones (m6::KvmlProfile), and the thicknesses it was formed from
   // hipGraphs of the barotropic subcycle, keyed on everything baked into their nodes (barotropic.hip)
   std::vector<std::pair<std::string, void *>> bt_graphs;
   hipStream_t cap_stream = nullptr;
@@ -255,9 +257,15 @@ int set_viscous_BBL_dev(mom6hip_ctx *ctx, const mom6hip_set_visc_cs_t *cs, const
 // the velocities of vertvisc_coef / vertvisc as the increment the RK2 step applies just before them:
 // u = mask2dCu * (u0 + dtv * (a1u [+ a2u])), v likewise (device pointers; a2u / a2v may be null)
 struct VelIncrement { const double *u0, *v0, *a1u, *a1v, *a2u, *a2v; double dtv; };
+// What the caller of vertvisc_step_inc states about the KV_ML_INVZ2 viscosity profile of find_coupling_coef (:1873-1886), a function of
+// the thicknesses (h, or dz) and of constants, not of the velocities.  AS_NOW: nothing; the call forms the profile and parks it in a(K).
+// PRODUCE: the call forms it and keeps it in the context.  CONSUME: h and dz are the arrays of the last PRODUCE call and nothing has
+// written them since, so the call reads the profile kept there and does not run the top-down sweep.
+enum KvmlProfile { KVML_AS_NOW = 0, KVML_PRODUCE = 1, KVML_CONSUME = 2 };
 int vertvisc_step_inc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double *u, double *v, const double *h, const double *dz,
                       const double *taux, const double *tauy, const mom6hip_vertvisc_type_t *visc, double dt, int32_t update_velocities,
-                      double *taux_bot, double *tauy_bot, double *visc_rem_u, double *visc_rem_v, const VelIncrement *inc, int32_t memspace);
+                      double *taux_bot, double *tauy_bot, double *visc_rem_u, double *visc_rem_v, const VelIncrement *inc, int32_t memspace,
+                      KvmlProfile kvml = KVML_AS_NOW);
 // open boundaries (open_boundary.hip): the side maps of the zero-gradient projections, and the store of the specified segments' velocities
 class Stager;
 int obc_side_maps(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_obc_t *obc, const int32_t **side_u, const int32_t **side_v, const char *who);

@@ -56,6 +56,11 @@ int pass_start(mom6hip_ctx_t *ctx, std::initializer_list<std::pair<double *, int
   const bool now = blocking == 1 || (blocking > 1 && ((blocking >> 1) >> seam) & 1);
   return now ? m6::complete_group_pass(ctx) : 0;
 }
+// MOM6HIP_VV_KVML_ONCE=0 (read once): every vertvisc call of a step forms the KV_ML_INVZ2 profile itself (comparison runs, bisecting)
+bool kvml_once() {
+  static const bool on = !(getenv("MOM6HIP_VV_KVML_ONCE") && atoi(getenv("MOM6HIP_VV_KVML_ONCE")) == 0);
+  return on;
+}
 // Whether the rows of the tile are worth splitting around a pass in flight: the pass must leave the x halos final at its start
 // (the tile spans x) and the tile must be tall enough to have inner rows.
 bool split_rows(mom6hip_ctx_t *ctx) {
@@ -432,6 +437,8 @@ int mom6hip_step_dyn_split_rk2(mom6hip_ctx_t *ctx, mom6hip_dyn_split_rk2_cs_t *c
   const bool inviscid = (cs->hooks == nullptr) && (cs->hor_visc == nullptr);      // diffu = diffv = 0
   const bool vv_fused = VV && !(hk && (hk->visc_remnant_pred || hk->vertvisc));
   const bool need_up1 = (!inviscid || VV) && !vv_fused;
+  const bool kv_once = vv_fused && kvml_once();
+  const m6::KvmlProfile kv_first = kv_once ? m6::KVML_PRODUCE : m6::KVML_AS_NOW, kv_later = kv_once ? m6::KVML_CONSUME : m6::KVML_AS_NOW;
   mom6hip_ctx::BcAccelFuse fuse1{nullptr, nullptr, cs->diffu, cs->diffv, u_bc, v_bc, inviscid ? 1 : 0, false};
   static const bool fuse_off = getenv("MOM6HIP_BC_FUSE") && atoi(getenv("MOM6HIP_BC_FUSE")) == 0;
   const bool try_fuse1 = !need_up1 && !fuse_off;
@@ -486,8 +493,12 @@ int mom6hip_step_dyn_split_rk2(mom6hip_ctx_t *ctx, mom6hip_dyn_split_rk2_cs_t *c
                                   (double *)cs->visc->nkml_visc_u, (double *)cs->visc->nkml_visc_v, dt));
     }
     const m6::VelIncrement inc1{u_inst, v_inst, u_bc, v_bc, nullptr, nullptr, dt};      // up = mask * (u + dt * u_bc_accel) :582-589
+    // The KV_ML_INVZ2 profile (find_coupling_coef :1873-1886) is a function of the thicknesses and of constants.  The three calls of
+    // the step (here, :717 and :974 of the reference) all pass this h with no dz, and nothing writes h before the continuity of :1015,
+    // after the third: the profile is formed here and the other two calls read it (kv_first, kv_later).  A hook in place of any of
+    // the three calls (vv_fused) or MOM6HIP_VV_KVML_ONCE=0 leaves every call forming its own.
     CALL(m6::vertvisc_step_inc(ctx, VV, up, vp, h, nullptr, nullptr, nullptr, cs->visc, dt, 0, nullptr, nullptr, cs->visc_rem_u, cs->visc_rem_v,
-                               vv_fused ? &inc1 : nullptr, D));
+                               vv_fused ? &inc1 : nullptr, D, kv_first));
   }
   // pass_eta, pass_visc_rem :541 / :607-611 / :631: in flight behind btcalc and bt_mass_source, which read no halo (the reference
   // completes pass_visc_rem at :631 for the same reason: the continuity below forms fluxes in the rows of visc_rem's halo)
@@ -535,7 +546,7 @@ int mom6hip_step_dyn_split_rk2(mom6hip_ctx_t *ctx, mom6hip_dyn_split_rk2_cs_t *c
   } else if (VV) {            // :717-744, with the increment of :667-676 formed in the coefficient sweep
     const m6::VelIncrement inc2{u_inst, v_inst, u_bc, v_bc, cs->u_accel_bt, cs->v_accel_bt, dt_pred};
     CALL(m6::vertvisc_step_inc(ctx, VV, up, vp, h, nullptr, taux, tauy, cs->visc, dt_pred, 1, nullptr, nullptr, cs->visc_rem_u, cs->visc_rem_v,
-                               vv_fused ? &inc2 : nullptr, D));
+                               vv_fused ? &inc2 : nullptr, D, kv_later));
   }
   // pass_visc_rem, pass_uvp :741-751 in flight behind the continuity's own rows (continuity_around_pass)
   CALL(pass_start(ctx, {{cs->visc_rem_u, PUs}, {cs->visc_rem_v, PVs}, {up, PU}, {vp, PV}}, nz, 1));
@@ -598,7 +609,7 @@ int mom6hip_step_dyn_split_rk2(mom6hip_ctx_t *ctx, mom6hip_dyn_split_rk2_cs_t *c
   } else if (VV) {            // :974-994, with the increment of :930-939 formed in place in the coefficient sweep
     const m6::VelIncrement inc3{u_inst, v_inst, u_bc, v_bc, cs->u_accel_bt, cs->v_accel_bt, dt};
     CALL(m6::vertvisc_step_inc(ctx, VV, u_inst, v_inst, h, nullptr, taux, tauy, cs->visc, dt, 1, nullptr, nullptr, cs->visc_rem_u, cs->visc_rem_v,
-                               vv_fused ? &inc3 : nullptr, D));
+                               vv_fused ? &inc3 : nullptr, D, kv_later));
   }
   launch3d(s, is - 2, ie + 2, js - 2, je + 2, nz, [=] __device__(int i, int j, int k) { h_av[g.h3(i, j, k)] = h[g.h3(i, j, k)]; });   // :1000
   CALL(pass_start(ctx, {{cs->visc_rem_u, PUs}, {cs->visc_rem_v, PVs}, {u_inst, PU}, {v_inst, PV}}, nz, 3));     // :991-1008
@@ -746,9 +757,14 @@ int mom6hip_step_dyn_split_rk2b(mom6hip_ctx_t *ctx, mom6hip_dyn_split_rk2_cs_t *
   auto btcalc = [&](const double *hu, const double *hv) -> int {
     return OBC ? mom6hip_btcalc_obc(ctx, BT, h, hu, hv, 0, OBC, D) : mom6hip_btcalc(ctx, BT, h, hu, hv, 0, D);
   };
+  // The KV_ML_INVZ2 profile is formed by the first of the step's three calls (:604, :724, :946) and read by the other two, as in
+  // step_MOM_dyn_split_RK2 above: all three pass this h with no dz, and h is first written by the continuity of :979.  Not with a hook
+  // in place of one of the calls, nor through the separate entries an OBC takes.
+  const bool kv_once = VV && !OBC && !(hk && (hk->visc_remnant_pred || hk->vertvisc)) && kvml_once();
   auto vertvisc_step = [&](double *uu, double *vv, double dtx, int update) -> int {
-    if (!OBC) return mom6hip_vertvisc_step(ctx, VV, uu, vv, h, nullptr, update ? taux : nullptr, update ? tauy : nullptr, cs->visc, dtx, update, nullptr,
-                                           nullptr, cs->visc_rem_u, cs->visc_rem_v, D);
+    if (!OBC) return m6::vertvisc_step_inc(ctx, VV, uu, vv, h, nullptr, update ? taux : nullptr, update ? tauy : nullptr, cs->visc, dtx, update, nullptr,
+                                           nullptr, cs->visc_rem_u, cs->visc_rem_v, nullptr, D,
+                                           !kv_once ? m6::KVML_AS_NOW : (update ? m6::KVML_CONSUME : m6::KVML_PRODUCE));      // (the first call is the one without an update)
     CALL(mom6hip_vertvisc_coef_obc(ctx, VV, uu, vv, h, nullptr, cs->visc, dtx, OBC, D));
     if (update) CALL(mom6hip_vertvisc_obc(ctx, VV, uu, vv, h, taux, tauy, cs->visc, dtx, nullptr, nullptr, OBC, D));
     return mom6hip_vertvisc_remnant(ctx, VV, cs->visc, cs->visc_rem_u, cs->visc_rem_v, dtx, D);

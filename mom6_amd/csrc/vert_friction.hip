@@ -14,6 +14,8 @@
 // Algorithmic traffic per cell: coef 8 (h) + 4 (vel) + 16 (a, h_vel) [B, both directions: x2 on vel/a/h_vel];
 // solve: read a, h_vel, x, write x, c1, read both again, write x.
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 
 #include "common.hpp"
 
@@ -49,6 +51,13 @@ struct CoefArgs {
   // open boundaries (the OBC instantiation only): per face, the cell the thicknesses, the depth, Kv_shear and ustar are projected
   // outward from, -1 the first (OBC_DIRECTION_E | N), +1 the second (W | S), 0 not on a segment (m6::obc_side_maps)
   const int32_t *side;
+  // the KV_ML_INVZ2 profile of :1873-1886 kept apart from a(K), for a caller that knows h (or dz) stays as it is between calls
+  // (m6::KvmlProfile).  Both null: the top-down sweep parks the profile in a(K), as the reference does.  kvml_dst: the sweep stores it
+  // there instead and the bottom-up sweep reads it from there.  kvml_src: no top-down sweep, the bottom-up sweep reads what an earlier
+  // call stored.  Which of the three is a template parameter of coef_column (KV), so that each form keeps the registers of the one sweep it
+  // runs: as a run-time choice the two extra pointers pushed the fused kernel over its scalar registers and into scratch.
+  const double *kvml_src;
+  double *kvml_dst;
 };
 
 // the velocity of layer k of the face column at f2: read, or formed from the step's increment (the reference's expression)
@@ -59,7 +68,8 @@ __device__ __forceinline__ double coef_vel(const CoefArgs &A, long n, double mas
 }
 
 // vertvisc_coef + find_coupling_coef for the face column (i, j); the caller has checked do_i
-template <int DIR, bool OBC = false>
+enum { KV_PARK = 0, KV_PRODUCE = 1, KV_CONSUME = 2 };      // where the KV_ML_INVZ2 profile goes: a(K) | kvml_dst | read from kvml_src
+template <int DIR, bool OBC = false, int KV = KV_PARK>
 __device__ __forceinline__ void coef_column(const CoefArgs &A, int i, int j) {
   const m6::GridDev &g = A.g;
   const VVPar &P = A.p;
@@ -82,9 +92,11 @@ __device__ __forceinline__ void coef_column(const CoefArgs &A, int i, int j) {
   auto DZ = [&](long c, int k) { return A.dz ? A.dz[c + hpl * k] : g.H_to_Z * A.h[c + hpl * k]; };
   const int side = OBC ? A.side[f2] : 0;      // :1335-1355 / :1546-1566 (zi_dir)
 
-  // ---- KV_ML_INVZ2: the top-down viscosity profile :1873-1886, parked in a(K) ----
+  // ---- KV_ML_INVZ2: the top-down viscosity profile :1873-1886, parked in a(K) (or in kvml_dst; not formed at all with kvml_src) ----
   const bool kvml = P.Kvml_invZ2 > 0.0;
-  if (kvml) {
+  double *const kv_w = (KV == KV_PRODUCE) ? A.kvml_dst : A.a;
+  const double *const kv_r = (KV == KV_CONSUME) ? A.kvml_src : kv_w;
+  if (kvml && KV != KV_CONSUME) {
     const double I_Hmix = 1.0 / (P.Hmix + hn);
     double z_t = hn * I_Hmix;
     for (int Kb = 1; Kb < nz; Kb += VB) {
@@ -103,7 +115,7 @@ __device__ __forceinline__ void coef_column(const CoefArgs &A, int i, int j) {
         double dz_harm = 2.0 * d0 * d1 / (d0 + d1 + dz_neglect);
         if (OBC && side) dz_harm = (side < 0) ? d0 : d1;
         z_t = z_t + dz_harm * I_Hmix;
-        A.a[f2 + fpl * K] = P.Kv + P.Kvml_invZ2 / ((z_t * z_t) * (1.0 + 0.09 * z_t * z_t * z_t * z_t * z_t * z_t));
+        kv_w[f2 + fpl * K] = P.Kv + P.Kvml_invZ2 / ((z_t * z_t) * (1.0 + 0.09 * z_t * z_t * z_t * z_t * z_t * z_t));
       }
     }
   }
@@ -127,7 +139,7 @@ __device__ __forceinline__ void coef_column(const CoefArgs &A, int i, int j) {
         if (A.dz) { b_d0[q] = A.dz[c0 + hpl * k]; b_d1[q] = A.dz[c1 + hpl * k]; }
         b_vel[q] = coef_vel(A, f2 + fpl * k, fmask);
         if (k + 1 < nz) {
-          if (kvml) b_kvml[q] = A.a[f2 + fpl * (k + 1)];
+          if (kvml) b_kvml[q] = kv_r[f2 + fpl * (k + 1)];
           if (A.Kv_shear) {
             b_ksh[q] = 0.5 * (A.Kv_shear[c0 + hpl * (k + 1)] + A.Kv_shear[c1 + hpl * (k + 1)]);
             if (OBC && side) b_ksh[q] = A.Kv_shear[((side < 0) ? c0 : c1) + hpl * (k + 1)];      // :1901-1909, :1917-1925
@@ -439,9 +451,9 @@ __global__ __launch_bounds__(64) void vv_solve_kernel(SolveArgs A) {
 // vertvisc_coef followed by the solve(s) of the same column: the coupling coefficients and thicknesses the bottom-up sweep
 // has just stored are read back by the same lane while they are still in L2, instead of by a second kernel from HBM.
 #ifndef VV_OCC
-#define VV_OCC 4      // waves per SIMD the register allocation aims at (121 VGPRs: 4; tools/build_variant.sh for experiments)
+#define VV_OCC 4      // waves per SIMD the register allocation aims at (at most 128 VGPRs: 4; tools/build_variant.sh for experiments)
 #endif
-template <int DIR>
+template <int DIR, int KV>
 __global__ __launch_bounds__(64, VV_OCC) void vv_coef_solve_kernel(CoefArgs C, SolveArgs A) {
   const m6::GridDev &g = A.g;
   const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 64 + threadIdx.x;
@@ -449,7 +461,7 @@ __global__ __launch_bounds__(64, VV_OCC) void vv_coef_solve_kernel(CoefArgs C, S
   if (i > g.iec) return;
   const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
   const double mask = DIR ? g.mask2dCv[f2] : g.mask2dCu[f2];
-  if (mask > 0.0) coef_column<DIR>(C, i, j);
+  if (mask > 0.0) coef_column<DIR, false, KV>(C, i, j);
   else if (C.f_u0 && C.f_store) {      // a masked column: the increment alone (0 * (...)), as the step's sweep would have left it
     const long fpl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
     for (int k = 0; k < g.nk; k++) C.f_store[f2 + fpl * k] = coef_vel(C, f2 + fpl * k, mask);
@@ -584,6 +596,7 @@ extern "C" int mom6hip_vertvisc_coef_obc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs
   for (int d = 0; d < 2; d++) {
     A[d].ustar = A[d].nkml_visc = nullptr; A[d].dzv = nullptr;
     A[d].f_u0 = A[d].f_a1 = A[d].f_a2 = nullptr; A[d].f_dt = 0.0; A[d].f_store = nullptr;
+    A[d].kvml_src = nullptr; A[d].kvml_dst = nullptr;
   }
   if (surface_bl) {
     const double *dus = st.in(visc->ustar, sz.h2);
@@ -718,17 +731,20 @@ extern "C" int mom6hip_vertvisc_step(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *
                                      const double *dz, const double *taux, const double *tauy, const mom6hip_vertvisc_type_t *visc,
                                      double dt, int32_t update_velocities, double *taux_bot, double *tauy_bot, double *visc_rem_u,
                                      double *visc_rem_v, int32_t memspace) {
+  // (KVML_AS_NOW: a caller from outside cannot promise that h stays as it is between two calls)
   return m6::vertvisc_step_inc(ctx, cs, u, v, h, dz, taux, tauy, visc, dt, update_velocities, taux_bot, tauy_bot, visc_rem_u, visc_rem_v,
-                               nullptr, memspace);
+                               nullptr, memspace, m6::KVML_AS_NOW);
 }
 
 // mom6hip_vertvisc_step with the velocities given as the increment of the RK2 step (inc, device pointers; null: u and v as they
 // are).  With update_velocities the incremented velocities are what u and v hold on entry of the reference's vertvisc_coef, so
 // they are stored to u and v before the solve reads them; without it they are only used.  u, v may be the increment's own u0, v0.
+// kvml: what the caller states about the KV_ML_INVZ2 profile (m6::KvmlProfile, common.hpp).  It only acts in the one-kernel form on device
+// arrays with KV_ML_INVZ2 > 0; everywhere else every call forms the profile itself, which is always right.
 int m6::vertvisc_step_inc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double *u, double *v, const double *h, const double *dz,
                           const double *taux, const double *tauy, const mom6hip_vertvisc_type_t *visc, double dt, int32_t update_velocities,
                           double *taux_bot, double *tauy_bot, double *visc_rem_u, double *visc_rem_v, const m6::VelIncrement *inc,
-                          int32_t memspace) {
+                          int32_t memspace, m6::KvmlProfile kvml) {
   M6_REQUIRE(ctx != nullptr, "MOM_vert_friction(visc): Module must be initialized before it is used.");
   M6_REQUIRE(cs && u && v && h && visc && visc_rem_u && visc_rem_v, "vertvisc_step: null argument");
   M6_REQUIRE(!update_velocities || (taux && tauy), "vertvisc_step: the wind stress is needed to update the velocities");
@@ -781,11 +797,28 @@ int m6::vertvisc_step_inc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double 
     }
     cnt = (unsigned long long *)ctx->vv_ntrunc.p;
   }
+  // the KV_ML_INVZ2 profile kept from one call of a step to the next: two interface-sized arrays of the context, reserved the first time
+  // a caller produces (never without KV_ML_INVZ2).  Not a cache: nothing is looked up, the caller states what it knows; that the
+  // thicknesses are the array the profile was formed from is checked all the same.
+  if (!(cs->Kvml_invZ2 > 0.0) || memspace != MOM6HIP_MEM_DEVICE) kvml = m6::KVML_AS_NOW;
+  if (kvml == m6::KVML_PRODUCE) {
+    // MOM6HIP_VV_KVML_REPORT=1: a line on stderr whenever the two arrays are reserved or grow (tests: never without KV_ML_INVZ2)
+    static const bool report = getenv("MOM6HIP_VV_KVML_REPORT") && atoi(getenv("MOM6HIP_VV_KVML_REPORT")) == 1;
+    if (report && (ctx->vv_kvml[0].bytes < sz.ui || ctx->vv_kvml[1].bytes < sz.vi))
+      fprintf(stderr, "mom6hip: KV_ML_INVZ2 profile arrays reserved: %zu + %zu bytes\n", sz.ui, sz.vi);
+    M6_REQUIRE(ctx->vv_kvml[0].reserve(sz.ui) == 0 && ctx->vv_kvml[1].reserve(sz.vi) == 0, "vertvisc_step: out of device memory");
+    ctx->vv_kvml_h = ddz ? ddz : dh;
+  } else if (kvml == m6::KVML_CONSUME) {
+    M6_REQUIRE(ctx->vv_kvml[0].p && ctx->vv_kvml[1].p && ctx->vv_kvml[0].bytes >= sz.ui && ctx->vv_kvml[1].bytes >= sz.vi &&
+               ctx->vv_kvml_h == (ddz ? ddz : dh), "vertvisc_step: no KV_ML_INVZ2 profile of these thicknesses has been produced");
+  }
   for (int d = 0; d < 2; d++) {
     CoefArgs C;
     C.g = g; C.p = par_of(cs); C.vel = x[d]; C.h = dh; C.dz = ddz; C.kv_bbl = kvb[d]; C.bbl_thick = bth[d]; C.Kv_shear = dks;
     C.a = a[d]; C.hv = hv[d]; C.ustar = C.nkml_visc = nullptr; C.dzv = nullptr;
     C.f_u0 = C.f_a1 = C.f_a2 = nullptr; C.f_dt = 0.0; C.f_store = nullptr; C.side = nullptr;
+    C.kvml_src = (kvml == m6::KVML_CONSUME) ? (const double *)ctx->vv_kvml[d].p : nullptr;
+    C.kvml_dst = (kvml == m6::KVML_PRODUCE) ? (double *)ctx->vv_kvml[d].p : nullptr;
     if (inc) {
       C.f_u0 = d ? inc->v0 : inc->u0; C.f_a1 = d ? inc->a1v : inc->a1u; C.f_a2 = d ? inc->a2v : inc->a2u; C.f_dt = inc->dtv;
       C.f_store = update_velocities ? x[d] : nullptr;
@@ -797,8 +830,10 @@ int m6::vertvisc_step_inc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double 
     // MOM6HIP_VV_LDS_BYTES: unused dynamic LDS per block, an occupancy throttle for experiments (a column's intermediates stay in
     // the memory-side cache only while few enough waves are in flight); 0 = none
     static const int lds_throttle = [] { const char *e = getenv("MOM6HIP_VV_LDS_BYTES"); return e ? atoi(e) : 0; }();
-    if (d == 0) hipLaunchKernelGGL(vv_coef_solve_kernel<0>, grid, dim3(64), lds_throttle, ctx->stream, C, A);
-    else hipLaunchKernelGGL(vv_coef_solve_kernel<1>, grid, dim3(64), lds_throttle, ctx->stream, C, A);
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds_throttle, ctx->stream, C, A); };
+    if (kvml == m6::KVML_PRODUCE) { if (d == 0) launch(vv_coef_solve_kernel<0, KV_PRODUCE>); else launch(vv_coef_solve_kernel<1, KV_PRODUCE>); }
+    else if (kvml == m6::KVML_CONSUME) { if (d == 0) launch(vv_coef_solve_kernel<0, KV_CONSUME>); else launch(vv_coef_solve_kernel<1, KV_CONSUME>); }
+    else { if (d == 0) launch(vv_coef_solve_kernel<0, KV_PARK>); else launch(vv_coef_solve_kernel<1, KV_PARK>); }
   }
   M6_HIP(hipGetLastError());
   const int rc = st.finish();
