@@ -221,8 +221,6 @@ struct FluxArgs {
   const int32_t *fa_code;                // faces of the open segments of this direction over their whole range (:782-805, :1058-1088):
                                          // 1 interior = minus-side cell, 2 interior = plus-side cell (the last segment wins)
   const struct SegDev *segs;             // the segments (device table)
-  int xcd_w, nbx;                        // block-cooperative kernels, meridional: blocks dealt to the 8 XCDs in strips of xcd_w block columns
-                                         // (0: the launch order), of nbx real block columns (xcd_block below)
   const int32_t *skip;                   // block-cooperative kernels: faces they leave alone (null: none) -- the strips around the open
                                          // segments, which the lane kernel forms with the OBC (continuity_PPM below)
 };
@@ -314,6 +312,64 @@ __device__ __forceinline__ double ratio_max(double a, double b, double maxrat) {
   return a / b;
 }
 
+// One iteration of flux_adjust's scalar logic for a face (:1120-1190): the bracket takes du on the side the error lies, then either
+// the face has converged (do_I = false) or du takes a Newton step, halved into the bracket where it would leave it.  Returns whether
+// the transports are to be evaluated again at the new du.  The one copy of this text: the lane kernel and both block-cooperative
+// kernels call it (those keep the bracket in LDS and load / store it around the call).
+__device__ __forceinline__ bool adjust_step(const ContOpts &o, double dt, int itt, double uh_err, double duhdu_tot, double uh_err_best,
+                                            double IaT, double &du, double &du_max, double &du_min, bool &do_I) {
+  double tol_eta;
+  if (itt <= 1) tol_eta = 1e-6 * o.tol_eta;
+  else if (itt == 2) tol_eta = 1e-4 * o.tol_eta;
+  else if (itt == 3) tol_eta = 1e-2 * o.tol_eta;
+  else tol_eta = o.tol_eta;
+  const double tol_vel = o.tol_vel;
+  if (uh_err > 0.0) du_max = du;
+  else if (uh_err < 0.0) du_min = du;
+  else do_I = false;
+  bool domore = false;
+  if (do_I) {
+    if ((dt * IaT * fabs(uh_err) > tol_eta) ||
+        (o.better_iter && ((fabs(uh_err) > tol_vel * duhdu_tot) || (fabs(uh_err) > uh_err_best)))) {
+      const double ddu = -uh_err / duhdu_tot;
+      const double du_prev = du;
+      du = du + ddu;
+      if (fabs(ddu) < 1.0e-15 * fabs(du)) {
+        do_I = false;
+      } else if (ddu > 0.0) {
+        if (du >= du_max) {
+          du = 0.5 * (du_prev + du_max);
+          if (du_max - du_prev < 1.0e-15 * fabs(du)) do_I = false;
+        }
+      } else {
+        if (du <= du_min) {
+          du = 0.5 * (du_prev + du_min);
+          if (du_prev - du_min < 1.0e-15 * fabs(du)) do_I = false;
+        }
+      }
+      if (do_I) domore = true;
+    } else {
+      do_I = false;
+    }
+  }
+  return domore;
+}
+
+// The BT_cont fit of one side of a face, the end of set_zonal_BT_cont (:1375-1398): from the marginal areas at du0 and at the side's
+// velocity change (FAmt_0, FAmt_x), the transport there (uhtot_x) and ddu = dux - du0, the face area at du0 (FA_0), the one at the
+// changed velocity (FA_xx) and the velocity at which the area becomes FA_xx (uBT_xx).  (The reference writes the last test of the
+// plus side as |FAmt_R - FA_0|: the same bits.)
+__device__ __forceinline__ void bt_cont_fit(double FAmt_0, double FAmt_x, double uhtot_x, double ddu, double &FA_0_out, double &FA_xx,
+                                            double &uBT_xx) {
+  double FA_0 = FAmt_0, FA_avg = FAmt_0;
+  if (ddu != 0.0) FA_avg = uhtot_x / ddu;
+  if (FA_avg > max2(FA_0, FAmt_x)) FA_avg = max2(FA_0, FAmt_x);
+  else if (FA_avg < min2(FA_0, FAmt_x)) FA_0 = FA_avg;
+  FA_0_out = FA_0; FA_xx = FAmt_x;
+  if (fabs(FA_0 - FAmt_x) <= 1e-12 * FA_0) uBT_xx = 0.0;
+  else uBT_xx = (1.5 * ddu) * ((FAmt_x - FA_avg) / (FAmt_x - FA_0));
+}
+
 // flux_adjust :1094-1243 for this lane's face column.  If write_uh, the re-evaluated layer transports
 // are stored to p.uh (the reference's uh_3d argument).
 template <int DIR>
@@ -328,41 +384,7 @@ __device__ double flux_adjust(const FluxArgs &p, const Dir<DIR> &D, long o3_0, l
   bool do_I = true;
   const double IaT = min2(g.IareaT[o2], g.IareaT[o2 + D.sa()]);
   for (int itt = 1; itt <= max_itts; itt++) {
-    double tol_eta;
-    if (itt <= 1) tol_eta = 1e-6 * p.o.tol_eta;
-    else if (itt == 2) tol_eta = 1e-4 * p.o.tol_eta;
-    else if (itt == 3) tol_eta = 1e-2 * p.o.tol_eta;
-    else tol_eta = p.o.tol_eta;
-    const double tol_vel = p.o.tol_vel;
-    if (uh_err > 0.0) du_max = du;
-    else if (uh_err < 0.0) du_min = du;
-    else do_I = false;
-    bool domore = false;
-    if (do_I) {
-      if ((p.dt * IaT * fabs(uh_err) > tol_eta) ||
-          (p.o.better_iter && ((fabs(uh_err) > tol_vel * duhdu_tot) || (fabs(uh_err) > uh_err_best)))) {
-        const double ddu = -uh_err / duhdu_tot;
-        const double du_prev = du;
-        du = du + ddu;
-        if (fabs(ddu) < 1.0e-15 * fabs(du)) {
-          do_I = false;
-        } else if (ddu > 0.0) {
-          if (du >= du_max) {
-            du = 0.5 * (du_prev + du_max);
-            if (du_max - du_prev < 1.0e-15 * fabs(du)) do_I = false;
-          }
-        } else {
-          if (du <= du_min) {
-            du = 0.5 * (du_prev + du_min);
-            if (du_prev - du_min < 1.0e-15 * fabs(du)) do_I = false;
-          }
-        }
-        if (do_I) domore = true;
-      } else {
-        do_I = false;
-      }
-    }
-    if (!domore) break;
+    if (!adjust_step(p.o, p.dt, itt, uh_err, duhdu_tot, uh_err_best, IaT, du, du_max, du_min, do_I)) break;
     if ((itt < max_itts) || write_uh) {
       double usum = -uhbt, dsum = 0.0;
       for (int k = 0; k < nz; k++) {
@@ -515,22 +537,8 @@ __global__ __launch_bounds__(64) void cont_flux_kernel(FluxArgs p) {
       if (cor) { uc = uk + du * vr; p.u_cor[f3_0 + k * fpl] = uc; }
       if (p.h_face) p.h_face[f3_0 + k * fpl] = flux_thickness_layer<DIR>(p, D, uc, o3_0 + k * hpl, o2, f2, vr);
     }
-    double FA_0 = FAmt_0, FA_avg = FAmt_0;
-    if ((duL - du0) != 0.0) FA_avg = uhtot_L / (duL - du0);
-    if (FA_avg > max2(FA_0, FAmt_L)) FA_avg = max2(FA_0, FAmt_L);
-    else if (FA_avg < min2(FA_0, FAmt_L)) FA_0 = FA_avg;
-    p.FA_0m[f2] = FA_0; p.FA_mm[f2] = FAmt_L;
-    if (fabs(FA_0 - FAmt_L) <= 1e-12 * FA_0) p.uBT_mm[f2] = 0.0;
-    else p.uBT_mm[f2] = (1.5 * (duL - du0)) * ((FAmt_L - FA_avg) / (FAmt_L - FA_0));
-
-    FA_0 = FAmt_0; FA_avg = FAmt_0;
-    if ((duR - du0) != 0.0) FA_avg = uhtot_R / (duR - du0);
-    if (FA_avg > max2(FA_0, FAmt_R)) FA_avg = max2(FA_0, FAmt_R);
-    else if (FA_avg < min2(FA_0, FAmt_R)) FA_0 = FA_avg;
-    p.FA_0p[f2] = FA_0; p.FA_pp[f2] = FAmt_R;
-    if (fabs(FAmt_R - FA_0) <= 1e-12 * FA_0) p.uBT_pp[f2] = 0.0;
-    else p.uBT_pp[f2] = (1.5 * (duR - du0)) * ((FAmt_R - FA_avg) / (FAmt_R - FA_0));
-
+    bt_cont_fit(FAmt_0, FAmt_L, uhtot_L, duL - du0, p.FA_0m[f2], p.FA_mm[f2], p.uBT_mm[f2]);
+    bt_cont_fit(FAmt_0, FAmt_R, uhtot_R, duR - du0, p.FA_0p[f2], p.FA_pp[f2], p.uBT_pp[f2]);
   }
   // the faces of open segments: the face areas and thicknesses of the interior cell (:782-805 / :1058-1088, after every row in the
   // reference: the last word on these faces)
@@ -544,20 +552,6 @@ __global__ __launch_bounds__(64) void cont_flux_kernel(FluxArgs p) {
       for (int k = 0; k < nz; k++)
         p.h_face[f3_0 + k * fpl] = p.visc_rem ? p.h_in[oi + k * hpl] * (p.visc_rem[f3_0 + k * fpl] * 1.0) : p.h_in[oi + k * hpl] * 1.0;
   }
-}
-
-// The block a workgroup works on.  Workgroups are dealt round-robin to the 8 XCDs in launch order (x fastest), each XCD with an L2 of its
-// own; a meridional block reads six rows of h of which the block of the next row reads five again.  With xcd_w > 0 the launch has 8 * xcd_w
-// block columns and the workgroups of one XCD (launch index mod 8) walk a strip of xcd_w adjacent real columns row by row, so a row's
-// re-reads hit that XCD's L2 instead of arriving once per XCD.  Placement only: any mapping gives the same results.  Returns false for
-// the workgroups beyond the last real column (they leave before any barrier).
-__device__ __forceinline__ bool xcd_block(int xcd_w, int nbx, int &bx, int &by) {
-  bx = blockIdx.x; by = blockIdx.y;
-  if (xcd_w <= 0) return true;
-  const unsigned L = blockIdx.x + gridDim.x * blockIdx.y;
-  const unsigned xcd = L & 7u, slot = L >> 3;
-  bx = (int)(xcd * xcd_w + slot % xcd_w); by = (int)(slot / xcd_w);
-  return bx < nbx;
 }
 
 // ---- mass fluxes, block-cooperative form -----------------------------------------------------------
@@ -574,15 +568,16 @@ __device__ __forceinline__ bool xcd_block(int xcd_w, int nbx, int &bx, int &by) 
 // whose state runs through k (the CFL brackets :663-716 and the duL/duR limits of set_*_BT_cont) are serial chains
 // walked by one (half-)wave; the divisions of the bracket chain do not depend on the running state and are formed by all
 // threads beforehand.
-#ifndef FC_NW_DEF
-#define FC_NW_DEF 4
-#endif
-constexpr int FC_NW = FC_NW_DEF;      // waves per block (experiments: -DFC_NW_DEF=2 -DFC_OCC=2: 20 layers a thread, one wave a SIMD)
+constexpr int FC_NW = 4;      // waves per block
 constexpr int FC_KSMAX = 80 / (2 * FC_NW);      // layers per thread of the largest instance
 constexpr int FC_FL = 32;     // face columns per block: a wave is two half-waves of 32 faces holding different layers
 constexpr int FC_NS = 2 * FC_NW;      // layer slabs per block (one per half-wave)
 
 struct FaceConst { double dLf, cm, cp, dt; };
+
+// LDS of cont_flux_coop_kernel<DIR, KS> (its layout is at the head of the kernel)
+template <int KS>
+constexpr size_t fc_lds_bytes() { return ((size_t)3 * KS * FC_NS * FC_FL + 8 * FC_FL + FC_NS * FC_FL + 15 * FC_FL + 4 * FC_NS * FC_FL) * sizeof(double); }
 
 // Marks a register value as redefined here, so that products of it are formed where the reference forms them (inside
 // the pass) instead of being hoisted out of the Newton loop and held in registers for every layer.
@@ -604,6 +599,20 @@ __device__ __forceinline__ double flux_reg(const FaceConst &F, double u, double 
   return uh;
 }
 
+// flux_thickness :976-1057 from the same register set
+__device__ __forceinline__ double thick_reg(const FaceConst &F, int marginal, bool have_vr, double uc, double vr, double mE, double mD,
+                                            double mC, double pW, double pD, double pC) {
+  const bool pos = uc > 0.0;
+  const double E = pos ? mE : pW, Dd = pos ? mD : pD, Cc = pos ? mC : pC, cf = pos ? F.cm : F.cp;
+  const double CFL = (fabs(uc) * F.dt) * cf;
+  double h_avg = E + CFL * (0.5 * Dd + Cc * (CFL - 1.5));
+  double h_marg = E + CFL * (Dd + 3.0 * Cc * (CFL - 1.0));
+  if (uc == 0.0) { h_avg = 0.5 * (pW + mE); h_marg = 0.5 * (pW + mE); }
+  double hu = marginal ? h_marg : h_avg;
+  if (have_vr) hu = hu * (vr * 1.0); else hu = hu * 1.0;
+  return hu;
+}
+
 // The k-ordered sums of the layer values the waves left in the LDS planes 0 .. nsum-1, each started from its init value:
 // half-wave q < nsum adds plane q; every thread gets all results.
 __device__ __forceinline__ void ksums(double *fsm, int plane, int roff, int fl, int sb, int nz, int nsum, double i0, double i1,
@@ -612,6 +621,7 @@ __device__ __forceinline__ void ksums(double *fsm, int plane, int roff, int fl, 
   if (sb < nsum) {
     double acc = (sb == 0) ? i0 : ((sb == 1) ? i1 : i2);
     const int base = sb * plane + fl;
+#pragma unroll 8
     for (int k = 0; k < nz; k++) acc = acc + fsm[base + k * FC_FL];
     fsm[roff + sb * FC_FL + fl] = acc;
   }
@@ -632,10 +642,7 @@ __device__ unsigned long long fc_trace[128];      // [direction][slot]
 #endif
 
 template <int DIR, int KS>
-#ifndef FC_OCC
-#define FC_OCC 2      // blocks per CU the register budget is set for (experiments: tools/build_variant.sh ... -DFC_OCC=1)
-#endif
-__global__ __launch_bounds__(64 * FC_NW, FC_OCC) void cont_flux_coop_kernel(FluxArgs p) {
+__global__ __launch_bounds__(64 * FC_NW, 2) void cont_flux_coop_kernel(FluxArgs p) {
 #ifdef FC_TRACE
   unsigned long long fc_t0 = __builtin_readcyclecounter();
   if (threadIdx.x == 0) atomicAdd(&fc_trace[64 * DIR + 15], 1ull);
@@ -647,8 +654,7 @@ __global__ __launch_bounds__(64 * FC_NW, FC_OCC) void cont_flux_coop_kernel(Flux
   const int fl = lane & (FC_FL - 1), sb = 2 * w + (lane >> 5);      // face within the block; layer slab of this half-wave
   const int nz = g.nk;
   constexpr int FPB = (DIR == 0) ? FC_FL - 1 : FC_FL;      // faces per block
-  int bx, by;
-  if (!xcd_block(p.xcd_w, p.nbx, bx, by)) return;
+  const int bx = blockIdx.x, by = blockIdx.y;
   const int fi_raw = p.fi0 + bx * FPB + fl;
   const bool valid = fl < FPB && fi_raw <= p.fi1 && !(p.skip && p.skip[D.f2(min(fi_raw, p.fi1), p.fj0 + by)]);
   // lanes past the row (and the last lane of a zonal half-wave) do everything but store, so barriers stay uniform; they sit
@@ -814,14 +820,7 @@ __global__ __launch_bounds__(64 * FC_NW, FC_OCC) void cont_flux_coop_kernel(Flux
         double uc = uk;
         if (cor_d) { uc = uk + du_dead * vr; if (valid) p.u_cor[f3] = uc; }
         if (p.h_face) {      // flux_thickness :976-1057 at uc = 0 (or whatever u + 0*visc_rem is)
-          const bool pos = uc > 0.0;
-          const double E = pos ? mE[m] : pW[m], Dd = pos ? mD[m] : pD[m], Cc = pos ? mC[m] : pC[m], cf = pos ? F0.cm : F0.cp;
-          const double CFL = (fabs(uc) * p.dt) * cf;
-          double h_avg = E + CFL * (0.5 * Dd + Cc * (CFL - 1.5));
-          double h_marg = E + CFL * (Dd + 3.0 * Cc * (CFL - 1.0));
-          if (uc == 0.0) { h_avg = 0.5 * (pW[m] + mE[m]); h_marg = 0.5 * (pW[m] + mE[m]); }
-          double hu = p.o.marginal_faces ? h_marg : h_avg;
-          if (p.visc_rem) hu = hu * (vr * 1.0); else hu = hu * 1.0;
+          const double hu = thick_reg(F0, p.o.marginal_faces, p.visc_rem != nullptr, uc, vr, mE[m], mD[m], mC[m], pW[m], pD[m], pC[m]);
           if (valid) p.h_face[f3] = hu;
         }
       }
@@ -953,44 +952,12 @@ __global__ __launch_bounds__(64 * FC_NW, FC_OCC) void cont_flux_coop_kernel(Flux
 #endif
 #pragma unroll 1
     for (int itt = 1; itt <= max_itts; itt++) {
-      bool domore = false;
-      if (alive) {
-        double tol_eta;
-        if (itt <= 1) tol_eta = 1e-6 * p.o.tol_eta;
-        else if (itt == 2) tol_eta = 1e-4 * p.o.tol_eta;
-        else if (itt == 3) tol_eta = 1e-2 * p.o.tol_eta;
-        else tol_eta = p.o.tol_eta;
-        const double tol_vel = p.o.tol_vel;
+      if (alive) {      // (the bracket lives in LDS: its copy takes du on the side of the error, as adjust_step's does)
         double du_max = fsm[pv], du_min = fsm[pv + PVS];
         const double uh_err_best = fsm[pv + 2 * PVS], IaT = fsm[PK_IAT + fl];
-        if (uh_err > 0.0) { du_max = du; fsm[pv] = du; }
-        else if (uh_err < 0.0) { du_min = du; fsm[pv + PVS] = du; }
-        else do_I = false;
-        if (do_I) {
-          if ((p.dt * IaT * fabs(uh_err) > tol_eta) ||
-              (p.o.better_iter && ((fabs(uh_err) > tol_vel * duhdu_tot) || (fabs(uh_err) > uh_err_best)))) {
-            const double ddu = -uh_err / duhdu_tot;
-            const double du_prev = du;
-            du = du + ddu;
-            if (fabs(ddu) < 1.0e-15 * fabs(du)) {
-              do_I = false;
-            } else if (ddu > 0.0) {
-              if (du >= du_max) {
-                du = 0.5 * (du_prev + du_max);
-                if (du_max - du_prev < 1.0e-15 * fabs(du)) do_I = false;
-              }
-            } else {
-              if (du <= du_min) {
-                du = 0.5 * (du_prev + du_min);
-                if (du_prev - du_min < 1.0e-15 * fabs(du)) do_I = false;
-              }
-            }
-            if (do_I) domore = true;
-          } else {
-            do_I = false;
-          }
-        }
-        if (!domore) alive = false;
+        if (uh_err > 0.0) fsm[pv] = du;
+        else if (uh_err < 0.0) fsm[pv + PVS] = du;
+        alive = adjust_step(p.o, p.dt, itt, uh_err, duhdu_tot, uh_err_best, IaT, du, du_max, du_min, do_I);
       }
       if (!__any(alive)) break;      // the same in every wave of the block: they hold the same values
       if ((itt < max_itts) || write_uh) {
@@ -1110,14 +1077,7 @@ __global__ __launch_bounds__(64 * FC_NW, FC_OCC) void cont_flux_coop_kernel(Flux
       double uc = uk;
       if (cor) { uc = uk + du * vr; if (valid) p.u_cor[f3] = uc; }
       if (p.h_face) {
-        const bool pos = uc > 0.0;
-        const double E = pos ? mE[m] : pW[m], Dd = pos ? mD[m] : pD[m], Cc = pos ? mC[m] : pC[m], cf = pos ? F.cm : F.cp;
-        const double CFL = (fabs(uc) * p.dt) * cf;
-        double h_avg = E + CFL * (0.5 * Dd + Cc * (CFL - 1.5));
-        double h_marg = E + CFL * (Dd + 3.0 * Cc * (CFL - 1.0));
-        if (uc == 0.0) { h_avg = 0.5 * (pW[m] + mE[m]); h_marg = 0.5 * (pW[m] + mE[m]); }
-        double hu = p.o.marginal_faces ? h_marg : h_avg;
-        if (p.visc_rem) hu = hu * (vr * 1.0); else hu = hu * 1.0;
+        const double hu = thick_reg(F, p.o.marginal_faces, p.visc_rem != nullptr, uc, vr, mE[m], mD[m], mC[m], pW[m], pD[m], pC[m]);
         if (valid) p.h_face[f3] = hu;
       }
     }
@@ -1136,35 +1096,24 @@ __global__ __launch_bounds__(64 * FC_NW, FC_OCC) void cont_flux_coop_kernel(Flux
   ksums(fsm, PL, RO, fl, sb, nz, 2, 0.0, 0.0, 0.0, FAmt_R, uhtot_R, d2);
   FC_MARK(8);
   if (sb == 0 && valid) {
-    double FA_0 = FAmt_0, FA_avg = FAmt_0;
-    if ((duL - du0) != 0.0) FA_avg = uhtot_L / (duL - du0);
-    if (FA_avg > max2(FA_0, FAmt_L)) FA_avg = max2(FA_0, FAmt_L);
-    else if (FA_avg < min2(FA_0, FAmt_L)) FA_0 = FA_avg;
-    p.FA_0m[f2] = FA_0; p.FA_mm[f2] = FAmt_L;
-    if (fabs(FA_0 - FAmt_L) <= 1e-12 * FA_0) p.uBT_mm[f2] = 0.0;
-    else p.uBT_mm[f2] = (1.5 * (duL - du0)) * ((FAmt_L - FA_avg) / (FAmt_L - FA_0));
-
-    FA_0 = FAmt_0; FA_avg = FAmt_0;
-    if ((duR - du0) != 0.0) FA_avg = uhtot_R / (duR - du0);
-    if (FA_avg > max2(FA_0, FAmt_R)) FA_avg = max2(FA_0, FAmt_R);
-    else if (FA_avg < min2(FA_0, FAmt_R)) FA_0 = FA_avg;
-    p.FA_0p[f2] = FA_0; p.FA_pp[f2] = FAmt_R;
-    if (fabs(FAmt_R - FA_0) <= 1e-12 * FA_0) p.uBT_pp[f2] = 0.0;
-    else p.uBT_pp[f2] = (1.5 * (duR - du0)) * ((FAmt_R - FA_avg) / (FAmt_R - FA_0));
+    bt_cont_fit(FAmt_0, FAmt_L, uhtot_L, duL - du0, p.FA_0m[f2], p.FA_mm[f2], p.uBT_mm[f2]);
+    bt_cont_fit(FAmt_0, FAmt_R, uhtot_R, duR - du0, p.FA_0p[f2], p.FA_pp[f2], p.uBT_pp[f2]);
   }
 }
 
 // ---- mass fluxes, block-cooperative form at three or four waves a SIMD (round 5) -------------------------------------
-// The same decomposition as cont_flux_coop_kernel (a half-wave = 32 face columns x one slab of KS layers, the slabs of a face
-// spread over the NW waves of a block, k-ordered sums through LDS planes), with the per-layer register set cut so that three
-// (6 waves x 7 layers) or four (8 waves x 5 layers) waves fit a SIMD without scratch:
+// The zonal kernel for deep columns.  The same decomposition as cont_flux_coop_kernel (a half-wave = 32 face columns x one slab of
+// KS layers, the slabs of a face spread over the NW waves of a block, k-ordered sums through LDS planes), with the per-layer
+// register set cut so that four waves (8 waves x 5 layers a block) fit a SIMD without scratch:
 //  * a cell is held as (h_L, h_R, curvature): the upwind edge E, the other edge O and the curvature C are picked by selects and
 //    the edge difference of flux_layer is O - E in both of its branches (the reference's own subtraction);
-//  * zonal: a lane holds ONE cell, the minus-side cell of its face; the plus-side cell is the next lane's, fetched in every
-//    evaluation by a DPP wave shift (no LDS, no registers).  Meridional: both cells (the next row belongs to another block);
+//  * a lane holds ONE cell, the minus-side cell of its face; the plus-side cell is the next lane's, fetched in every evaluation by
+//    a DPP wave shift (no LDS, no registers).  That is what keeps the kernel zonal: meridionally the next row belongs to another
+//    block, a thread has to hold both cells (7 doubles a layer) and spills at every shape that fits three or four waves a SIMD
+//    (profiles/r05_experiments.txt), so cont_flux_coop_kernel<1, 10> stays the meridional kernel;
 //  * visc_rem lives in an LDS plane for the whole kernel (the chain walkers read it there anyway), a thread reads its own slots;
 //  * the Newton bracket and best error of a face are one LDS copy per block and phase (every half-wave computes the same values).
-// Zonal 4 doubles a layer in registers, meridional 7 (cont_flux_coop_kernel: 8).
+// 4 doubles a layer in registers (cont_flux_coop_kernel: 8).
 __device__ __forceinline__ double dpp_next_lane(double x) {      // the value of lane + 1 (0 in lane 63)
   int lo = __double2loint(x), hi = __double2hiint(x);
   lo = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, true);      // wave_shl:1
@@ -1201,39 +1150,10 @@ __device__ __forceinline__ double thick_lrc(const FaceConst &F, int marginal, bo
   return hu;
 }
 
-#ifndef FC3_GRP
 #define FC3_GRP 2      // layers of a thread the scheduler may interleave in an evaluation pass (bounds the temporaries)
-#endif
 #define FC3_SCHED(m) do { if (((m) + 1) % FC3_GRP == 0) __builtin_amdgcn_sched_barrier(0); } while (0)
-// FC3_UNCOND = 1: the evaluation passes run over all KS layers of a thread without a test on k (layers past nk hold zeros: u = 0 gives
-// uh = +0 and a marginal thickness of 0; their rows of the planes exist and no sum reads them), one basic block the scheduler can
-// interleave FC3_GRP layers in.  Measured (profiles/r05_experiments.txt): the test on k is the faster form (the slabs past nk do nothing).
-#ifndef FC3_PF
 #define FC3_PF 2      // layers of thicknesses a thread has in flight ahead of its reconstruction (>= KS: all of them at once)
-#endif
-#ifndef FC3_CHAIN_UNROLL
 #define FC3_CHAIN_UNROLL 8      // LDS reads a chain walker issues ahead of its dependent arithmetic
-#endif
-#ifndef FC3_UNCOND
-#define FC3_UNCOND 0
-#endif
-#define FC3_LIVE(m) (FC3_UNCOND || (k0 + (m) < nz))
-
-__device__ __forceinline__ void ksums3(double *fsm, int plane, int roff, int fl, int sb, int nz, int nsum, double i0, double i1,
-                                       double i2, double &r0, double &r1, double &r2) {
-  __syncthreads();
-  if (sb < nsum) {
-    double acc = (sb == 0) ? i0 : ((sb == 1) ? i1 : i2);
-    const int base = sb * plane + fl;
-#pragma unroll 8
-    for (int k = 0; k < nz; k++) acc = acc + fsm[base + k * FC_FL];
-    fsm[roff + sb * FC_FL + fl] = acc;
-  }
-  __syncthreads();
-  r0 = fsm[roff + fl];
-  r1 = (nsum > 1) ? fsm[roff + FC_FL + fl] : 0.;
-  r2 = (nsum > 2) ? fsm[roff + 2 * FC_FL + fl] : 0.;
-}
 
 template <int KS, int NW>
 constexpr size_t fc3_lds_bytes() { return ((size_t)3 * KS * 2 * NW * FC_FL + 8 * FC_FL + 2 * NW * FC_FL + 15 * FC_FL + 6 * FC_FL) * sizeof(double); }
@@ -1246,6 +1166,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
   unsigned long long fc_t0 = __builtin_readcyclecounter();
   if (threadIdx.x == 0) atomicAdd(&fc_trace[64 * DIR + 15], 1ull);
 #endif
+  static_assert(DIR == 0, "the plus-side cell of a face is the next lane's: zonal only");
   extern __shared__ double fsm[];
   constexpr int NS = 2 * NW;
   const m6::GridDev &g = p.g;
@@ -1253,12 +1174,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int fl = lane & (FC_FL - 1), sb = 2 * w + (lane >> 5);      // face within the block; layer slab of this half-wave
   const int nz = g.nk;
-  constexpr int FPB = (DIR == 0) ? FC_FL - 1 : FC_FL;      // faces per block (the last zonal lane only serves its neighbour)
-  int bx, by;
-  if (!xcd_block(p.xcd_w, p.nbx, bx, by)) return;
+  constexpr int FPB = FC_FL - 1;      // faces per block (the last lane of a half-wave only serves its neighbour)
+  const int bx = blockIdx.x, by = blockIdx.y;
   const int fi_raw = p.fi0 + bx * FPB + fl;
   const bool valid = fl < FPB && fi_raw <= p.fi1 && !(p.skip && p.skip[D.f2(min(fi_raw, p.fi1), p.fj0 + by)]);
-  const int fi_last = (DIR == 0) ? p.fi1 + 1 : p.fi1;
+  const int fi_last = p.fi1 + 1;      // (idle lanes sit on the cell after the last face, whose reconstruction the last face needs)
   const int fi = (fi_raw <= fi_last) ? fi_raw : fi_last;
   const int fj = p.fj0 + by;
   const long hpl = (long)g.nih * g.njh, fpl = D.fplane();
@@ -1281,29 +1201,27 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
 
   // ---- the thread's layers into registers (every global load issued before anything is computed from one of them)
   const bool wide = !(p.o.upwind_1st || p.o.simple_2nd);      // the 5-point stencil is only read by the PPM branch
-  const long s2w = wide ? 2 * s : 0, s3w = (wide && DIR == 1) ? 3 * s : 0;
+  const long s2w = wide ? 2 * s : 0;
   double dLf_r = D.dL_face()[f2];
   double cm_r = (p.o.vol_CFL ? g.IareaT : D.IdL_T())[o2], cp_r = (p.o.vol_CFL ? g.IareaT : D.IdL_T())[o2 + s];
-  double mk[6];                                               // mask2dT of cells -2 .. +3 along the direction
+  double mk[5];                                               // mask2dT of cells -2 .. +2 along the direction
   {
     const double *mm = g.mask2dT + o2;
     mk[0] = mm[-s2w]; mk[1] = mm[-s]; mk[2] = mm[0]; mk[3] = mm[s]; mk[4] = mm[2 * s];
-    mk[5] = mm[s3w];      // (only the meridional pair of reconstructions reads cell +3)
   }
   double pk_mf = D.mask_face()[f2], pk_ub = p.uhbt ? p.uhbt[f2] : 0.0;
-  constexpr int KP = (DIR == 1) ? KS : 1;      // the plus-side cell is held only meridionally
-  double ru[KS], sL[KS], sR[KS], sC[KS], tL[KP], tR[KP], tC[KP];
-  constexpr int NH = (DIR == 0) ? 5 : 6;      // cells -2 .. +2 along the direction (+3 for the meridional pair)
+  double ru[KS], sL[KS], sR[KS], sC[KS];
+  constexpr int NH = 5;      // cells -2 .. +2 along the direction
   // The loads of a thread are a software pipeline over its layers (round 5): u, visc_rem, the 2-D values and the thicknesses of the
   // first FC3_PF layers are issued at once; the reconstruction of layer m then runs behind the loads of layer m + FC3_PF.  With every
   // load of the thread in flight at once (cont_flux_coop_kernel) the landing registers of KS x (NH + 2) values are the peak of the
-  // kernel's register demand -- 200 VGPRs meridionally, the budget of four waves a SIMD is 128 -- and what does not fit goes to
-  // scratch memory for the whole kernel.
+  // kernel's register demand, the budget of four waves a SIMD is 128, and what does not fit goes to scratch memory for the whole
+  // kernel.
   double hr[KS][NH];
   const char *hb[NH];
 #pragma unroll
   for (int q = 0; q < NH; q++) {
-    const long disp = (q == 0) ? -s2w : ((q == 5) ? s3w : (q - 2) * s);
+    const long disp = (q == 0) ? -s2w : (q - 2) * s;
     hb[q] = (const char *)(p.h_in + disp);
   }
   const unsigned o2b = (unsigned)(o2 * 8), hstep = (unsigned)(hpl * 8);
@@ -1341,9 +1259,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
     }
     fsm[VO + sb * FC_FL + fl] = vmax_w;
 #pragma unroll
-    for (int q = 0; q < 6; q++) pin(mk[q]);
-    if (!wide) { mk[0] = 0.0; mk[5] = 0.0; }
-    if (DIR == 0) mk[5] = 0.0;
+    for (int q = 0; q < 5; q++) pin(mk[q]);
+    if (!wide) mk[0] = 0.0;
   }
   // The face constants of flux_layer go to LDS at once (every half-wave stores the same values: no ordering between them is needed,
   // and none of them is held in registers through the reconstruction): every pass reads them back from there
@@ -1358,11 +1275,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
     dead_lane = (pk_mf == 0.0) & (dLf_r == 0.0) & (pk_ub == 0.0);
   }
 #define FC3_FACE(F) FaceConst F; F.dLf = fsm[PK_DLF + fl]; F.cm = fsm[PK_CM + fl]; F.cp = fsm[PK_CP + fl]; F.dt = p.dt
-  // the plus-side cell of layer m: the next lane's cell (zonal; fetched outside every condition: a DPP fetch needs its source
-  // lane active), or the thread's own registers (meridional)
-#define FC3_PLUS(m) \
-  const double pL_ = DIR ? tL[DIR ? (m) : 0] : dpp_next_lane(sL[m]), pR_ = DIR ? tR[DIR ? (m) : 0] : dpp_next_lane(sR[m]), \
-               pC_ = DIR ? tC[DIR ? (m) : 0] : dpp_next_lane(sC[m])
+  // the plus-side cell of layer m: the next lane's cell (fetched outside every condition: a DPP fetch needs its source lane active)
+#define FC3_PLUS(m) const double pL_ = dpp_next_lane(sL[m]), pR_ = dpp_next_lane(sR[m]), pC_ = dpp_next_lane(sC[m])
 
   // ---- blocks whose 32 faces are all land: nothing to solve (see cont_flux_coop_kernel)
 #pragma unroll
@@ -1391,20 +1305,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
     if (k < nz) {
       const double hm1 = hr[m][1], hc0 = hr[m][2], hp1 = hr[m][3], hp2 = hr[m][4];
       double Lm, Rm;
-      if (DIR == 0) {
-        if (p.o.upwind_1st) { Lm = hc0; Rm = hc0; }
-        else edge_values(p.o, g.Angstrom_H, hr[m][0], hm1, hc0, hp1, wide ? hp2 : 0.0, mk[0], mk[1], mk[2], mk[3],
-                         wide ? mk[4] : 0.0, Lm, Rm);
-      } else {      // both cells at once: the slopes of the two cells serve both reconstructions
-        const double h6[6] = {hr[m][0], hm1, hc0, hp1, hp2, hr[m][NH - 1]};
-        double Lp, Rp;
-        edge_values2(p.o, g.Angstrom_H, h6, mk, Lm, Rm, Lp, Rp);
-        tL[DIR ? m : 0] = Lp; tR[DIR ? m : 0] = Rp; tC[DIR ? m : 0] = Lp + Rp - 2.0 * hp1;
-      }
+      if (p.o.upwind_1st) { Lm = hc0; Rm = hc0; }
+      else edge_values(p.o, g.Angstrom_H, hr[m][0], hm1, hc0, hp1, wide ? hp2 : 0.0, mk[0], mk[1], mk[2], mk[3],
+                       wide ? mk[4] : 0.0, Lm, Rm);
       sL[m] = Lm; sR[m] = Rm; sC[m] = Lm + Rm - 2.0 * hc0;
     } else {
       sL[m] = 0.; sR[m] = 0.; sC[m] = 0.;
-      if (DIR) { tL[DIR ? m : 0] = 0.; tR[DIR ? m : 0] = 0.; tC[DIR ? m : 0] = 0.; }
     }
   }
   FC_MARK(1);
@@ -1454,17 +1360,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
   for (int m = 0; m < KS; m++) {
     FC3_PLUS(m);
-    if (FC3_LIVE(m)) {
+    if (k0 + m < nz) {
       double dd;
       const double uhk = flux_lrc(F0, ru[m], VR(m), sL[m], sR[m], sC[m], pL_, pR_, pC_, dd);
-      if (valid && !p.uhbt && k0 + m < nz) p.uh[FC3_F3(m)] = uhk;      // (with uhbt, uh is stored once, after the solve)
+      if (valid && !p.uhbt) p.uh[FC3_F3(m)] = uhk;      // (with uhbt, uh is stored once, after the solve)
       fsm[sl + m * FC_FL] = uhk; fsm[PL + sl + m * FC_FL] = dd;
     }
     FC3_SCHED(m);
   }
   }
   double uh_tot_0, duhdu_tot_0, dummy;
-  ksums3(fsm, PL, RO, fl, sb, nz, 2, 0.0, 0.0, 0.0, uh_tot_0, duhdu_tot_0, dummy);
+  ksums(fsm, PL, RO, fl, sb, nz, 2, 0.0, 0.0, 0.0, uh_tot_0, duhdu_tot_0, dummy);
   double visc_rem_max = 0.0;
   for (int q = 0; q < NS; q++) visc_rem_max = max2(visc_rem_max, fsm[VO + q * FC_FL + fl]);      // (max is order-free)
   if (!(p.visc_rem && p.o.use_visc_rem_max)) visc_rem_max = 1.0;
@@ -1480,7 +1386,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
   if (visc_rem_max > 0.0) I_vrm = 1.0 / visc_rem_max;
   {
     const double dx_W = fsm[PK_DXW + fl], dx_E = fsm[PK_DXE + fl], mface = fsm[PK_MF + fl];
-    // (no barrier needed before the planes are rewritten: every read of them lies between the two barriers of ksums3)
+    // (no barrier needed before the planes are rewritten: every read of them lies between the two barriers of ksums)
 #pragma unroll
     for (int m = 0; m < KS; m++) {
       if (k0 + m < nz) {
@@ -1567,44 +1473,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
     bool do_I = true, alive = valid;
 #pragma unroll 1
     for (int itt = 1; itt <= max_itts; itt++) {
-      bool domore = false;
-      if (alive) {
-        double tol_eta;
-        if (itt <= 1) tol_eta = 1e-6 * p.o.tol_eta;
-        else if (itt == 2) tol_eta = 1e-4 * p.o.tol_eta;
-        else if (itt == 3) tol_eta = 1e-2 * p.o.tol_eta;
-        else tol_eta = p.o.tol_eta;
-        const double tol_vel = p.o.tol_vel;
+      if (alive) {      // (the bracket lives in LDS: its copy takes du on the side of the error, as adjust_step's does)
         double du_max = fsm[pv], du_min = fsm[pv + FC_FL];
         const double uh_err_best = fsm[pv + 2 * FC_FL], IaT = fsm[PK_IAT + fl];
-        if (uh_err > 0.0) { du_max = du; fsm[pv] = du; }
-        else if (uh_err < 0.0) { du_min = du; fsm[pv + FC_FL] = du; }
-        else do_I = false;
-        if (do_I) {
-          if ((p.dt * IaT * fabs(uh_err) > tol_eta) ||
-              (p.o.better_iter && ((fabs(uh_err) > tol_vel * duhdu_tot) || (fabs(uh_err) > uh_err_best)))) {
-            const double ddu = -uh_err / duhdu_tot;
-            const double du_prev = du;
-            du = du + ddu;
-            if (fabs(ddu) < 1.0e-15 * fabs(du)) {
-              do_I = false;
-            } else if (ddu > 0.0) {
-              if (du >= du_max) {
-                du = 0.5 * (du_prev + du_max);
-                if (du_max - du_prev < 1.0e-15 * fabs(du)) do_I = false;
-              }
-            } else {
-              if (du <= du_min) {
-                du = 0.5 * (du_prev + du_min);
-                if (du_prev - du_min < 1.0e-15 * fabs(du)) do_I = false;
-              }
-            }
-            if (do_I) domore = true;
-          } else {
-            do_I = false;
-          }
-        }
-        if (!domore) alive = false;
+        if (uh_err > 0.0) fsm[pv] = du;
+        else if (uh_err < 0.0) fsm[pv + FC_FL] = du;
+        alive = adjust_step(p.o, p.dt, itt, uh_err, duhdu_tot, uh_err_best, IaT, du, du_max, du_min, do_I);
       }
       if (!__any(alive)) break;      // the same in every wave of the block: they hold the same values
       if ((itt < max_itts) || write_uh) {
@@ -1617,7 +1491,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
         for (int m = 0; m < KS; m++) {
           pin(sC[m]);
           FC3_PLUS(m);
-          if (FC3_LIVE(m)) {
+          if (k0 + m < nz) {
             double dd;
             const double vr = VR(m);
             const double uhk = flux_lrc(F, ru[m] + du * vr, vr, sL[m], sR[m], sC[m], pL_, pR_, pC_, dd);
@@ -1626,7 +1500,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
           FC3_SCHED(m);
         }
         double usum, dsum, d2;
-        ksums3(fsm, PL, RO, fl, sb, nz, 2, -uhbt, 0.0, 0.0, usum, dsum, d2);
+        ksums(fsm, PL, RO, fl, sb, nz, 2, -uhbt, 0.0, 0.0, usum, dsum, d2);
         if (alive && itt < max_itts) {
           uh_err = usum; duhdu_tot = dsum;
           fsm[pv + 2 * FC_FL] = min2(fsm[pv + 2 * FC_FL], fabs(uh_err));
@@ -1643,11 +1517,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
       for (int m = 0; m < KS; m++) {
         pin(sC[m]);
         FC3_PLUS(m);
-        if (FC3_LIVE(m)) {
+        if (k0 + m < nz) {
           double dd;
           const double vr = VR(m);
           const double uhk = flux_lrc(F, ru[m] + du_eval * vr, vr, sL[m], sR[m], sC[m], pL_, pR_, pC_, dd);
-          if (valid && k0 + m < nz) p.uh[FC3_F3(m)] = uhk;
+          if (valid) p.uh[FC3_F3(m)] = uhk;
         }
         FC3_SCHED(m);
       }
@@ -1712,29 +1586,28 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
   for (int m = 0; m < KS; m++) {
     pin(sC[m]);
     FC3_PLUS(m);
-    if (FC3_LIVE(m)) {
+    if (k0 + m < nz) {
       const long f3 = FC3_F3(m);
       const double vr = VR(m), uk = ru[m];
-      const bool st = valid && (k0 + m < nz);
       double dL;
       const double uh_L = flux_lrc(F, uk + duL * vr, vr, sL[m], sR[m], sC[m], pL_, pR_, pC_, dL);
       fsm[sl + m * FC_FL] = dL; fsm[PL + sl + m * FC_FL] = uh_L;
       double uc = uk;
-      if (cor) { uc = uk + du * vr; if (st) p.u_cor[f3] = uc; }
+      if (cor) { uc = uk + du * vr; if (valid) p.u_cor[f3] = uc; }
       if (p.h_face) {
         const double hu = thick_lrc(F, p.o.marginal_faces, p.visc_rem != nullptr, uc, vr, sL[m], sR[m], sC[m], pL_, pR_, pC_);
-        if (st) p.h_face[f3] = hu;
+        if (valid) p.h_face[f3] = hu;
       }
     }
     FC3_SCHED(m);
   }
   double FAmt_0, FAmt_L, FAmt_R, uhtot_L, uhtot_R, d2;
-  ksums3(fsm, PL, RO, fl, sb, nz, 2, 0.0, 0.0, 0.0, FAmt_L, uhtot_L, d2);
+  ksums(fsm, PL, RO, fl, sb, nz, 2, 0.0, 0.0, 0.0, FAmt_L, uhtot_L, d2);
 #pragma unroll
   for (int m = 0; m < KS; m++) {
     pin(sC[m]);
     FC3_PLUS(m);
-    if (FC3_LIVE(m)) {
+    if (k0 + m < nz) {
       double dR, d0;
       const double vr = VR(m), uk = ru[m];
       const double uh_R = flux_lrc(F, uk + duR * vr, vr, sL[m], sR[m], sC[m], pL_, pR_, pC_, dR);
@@ -1743,24 +1616,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
     }
     FC3_SCHED(m);
   }
-  ksums3(fsm, PL, RO, fl, sb, nz, 3, 0.0, 0.0, 0.0, FAmt_R, uhtot_R, FAmt_0);
+  ksums(fsm, PL, RO, fl, sb, nz, 3, 0.0, 0.0, 0.0, FAmt_R, uhtot_R, FAmt_0);
   FC_MARK(8);
   if (sb == 0 && valid) {
-    double FA_0 = FAmt_0, FA_avg = FAmt_0;
-    if ((duL - du0) != 0.0) FA_avg = uhtot_L / (duL - du0);
-    if (FA_avg > max2(FA_0, FAmt_L)) FA_avg = max2(FA_0, FAmt_L);
-    else if (FA_avg < min2(FA_0, FAmt_L)) FA_0 = FA_avg;
-    p.FA_0m[f2] = FA_0; p.FA_mm[f2] = FAmt_L;
-    if (fabs(FA_0 - FAmt_L) <= 1e-12 * FA_0) p.uBT_mm[f2] = 0.0;
-    else p.uBT_mm[f2] = (1.5 * (duL - du0)) * ((FAmt_L - FA_avg) / (FAmt_L - FA_0));
-
-    FA_0 = FAmt_0; FA_avg = FAmt_0;
-    if ((duR - du0) != 0.0) FA_avg = uhtot_R / (duR - du0);
-    if (FA_avg > max2(FA_0, FAmt_R)) FA_avg = max2(FA_0, FAmt_R);
-    else if (FA_avg < min2(FA_0, FAmt_R)) FA_0 = FA_avg;
-    p.FA_0p[f2] = FA_0; p.FA_pp[f2] = FAmt_R;
-    if (fabs(FAmt_R - FA_0) <= 1e-12 * FA_0) p.uBT_pp[f2] = 0.0;
-    else p.uBT_pp[f2] = (1.5 * (duR - du0)) * ((FAmt_R - FA_avg) / (FAmt_R - FA_0));
+    bt_cont_fit(FAmt_0, FAmt_L, uhtot_L, duL - du0, p.FA_0m[f2], p.FA_mm[f2], p.uBT_mm[f2]);
+    bt_cont_fit(FAmt_0, FAmt_R, uhtot_R, duR - du0, p.FA_0p[f2], p.FA_pp[f2], p.uBT_pp[f2]);
   }
 #undef FC3_PLUS
 #undef FC3_F3
@@ -1775,91 +1635,40 @@ bool flux_lane_only() {
   return v != 0;
 }
 
-// Whether a flux launch takes the block-cooperative kernel (which forms the edge values itself): when there is a velocity
+// Whether a flux launch takes a block-cooperative kernel (which forms the edge values itself): when there is a velocity
 // correction or BT_cont to compute and the layers fit its registers; the single-pass lane-per-column kernel otherwise.
-// The shape of the block-cooperative kernel for deep columns: MOM6HIP_CONT_COOP=4x10 keeps round 1's (4 waves x 10 layers a thread, two
-// waves a SIMD); 6x7 and 8x5 are round 5's cont_flux_coop3_kernel at three and four waves a SIMD
-// (defaults from profiles/r05_experiments.txt: zonally 8 x 5 at four waves a SIMD; meridionally the thread holds both cells of a
-// face, 7 doubles a layer, and spills at every shape that fits three or four waves: round 1's kernel stays)
-#ifndef FC3_DEFAULT_X
-#define FC3_DEFAULT_X 85
-#endif
-#ifndef FC3_DEFAULT_Y
-#define FC3_DEFAULT_Y 410
-#endif
-int flux_coop_shape(int dir) {      // 410: round 1's kernel; 67, 85: cont_flux_coop3_kernel; 853 (8x5w3), 163 (16x3), 124 (12x4), 104 (10x4): experiments of round 5
-  auto parse = [](const char *e, int dflt) {
-    if (!e) return dflt;
-    if (strcmp(e, "4x10") == 0) return 410;
-    if (strcmp(e, "8x5") == 0) return 85;
-    if (strcmp(e, "8x5w3") == 0) return 853;
-    if (strcmp(e, "16x3") == 0) return 163;
-    if (strcmp(e, "12x4") == 0) return 124;
-    if (strcmp(e, "10x4") == 0) return 104;
-    return 67;
-  };
-  static const int v[2] = {
-      [&] { const char *e = getenv("MOM6HIP_CONT_COOP_X"); if (!e) e = getenv("MOM6HIP_CONT_COOP"); return parse(e, FC3_DEFAULT_X); }(),
-      [&] { const char *e = getenv("MOM6HIP_CONT_COOP_Y"); if (!e) e = getenv("MOM6HIP_CONT_COOP"); return parse(e, FC3_DEFAULT_Y); }()};
-  return v[dir];
-}
-int flux_coop_nk_max() {
-  auto cap = [](int shape) { return shape == 410 ? FC_KSMAX * FC_NS : (shape == 67 ? 84 : ((shape == 163 || shape == 124) ? 96 : 80)); };
-  return std::min(cap(flux_coop_shape(0)), cap(flux_coop_shape(1)));
-}
-
+constexpr int FLUX_COOP_NK_MAX = 80;      // layers of the deepest instances: 8 slabs of FC_KSMAX, 16 slabs of 5
 bool flux_is_coop(const FluxArgs &f) {
   // (and a 3-D array stays below 4 GB: the kernel addresses its layers with 32-bit byte offsets)
   const bool small = (size_t)(f.g.nih + 1) * (f.g.njh + 1) * f.g.nk * sizeof(double) < ((size_t)1 << 32);
-  const int nk_max = flux_coop_nk_max();
-  return (f.uhbt || f.set_BT_cont) && f.g.nk <= nk_max && small && !flux_lane_only() && !f.obc_on;      // (OBC: the lane kernel)
+  return (f.uhbt || f.set_BT_cont) && f.g.nk <= FLUX_COOP_NK_MAX && small && !flux_lane_only() && !f.obc_on;      // (OBC: the lane kernel)
 }
 
+// The one path of a flux launch, chosen by the direction and the number of layers: up to 8 and up to 32 layers cont_flux_coop_kernel
+// with 1 and 4 layers a thread; up to 80 zonally cont_flux_coop3_kernel (8 waves x 5 layers, four waves a SIMD) and meridionally
+// cont_flux_coop_kernel with 10 layers a thread (a thread holds both cells of a face there: profiles/r05_experiments.txt has every
+// other shape slower); the lane kernel for everything flux_is_coop leaves.
 template <int DIR>
-int launch_flux(mom6hip_ctx_t *ctx, const FluxArgs &f_in, int n_along, int n_rows) {
-  const int nk = f_in.g.nk;
-  dim3 grid((n_along + 63) / 64, n_rows);
-  if (flux_is_coop(f_in)) {
-    grid.x = (DIR == 0) ? (n_along + FC_FL - 2) / (FC_FL - 1) : (n_along + FC_FL - 1) / FC_FL;      // a zonal block yields 31 faces
-    FluxArgs f = f_in;
-    f.xcd_w = 0; f.nbx = (int)grid.x;
-    static const int xcd_mode = getenv("MOM6HIP_CONT_XCD") ? atoi(getenv("MOM6HIP_CONT_XCD")) : 0;      // 0: launch order (the default: the strips measured slower, profiles/r05_experiments.txt section 5); 1: meridional; 3: both
-    if (((DIR == 1 && xcd_mode >= 1) || (DIR == 0 && xcd_mode >= 3)) && grid.x >= 16 && n_rows >= 8) {      // (xcd_block)
-      f.xcd_w = ((int)grid.x + 7) / 8;
-      grid.x = 8 * f.xcd_w;
-    }
-    auto go = [&](auto kern, int KS) -> int {
-      const size_t lds = ((size_t)3 * KS * FC_NS * FC_FL + 8 * FC_FL + FC_NS * FC_FL + 15 * FC_FL + 4 * FC_NS * FC_FL) * sizeof(double);
-      std::vector<const void *> &configured = ctx->lds_configured;      // the attribute is per device: kept with the context
-      if (std::find(configured.begin(), configured.end(), (const void *)kern) == configured.end()) {
-        M6_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured.push_back((const void *)kern);
-      }
-      hipLaunchKernelGGL(kern, grid, dim3(64 * FC_NW), lds, ctx->stream, f);
-      return 0;
-    };
-    if (nk <= FC_NS) return go(cont_flux_coop_kernel<DIR, 1>, 1);
-    if (nk <= 4 * FC_NS) return go(cont_flux_coop_kernel<DIR, 4>, 4);
-    auto go3 = [&](auto kern, int nw, size_t lds) -> int {
-      std::vector<const void *> &configured = ctx->lds_configured;
-      if (std::find(configured.begin(), configured.end(), (const void *)kern) == configured.end()) {
-        M6_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured.push_back((const void *)kern);
-      }
-      hipLaunchKernelGGL(kern, grid, dim3(64 * nw), lds, ctx->stream, f);
-      return 0;
-    };
-    const int shape = flux_coop_shape(DIR);
-    if (shape == 67) return go3(cont_flux_coop3_kernel<DIR, 7, 6, 3>, 6, fc3_lds_bytes<7, 6>());
-    if (shape == 85) return go3(cont_flux_coop3_kernel<DIR, 5, 8, 4>, 8, fc3_lds_bytes<5, 8>());
-    if (shape == 853) return go3(cont_flux_coop3_kernel<DIR, 5, 8, 3>, 8, fc3_lds_bytes<5, 8>());
-    if (shape == 163) return go3(cont_flux_coop3_kernel<DIR, 3, 16, 4>, 16, fc3_lds_bytes<3, 16>());
-    if (shape == 124) return go3(cont_flux_coop3_kernel<DIR, 4, 12, 3>, 12, fc3_lds_bytes<4, 12>());
-    if (shape == 104) return go3(cont_flux_coop3_kernel<DIR, 4, 10, 3>, 10, fc3_lds_bytes<4, 10>());
-    return go(cont_flux_coop_kernel<DIR, FC_KSMAX>, FC_KSMAX);
+int launch_flux(mom6hip_ctx_t *ctx, const FluxArgs &f, int n_along, int n_rows) {
+  if (!flux_is_coop(f)) {
+    hipLaunchKernelGGL(cont_flux_kernel<DIR>, dim3((n_along + 63) / 64, n_rows), dim3(64), 0, ctx->stream, f);
+    return 0;
   }
-  hipLaunchKernelGGL(cont_flux_kernel<DIR>, grid, dim3(64), 0, ctx->stream, f_in);
-  return 0;
+  const dim3 grid((DIR == 0) ? (n_along + FC_FL - 2) / (FC_FL - 1) : (n_along + FC_FL - 1) / FC_FL, n_rows);      // a zonal block yields 31 faces
+  auto go = [&](auto kern, int nw, size_t lds) -> int {
+    std::vector<const void *> &configured = ctx->lds_configured;      // the attribute is per device: kept with the context
+    if (std::find(configured.begin(), configured.end(), (const void *)kern) == configured.end()) {
+      M6_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      configured.push_back((const void *)kern);
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(64 * nw), lds, ctx->stream, f);
+    return 0;
+  };
+  const int nk = f.g.nk;
+  if (nk <= FC_NS) return go(cont_flux_coop_kernel<DIR, 1>, FC_NW, fc_lds_bytes<1>());
+  if (nk <= 4 * FC_NS) return go(cont_flux_coop_kernel<DIR, 4>, FC_NW, fc_lds_bytes<4>());
+  if constexpr (DIR == 0) return go(cont_flux_coop3_kernel<0, 5, 8, 4>, 8, fc3_lds_bytes<5, 8>());
+  else return go(cont_flux_coop_kernel<1, FC_KSMAX>, FC_NW, fc_lds_bytes<FC_KSMAX>());
 }
 
 // ---- convergence ---------------------------------------------------------------------------------
@@ -1892,6 +1701,187 @@ __global__ __launch_bounds__(256) void cont_conv_kernel(ConvArgs p) {
   const double hn = max2(p.hin[o3] - p.dt * g.IareaT[o2] * (uhp - uhm), p.h_min);
   p.h[o3] = hn;
   if (p.h2 && (j < p.j2lo || j > p.j2hi)) p.h2[o3] = hn;
+}
+
+// ---- the host side of a call ----------------------------------------------------------------------
+// what the kernels read of OBC for one direction (device maps: build_obc_tables)
+struct ObcDir { int on = 0, open = 0, simple = 0, specified = 0; const int32_t *segnum = nullptr, *cell = nullptr, *fa = nullptr, *skip = nullptr; };
+
+// Open boundaries: what the kernels read of OBC, on the device (built once per OBC and kept with the context)
+int build_obc_tables(mom6hip_ctx_t *ctx, m6::Stager &st, const mom6hip_obc_t *obc, ObcDir ob[2], const SegDev **d_segs) {
+  const m6::GridDev &g = ctx->g;
+  M6_REQUIRE(ctx->cont_phase == 0, "continuity_PPM: open boundaries with a continuity call in two phases are not provided");
+  M6_REQUIRE(obc->segment && obc->segnum_u && obc->segnum_v, "continuity_PPM: OBC%%segment, segnum_u and segnum_v are required");
+  const int nseg = obc->number_of_segments;
+  M6_REQUIRE(nseg <= 1024, "continuity_PPM: at most 1024 OBC segments");
+  const size_t nH2 = (size_t)g.nih * g.njh, nU2 = (size_t)(g.nih + 1) * g.njh, nV2 = (size_t)g.nih * (g.njh + 1);
+  // The validity of the segments and the device pointers of the specified ones' data (checked and staged at every call: the data may be
+  // host arrays), then the two device tables, each built and uploaded once per OBC (m6::obc_table): the maps -- segnum_u, segnum_v, the
+  // cells' reconstruction codes of either direction, the open faces' interior side -- and the segment table (keyed on the data pointers too)
+  std::vector<SegDev> segs(nseg);
+  const int open_d[2] = {obc->open_u_BCs_exist_globally != 0, obc->open_v_BCs_exist_globally != 0};
+  uint64_t key = m6::obc_fingerprint(ctx, obc), key_segs = key;
+  for (int n = 0; n < nseg; n++) {
+    const mom6hip_obc_segment_t &S = obc->segment[n];
+    SegDev &d = segs[n];
+    d.direction = S.direction; d.open = S.open; d.specified = S.specified; d.pad = 0;
+    d.IsdB = S.IsdB; d.IedB = S.IedB; d.JsdB = S.JsdB; d.JedB = S.JedB; d.isd = S.isd; d.ied = S.ied; d.jsd = S.jsd; d.jed = S.jed;
+    d.normal_trans = nullptr; d.normal_vel = nullptr;
+    const bool ew = S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_W;
+    const bool ns = S.direction == MOM6HIP_OBC_DIRECTION_N || S.direction == MOM6HIP_OBC_DIRECTION_S;
+    if (!S.on_pe) continue;
+    M6_REQUIRE(ew || ns, "continuity_PPM: OBC segment %d has no direction", n + 1);
+    // (setup_u/v_point_obc leave a segment off the PE unless its faces lie two points inside the data domain :1448, :1588)
+    M6_REQUIRE(ew ? (S.IsdB >= g.isd + 1 && S.IsdB <= g.ied - 2 && S.jsd >= g.jsd && S.jed <= g.jed)
+                  : (S.JsdB >= g.jsd + 1 && S.JsdB <= g.jed - 2 && S.isd >= g.isd && S.ied <= g.ied),
+               "continuity_PPM: OBC segment %d lies outside the data domain", n + 1);
+    if (S.specified) {
+      M6_REQUIRE(S.normal_trans && S.normal_vel, "continuity_PPM: segment %d is specified: normal_trans and normal_vel are required", n + 1);
+      const size_t cnt = ew ? (size_t)(S.IedB - S.IsdB + 1) * (S.jed - S.jsd + 1) * g.nk : (size_t)(S.ied - S.isd + 1) * (S.JedB - S.JsdB + 1) * g.nk;
+      d.normal_trans = st.in(S.normal_trans, cnt * 8); d.normal_vel = st.in(S.normal_vel, cnt * 8);
+    }
+    key_segs = m6::obc_mix(m6::obc_mix(key_segs, (uint64_t)(uintptr_t)d.normal_trans), (uint64_t)(uintptr_t)d.normal_vel);
+  }
+  M6_REQUIRE(!st.failed(), "continuity_PPM: staging of the open boundaries failed");
+  const size_t n_maps = 3 * nU2 + 3 * nV2 + 2 * nH2;
+  const int32_t *maps = (const int32_t *)m6::obc_table(ctx, m6::OBC_SITE_CONT, key, 4 * n_maps, [&](void *host) -> int {
+    int32_t *su = (int32_t *)host, *sv = su + nU2, *cx = sv + nV2, *cy = cx + nH2, *fx = cy + nH2, *fy = fx + nU2;
+    int32_t *kx = fy + nV2, *ky = kx + nU2;
+    memset(cx, 0, 4 * (2 * nH2 + 2 * nU2 + 2 * nV2));
+    memcpy(su, obc->segnum_u, 4 * nU2); memcpy(sv, obc->segnum_v, 4 * nV2);
+    int32_t *cell[2] = {cx, cy}, *fa[2] = {fx, fy}, *skip[2] = {kx, ky};
+    for (int n = 0; n < nseg; n++) {
+      const mom6hip_obc_segment_t &S = obc->segment[n];
+      if (!S.on_pe) continue;
+      const bool ew = S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_W;
+      const int dd = ew ? 0 : 1;
+      const int A = ew ? S.IsdB : S.JsdB, c0 = ew ? S.jsd : S.isd, c1 = ew ? S.jed : S.ied;
+      const bool plus = S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_N;
+      for (int c = c0; c <= c1; c++) {
+        for (int a = A - OBC_STRIP; a <= A + OBC_STRIP; a++)      // the faces the lane kernel forms (OBC_STRIP above)
+          if (a >= (ew ? g.isd - 1 : g.jsd - 1) && a <= (ew ? g.ied : g.jed)) skip[dd][ew ? g.u2(a, c) : g.v2(c, a)] = 1;
+        const long ca = ew ? g.h2(A, c) : g.h2(c, A), cb = ew ? g.h2(A + 1, c) : g.h2(c, A + 1);
+        if (open_d[dd]) {      // PPM_reconstruction_x/y :2385-2432: zero slopes, then the edge values (a later segment has the last word)
+          cell[dd][ca] = 1 | ((plus ? 1 : 3) << 1);
+          cell[dd][cb] = 1 | ((plus ? 2 : 1) << 1);
+          if (S.open && (ew ? S.is_E_or_W : S.is_N_or_S)) fa[dd][ew ? g.u2(A, c) : g.v2(c, A)] = plus ? 1 : 2;      // :782-805, :1058-1088
+        }
+      }
+    }
+    return 0;
+  });
+  const SegDev *ds = (const SegDev *)m6::obc_table(ctx, m6::OBC_SITE_CONT, m6::obc_mix(key_segs, 0x5e95ull), sizeof(SegDev) * nseg,
+                                                   [&](void *host) -> int { memcpy(host, segs.data(), sizeof(SegDev) * nseg); return 0; });
+  if (!maps || !ds) return 1;
+  const int32_t *dsu = maps, *dsv = dsu + nU2, *dcx = dsv + nV2, *dcy = dcx + nH2, *dfx = dcy + nH2, *dfy = dfx + nU2;
+  ob[0].skip = dfy + nV2; ob[1].skip = ob[0].skip + nU2;
+  *d_segs = ds;
+  const int pe = obc->OBC_pe != 0;
+  ob[0].on = ob[1].on = 1;
+  ob[0].open = open_d[0]; ob[1].open = open_d[1];
+  ob[0].specified = pe && obc->specified_u_BCs_exist_globally; ob[1].specified = pe && obc->specified_v_BCs_exist_globally;
+  ob[0].simple = pe && (obc->specified_u_BCs_exist_globally || obc->Flather_u_BCs_exist_globally);
+  ob[1].simple = pe && (obc->specified_v_BCs_exist_globally || obc->Flather_v_BCs_exist_globally);
+  ob[0].segnum = dsu; ob[1].segnum = dsv; ob[0].cell = dcx; ob[1].cell = dcy; ob[0].fa = dfx; ob[1].fa = dfy;
+  return 0;
+}
+
+int side_fork(mom6hip_ctx_t *ctx) {      // the side streams wait for what the compute stream has been given so far
+  if (!ctx->side_fork) {
+    for (hipStream_t &st : ctx->side_stream) M6_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    M6_HIP(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
+    for (hipEvent_t &e : ctx->side_join) M6_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  M6_HIP(hipEventRecord(ctx->side_fork, ctx->stream));
+  for (hipStream_t st : ctx->side_stream) M6_HIP(hipStreamWaitEvent(st, ctx->side_fork, 0));
+  return 0;
+}
+int side_join(mom6hip_ctx_t *ctx) {      // the compute stream waits for the side streams
+  M6_HIP(hipGetLastError());
+  for (int q = 0; q < mom6hip_ctx::NSIDE; q++) {
+    M6_HIP(hipEventRecord(ctx->side_join[q], ctx->side_stream[q]));
+    M6_HIP(hipStreamWaitEvent(ctx->stream, ctx->side_join[q], 0));
+  }
+  return 0;
+}
+
+// What a direction's pass needs of the call: per direction the flux arguments with everything but the thicknesses and the face range
+// filled in (the arrays of the direction, the options, the OBC), and the cell codes of the reconstruction
+struct ContCall {
+  mom6hip_ctx_t *ctx;
+  const mom6hip_obc_t *obc;
+  FluxArgs f[2];
+  ObcDir ob[2];
+  double *h_L, *h_R;      // the edge values, where a pass forms them in memory (cont_edge_kernel)
+  bool x_first;
+};
+
+// cont_edge_kernel over the cells i0 .. i1, j0 .. j1 on a stream
+template <int DIR>
+void launch_edge(const ContCall &c, hipStream_t stream, const double *hsrc, int i0, int i1, int j0, int j1) {
+  const FluxArgs &f = c.f[DIR];
+  EdgeArgs e; e.g = f.g; e.o = f.o; e.h_in = hsrc; e.h_L = c.h_L; e.h_R = c.h_R; e.cell_code = c.ob[DIR].open ? c.ob[DIR].cell : nullptr;
+  e.i0 = i0; e.i1 = i1; e.j0 = j0; e.j1 = j1;
+  const int rows = DIR ? (j1 - j0 + EDGE_RJ) / EDGE_RJ : j1 - j0 + 1;
+  hipLaunchKernelGGL(cont_edge_kernel<DIR>, dim3((i1 - i0 + 256) / 256, rows, f.g.nk), dim3(256), 0, stream, e);
+}
+
+// With open boundaries the block-cooperative kernels run over the whole range as on a closed domain but leave the faces a segment can
+// reach alone (FluxArgs::skip); those are formed by the lane kernel with the OBC, on the side stream at the same time (a face's column
+// depends on its own inputs only, and both kernels leave the same bits where no segment reaches; the lane kernel's walk of a column
+// takes as long for a strip as for the grid, so it has to run beside the block kernel, not after it).  What a segment at face A of its direction reaches: the face itself (flux_layer :956-971, the
+// specified transports :629-634, the face areas :782-805) and, through the zeroed slopes and the copied edge values of the cells A
+// and A+1 (PPM_reconstruction :2385-2432) that enter the edge values of A-1 .. A+2, the faces A-2 .. A+2 -- along the segment's own
+// extent (its cell codes and face codes are set there only).  OBC_STRIP = 3 faces either side.
+// One direction's pass: the fluxes of the faces fi0 .. fi1, fj0 .. fj1 from the thicknesses hsrc, then the thicknesses of the cells
+// ci0 .. ci1, cj0 .. cj1 into hdst (and, outside the rows j2lo .. j2hi, into `also`: the phased call).  Either range may be empty.
+template <int DIR>
+int cont_pass(const ContCall &c, const double *hsrc, double hmin, int fi0, int fi1, int fj0, int fj1, int ci0, int ci1, int cj0, int cj1,
+              double *hdst, double *also = nullptr, int j2lo = 0, int j2hi = -1) {
+  mom6hip_ctx_t *ctx = c.ctx;
+  const m6::GridDev &g = ctx->g;
+  hipStream_t s = ctx->stream;
+  if (fi1 >= fi0 && fj1 >= fj0) {
+    FluxArgs f = c.f[DIR]; f.h_in = hsrc; f.fi0 = fi0; f.fi1 = fi1; f.fj0 = fj0; f.fj1 = fj1;
+    static const bool strips_off = getenv("MOM6HIP_CONT_OBC_STRIPS") && atoi(getenv("MOM6HIP_CONT_OBC_STRIPS")) == 0;
+    bool strips = false;
+    if (f.obc_on && !strips_off) { FluxArgs closed = f; closed.obc_on = 0; strips = flux_is_coop(closed); }
+    if (strips) {      // the faces a segment of this direction can reach: the lane kernel with the OBC, on the side streams beside the block kernel
+      if (side_fork(ctx)) return 1;
+      int nstrip = 0;
+      for (int n = 0; n < c.obc->number_of_segments; n++) {
+        const mom6hip_obc_segment_t &S = c.obc->segment[n];
+        const bool mine = DIR ? (S.direction == MOM6HIP_OBC_DIRECTION_N || S.direction == MOM6HIP_OBC_DIRECTION_S)
+                              : (S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_W);
+        if (!S.on_pe || !mine) continue;
+        hipStream_t ss = ctx->side_stream[nstrip++ % mom6hip_ctx::NSIDE];      // (a strip's walk is latency: strips run beside each other)
+        FluxArgs fl = f;
+        if (DIR == 0) {
+          fl.fi0 = std::max(fi0, S.IsdB - OBC_STRIP); fl.fi1 = std::min(fi1, S.IsdB + OBC_STRIP);
+          fl.fj0 = std::max(fj0, S.jsd); fl.fj1 = std::min(fj1, S.jed);
+        } else {
+          fl.fi0 = std::max(fi0, S.isd); fl.fi1 = std::min(fi1, S.ied);
+          fl.fj0 = std::max(fj0, S.JsdB - OBC_STRIP); fl.fj1 = std::min(fj1, S.JsdB + OBC_STRIP);
+        }
+        if (fl.fi1 < fl.fi0 || fl.fj1 < fl.fj0) continue;
+        launch_edge<DIR>(c, ss, hsrc, fl.fi0, fl.fi1 + (DIR ? 0 : 1), fl.fj0, fl.fj1 + (DIR ? 1 : 0));
+        hipLaunchKernelGGL(cont_flux_kernel<DIR>, dim3((fl.fi1 - fl.fi0 + 64) / 64, fl.fj1 - fl.fj0 + 1), dim3(64), 0, ss, fl);
+      }
+      f.obc_on = 0; f.skip = c.ob[DIR].skip;
+    }
+    if (!flux_is_coop(f)) launch_edge<DIR>(c, s, hsrc, fi0, fi1 + (DIR ? 0 : 1), fj0, fj1 + (DIR ? 1 : 0));
+    { m6::KTimer kt(ctx, DIR ? MOM6HIP_KT_CONT_FLUX_Y : MOM6HIP_KT_CONT_FLUX_X);
+      if (launch_flux<DIR>(ctx, f, fi1 - fi0 + 1, fj1 - fj0 + 1)) return 1; }
+    if (strips && side_join(ctx)) return 1;
+  }
+  const bool second = DIR ? c.x_first : !c.x_first;
+  if (ci1 >= ci0 && cj1 >= cj0 && !(second && ctx->cont_fluxes_only)) {      // (the second direction's thicknesses are not wanted: see the context)
+    ConvArgs cv; cv.g = g; cv.hin = hsrc; cv.uh = c.f[DIR].uh; cv.h = hdst; cv.dt = c.f[DIR].dt; cv.h_min = hmin;
+    cv.i0 = ci0; cv.i1 = ci1; cv.j0 = cj0; cv.j1 = cj1; cv.h2 = also; cv.j2lo = j2lo; cv.j2hi = j2hi;
+    hipLaunchKernelGGL(cont_conv_kernel<DIR>, dim3((ci1 - ci0 + 256) / 256, cj1 - cj0 + 1, g.nk), dim3(256), 0, s, cv);
+  }
+  M6_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // namespace
@@ -1977,208 +1967,32 @@ extern "C" int mom6hip_continuity_obc(mom6hip_ctx_t *ctx, const mom6hip_continui
   const bool x_first = (ctx->host.first_direction % 2) == 0;
   const double h_min = g.Angstrom_H;
 
-  // ---- open boundaries: what the kernels read of OBC, on the device (built once per OBC and kept with the context) ----
-  struct ObcDir { int on = 0, open = 0, simple = 0, specified = 0; const int32_t *segnum = nullptr, *cell = nullptr, *fa = nullptr, *skip = nullptr; } ob[2];
+  // ---- what the passes share: per direction the flux arguments but for the thicknesses and the face range; the OBC tables ----
+  ContCall c = {};
+  c.ctx = ctx; c.obc = obc; c.h_L = h_L; c.h_R = h_R; c.x_first = x_first;
   const SegDev *d_segs = nullptr;
-  if (obc && obc->number_of_segments > 0) {
-    M6_REQUIRE(ctx->cont_phase == 0, "continuity_PPM: open boundaries with a continuity call in two phases are not provided");
-    M6_REQUIRE(obc->segment && obc->segnum_u && obc->segnum_v, "continuity_PPM: OBC%%segment, segnum_u and segnum_v are required");
-    const int nseg = obc->number_of_segments;
-    M6_REQUIRE(nseg <= 1024, "continuity_PPM: at most 1024 OBC segments");
-    const size_t nH2 = (size_t)g.nih * g.njh, nU2 = (size_t)(g.nih + 1) * g.njh, nV2 = (size_t)g.nih * (g.njh + 1);
-    // The validity of the segments and the device pointers of the specified ones' data (checked and staged at every call: the data may be
-    // host arrays), then the two device tables, each built and uploaded once per OBC (m6::obc_table): the maps -- segnum_u, segnum_v, the
-    // cells' reconstruction codes of either direction, the open faces' interior side -- and the segment table (keyed on the data pointers too)
-    std::vector<SegDev> segs(nseg);
-    const int open_d[2] = {obc->open_u_BCs_exist_globally != 0, obc->open_v_BCs_exist_globally != 0};
-    uint64_t key = m6::obc_fingerprint(ctx, obc), key_segs = key;
-    for (int n = 0; n < nseg; n++) {
-      const mom6hip_obc_segment_t &S = obc->segment[n];
-      SegDev &d = segs[n];
-      d.direction = S.direction; d.open = S.open; d.specified = S.specified; d.pad = 0;
-      d.IsdB = S.IsdB; d.IedB = S.IedB; d.JsdB = S.JsdB; d.JedB = S.JedB; d.isd = S.isd; d.ied = S.ied; d.jsd = S.jsd; d.jed = S.jed;
-      d.normal_trans = nullptr; d.normal_vel = nullptr;
-      const bool ew = S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_W;
-      const bool ns = S.direction == MOM6HIP_OBC_DIRECTION_N || S.direction == MOM6HIP_OBC_DIRECTION_S;
-      if (!S.on_pe) continue;
-      M6_REQUIRE(ew || ns, "continuity_PPM: OBC segment %d has no direction", n + 1);
-      // (setup_u/v_point_obc leave a segment off the PE unless its faces lie two points inside the data domain :1448, :1588)
-      M6_REQUIRE(ew ? (S.IsdB >= g.isd + 1 && S.IsdB <= g.ied - 2 && S.jsd >= g.jsd && S.jed <= g.jed)
-                    : (S.JsdB >= g.jsd + 1 && S.JsdB <= g.jed - 2 && S.isd >= g.isd && S.ied <= g.ied),
-                 "continuity_PPM: OBC segment %d lies outside the data domain", n + 1);
-      if (S.specified) {
-        M6_REQUIRE(S.normal_trans && S.normal_vel, "continuity_PPM: segment %d is specified: normal_trans and normal_vel are required", n + 1);
-        const size_t cnt = ew ? (size_t)(S.IedB - S.IsdB + 1) * (S.jed - S.jsd + 1) * g.nk : (size_t)(S.ied - S.isd + 1) * (S.JedB - S.JsdB + 1) * g.nk;
-        d.normal_trans = st.in(S.normal_trans, cnt * 8); d.normal_vel = st.in(S.normal_vel, cnt * 8);
-      }
-      key_segs = m6::obc_mix(m6::obc_mix(key_segs, (uint64_t)(uintptr_t)d.normal_trans), (uint64_t)(uintptr_t)d.normal_vel);
-    }
-    M6_REQUIRE(!st.failed(), "continuity_PPM: staging of the open boundaries failed");
-    const size_t n_maps = 3 * nU2 + 3 * nV2 + 2 * nH2;
-    const int32_t *maps = (const int32_t *)m6::obc_table(ctx, m6::OBC_SITE_CONT, key, 4 * n_maps, [&](void *host) -> int {
-      int32_t *su = (int32_t *)host, *sv = su + nU2, *cx = sv + nV2, *cy = cx + nH2, *fx = cy + nH2, *fy = fx + nU2;
-      int32_t *kx = fy + nV2, *ky = kx + nU2;
-      memset(cx, 0, 4 * (2 * nH2 + 2 * nU2 + 2 * nV2));
-      memcpy(su, obc->segnum_u, 4 * nU2); memcpy(sv, obc->segnum_v, 4 * nV2);
-      int32_t *cell[2] = {cx, cy}, *fa[2] = {fx, fy}, *skip[2] = {kx, ky};
-      for (int n = 0; n < nseg; n++) {
-        const mom6hip_obc_segment_t &S = obc->segment[n];
-        if (!S.on_pe) continue;
-        const bool ew = S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_W;
-        const int dd = ew ? 0 : 1;
-        const int A = ew ? S.IsdB : S.JsdB, c0 = ew ? S.jsd : S.isd, c1 = ew ? S.jed : S.ied;
-        const bool plus = S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_N;
-        for (int c = c0; c <= c1; c++) {
-          for (int a = A - OBC_STRIP; a <= A + OBC_STRIP; a++)      // the faces the lane kernel forms (OBC_STRIP above)
-            if (a >= (ew ? g.isd - 1 : g.jsd - 1) && a <= (ew ? g.ied : g.jed)) skip[dd][ew ? g.u2(a, c) : g.v2(c, a)] = 1;
-          const long ca = ew ? g.h2(A, c) : g.h2(c, A), cb = ew ? g.h2(A + 1, c) : g.h2(c, A + 1);
-          if (open_d[dd]) {      // PPM_reconstruction_x/y :2385-2432: zero slopes, then the edge values (a later segment has the last word)
-            cell[dd][ca] = 1 | ((plus ? 1 : 3) << 1);
-            cell[dd][cb] = 1 | ((plus ? 2 : 1) << 1);
-            if (S.open && (ew ? S.is_E_or_W : S.is_N_or_S)) fa[dd][ew ? g.u2(A, c) : g.v2(c, A)] = plus ? 1 : 2;      // :782-805, :1058-1088
-          }
-        }
-      }
-      return 0;
-    });
-    const SegDev *ds = (const SegDev *)m6::obc_table(ctx, m6::OBC_SITE_CONT, m6::obc_mix(key_segs, 0x5e95ull), sizeof(SegDev) * nseg,
-                                                     [&](void *host) -> int { memcpy(host, segs.data(), sizeof(SegDev) * nseg); return 0; });
-    if (!maps || !ds) return 1;
-    const int32_t *dsu = maps, *dsv = dsu + nU2, *dcx = dsv + nV2, *dcy = dcx + nH2, *dfx = dcy + nH2, *dfy = dfx + nU2;
-    ob[0].skip = dfy + nV2; ob[1].skip = ob[0].skip + nU2;
-    d_segs = ds;
-    const int pe = obc->OBC_pe != 0;
-    ob[0].on = ob[1].on = 1;
-    ob[0].open = open_d[0]; ob[1].open = open_d[1];
-    ob[0].specified = pe && obc->specified_u_BCs_exist_globally; ob[1].specified = pe && obc->specified_v_BCs_exist_globally;
-    ob[0].simple = pe && (obc->specified_u_BCs_exist_globally || obc->Flather_u_BCs_exist_globally);
-    ob[1].simple = pe && (obc->specified_v_BCs_exist_globally || obc->Flather_v_BCs_exist_globally);
-    ob[0].segnum = dsu; ob[1].segnum = dsv; ob[0].cell = dcx; ob[1].cell = dcy; ob[0].fa = dfx; ob[1].fa = dfy;
-  }
-  auto set_obc = [&](FluxArgs &f, int dd) {
-    f.obc_on = ob[dd].on; f.obc_open = ob[dd].open; f.obc_simple = ob[dd].simple; f.obc_specified = ob[dd].specified;
+  if (obc && obc->number_of_segments > 0)
+    if (const int rc = build_obc_tables(ctx, st, obc, c.ob, &d_segs)) return rc;
+  for (int dd = 0; dd < 2; dd++) {
+    FluxArgs &f = c.f[dd];
+    f.g = g; f.o = o; f.h_L = h_L; f.h_R = h_R; f.set_BT_cont = BT_cont != nullptr; f.dt = dt;
+    f.u = dd ? d_v : d_u; f.uhbt = dd ? d_vhbt : d_uhbt; f.visc_rem = dd ? d_vrv : d_vru;
+    f.uh = dd ? d_vh : d_uh; f.u_cor = dd ? d_vcor : d_ucor; f.du_cor = dd ? d_dvcor : d_ducor;
+    f.FA_0m = dd ? bt.FA_v_S0 : bt.FA_u_W0; f.FA_mm = dd ? bt.FA_v_SS : bt.FA_u_WW; f.FA_0p = dd ? bt.FA_v_N0 : bt.FA_u_E0;
+    f.FA_pp = dd ? bt.FA_v_NN : bt.FA_u_EE; f.uBT_mm = dd ? bt.vBT_SS : bt.uBT_WW; f.uBT_pp = dd ? bt.vBT_NN : bt.uBT_EE;
+    f.h_face = dd ? bt.h_v : bt.h_u;
+    const ObcDir &ob = c.ob[dd];
+    f.obc_on = ob.on; f.obc_open = ob.open; f.obc_simple = ob.simple; f.obc_specified = ob.specified;
     f.obc_dir_plus = dd ? MOM6HIP_OBC_DIRECTION_N : MOM6HIP_OBC_DIRECTION_E;
-    f.segnum = ob[dd].segnum; f.fa_code = ob[dd].fa; f.segs = d_segs; f.skip = nullptr; f.xcd_w = 0; f.nbx = 0;
-  };
-
-  // With open boundaries the block-cooperative kernels run over the whole range as on a closed domain but leave the faces a segment can
-  // reach alone (FluxArgs::skip); those are formed by the lane kernel with the OBC, on the side stream at the same time (a face's column
-  // depends on its own inputs only, and both kernels leave the same bits where no segment reaches; the lane kernel's walk of a column
-  // takes as long for a strip as for the grid, so it has to run beside the block kernel, not after it).  What a segment at face A of its direction reaches: the face itself (flux_layer :956-971, the
-  // specified transports :629-634, the face areas :782-805) and, through the zeroed slopes and the copied edge values of the cells A
-  // and A+1 (PPM_reconstruction :2385-2432) that enter the edge values of A-1 .. A+2, the faces A-2 .. A+2 -- along the segment's own
-  // extent (its cell codes and face codes are set there only).  OBC_STRIP = 3 faces either side.
-  static const bool strips_off = getenv("MOM6HIP_CONT_OBC_STRIPS") && atoi(getenv("MOM6HIP_CONT_OBC_STRIPS")) == 0;
-  auto side_fork = [&]() -> int {      // the side streams wait for what the compute stream has been given so far
-    if (!ctx->side_fork) {
-      for (hipStream_t &st : ctx->side_stream) M6_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      M6_HIP(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
-      for (hipEvent_t &e : ctx->side_join) M6_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    M6_HIP(hipEventRecord(ctx->side_fork, s));
-    for (hipStream_t st : ctx->side_stream) M6_HIP(hipStreamWaitEvent(st, ctx->side_fork, 0));
-    return 0;
-  };
-  auto side_join = [&]() -> int {      // the compute stream waits for the side streams
-    M6_HIP(hipGetLastError());
-    for (int q = 0; q < mom6hip_ctx::NSIDE; q++) {
-      M6_HIP(hipEventRecord(ctx->side_join[q], ctx->side_stream[q]));
-      M6_HIP(hipStreamWaitEvent(s, ctx->side_join[q], 0));
-    }
-    return 0;
-  };
-  auto obc_strips = [&](const FluxArgs &f) -> bool {
-    if (!f.obc_on || strips_off) return false;
-    FluxArgs c = f; c.obc_on = 0;
-    return flux_is_coop(c);
-  };
-  // hdst: where the thicknesses after this direction go (the output array, or the scratch of the phased call)
+    f.segnum = ob.segnum; f.fa_code = ob.fa; f.segs = d_segs; f.skip = nullptr;
+  }
+  // the zonal pass of the rows jsh .. jeh (hdst: where the thicknesses after it go: the output array, or the scratch of the phased
+  // call); the meridional pass of the columns ish .. ieh: faces fj0 .. fj1, then the cells cj0 .. cj1
   auto zonal = [&](const double *hsrc, int jsh, int jeh, double hmin, double *hdst, double *also) -> int {
-    if (jeh < jsh) return 0;
-    FluxArgs f; f.g = g; f.o = o; f.u = d_u; f.h_in = hsrc; f.h_L = h_L; f.h_R = h_R; f.uhbt = d_uhbt; f.visc_rem = d_vru;
-    f.uh = d_uh; f.u_cor = d_ucor; f.du_cor = d_ducor;
-    f.FA_0m = bt.FA_u_W0; f.FA_mm = bt.FA_u_WW; f.FA_0p = bt.FA_u_E0; f.FA_pp = bt.FA_u_EE; f.uBT_mm = bt.uBT_WW;
-    f.uBT_pp = bt.uBT_EE; f.h_face = bt.h_u; f.set_BT_cont = BT_cont != nullptr; f.dt = dt;
-    f.fi0 = is - 1; f.fi1 = ie; f.fj0 = jsh; f.fj1 = jeh;
-    set_obc(f, 0);
-    const bool strips = obc_strips(f);
-    if (strips) {      // the faces an E or W segment can reach: the lane kernel with the OBC, on the side stream beside the block kernel
-      if (side_fork()) return 1;
-      int nstrip = 0;
-      for (int n = 0; n < obc->number_of_segments; n++) {
-        const mom6hip_obc_segment_t &S = obc->segment[n];
-        if (!S.on_pe || !(S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_W)) continue;
-        hipStream_t ss = ctx->side_stream[nstrip++ % mom6hip_ctx::NSIDE];      // (a strip's walk is latency: strips run beside each other)
-        FluxArgs fl = f;
-        fl.fi0 = std::max(is - 1, S.IsdB - OBC_STRIP); fl.fi1 = std::min(ie, S.IsdB + OBC_STRIP);
-        fl.fj0 = std::max(jsh, S.jsd); fl.fj1 = std::min(jeh, S.jed);
-        if (fl.fi1 < fl.fi0 || fl.fj1 < fl.fj0) continue;
-        EdgeArgs e; e.g = g; e.o = o; e.h_in = hsrc; e.h_L = h_L; e.h_R = h_R; e.cell_code = ob[0].open ? ob[0].cell : nullptr;
-        e.i0 = fl.fi0; e.i1 = fl.fi1 + 1; e.j0 = fl.fj0; e.j1 = fl.fj1;
-        hipLaunchKernelGGL(cont_edge_kernel<0>, dim3((e.i1 - e.i0 + 256) / 256, e.j1 - e.j0 + 1, g.nk), dim3(256), 0, ss, e);
-        hipLaunchKernelGGL(cont_flux_kernel<0>, dim3((fl.fi1 - fl.fi0 + 64) / 64, fl.fj1 - fl.fj0 + 1), dim3(64), 0, ss, fl);
-      }
-      f.obc_on = 0; f.skip = ob[0].skip;
-    }
-    if (!flux_is_coop(f)) {
-      EdgeArgs e; e.g = g; e.o = o; e.h_in = hsrc; e.h_L = h_L; e.h_R = h_R; e.cell_code = ob[0].open ? ob[0].cell : nullptr;
-      e.i0 = is - 1; e.i1 = ie + 1; e.j0 = jsh; e.j1 = jeh;
-      hipLaunchKernelGGL(cont_edge_kernel<0>, dim3((e.i1 - e.i0 + 256) / 256, jeh - jsh + 1, g.nk), dim3(256), 0, s, e);
-    }
-    { m6::KTimer kt(ctx, MOM6HIP_KT_CONT_FLUX_X);
-      if (launch_flux<0>(ctx, f, f.fi1 - f.fi0 + 1, jeh - jsh + 1)) return 1; }
-    if (strips && side_join()) return 1;
-    if (!x_first && ctx->cont_fluxes_only) return 0;      // (the second direction's thicknesses are not wanted: see the context)
-    ConvArgs c; c.g = g; c.hin = hsrc; c.uh = d_uh; c.h = hdst; c.dt = dt; c.h_min = hmin;
-    c.i0 = is; c.i1 = ie; c.j0 = jsh; c.j1 = jeh; c.h2 = also; c.j2lo = js; c.j2hi = je;
-    hipLaunchKernelGGL(cont_conv_kernel<0>, dim3((ie - is + 256) / 256, jeh - jsh + 1, g.nk), dim3(256), 0, s, c);
-    M6_HIP(hipGetLastError());
-    return 0;
+    return cont_pass<0>(c, hsrc, hmin, is - 1, ie, jsh, jeh, is, ie, jsh, jeh, hdst, also, js, je);
   };
-  // faces fj0 .. fj1, then the cells cj0 .. cj1 (the whole call: js-1 .. je and js .. je)
   auto merid = [&](const double *hsrc, int ish, int ieh, double hmin, int fj0, int fj1, int cj0, int cj1) -> int {
-    FluxArgs f; f.g = g; f.o = o; f.u = d_v; f.h_in = hsrc; f.h_L = h_L; f.h_R = h_R; f.uhbt = d_vhbt; f.visc_rem = d_vrv;
-    f.uh = d_vh; f.u_cor = d_vcor; f.du_cor = d_dvcor;
-    f.FA_0m = bt.FA_v_S0; f.FA_mm = bt.FA_v_SS; f.FA_0p = bt.FA_v_N0; f.FA_pp = bt.FA_v_NN; f.uBT_mm = bt.vBT_SS;
-    f.uBT_pp = bt.vBT_NN; f.h_face = bt.h_v; f.set_BT_cont = BT_cont != nullptr; f.dt = dt;
-    f.fi0 = ish; f.fi1 = ieh; f.fj0 = fj0; f.fj1 = fj1;
-    set_obc(f, 1);
-    if (fj1 >= fj0) {
-      const bool strips = obc_strips(f);
-      if (strips) {      // the faces a N or S segment can reach: the lane kernel with the OBC, on the side stream beside the block kernel
-        if (side_fork()) return 1;
-        int nstrip = 0;
-        for (int n = 0; n < obc->number_of_segments; n++) {
-          const mom6hip_obc_segment_t &S = obc->segment[n];
-          if (!S.on_pe || !(S.direction == MOM6HIP_OBC_DIRECTION_N || S.direction == MOM6HIP_OBC_DIRECTION_S)) continue;
-          hipStream_t ss = ctx->side_stream[nstrip++ % mom6hip_ctx::NSIDE];
-          FluxArgs fl = f;
-          fl.fi0 = std::max(ish, S.isd); fl.fi1 = std::min(ieh, S.ied);
-          fl.fj0 = std::max(fj0, S.JsdB - OBC_STRIP); fl.fj1 = std::min(fj1, S.JsdB + OBC_STRIP);
-          if (fl.fi1 < fl.fi0 || fl.fj1 < fl.fj0) continue;
-          EdgeArgs e; e.g = g; e.o = o; e.h_in = hsrc; e.h_L = h_L; e.h_R = h_R; e.cell_code = ob[1].open ? ob[1].cell : nullptr;
-          e.i0 = fl.fi0; e.i1 = fl.fi1; e.j0 = fl.fj0; e.j1 = fl.fj1 + 1;
-          hipLaunchKernelGGL(cont_edge_kernel<1>, dim3((e.i1 - e.i0 + 256) / 256, (e.j1 - e.j0 + EDGE_RJ) / EDGE_RJ, g.nk), dim3(256), 0, ss, e);
-          hipLaunchKernelGGL(cont_flux_kernel<1>, dim3((fl.fi1 - fl.fi0 + 64) / 64, fl.fj1 - fl.fj0 + 1), dim3(64), 0, ss, fl);
-        }
-        f.obc_on = 0; f.skip = ob[1].skip;
-      }
-      if (!flux_is_coop(f)) {
-        EdgeArgs e; e.g = g; e.o = o; e.h_in = hsrc; e.h_L = h_L; e.h_R = h_R; e.cell_code = ob[1].open ? ob[1].cell : nullptr;
-        e.i0 = ish; e.i1 = ieh; e.j0 = fj0; e.j1 = fj1 + 1;
-        hipLaunchKernelGGL(cont_edge_kernel<1>, dim3((ieh - ish + 256) / 256, (e.j1 - e.j0 + EDGE_RJ) / EDGE_RJ, g.nk), dim3(256), 0, s, e);
-      }
-      { m6::KTimer kt(ctx, MOM6HIP_KT_CONT_FLUX_Y);
-        if (launch_flux<1>(ctx, f, ieh - ish + 1, f.fj1 - f.fj0 + 1)) return 1; }
-      if (strips && side_join()) return 1;
-    }
-    if (cj1 >= cj0 && !(x_first && ctx->cont_fluxes_only)) {
-      ConvArgs c; c.g = g; c.hin = hsrc; c.uh = d_vh; c.h = d_h; c.dt = dt; c.h_min = hmin;
-      c.i0 = ish; c.i1 = ieh; c.j0 = cj0; c.j1 = cj1;
-      hipLaunchKernelGGL(cont_conv_kernel<1>, dim3((ieh - ish + 256) / 256, cj1 - cj0 + 1, g.nk), dim3(256), 0, s, c);
-    }
-    M6_HIP(hipGetLastError());
-    return 0;
+    return cont_pass<1>(c, hsrc, hmin, ish, ieh, fj0, fj1, ish, ieh, cj0, cj1, d_h);
   };
 
   // ---- the phased call (ctx->cont_phase, set by the RK2 step around a group pass in flight; x first, device arrays) ----------

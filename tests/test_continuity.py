@@ -111,9 +111,9 @@ def test_gpu_parity(oracle, variant, first_direction):
     from mom6_amd.continuity import BT_cont_type, continuity
     from mom6_amd.tracer_advect import DeviceGrid
     cskw = VARIANTS[variant]
-    # nk = 20 and 75 reach the 4-layers-per-slab form and the deep form (6 waves x 7 layers, or MOM6HIP_CONT_COOP = 8x5 / 4x10) of the
-    # block-cooperative flux kernel, nk = 83 the last, partly filled slab of the 6 x 7 form; nk = 90 is past its register budget and
-    # takes the lane-per-column kernels
+    # nk = 20 and 75 reach the 4-layers-per-slab form and the deep forms (zonally 8 waves x 5 layers, meridionally 4 waves x 10 layers)
+    # of the block-cooperative flux kernels, with the last slabs partly filled; nk = 83 and 90 are past their 80 layers and take the
+    # lane-per-column kernels
     # the last grid has halo = the PPM stencil (3): the first pass then runs to the very edge of the data domain
     for (ni, nj, nk, topo, halo) in [(70, 21, 4, (True, False), 4), (44, 40, 2, (True, True), 4), (10, 8, 8, (False, False), 4),
                                      (36, 13, 20, (True, True), 4), (67, 9, 75, (True, False), 4), (14, 9, 90, (True, False), 4),
