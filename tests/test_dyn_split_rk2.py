@@ -1,6 +1,8 @@
 """step_MOM_dyn_split_RK2: the oracle's step (oracle/dyn_split_rk2.c, the reference's order of calls with zero
 viscosities) against invariants on the CPU, and the library's step against the oracle on the GPU, bit for bit,
 over several steps."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -497,3 +499,165 @@ def test_step_with_the_testing_switch_sets_matches_oracle_bitwise(name):
             an = a.cpu().numpy()
             assert bits_equal(an, b), (name, n, nm, float(np.abs(an - b).max()))
     dg.close()
+
+
+# ---- one context, one stepper after the other (the steppers share the context's scratch block) -----------------------------------
+@pytest.mark.gpu
+def test_steppers_sharing_one_context_match_oracle_bitwise():
+    """a closed RK2 step, an RK2B step, an RK2 step with open boundaries and a closed RK2 step again on one device grid, each from a
+    freshly initialised control structure and the same initial fields, each against its own oracle.  Closed edges in x and y: the halo
+    faces of up, vp beyond them are the ones no sweep writes, so they show what an earlier stepper left in the shared block.  The grid
+    keeps its walls (the closed steps need them): the segment along the eastern edge lies on masked faces, the one inside the domain
+    is a real open boundary."""
+    import copy
+    import torch
+    from mom6_amd.dynamics_split_rk2 import (initialize_dyn_split_RK2, initialize_dyn_split_RK2b, step_MOM_dyn_split_RK2,
+                                             step_MOM_dyn_split_RK2b)
+    from mom6_amd.tracer_advect import DeviceGrid
+    from mom6_amd.vert_friction import vertvisc_type
+    from mom6_amd.open_boundary import ocean_OBC_type
+    from test_dyn_split_rk2_obc import DT, HV, TC3_FLAGS, oracle_state, rk2_obc_case, visc_arrays
+    from test_hor_visc import REF_NAMES
+    U, V, H = _abi.POS_U, _abi.POS_V, _abi.POS_H
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    for viscous in (False, True):
+        g, d, taux, tauy, _ = rk2_obc_case(None, ni=22, nj=16, nk=3)
+        OBC = ocean_OBC_type(g, ["I=N,J=0:N,FLATHER,ORLANSKI", "J=7,I=N:0,SIMPLE"], gamma_uv=0.3, rx_max=10.0, **TC3_FLAGS)
+        OBC.rx_normal, OBC.ry_normal = g.zeros3(U), g.zeros3(V)
+        rng = np.random.default_rng(4)
+        for s in OBC.segment:      # external values of the specified and Flather segments
+            if s.on_pe and s.specified:
+                s.normal_vel[:] = 0.05 * rng.standard_normal(s.normal_vel.shape)
+                s.normal_trans[:] = s.normal_vel * (3.0e4 * (5.0 + 50.0 * rng.random(s.normal_vel.shape)))
+            if s.on_pe and s.Flather:
+                s.normal_vel_bt[:] = 0.02 * rng.standard_normal(s.normal_vel_bt.shape); s.SSH[:] = 0.05 * rng.standard_normal(s.SSH.shape)
+        OBCo = copy.deepcopy(OBC)
+        bbl = visc_arrays(g)
+        kw = dict(vertvisc=dict(KV=1.0e-3, HBBL=10.0), hor_visc={REF_NAMES[k]: x for k, x in HV.items()}) if viscous else {}
+        dg = DeviceGrid(g)
+        tx, ty = T(taux), T(tauy)
+        for n, (rk2b, obc) in enumerate([(False, None), (True, None), (False, OBC), (False, None)]):
+            ref = oracle_state(g, d, None if obc is None else OBCo, viscous, bbl=bbl, rk2b=rk2b)
+            ref.step(taux, tauy)
+            u, v, h, Tt, Ss = (T(d[k]) for k in ("u", "v", "h", "T", "S"))
+            Z = lambda pos, k3=True: torch.zeros(g.shape3(pos) if k3 else g.shape2(pos), dtype=torch.float64, device="cuda")
+            uh, vh, uhtr, vhtr, eta_av = Z(U), Z(V), Z(U), Z(V), Z(H, False)
+            CS = (initialize_dyn_split_RK2b if rk2b else initialize_dyn_split_RK2)(
+                u, v, h, uh, vh, DT, dg, coriolis=dict(bound_coriolis=True), OBC=None if obc is None else obc.cuda(), **kw)
+            CS.barotropic_CSp.st.dtbt = DT / 12.6
+            visc = vertvisc_type(**{k: T(a) for k, a in bbl.items()}) if viscous else None
+            (step_MOM_dyn_split_RK2b if rk2b else step_MOM_dyn_split_RK2)(u, v, h, (Tt, Ss), visc, None, DT, (tx, ty), None, None, uh, vh, uhtr,
+                                                                          vhtr, eta_av, dg, CS)
+            dg.sync()
+            want = dict(u=(u, ref.u), v=(v, ref.v), h=(h, ref.h), uh=(uh, ref.uh), vh=(vh, ref.vh), uhtr=(uhtr, ref.uhtr), vhtr=(vhtr, ref.vhtr),
+                        eta_av=(eta_av, ref.eta_av), u_av=(CS.u_av, ref.arrs["u_av"]), v_av=(CS.v_av, ref.arrs["v_av"]),
+                        diffu=(CS.diffu, ref.arrs["diffu"]), eta=(CS.eta, ref.arrs["eta"]), h_av=(CS.h_av, ref.arrs["h_av"]))
+            if not rk2b:
+                want["CAu_pred"] = (CS.CAu_pred, ref.arrs["CAu_pred"])
+            for name, (a, b) in want.items():
+                an = a.cpu().numpy()
+                assert bits_equal(an, b), (viscous, n, name, np.argwhere(an != b)[:4].tolist())
+            if obc is not None:
+                assert bits_equal(OBC.rx_normal.cpu().numpy(), OBCo.rx_normal) and bits_equal(OBC.ry_normal.cpu().numpy(), OBCo.ry_normal)
+        dg.close()
+
+
+# ---- the seams of the host's own viscosities (mom6hip_visc_hooks_t) ---------------------------------------------------------------
+_HOOK_REM = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p)
+_HOOK_HV = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+class _ViscHooks(C.Structure):      # mom6hip_visc_hooks_t
+    _fields_ = [("user", C.c_void_p), ("visc_remnant_pred", _HOOK_REM), ("vertvisc", _HOOK_REM), ("horizontal_viscosity", _HOOK_HV)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rk2b", [False, True], ids=["RK2", "RK2B"])
+def test_step_with_viscosity_hooks_matches_the_library_path_bitwise(rk2b):
+    """cs->hooks set to three callbacks that forward their device pointers to the library's own public entries, vertvisc_CSp = hor_visc =
+    NULL: the step through the hook seams (:592-600, :717-744, :860, :974-994) is the step with the library's own viscosity, and so the
+    oracle's, bit for bit.  (No DYNAMIC_VISCOUS_ML: the hook seam has no set_viscous_ML.)"""
+    import torch
+    from mom6_amd import dynamics_split_rk2 as m
+    from mom6_amd import hor_visc as hvm, vert_friction as vvm
+    from mom6_amd.tracer_advect import DeviceGrid
+    g, d, taux, tauy = make_case(ni=20, nj=16, nk=3)
+    dt, D = 1800.0, _abi.MEM_DEVICE
+    arrs = _visc_arrays(g)
+    HV = dict(Smag_bi_const=0.06, Ah_vel_scale=0.01)
+    ref = orc.DynState(g, d["u"], d["v"], d["h"], d["T"], d["S"], dt, rk2b=rk2b,
+                       vertvisc=orc.vertvisc_cs(g, Kv=1.0e-3, Hbbl=10.0, Hmix=20.0, Kvml_invZ2=1.0e-3), visc=orc.vertvisc_type(**arrs),
+                       hor_visc=orc.hor_visc_cs(g, dt, biharmonic=True, Smagorinsky_Ah=True, **HV))
+    ref.bcs.dtbt = dt / 9.6
+    params = dict(coriolis=dict(bound_coriolis=True), vertvisc=dict(KV=1.0e-3, HBBL=10.0, HMIX_FIXED=20.0, KV_ML_INVZ2=1.0e-3),
+                  hor_visc=dict(BIHARMONIC=True, SMAGORINSKY_AH=True, SMAG_BI_CONST=HV["Smag_bi_const"], AH_VEL_SCALE=HV["Ah_vel_scale"]))
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    step = m.step_MOM_dyn_split_RK2b if rk2b else m.step_MOM_dyn_split_RK2
+
+    def run(hooked):
+        dg = DeviceGrid(g)
+        u, v, h, Tt, Ss = (T(d[k]) for k in ("u", "v", "h", "T", "S"))
+        Z = lambda pos, k3=True: torch.zeros(g.shape3(pos) if k3 else g.shape2(pos), dtype=torch.float64, device="cuda")
+        uh, vh, uhtr, vhtr, eta_av = Z(_abi.POS_U), Z(_abi.POS_V), Z(_abi.POS_U), Z(_abi.POS_V), Z(_abi.POS_H, False)
+        visc = vvm.vertvisc_type(**{n: T(a) for n, a in arrs.items()})
+        tx, ty = T(taux), T(tauy)
+        calls = dict(rem=0, vv=0, hv=0)
+        if not hooked:
+            CS = (m.initialize_dyn_split_RK2b if rk2b else m.initialize_dyn_split_RK2)(u, v, h, uh, vh, dt, dg, **params)
+        else:
+            CS = m.MOM_dyn_split_RK2_CS(dg, DT=dt, **params)
+            L = m._setup(); vvm._setup(); hvm._setup()
+            vcs, hcs, vt = C.byref(CS.vertvisc_CSp.st), C.byref(CS.hor_visc.st), C.byref(visc.st)
+            bt = CS._bt_struct
+
+            def rem(user, up, vp, hh, dtx, vru, vrv):      # vertvisc_coef, vertvisc_remnant :598-600
+                calls["rem"] += 1
+                return int(L.mom6hip_vertvisc_coef(dg.handle, vcs, up, vp, hh, None, vt, dtx, D)
+                           or L.mom6hip_vertvisc_remnant(dg.handle, vcs, vt, vru, vrv, dtx, D))
+
+            def vv(user, uu, vv_, hh, dtx, vru, vrv):      # vertvisc_coef, vertvisc, vertvisc_remnant :717-744, :974-994
+                calls["vv"] += 1
+                return int(L.mom6hip_vertvisc_coef(dg.handle, vcs, uu, vv_, hh, None, vt, dtx, D)
+                           or L.mom6hip_vertvisc(dg.handle, vcs, uu, vv_, hh, tx.data_ptr(), ty.data_ptr(), vt, dtx, None, None, D)
+                           or L.mom6hip_vertvisc_remnant(dg.handle, vcs, vt, vru, vrv, dtx, D))
+
+            def hv(user, ua, va, ha, du, dv):      # horizontal_viscosity :860
+                calls["hv"] += 1
+                return int(L.mom6hip_horizontal_viscosity(dg.handle, hcs, ua, va, ha, du, dv, dt, bt.h_u, bt.h_v, D))
+
+            hooks = _ViscHooks(None, _HOOK_REM(rem), _HOOK_REM(vv), _HOOK_HV(hv))
+            CS._hooks = hooks      # (kept alive with the control structure)
+            CS.st.vertvisc_CSp, CS.st.hor_visc, CS.st.hooks = None, None, C.addressof(hooks)
+            if rk2b:
+                CS.split_RK2b = True
+                m.check(L.mom6hip_dyn_split_rk2b_init(dg.handle, C.byref(CS.st), h.data_ptr()), "initialize_dyn_split_RK2b")
+            else:
+                m.check(L.mom6hip_dyn_split_rk2_init(dg.handle, C.byref(CS.st), u.data_ptr(), v.data_ptr(), h.data_ptr(), uh.data_ptr(),
+                                                     vh.data_ptr(), dt), "initialize_dyn_split_RK2")
+            CS.module_is_initialized = True
+        CS.barotropic_CSp.st.dtbt = ref.bcs.dtbt
+        out = []
+        for n in range(2):
+            step(u, v, h, (Tt, Ss), visc, None, dt, (tx, ty), None, None, uh, vh, uhtr, vhtr, eta_av, dg, CS)
+            dg.sync()
+            f = dict(u=u, v=v, h=h, uh=uh, vh=vh, uhtr=uhtr, vhtr=vhtr, eta_av=eta_av, eta=CS.eta, u_av=CS.u_av, v_av=CS.v_av, h_av=CS.h_av,
+                     diffu=CS.diffu, diffv=CS.diffv, visc_rem_u=CS.visc_rem_u, visc_rem_v=CS.visc_rem_v, CAu=CS.CAu, CAu_pred=CS.CAu_pred,
+                     CAv_pred=CS.CAv_pred)
+            out.append({k: a.cpu().numpy().copy() for k, a in f.items()})
+        if hooked:      # every seam was taken: one predictor remnant, two vertvisc and one (RK2B: two) horizontal_viscosity a step
+            assert calls == dict(rem=2, vv=4, hv=4 if rk2b else 3), calls      # (RK2: one more from initialize_dyn_split_RK2 :1543-1550)
+        dg.close()
+        return out
+
+    lib_out, hook_out = run(False), run(True)
+    for n in range(2):
+        ref.step(taux, tauy)
+        want = dict(u=ref.u, v=ref.v, h=ref.h, uh=ref.uh, vh=ref.vh, uhtr=ref.uhtr, vhtr=ref.vhtr, eta_av=ref.eta_av,
+                    **{k: ref.arrs[k] for k in ("eta", "u_av", "v_av", "h_av", "diffu", "diffv", "visc_rem_u", "visc_rem_v")})
+        # (the Coriolis terms the neighbouring tests compare: in the RK2 scheme the library's CAu holds scratch of initialize_dyn_split_RK2
+        # beyond the faces CorAdCalc writes)
+        want.update({k: ref.arrs[k] for k in (("CAu", "CAv_pred") if rk2b else ("CAu_pred",))})
+        for name in hook_out[n]:
+            assert bits_equal(hook_out[n][name], lib_out[n][name]), (n, name, "hooks against the library's own viscosity")
+        for name, b in want.items():
+            assert bits_equal(hook_out[n][name], b), (n, name, float(np.abs(hook_out[n][name] - b).max()))
