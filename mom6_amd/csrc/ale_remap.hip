@@ -6,9 +6,11 @@
 // Remapping has two forms, both with lanes along i so that every k-strided access is a contiguous row across the wave:
 //   ale_remap_stream_kernel<NF>   PPM_H4 without boundary extrapolation on >= 6 layers (the OM4-class setting): one lane per column,
 //                                 one top-down walk with a constant amount of state and no arrays (its header below);
-//   ale_sub_cells_kernel + ale_remap_wave_kernel   every scheme (PCM, PLM, PPM_H4, PPM_IH4, PPM_CW, the three HYBGEN ones), with
-//                                 or without extrapolation: the sub-cell structure per column, then one WAVE per column with the
-//                                 column's arrays in LDS.
+//   ale_sub_cells_kernel + ale_remap_wave_kernel   every scheme (PCM, PLM, PPM_H4, PPM_IH4, PPM_CW, PQM_IH4IH3, PQM_IH6IH5 and the
+//                                 three HYBGEN ones), with or without extrapolation: the sub-cell structure per column, then one
+//                                 WAVE per column with the column's arrays in LDS.
+// The per-cell pieces of the reconstructions (edge weights, bounds, limiters, the tridiagonal solver) are scalar functions that both
+// forms call; the wave path has one function per stage of a scheme and w_build_reconstructions chooses among them.
 // Algorithmic traffic: read h_old, h_new once per launch + read/write each field = (16 / NF + 16) B per cell and field.
 #include <algorithm>
 #include <cfloat>
@@ -103,6 +105,118 @@ __device__ void end_value_h4(const double dz[4], const double u[4], double Csys[
   Csys[1] = (W12 * (u[1] - u[0]) + W22 * (u[2] - u[1])) + W32 * (u[3] - u[2]);
   Csys[2] = (W13 * (u[1] - u[0]) + W23 * (u[2] - u[1])) + W33 * (u[3] - u[2]);
   Csys[3] = (W14 * (u[1] - u[0]) + W24 * (u[2] - u[1])) + W34 * (u[3] - u[2]);
+}
+
+struct EdgeW { double A1, A2, B, Cc, Hs; };
+// the thickness-only factors of edge_values_explicit_h4 (regrid_edge_values.F90:262-300) at the interface above cell i
+__device__ __forceinline__ EdgeW edge_weights_h4(double h0, double h1, double h2, double h3, double hNeglect) {
+  const double hMinFrac = 1.e-5;
+  if (h0 + h1 == 0.0 || h1 + h2 == 0.0 || h2 + h3 == 0.0) {
+    const double h_min = hMinFrac * fmax(hNeglect, (h0 + h1) + (h2 + h3));
+    h0 = fmax(h_min, h0); h1 = fmax(h_min, h1); h2 = fmax(h_min, h2); h3 = fmax(h_min, h3);
+  }
+  const double I_h12 = 1.0 / (h1 + h2);
+  const double I_den_et2 = 1.0 / (((h0 + h1) + h2) * (h0 + h1)); const double I_h012 = (h0 + h1) * I_den_et2;
+  const double I_den_et3 = 1.0 / ((h1 + (h2 + h3)) * (h2 + h3)); const double I_h123 = (h2 + h3) * I_den_et3;
+  EdgeW w;
+  w.A1 = (1.0 + (h1 * I_h012 + (h0 + h1) * I_h123)) * I_h12 * (h2 * (h2 + h3));
+  w.A2 = (1.0 + (h2 * I_h123 + (h2 + h3) * I_h012)) * I_h12 * (h1 * (h0 + h1));
+  w.B = (h1 * (h2 * (h2 + h3)) * I_den_et2);
+  w.Cc = (h2 * (h1 * (h0 + h1)) * I_den_et3);
+  w.Hs = (h0 + h1) + (h2 + h3);
+  return w;
+}
+__device__ __forceinline__ double edge_value_h4(const EdgeW &w, double um2, double um1, double u0, double up1) {
+  const double et1 = w.A1 * um1 + w.A2 * u0;
+  const double et2 = w.B * (um1 - um2);
+  const double et3 = w.Cc * (u0 - up1);
+  return (et1 + (et2 + et3)) / w.Hs;
+}
+// the slope of bound_edge_values (regrid_edge_values.F90:71-82) with hr = h(k) / ((h(km1) + h(kp1)) + 2 h(k)) or a negative hr for "no slope"
+__device__ __forceinline__ double bound_slope(double ukm1, double uk, double ukp1, double hr) {
+  double slope_x_h = 0.0;
+  if (hr >= 0.0) {
+    const double sigma_l = (uk - ukm1);
+    const double sigma_c = (ukp1 - ukm1) * hr;
+    const double sigma_r = (ukp1 - uk);
+    if ((sigma_l * sigma_r) > 0.0) slope_x_h = fsign(min3(fabs(sigma_l), fabs(sigma_c), fabs(sigma_r)), sigma_c);
+  }
+  return slope_x_h;
+}
+__device__ __forceinline__ double bound_left(double EL, double ukm1, double uk, double slope) {
+  if ((ukm1 - EL) * (EL - uk) < 0.0) EL = uk - fsign(fmin(fabs(slope), fabs(EL - uk)), slope);
+  return fmax(fmin(EL, fmax(ukm1, uk)), fmin(ukm1, uk));
+}
+__device__ __forceinline__ double bound_right(double ER, double ukp1, double uk, double slope) {
+  if ((ukp1 - ER) * (ER - uk) < 0.0) ER = uk + fsign(fmin(fabs(slope), fabs(ER - uk)), slope);
+  return fmax(fmin(ER, fmax(ukp1, uk)), fmin(ukp1, uk));
+}
+// check_discontinuous_edge_values :141-159 at the interface between cells k and k+1 (er the right edge of k, el_next the left edge of
+// k+1): the test, and the value both edges take when it holds
+__device__ __forceinline__ bool edges_discontinuous(double u_k, double u_kp1, double er, double el_next) {
+  return (el_next - er) * (u_kp1 - u_k) < 0.0;
+}
+__device__ __forceinline__ double bounded_edge_average(double u_k, double u_kp1, double er, double el_next) {
+  const double u0_avg = 0.5 * (er + el_next);
+  return fmax(fmin(u0_avg, fmax(u_k, u_kp1)), fmin(u_k, u_kp1));
+}
+
+// ---- regrid_solvers.F90 ---------------------------------------------------------------------------
+// solve_diag_dominant_tridiag :246-280 as a serial walk by one lane; the solution overwrites the right-hand side, c1 is work space
+__device__ void solve_diag_dominant_tridiag(const double *tri_l, const double *tri_c, const double *tri_u, double *tri_b, double *c1, int N) {
+  double I_pivot = 1.0 / (tri_c[0] + tri_u[0]);
+  double d1 = tri_c[0] * I_pivot;
+  c1[0] = tri_u[0] * I_pivot;
+  tri_b[0] = tri_b[0] * I_pivot;
+  for (int k = 1; k < N - 1; k++) {
+    const double denom_t1 = tri_c[k] + d1 * tri_l[k];
+    I_pivot = 1.0 / (denom_t1 + tri_u[k]);
+    d1 = denom_t1 * I_pivot;
+    c1[k] = tri_u[k] * I_pivot;
+    tri_b[k] = (tri_b[k] - tri_l[k] * tri_b[k - 1]) * I_pivot;
+  }
+  I_pivot = 1.0 / (tri_c[N - 1] + d1 * tri_l[N - 1]);
+  tri_b[N - 1] = (tri_b[N - 1] - tri_l[N - 1] * tri_b[N - 2]) * I_pivot;
+  for (int k = N - 2; k >= 0; k--) tri_b[k] = tri_b[k] - c1[k] * tri_b[k + 1];
+}
+
+// ---- PPM_functions.F90, MOM_remapping.F90 -----------------------------------------------------------
+// PPM_limiter_standard for an interior cell (PPM_functions.F90:84-121)
+__device__ __forceinline__ void ppm_limit_cell(double u_l, double u_c, double u_r, double &edge_l, double &edge_r) {
+  if ((u_r - u_c) * (u_c - u_l) <= 0.0) {
+    edge_l = u_c; edge_r = u_c;
+  } else {
+    const double expr1 = 3.0 * (edge_r - edge_l) * ((u_c - edge_l) + (u_c - edge_r));
+    const double expr2 = (edge_r - edge_l) * (edge_r - edge_l);
+    if (expr1 > expr2) {
+      edge_l = u_c + 2.0 * (u_c - edge_r);
+      edge_l = fmax(fmin(edge_l, fmax(u_l, u_c)), fmin(u_l, u_c));
+    } else if (expr1 < -expr2) {
+      edge_r = u_c + 2.0 * (u_c - edge_l);
+      edge_r = fmax(fmin(edge_r, fmax(u_r, u_c)), fmin(u_r, u_c));
+    }
+  }
+  if (fabs(edge_r - edge_l) < fmax(1.e-60, DBL_EPSILON * fabs(u_c))) { edge_l = u_c; edge_r = u_c; }
+}
+// average_value_ppoly for INT_PPM (MOM_remapping.F90:998-1099)
+__device__ __forceinline__ double average_ppm(double a_L, double a_R, double u_c, double xa, double xb) {
+  if (xb > xa) {
+    const double mx = 0.5 * (xa + xb);
+    const double a_c = 0.5 * ((u_c - a_L) + (u_c - a_R));
+    if (mx < 0.5) {
+      const double xa2b2ab = (xa * xa + xb * xb) + xa * xb;
+      return a_L + ((a_R - a_L) * mx + a_c * (3. * (xb + xa) - 2. * xa2b2ab));
+    } else {
+      const double Ya = 1. - xa, Yb = 1. - xb;
+      const double my = 0.5 * (Ya + Yb);
+      const double Ya2b2ab = (Ya * Ya + Yb * Yb) + Ya * Yb;
+      return a_R + ((a_L - a_R) * my + a_c * (3. * (Yb + Ya) - 2. * Ya2b2ab));
+    }
+  }
+  const double Ya = 1. - xa;
+  const double a_c = 3. * ((u_c - a_L) + (u_c - a_R));
+  if (xa < 0.5) return a_L + xa * ((a_R - a_L) + a_c * Ya);
+  return a_R + Ya * ((a_L - a_R) + a_c * xa);
 }
 
 // ---- ALE_regrid, z* (MOM_regridding.F90:763-889, :1174-1284; coord_zlike.F90:63-144) ------------------------------
@@ -389,6 +503,38 @@ __device__ bool pqm_bad_inflexion(const Quartic &q, double slope, bool closed) {
   }
   return bad;
 }
+// A cell of mean u_c and width h_c whose quartic has a bad inflexion point: collapse the inflexion points onto the left edge
+// (PQM_limiter :271-294, PQM_boundary_extrapolation_v1 :634-657).  The bottom cell's extrapolation (:787-810) divides by the width
+// alone: it passes hNeglect = 0
+__device__ __forceinline__ void pqm_collapse_left(double u_c, double h_c, double hNeglect, double slope, double &u0_l, double &u0_r,
+                                                  double &u1_l, double &u1_r) {
+  u1_l = (10.0 * u_c - 2.0 * u0_r - 8.0 * u0_l) / (3.0 * h_c + hNeglect);
+  u1_r = (-10.0 * u_c + 6.0 * u0_r + 4.0 * u0_l) / (h_c + hNeglect);
+  if (u1_l * slope < 0.0) {
+    u1_l = 0.0;
+    u0_r = 5.0 * u_c - 4.0 * u0_l;
+    u1_r = 20.0 * (u_c - u0_l) / (h_c + hNeglect);
+  } else if (u1_r * slope < 0.0) {
+    u1_r = 0.0;
+    u0_l = (5.0 * u_c - 3.0 * u0_r) / 2.0;
+    u1_l = 10.0 * (-u_c + u0_r) / (3.0 * h_c + hNeglect);
+  }
+}
+// ... onto the right edge (PQM_limiter :296-319, PQM_boundary_extrapolation_v1 :787-810)
+__device__ __forceinline__ void pqm_collapse_right(double u_c, double h_c, double hNeglect, double slope, double &u0_l, double &u0_r,
+                                                   double &u1_l, double &u1_r) {
+  u1_r = (-10.0 * u_c + 8.0 * u0_r + 2.0 * u0_l) / (3.0 * h_c + hNeglect);
+  u1_l = (10.0 * u_c - 4.0 * u0_r - 6.0 * u0_l) / (h_c + hNeglect);
+  if (u1_l * slope < 0.0) {
+    u1_l = 0.0;
+    u0_r = (5.0 * u_c - 3.0 * u0_l) / 2.0;
+    u1_r = 10.0 * (u_c - u0_l) / (3.0 * h_c + hNeglect);
+  } else if (u1_r * slope < 0.0) {
+    u1_r = 0.0;
+    u0_l = 5.0 * u_c - 4.0 * u0_r;
+    u1_l = 20.0 * (-u_c + u0_r) / (h_c + hNeglect);
+  }
+}
 
 // ---- PQM_IH6IH5: the 6x6 systems behind edge_values_implicit_h6 and edge_slopes_implicit_h5 (regrid_edge_values.F90:977-1454)
 // linear_solver (regrid_solvers.F90:115-176): Gaussian elimination with the first nonzero pivot, A[row][col].  A singular system (a
@@ -580,539 +726,482 @@ __device__ void w_ih65_system(const WCol &c, int lane, int n, double hNeglect) {
   wsync();
 }
 
-// build_reconstructions_1d across the lanes; returns the integration method (uniform over the wave).
+// ---- build_reconstructions_1d across the lanes: the stages of the schemes, then the dispatcher -----------------------------------------
 // Of ppoly_coef only the slope column is stored: coef(:,1) always equals the left edge value, and coef(:,3) is only read
 // by the PPM boundary extrapolation, which recomputes it from the final edges with the expression that defined it.
-__device__ int w_build_reconstructions(const WCol &c, int lane, int scheme, bool extrap, int n, double h_neglect, double h_neglect_edge) {
+
+// The solution X[0 .. n] of a system over the interfaces, as the left and the right value of every cell
+__device__ void w_take_interfaces(const double *X, double *left, double *right, int lane, int n) {
+  for (int k = lane; k < n; k += 64) { left[k] = X[k]; right[k] = X[k + 1]; }
+  wsync();
+}
+
+// The cubic of end_value_h4 through the first (last = false) or the last four cells of the column, counted from the end, their widths
+// floored at hNeglect; returns the floored width of the end cell.  Lanes 62 and 63 call it in every h4 / h3 scheme: the two lanes that
+// have no second interior row to do, one code path for both ends
+__device__ double w_end_polynomial_h4(const WCol &c, bool last, int n, double hNeglect, double Cs[4]) {
+  double dz[4], ut[4];
+  for (int i = 0; i < 4; i++) { const int q = last ? n - 1 - i : i; dz[i] = fmax(hNeglect, c.h0[q]); ut[i] = c.u0[q]; }
+  end_value_h4(dz, ut, Cs);
+  return dz[0];
+}
+
+// PLM_boundary_extrapolation :272-307, by one lane
+__device__ void w_plm_boundary_extrapolation(const WCol &c, int n, double h_neglect) {
   const double *h = c.h0, *u = c.u0;
   double *EL = c.EL, *ER = c.ER;
+  double slope = -plm_extrapolate_slope(h[1], h[0], h_neglect, u[1], u[0]);
+  EL[0] = u[0] - 0.5 * slope; ER[0] = u[0] + 0.5 * slope;
+  c.C1[0] = ER[0] - EL[0];
+  slope = plm_extrapolate_slope(h[n - 2], h[n - 1], h_neglect, u[n - 2], u[n - 1]);
+  EL[n - 1] = u[n - 1] - 0.5 * slope; ER[n - 1] = u[n - 1] + 0.5 * slope;
+  c.C1[n - 1] = ER[n - 1] - EL[n - 1];
+}
+
+// PLM: PLM_reconstruction :190-260
+__device__ void w_plm(const WCol &c, int lane, int n, bool extrap, double h_neglect) {
+  const double *h = c.h0, *u = c.u0;
+  double *EL = c.EL, *ER = c.ER;
+  const double almost_one = 1. - DBL_EPSILON;
+  double *slp = c.u_sub, *mslp = c.uh_sub;      // free until the sub-cell pass
+  for (int k = lane; k < n; k += 64)
+    slp[k] = (k >= 1 && k < n - 1) ? plm_slope_wa(h[k - 1], h[k], h[k + 1], h_neglect, u[k - 1], u[k], u[k + 1]) : 0.;
+  wsync();
+  for (int k = lane; k < n; k += 64)
+    mslp[k] = (k >= 1 && k < n - 1) ? plm_monotonized_slope(u[k - 1], u[k], u[k + 1], slp[k - 1], slp[k], slp[k + 1]) : 0.;
+  wsync();
+  for (int k = lane; k < n; k += 64) {
+    if (k >= 1 && k < n - 1) {
+      const double slope = mslp[k];
+      const double u_l = u[k] - 0.5 * slope;
+      const double u_r = u[k] + 0.5 * slope;
+      EL[k] = u_l; ER[k] = u_r;
+      double c1 = (u_r - u_l);
+      const double edge = c1 + u_l;
+      const double e_r = u[k + 1] - 0.5 * fsign(mslp[k + 1], slp[k + 1]);
+      if ((edge - u[k]) * (e_r - edge) < 0.) c1 = c1 * almost_one;
+      c.C1[k] = c1;
+    } else {
+      EL[k] = u[k]; ER[k] = u[k]; c.C1[k] = 0.;
+    }
+  }
+  wsync();
+  if (extrap && lane == 0) w_plm_boundary_extrapolation(c, n, h_neglect);
+  wsync();
+}
+
+// PLM_HYBGEN: hybgen_plm_coefs (MOM_hybgen_remap.F90:14-88), MOM_remapping.F90:306-315
+__device__ void w_plm_hybgen(const WCol &c, int lane, int n, bool extrap, double h_neglect) {
+  const double *h = c.h0, *u = c.u0;
+  const double thin = h_neglect;
+  for (int k = lane; k < n; k += 64) {
+    double sl = 0.0;
+    if (k >= 1 && k < n - 1 && !(h[k] <= thin)) {
+      const double qcen = h[k] / (h[k] + 0.5 * (h[k - 1] + h[k + 1]));
+      const double ztop = 2.0 * (u[k] - u[k - 1]);
+      const double zbot = 2.0 * (u[k + 1] - u[k]);
+      const double zcen = qcen * (u[k + 1] - u[k - 1]);
+      if (ztop * zbot > 0.0) sl = fsign(min3(fabs(zcen), fabs(zbot), fabs(ztop)), zbot);
+    }
+    c.C1[k] = sl;
+    c.EL[k] = u[k] - 0.5 * sl;
+    c.ER[k] = u[k] + 0.5 * sl;
+  }
+  wsync();
+  if (extrap && lane == 0) w_plm_boundary_extrapolation(c, n, h_neglect);
+  wsync();
+}
+
+// WENO_HYBGEN: hybgen_weno_coefs (MOM_hybgen_remap.F90:226-386): the edge slopes, the two one-sided estimates of every cell with their
+// weights, the weighted edge values, the final limiter -- four passes across the lanes
+__device__ void w_edges_weno_hybgen(const WCol &c, int lane, int n, double thin) {
+  const double *h = c.h0, *u = c.u0;
+  double *EL = c.EL, *ER = c.ER;
+  const double min_ratio = 1.0e-8;
+  auto dp = [&](int k) { return fmax(h[k], thin); };
+  double *slope_edge = c.u_sub, *zw1 = c.uh_sub, *zw2 = c.uh_sub + n, *val_edge = c.C1;      // (free until the limiter / the sub-cell pass)
+  for (int K = lane + 1; K < n; K += 64) slope_edge[K] = (1.0 / (dp(K - 1) + dp(K))) * (u[K] - u[K - 1]);
+  wsync();
+  for (int k = lane; k < n; k += 64) {
+    double e1 = u[k], e2 = u[k], w1 = 0.0, w2 = 0.0;
+    if (k >= 1 && k < n - 1 && !((slope_edge[k] * slope_edge[k + 1] < 0.0) || (dp(k) <= thin))) {
+      const double dpkm2kp = dp(k - 1) + 2.0 * dp(k) + dp(k + 1);
+      const double qdpkmkp = 1.0 / (dp(k - 1) + dp(k) + dp(k + 1));
+      double seh1 = dp(k) * slope_edge[k + 1];
+      double seh2 = dp(k) * slope_edge[k];
+      const double q01 = dpkm2kp * slope_edge[k + 1];
+      const double q02 = dpkm2kp * slope_edge[k];
+      if (fabs(seh1) > fabs(q02)) seh1 = q02;
+      if (fabs(seh2) > fabs(q01)) seh2 = q01;
+      const double curv_cell = (seh1 - seh2) * qdpkmkp;
+      const double q001 = seh1 - curv_cell * dp(k + 1);
+      const double q002 = seh2 + curv_cell * dp(k - 1);
+      e2 = u[k] + q001;
+      e1 = u[k] - q002;
+      w1 = (2.0 * q001 - q002) * (2.0 * q001 - q002);
+      w2 = (2.0 * q002 - q001) * (2.0 * q002 - q001);
+    }
+    EL[k] = e1; ER[k] = e2; zw1[k] = w1; zw2[k] = w2;
+  }
+  wsync();
+  for (int K = lane + 1; K < n; K += 64) {
+    double wt1;
+    if (zw1[K] + zw2[K - 1] <= 0.0) wt1 = 0.5;
+    else if (zw1[K] <= min_ratio * (zw1[K] + zw2[K - 1])) wt1 = min_ratio;
+    else if (zw2[K - 1] <= min_ratio * (zw1[K] + zw2[K - 1])) wt1 = (1.0 - min_ratio);
+    else wt1 = zw1[K] / (zw1[K] + zw2[K - 1]);
+    val_edge[K] = wt1 * ER[K - 1] + (1.0 - wt1) * EL[K];
+  }
+  wsync();
+  for (int k = lane + 1; k < n - 1; k += 64) {
+    if (!(dp(k) <= thin)) {
+      double q01 = val_edge[k + 1] - u[k];
+      double q02 = u[k] - val_edge[k];
+      if (q01 * q02 < 0.0) { q01 = 0.0; q02 = 0.0; }
+      else if (fabs(q01) > fabs(2.0 * q02)) q01 = 2.0 * q02;
+      else if (fabs(q02) > fabs(2.0 * q01)) q02 = 2.0 * q01;
+      EL[k] = u[k] - q02;
+      ER[k] = u[k] + q01;
+    }
+  }
+  wsync();
+}
+
+// What edge_values_implicit_h4 and edge_slopes_implicit_h3 do alike once the interior rows 1 .. n-1 of their tridiagonal system stand in
+// u_sub (lower diagonal, then the central one) and uh_sub (upper diagonal, then the right-hand side): the closing rows 0 and n from the
+// end polynomials -- their value, or with `slopes` their outward derivative -- on lanes 62 and 63, the solve by lane 0 with C1 as its work
+// array, and the solution as the left and the right value of every cell
+__device__ void w_close_and_solve_h4(const WCol &c, int lane, int n, double hNeglect, bool slopes, double *left, double *right) {
+  double *tri_l = c.u_sub, *tri_c = c.u_sub + (n + 1), *tri_u = c.uh_sub, *tri_b = c.uh_sub + (n + 1);
+  if (lane >= 62) {
+    const bool last = lane == 63;
+    double Cs[4];
+    w_end_polynomial_h4(c, last, n, hNeglect, Cs);
+    const int row = last ? n : 0;
+    tri_b[row] = slopes ? (last ? -Cs[1] : Cs[1]) : Cs[0];
+    tri_c[row] = 1.0; tri_u[row] = 0.0; tri_l[row] = 0.0;
+  }
+  wsync();
+  if (lane == 0) solve_diag_dominant_tridiag(tri_l, tri_c, tri_u, tri_b, c.C1, n + 1);
+  wsync();
+  w_take_interfaces(tri_b, left, right, lane, n);
+}
+
+// PPM_IH4, PQM_IH4IH3: edge_values_implicit_h4 (regrid_edge_values.F90:491-654, answer_date >= 20190101), the interior rows of the
+// tridiagonal system across the lanes
+__device__ void w_edges_implicit_h4(const WCol &c, int lane, int n, double hNeglect) {
+  const double *h = c.h0, *u = c.u0;
+  double *tri_l = c.u_sub, *tri_c = c.u_sub + (n + 1), *tri_u = c.uh_sub, *tri_b = c.uh_sub + (n + 1);
+  for (int i = lane; i < n - 1; i += 64) {
+    double h0 = fmax(h[i], hNeglect);
+    double h1 = fmax(h[i + 1], hNeglect);
+    if (fabs(h0) < 1.0e-12 * fabs(h1)) h0 = 1.0e-12 * h1;
+    if (fabs(h1) < 1.0e-12 * fabs(h0)) h1 = 1.0e-12 * h0;
+    const double I_h2 = 1.0 / ((h0 + h1) * (h0 + h1));
+    const double alpha = (h1 * h1) * I_h2;
+    const double beta = (h0 * h0) * I_h2;
+    const double abmix = (h0 * h1) * I_h2;
+    const double a = 2.0 * alpha * (alpha + 2.0 * beta + 3.0 * abmix);
+    const double b = 2.0 * beta * (beta + 2.0 * alpha + 3.0 * abmix);
+    tri_c[i + 1] = 2.0 * abmix; tri_l[i + 1] = alpha; tri_u[i + 1] = beta;
+    tri_b[i + 1] = a * u[i] + b * u[i + 1];
+  }
+  w_close_and_solve_h4(c, lane, n, hNeglect, false, c.EL, c.ER);
+}
+
+// PQM_IH4IH3: edge_slopes_implicit_h3 (regrid_edge_values.F90:803-972, answer_date >= 20190101): the same shape of system as the edge
+// values', with h_neglect; the left slopes go to C1 (the solver's work array until then), the right ones to SR
+__device__ void w_slopes_implicit_h3(const WCol &c, int lane, int n, double hNeglect) {
+  const double *h = c.h0, *u = c.u0;
+  double *tri_l = c.u_sub, *tri_c = c.u_sub + (n + 1), *tri_u = c.uh_sub, *tri_b = c.uh_sub + (n + 1);
+  for (int i = lane; i < n - 1; i += 64) {
+    double h0 = fmax(h[i], hNeglect);
+    double h1 = fmax(h[i + 1], hNeglect);
+    const double I_h = 1.0 / (h0 + h1);
+    h0 = h0 * I_h; h1 = h1 * I_h;
+    const double h0h1 = h0 * h1, h0_2 = h0 * h0, h1_2 = h1 * h1;
+    const double h0_3 = h0_2 * h0, h1_3 = h1_2 * h1;
+    const double I_d = 1.0 / (4.0 * h0h1 * (h0 + h1) + h1_3 + h0_3);
+    tri_l[i + 1] = (h1 * ((h0_2 + h0h1) - h1_2)) * I_d;
+    tri_c[i + 1] = 2.0 * ((h0_2 + h1_2) * (h0 + h1)) * I_d;
+    tri_u[i + 1] = (h0 * ((h1_2 + h0h1) - h0_2)) * I_d;
+    tri_b[i + 1] = 12.0 * (h0h1 * I_d) * ((u[i + 1] - u[i]) * I_h);
+  }
+  w_close_and_solve_h4(c, lane, n, hNeglect, true, c.C1, c.SR);
+}
+
+// PPM_CW: edge_values_explicit_h4cw (regrid_edge_values.F90:381-463) and PPM_monotonicity (PPM_functions.F90:132).
+// PPM_HYBGEN (hyb): hybgen_ppm_coefs (MOM_hybgen_remap.F90:91-222), the HYCOM routine the two above re-express: the same
+// arithmetic with the minimum thickness `thin` = hNeglect and layers no thicker than it treated as PCM (:140-147)
+__device__ void w_edges_h4cw(const WCol &c, int lane, int n, bool hyb, double hNeglect) {
+  const double *h = c.h0, *u = c.u0;
+  double *EL = c.EL, *ER = c.ER;
+  double *au = c.u_sub;      // the limited slopes of Colella & Woodward eq. 1.8, 0-based cell index
+  auto dp = [&](int k) { return fmax(h[k], hNeglect); };      // 0-based; the reference's dp(k+1)
+  auto pcm = [&](int k) { return hyb && (dp(k) <= hNeglect); };
+  for (int k = lane; k < n; k += 64) {
+    double a = 0.;
+    if (k >= 1 && k <= n - 2) {
+      const double slk = u[k] - u[k - 1];
+      const double srk = u[k + 1] - u[k];
+      if (!pcm(k) && slk * srk > 0.) {
+        // h2_h123(k), h112(K), I_h12(K+1), h122(K+1), I_h12(K) of the reference with K = k+1 (1-based)
+        const double h2_h123 = dp(k) / (dp(k) + (dp(k - 1) + dp(k + 1)));
+        const double h112 = 2. * dp(k - 1) + dp(k), h122p = dp(k) + 2. * dp(k + 1);
+        const double I_h12 = 1.0 / (dp(k - 1) + dp(k)), I_h12p = 1.0 / (dp(k) + dp(k + 1));
+        const double sck = h2_h123 * (h112 * srk * I_h12p + h122p * slk * I_h12);
+        a = fsign(min3(fabs(2.0 * slk), fabs(sck), fabs(2.0 * srk)), sck);
+      }
+    }
+    au[k] = a;
+  }
+  wsync();
+  for (int k = lane; k < n; k += 64) {      // al(k): the edge between cells k-1 and k; also ar(k-1)
+    if (k >= 2 && k <= n - 2) {
+      const double I_h12 = 1.0 / (dp(k - 1) + dp(k));
+      const double I_h0123 = 1.0 / ((dp(k - 2) + dp(k - 1)) + (dp(k) + dp(k + 1)));
+      const double h01_h112 = (dp(k - 2) + dp(k - 1)) / (2.0 * dp(k - 1) + dp(k));
+      const double h23_h122 = (dp(k) + dp(k + 1)) / (dp(k - 1) + 2.0 * dp(k));
+      const double al = (dp(k) * u[k - 1] + dp(k - 1) * u[k]) * I_h12 +
+                        I_h0123 * (2. * dp(k) * dp(k - 1) * I_h12 * (u[k] - u[k - 1]) * (h01_h112 - h23_h122) +
+                                   (dp(k) * au[k - 1] * h23_h122 - dp(k - 1) * au[k] * h01_h112));
+      EL[k] = al; ER[k - 1] = al;
+    }
+  }
+  if (lane == 0) { EL[0] = u[0]; ER[0] = u[0]; EL[1] = u[0]; ER[n - 2] = u[n - 1]; EL[n - 1] = u[n - 1]; ER[n - 1] = u[n - 1]; }
+  wsync();
+  for (int k = lane + 1; k < n - 1; k += 64) {      // PPM_monotonicity
+    if (pcm(k) || (u[k + 1] - u[k]) * (u[k] - u[k - 1]) <= 0.) {
+      EL[k] = u[k]; ER[k] = u[k];
+    } else {
+      const double da = ER[k] - EL[k];
+      const double a6 = 6.0 * u[k] - 3.0 * (EL[k] + ER[k]);
+      if (da * a6 > da * da) EL[k] = 3.0 * u[k] - 2.0 * ER[k];
+      else if (da * a6 < -da * da) ER[k] = 3.0 * u[k] - 2.0 * EL[k];
+    }
+  }
+  wsync();
+}
+
+// PPM_H4: edge_values_explicit_h4 :222-363
+__device__ void w_edges_explicit_h4(const WCol &c, int lane, int n, double hNeglect) {
+  const double *h = c.h0, *u = c.u0;
+  double *EL = c.EL, *ER = c.ER;
+  for (int i = lane + 2; i <= n - 2; i += 64) {
+    const EdgeW w = edge_weights_h4(h[i - 2], h[i - 1], h[i], h[i + 1], hNeglect);
+    const double ev = edge_value_h4(w, u[i - 2], u[i - 1], u[i], u[i + 1]);
+    EL[i] = ev; ER[i - 1] = ev;
+  }
+  if (lane >= 62) {      // the end values: the first (lane 62) and the last (lane 63) two interfaces
+    const bool last = lane == 63;
+    double Cs[4];
+    const double dz0 = w_end_polynomial_h4(c, last, n, hNeglect, Cs);
+    const double inner = Cs[0] + dz0 * (Cs[1] + dz0 * (Cs[2] + dz0 * Cs[3]));
+    if (last) { ER[n - 1] = Cs[0]; EL[n - 1] = inner; ER[n - 2] = inner; }
+    else { EL[0] = Cs[0]; ER[0] = inner; EL[1] = inner; }
+  }
+  wsync();
+}
+
+// PPM_reconstruction / PQM_limiter, first part: bound_edge_values :44-110, check_discontinuous_edge_values :141-159
+__device__ void w_bound_and_check(const WCol &c, int lane, int n) {
+  const double *h = c.h0, *u = c.u0;
+  double *EL = c.EL, *ER = c.ER;
+  for (int k = lane; k < n; k += 64) {
+    const int km1 = (k - 1 > 0) ? k - 1 : 0, kp1 = (k + 1 < n - 1) ? k + 1 : n - 1;
+    const double den = (h[km1] + h[kp1]) + 2.0 * h[k];
+    const double slope_x_h = bound_slope(u[km1], u[k], u[kp1], den > 0.0 ? h[k] / den : -1.0);
+    const double el = bound_left(EL[k], u[km1], u[k], slope_x_h);
+    const double er = bound_right(ER[k], u[kp1], u[k], slope_x_h);
+    EL[k] = el; ER[k] = er;
+  }
+  wsync();
+  for (int k = lane; k < n - 1; k += 64) {
+    if (edges_discontinuous(u[k], u[k + 1], ER[k], EL[k + 1])) {
+      const double u0_avg = bounded_edge_average(u[k], u[k + 1], ER[k], EL[k + 1]);
+      ER[k] = u0_avg; EL[k + 1] = u0_avg;
+    }
+  }
+  wsync();
+}
+
+// PPM_limiter_standard (PPM_functions.F90:84-121) and the slope column of ppoly_coef
+__device__ void w_ppm_limit(const WCol &c, int lane, int n) {
+  const double *u = c.u0;
+  for (int k = lane; k < n; k += 64) {
+    double edge_l = u[k], edge_r = u[k];      // the boundary cells are piecewise constant
+    if (k >= 1 && k < n - 1) {
+      edge_l = c.EL[k]; edge_r = c.ER[k];
+      ppm_limit_cell(u[k - 1], u[k], u[k + 1], edge_l, edge_r);
+    }
+    c.EL[k] = edge_l; c.ER[k] = edge_r;
+    c.C1[k] = 4.0 * (u[k] - edge_l) + 2.0 * (u[k] - edge_r);
+  }
+  wsync();
+}
+
+// PPM_boundary_extrapolation (PPM_functions.F90:162-316), by one lane
+__device__ void w_ppm_boundary_extrapolation(const WCol &c, int n, double h_neglect) {
+  const double *h = c.h0, *u = c.u0;
+  double *EL = c.EL, *ER = c.ER;
+  int i0 = 0, i1 = 1;
+  double h0 = h[i0], h1 = h[i1], u0 = u[i0], u1 = u[i1];
+  double b = c.C1[i1];
+  double u1_r = b * ((h0 + h_neglect) / (h1 + h_neglect));
+  double slope = 2.0 * (u1 - u0);
+  if (fabs(u1_r) > fabs(slope)) u1_r = slope;
+  double u0_r = EL[i1];
+  double u0_l = 3.0 * u0 + 0.5 * u1_r - 2.0 * u0_r;
+  double exp1 = (u0_r - u0_l) * (u0 - 0.5 * (u0_l + u0_r));
+  double exp2 = (u0_r - u0_l) * (u0_r - u0_l) / 6.0;
+  if (exp1 > exp2) u0_l = 3.0 * u0 - 2.0 * u0_r;
+  if (exp1 < -exp2) u0_r = 3.0 * u0 - 2.0 * u0_l;
+  EL[i0] = u0_l; ER[i0] = u0_r;
+  c.C1[i0] = 6.0 * u0 - 4.0 * u0_l - 2.0 * u0_r;
+  i0 = n - 2; i1 = n - 1;
+  h0 = h[i0]; h1 = h[i1]; u0 = u[i0]; u1 = u[i1];
+  b = c.C1[i0];
+  const double cc = 3.0 * ((ER[i0] - u[i0]) + (EL[i0] - u[i0]));      // ppoly_coef(i0,3)
+  double u1_l = (b + 2 * cc);
+  u1_l = u1_l * ((h1 + h_neglect) / (h0 + h_neglect));
+  slope = 2.0 * (u1 - u0);
+  if (fabs(u1_l) > fabs(slope)) u1_l = slope;
+  u0_l = ER[i0];
+  u0_r = 3.0 * u1 - 0.5 * u1_l - 2.0 * u0_l;
+  exp1 = (u0_r - u0_l) * (u1 - 0.5 * (u0_l + u0_r));
+  exp2 = (u0_r - u0_l) * (u0_r - u0_l) / 6.0;
+  if (exp1 > exp2) u0_l = 3.0 * u1 - 2.0 * u0_r;
+  if (exp1 < -exp2) u0_r = 3.0 * u1 - 2.0 * u0_l;
+  EL[i1] = u0_l; ER[i1] = u0_r;
+  c.C1[i1] = 6.0 * u1 - 4.0 * u0_l - 2.0 * u0_r;
+}
+
+// PQM_limiter (PQM_functions.F90:103-337): a cell reads its own edge values and slopes and its neighbours' means and widths
+__device__ void w_pqm_limit(const WCol &c, int lane, int n, double hNeglect) {
+  const double *h = c.h0, *u = c.u0;
+  double *EL = c.EL, *ER = c.ER, *SL = c.C1, *SR = c.SR;
+  for (int k = lane; k < n; k += 64) {
+    double u0_l = u[k], u0_r = u[k], u1_l = 0.0, u1_r = 0.0;      // the boundary cells :331-335
+    if (k >= 1 && k < n - 1) {
+      u0_l = EL[k]; u0_r = ER[k]; u1_l = SL[k]; u1_r = SR[k];
+      const double h_l = h[k - 1], h_c = h[k], h_r = h[k + 1];
+      const double u_l = u[k - 1], u_c = u[k], u_r = u[k + 1];
+      const double sigma_l = 2.0 * (u_c - u_l) / (h_c + hNeglect);
+      const double sigma_c = 2.0 * (u_r - u_l) / (h_l + 2.0 * h_c + h_r + hNeglect);
+      const double sigma_r = 2.0 * (u_r - u_c) / (h_c + hNeglect);
+      double slope = 0.0;
+      if ((sigma_l * sigma_r) > 0.0) slope = fsign(min3(fabs(sigma_l), fabs(sigma_c), fabs(sigma_r)), sigma_c);
+      if (u1_l * slope <= 0.0) u1_l = slope;
+      if (u1_r * slope <= 0.0) u1_r = slope;
+      if ((u0_r - u_c) * (u_c - u0_l) <= 0.0) {      // a local extremum: flat
+        u0_l = u_c; u0_r = u_c; u1_l = 0.0; u1_r = 0.0;
+      } else if (pqm_bad_inflexion(pqm_quartic(u_c, h_c, u0_l, u0_r, u1_l, u1_r), slope, true)) {
+        if (fabs(sigma_l) < fabs(sigma_r)) pqm_collapse_left(u_c, h_c, hNeglect, slope, u0_l, u0_r, u1_l, u1_r);
+        else pqm_collapse_right(u_c, h_c, hNeglect, slope, u0_l, u0_r, u1_l, u1_r);
+      }
+    }
+    EL[k] = u0_l; ER[k] = u0_r; SL[k] = u1_l; SR[k] = u1_r;
+  }
+  wsync();
+}
+
+// PQM_boundary_extrapolation_v1 (PQM_functions.F90:502-831) for the top or the bottom cell, by one lane each: the two read cells 1
+// and n-2 and write cells 0 and n-1 (n >= 5 here)
+__device__ void w_pqm_boundary_extrapolation(const WCol &c, bool bottom, int n, double hNeglect) {
+  const double *h = c.h0, *u = c.u0;
+  double *EL = c.EL, *ER = c.ER, *SL = c.C1, *SR = c.SR;
+  double u0_l, u0_r, u1_l, u1_r, slope, um;
+  if (!bottom) {
+    const double h0 = h[0], h1 = h[1], u0 = u[0], u1 = u[1];
+    um = u0;
+    slope = 2.0 * (u1 - u0) / ((h0 + h1) + hNeglect);
+    slope = slope * h0;
+    u0_r = EL[1];                                   // ppoly_coef(i1,1)
+    u1_r = (h1 * SL[1]) / (h1 + hNeglect);          // ppoly_coef(i1,2) / (h1 + hNeglect)
+    double beta = 0.;
+    if (u1_r != 0.) beta = 2.0 * (u0_r - um) / ((h0 + hNeglect) * u1_r) - 1.0;
+    const double br = u0_r + beta * u0_r - um;
+    const double ar = um + beta * um - br;
+    u0_l = ar;
+    const double u_plm = um - 0.5 * slope;
+    if (fabs(um - u0_l) < fabs(um - u_plm)) {
+      u1_l = 2.0 * (br - ar * beta);
+      u1_l = u1_l / (h0 + hNeglect);
+    } else {
+      u0_l = u_plm;
+      u1_l = slope / (h0 + hNeglect);
+    }
+    if (pqm_bad_inflexion(pqm_quartic(um, h0, u0_l, u0_r, u1_l, u1_r), slope, false))
+      pqm_collapse_left(um, h0, hNeglect, slope, u0_l, u0_r, u1_l, u1_r);
+  } else {
+    const int i0 = n - 2, i1 = n - 1;
+    const double h0 = h[i0], h1 = h[i1], u0 = u[i0], u1 = u[i1];
+    um = u1;
+    slope = 2.0 * (u1 - u0) / (h0 + h1);
+    slope = slope * h1;
+    const Quartic q0 = pqm_quartic(u0, h0, EL[i0], ER[i0], SL[i0], SR[i0]);      // ppoly_coef(i0,:), a = EL[i0]
+    u0_l = EL[i0] + q0.b + q0.c + q0.d + q0.e;
+    u1_l = (q0.b + 2 * q0.c + 3 * q0.d + 4 * q0.e) / h0;
+    double beta = 0.;
+    if (um - u0_l != 0.) beta = 0.5 * h1 * u1_l / (um - u0_l) - 1.0;
+    const double br = beta * um + um - u0_l;
+    const double ar = u0_l;
+    if (1 + beta != 0.) u0_r = (ar + 2 * br + beta * br) / ((1 + beta) * (1 + beta));
+    else u0_r = um + 0.5 * slope;
+    const double u_plm = um + 0.5 * slope;
+    if (fabs(um - u0_r) < fabs(um - u_plm)) {
+      u1_r = 2.0 * (br - ar * beta) / ((1 + beta) * (1 + beta) * (1 + beta));
+      u1_r = u1_r / h1;
+    } else {
+      u0_r = u_plm;
+      u1_r = slope / h1;
+    }
+    if (pqm_bad_inflexion(pqm_quartic(um, h1, u0_l, u0_r, u1_l, u1_r), slope, false))      // (the reference has no hNeglect at this end)
+      pqm_collapse_right(um, h1, 0.0, slope, u0_l, u0_r, u1_l, u1_r);
+  }
+  const int kb = bottom ? n - 1 : 0;
+  EL[kb] = u0_l; ER[kb] = u0_r; SL[kb] = u1_l; SR[kb] = u1_r;
+}
+
+// build_reconstructions_1d :257-386; returns the integration method (uniform over the wave)
+__device__ int w_build_reconstructions(const WCol &c, int lane, int scheme, bool extrap, int n, double h_neglect, double h_neglect_edge) {
   int local = scheme;
   if (n <= 1) local = REMAP_PCM;
   else if (n <= 3) local = (local < REMAP_PLM) ? local : REMAP_PLM;
   else if (n <= 4 && local != REMAP_PPM_CW) local = (local < REMAP_PPM_H4) ? local : REMAP_PPM_H4;      // :293
   if (local == REMAP_PCM) {
-    for (int k = lane; k < n; k += 64) { EL[k] = u[k]; ER[k] = u[k]; c.C1[k] = 0.; }
+    for (int k = lane; k < n; k += 64) { c.EL[k] = c.u0[k]; c.ER[k] = c.u0[k]; c.C1[k] = 0.; }
     wsync();
     return INT_PCM;
   }
-  if (local == REMAP_PLM) {      // PLM_reconstruction :190-260
-    const double almost_one = 1. - DBL_EPSILON;
-    double *slp = c.u_sub, *mslp = c.uh_sub;      // free until the sub-cell pass
-    for (int k = lane; k < n; k += 64)
-      slp[k] = (k >= 1 && k < n - 1) ? plm_slope_wa(h[k - 1], h[k], h[k + 1], h_neglect, u[k - 1], u[k], u[k + 1]) : 0.;
-    wsync();
-    for (int k = lane; k < n; k += 64)
-      mslp[k] = (k >= 1 && k < n - 1) ? plm_monotonized_slope(u[k - 1], u[k], u[k + 1], slp[k - 1], slp[k], slp[k + 1]) : 0.;
-    wsync();
-    for (int k = lane; k < n; k += 64) {
-      if (k >= 1 && k < n - 1) {
-        const double slope = mslp[k];
-        const double u_l = u[k] - 0.5 * slope;
-        const double u_r = u[k] + 0.5 * slope;
-        EL[k] = u_l; ER[k] = u_r;
-        double c1 = (u_r - u_l);
-        const double edge = c1 + u_l;
-        const double e_r = u[k + 1] - 0.5 * fsign(mslp[k + 1], slp[k + 1]);
-        if ((edge - u[k]) * (e_r - edge) < 0.) c1 = c1 * almost_one;
-        c.C1[k] = c1;
-      } else {
-        EL[k] = u[k]; ER[k] = u[k]; c.C1[k] = 0.;
-      }
-    }
-    wsync();
-    if (extrap && lane == 0) {      // PLM_boundary_extrapolation :272-307
-      double slope = -plm_extrapolate_slope(h[1], h[0], h_neglect, u[1], u[0]);
-      EL[0] = u[0] - 0.5 * slope; ER[0] = u[0] + 0.5 * slope;
-      c.C1[0] = ER[0] - EL[0];
-      slope = plm_extrapolate_slope(h[n - 2], h[n - 1], h_neglect, u[n - 2], u[n - 1]);
-      EL[n - 1] = u[n - 1] - 0.5 * slope; ER[n - 1] = u[n - 1] + 0.5 * slope;
-      c.C1[n - 1] = ER[n - 1] - EL[n - 1];
-    }
-    wsync();
-    return INT_PLM;
+  if (local == REMAP_PLM) { w_plm(c, lane, n, extrap, h_neglect); return INT_PLM; }
+  if (local == REMAP_PLM_HYBGEN) { w_plm_hybgen(c, lane, n, extrap, h_neglect); return INT_PLM; }
+  const bool pqm = local == REMAP_PQM_IH4IH3 || local == REMAP_PQM_IH6IH5;
+  // the edge values, and the edge slopes of the quartic schemes
+  if (local == REMAP_WENO_HYBGEN) w_edges_weno_hybgen(c, lane, n, h_neglect);
+  else if (local == REMAP_PPM_IH4 || local == REMAP_PQM_IH4IH3) w_edges_implicit_h4(c, lane, n, h_neglect_edge);
+  else if (local == REMAP_PQM_IH6IH5) {      // edge_values_implicit_h6
+    w_ih65_system<false>(c, lane, n, h_neglect_edge);
+    w_take_interfaces(c.uh_sub, c.EL, c.ER, lane, n);
   }
-  if (local == REMAP_PLM_HYBGEN) {      // hybgen_plm_coefs (MOM_hybgen_remap.F90:14-88), MOM_remapping.F90:306-315
-    const double thin = h_neglect;
-    for (int k = lane; k < n; k += 64) {
-      double sl = 0.0;
-      if (k >= 1 && k < n - 1 && !(h[k] <= thin)) {
-        const double qcen = h[k] / (h[k] + 0.5 * (h[k - 1] + h[k + 1]));
-        const double ztop = 2.0 * (u[k] - u[k - 1]);
-        const double zbot = 2.0 * (u[k + 1] - u[k]);
-        const double zcen = qcen * (u[k + 1] - u[k - 1]);
-        if (ztop * zbot > 0.0) sl = fsign(min3(fabs(zcen), fabs(zbot), fabs(ztop)), zbot);
-      }
-      c.C1[k] = sl;
-      EL[k] = u[k] - 0.5 * sl;
-      ER[k] = u[k] + 0.5 * sl;
-    }
-    wsync();
-    if (extrap && lane == 0) {      // PLM_boundary_extrapolation :272-307
-      double slope = -plm_extrapolate_slope(h[1], h[0], h_neglect, u[1], u[0]);
-      EL[0] = u[0] - 0.5 * slope; ER[0] = u[0] + 0.5 * slope;
-      c.C1[0] = ER[0] - EL[0];
-      slope = plm_extrapolate_slope(h[n - 2], h[n - 1], h_neglect, u[n - 2], u[n - 1]);
-      EL[n - 1] = u[n - 1] - 0.5 * slope; ER[n - 1] = u[n - 1] + 0.5 * slope;
-      c.C1[n - 1] = ER[n - 1] - EL[n - 1];
-    }
-    wsync();
-    return INT_PLM;
+  else if (local == REMAP_PPM_HYBGEN) w_edges_h4cw(c, lane, n, true, h_neglect);
+  else if (local == REMAP_PPM_CW) w_edges_h4cw(c, lane, n, false, h_neglect_edge);
+  else w_edges_explicit_h4(c, lane, n, h_neglect_edge);
+  if (local == REMAP_PQM_IH4IH3) w_slopes_implicit_h3(c, lane, n, h_neglect);
+  if (local == REMAP_PQM_IH6IH5) {      // edge_slopes_implicit_h5
+    w_ih65_system<true>(c, lane, n, h_neglect);
+    w_take_interfaces(c.uh_sub, c.C1, c.SR, lane, n);
   }
-  if (local == REMAP_WENO_HYBGEN) {
-    // ---- hybgen_weno_coefs (MOM_hybgen_remap.F90:226-386): the edge slopes, the two one-sided estimates of every cell with their
-    // weights, the weighted edge values, the final limiter -- four passes across the lanes
-    const double thin = h_neglect, min_ratio = 1.0e-8;
-    auto dp = [&](int k) { return fmax(h[k], thin); };
-    double *slope_edge = c.u_sub, *zw1 = c.uh_sub, *zw2 = c.uh_sub + n, *val_edge = c.C1;      // (free until the tail / the sub-cell pass)
-    for (int K = lane + 1; K < n; K += 64) slope_edge[K] = (1.0 / (dp(K - 1) + dp(K))) * (u[K] - u[K - 1]);
-    wsync();
-    for (int k = lane; k < n; k += 64) {
-      double e1 = u[k], e2 = u[k], w1 = 0.0, w2 = 0.0;
-      if (k >= 1 && k < n - 1 && !((slope_edge[k] * slope_edge[k + 1] < 0.0) || (dp(k) <= thin))) {
-        const double dpkm2kp = dp(k - 1) + 2.0 * dp(k) + dp(k + 1);
-        const double qdpkmkp = 1.0 / (dp(k - 1) + dp(k) + dp(k + 1));
-        double seh1 = dp(k) * slope_edge[k + 1];
-        double seh2 = dp(k) * slope_edge[k];
-        const double q01 = dpkm2kp * slope_edge[k + 1];
-        const double q02 = dpkm2kp * slope_edge[k];
-        if (fabs(seh1) > fabs(q02)) seh1 = q02;
-        if (fabs(seh2) > fabs(q01)) seh2 = q01;
-        const double curv_cell = (seh1 - seh2) * qdpkmkp;
-        const double q001 = seh1 - curv_cell * dp(k + 1);
-        const double q002 = seh2 + curv_cell * dp(k - 1);
-        e2 = u[k] + q001;
-        e1 = u[k] - q002;
-        w1 = (2.0 * q001 - q002) * (2.0 * q001 - q002);
-        w2 = (2.0 * q002 - q001) * (2.0 * q002 - q001);
-      }
-      EL[k] = e1; ER[k] = e2; zw1[k] = w1; zw2[k] = w2;
-    }
-    wsync();
-    for (int K = lane + 1; K < n; K += 64) {
-      double wt1;
-      if (zw1[K] + zw2[K - 1] <= 0.0) wt1 = 0.5;
-      else if (zw1[K] <= min_ratio * (zw1[K] + zw2[K - 1])) wt1 = min_ratio;
-      else if (zw2[K - 1] <= min_ratio * (zw1[K] + zw2[K - 1])) wt1 = (1.0 - min_ratio);
-      else wt1 = zw1[K] / (zw1[K] + zw2[K - 1]);
-      val_edge[K] = wt1 * ER[K - 1] + (1.0 - wt1) * EL[K];
-    }
-    wsync();
-    for (int k = lane + 1; k < n - 1; k += 64) {
-      if (!(dp(k) <= thin)) {
-        double q01 = val_edge[k + 1] - u[k];
-        double q02 = u[k] - val_edge[k];
-        if (q01 * q02 < 0.0) { q01 = 0.0; q02 = 0.0; }
-        else if (fabs(q01) > fabs(2.0 * q02)) q01 = 2.0 * q02;
-        else if (fabs(q02) > fabs(2.0 * q01)) q02 = 2.0 * q01;
-        EL[k] = u[k] - q02;
-        ER[k] = u[k] + q01;
-      }
-    }
-    wsync();
-  } else
-  if (local == REMAP_PPM_IH4 || local == REMAP_PQM_IH4IH3) {
-    // ---- PPM_IH4, PQM_IH4IH3: edge_values_implicit_h4 (regrid_edge_values.F90:491-654, answer_date >= 20190101).  The rows of the
-    // tridiagonal system across the lanes, the two closing rows on the last two lanes, solve_diag_dominant_tridiag
-    // (regrid_solvers.F90:246-280) as a serial walk by one lane (the solution overwrites the right-hand side).
-    const double hNeglect = h_neglect_edge;
-    double *tri_l = c.u_sub, *tri_c = c.u_sub + (n + 1), *tri_u = c.uh_sub, *tri_b = c.uh_sub + (n + 1), *c1 = c.C1;
-    for (int i = lane; i < n - 1; i += 64) {
-      double h0 = fmax(h[i], hNeglect);
-      double h1 = fmax(h[i + 1], hNeglect);
-      if (fabs(h0) < 1.0e-12 * fabs(h1)) h0 = 1.0e-12 * h1;
-      if (fabs(h1) < 1.0e-12 * fabs(h0)) h1 = 1.0e-12 * h0;
-      const double I_h2 = 1.0 / ((h0 + h1) * (h0 + h1));
-      const double alpha = (h1 * h1) * I_h2;
-      const double beta = (h0 * h0) * I_h2;
-      const double abmix = (h0 * h1) * I_h2;
-      const double a = 2.0 * alpha * (alpha + 2.0 * beta + 3.0 * abmix);
-      const double b = 2.0 * beta * (beta + 2.0 * alpha + 3.0 * abmix);
-      tri_c[i + 1] = 2.0 * abmix; tri_l[i + 1] = alpha; tri_u[i + 1] = beta;
-      tri_b[i + 1] = a * u[i] + b * u[i + 1];
-    }
-    if (lane >= 62) {      // the first (lane 62) and the last (lane 63) boundary value
-      const bool last = lane == 63;
-      double dz[4], ut[4], Cs[4];
-      for (int i = 0; i < 4; i++) { const int q = last ? n - 1 - i : i; dz[i] = fmax(hNeglect, h[q]); ut[i] = u[q]; }
-      end_value_h4(dz, ut, Cs);
-      const int row = last ? n : 0;
-      tri_b[row] = Cs[0]; tri_c[row] = 1.0; tri_u[row] = 0.0; tri_l[row] = 0.0;
-    }
-    wsync();
-    if (lane == 0) {
-      const int N = n + 1;
-      double I_pivot = 1.0 / (tri_c[0] + tri_u[0]);
-      double d1 = tri_c[0] * I_pivot;
-      c1[0] = tri_u[0] * I_pivot;
-      tri_b[0] = tri_b[0] * I_pivot;
-      for (int k = 1; k < N - 1; k++) {
-        const double denom_t1 = tri_c[k] + d1 * tri_l[k];
-        I_pivot = 1.0 / (denom_t1 + tri_u[k]);
-        d1 = denom_t1 * I_pivot;
-        c1[k] = tri_u[k] * I_pivot;
-        tri_b[k] = (tri_b[k] - tri_l[k] * tri_b[k - 1]) * I_pivot;
-      }
-      I_pivot = 1.0 / (tri_c[N - 1] + d1 * tri_l[N - 1]);
-      tri_b[N - 1] = (tri_b[N - 1] - tri_l[N - 1] * tri_b[N - 2]) * I_pivot;
-      for (int k = N - 2; k >= 0; k--) tri_b[k] = tri_b[k] - c1[k] * tri_b[k + 1];
-    }
-    wsync();
-    for (int k = lane; k < n; k += 64) { EL[k] = tri_b[k]; ER[k] = tri_b[k + 1]; }
-    wsync();
-  } else if (local == REMAP_PQM_IH6IH5) {
-    w_ih65_system<false>(c, lane, n, h_neglect_edge);      // edge_values_implicit_h6
-    for (int k = lane; k < n; k += 64) { EL[k] = c.uh_sub[k]; ER[k] = c.uh_sub[k + 1]; }
-    wsync();
-  } else if (local == REMAP_PPM_CW || local == REMAP_PPM_HYBGEN) {
-    // ---- PPM_CW: edge_values_explicit_h4cw (regrid_edge_values.F90:381-463) and PPM_monotonicity (PPM_functions.F90:132).
-    // ---- PPM_HYBGEN: hybgen_ppm_coefs (MOM_hybgen_remap.F90:91-222), the HYCOM routine the two above re-express: the same
-    //      arithmetic with the minimum thickness `thin` = h_neglect and layers no thicker than it treated as PCM (:140-147)
-    const bool hyb = local == REMAP_PPM_HYBGEN;
-    const double hNeglect = hyb ? h_neglect : h_neglect_edge;
-    double *au = c.u_sub;      // the limited slopes of Colella & Woodward eq. 1.8, 0-based cell index
-    auto dp = [&](int k) { return fmax(h[k], hNeglect); };      // 0-based; the reference's dp(k+1)
-    auto pcm = [&](int k) { return hyb && (dp(k) <= hNeglect); };
-    for (int k = lane; k < n; k += 64) {
-      double a = 0.;
-      if (k >= 1 && k <= n - 2) {
-        const double slk = u[k] - u[k - 1];
-        const double srk = u[k + 1] - u[k];
-        if (!pcm(k) && slk * srk > 0.) {
-          // h2_h123(k), h112(K), I_h12(K+1), h122(K+1), I_h12(K) of the reference with K = k+1 (1-based)
-          const double h2_h123 = dp(k) / (dp(k) + (dp(k - 1) + dp(k + 1)));
-          const double h112 = 2. * dp(k - 1) + dp(k), h122p = dp(k) + 2. * dp(k + 1);
-          const double I_h12 = 1.0 / (dp(k - 1) + dp(k)), I_h12p = 1.0 / (dp(k) + dp(k + 1));
-          const double sck = h2_h123 * (h112 * srk * I_h12p + h122p * slk * I_h12);
-          a = fsign(min3(fabs(2.0 * slk), fabs(sck), fabs(2.0 * srk)), sck);
-        }
-      }
-      au[k] = a;
-    }
-    wsync();
-    for (int k = lane; k < n; k += 64) {      // al(k): the edge between cells k-1 and k; also ar(k-1)
-      if (k >= 2 && k <= n - 2) {
-        const double I_h12 = 1.0 / (dp(k - 1) + dp(k));
-        const double I_h0123 = 1.0 / ((dp(k - 2) + dp(k - 1)) + (dp(k) + dp(k + 1)));
-        const double h01_h112 = (dp(k - 2) + dp(k - 1)) / (2.0 * dp(k - 1) + dp(k));
-        const double h23_h122 = (dp(k) + dp(k + 1)) / (dp(k - 1) + 2.0 * dp(k));
-        const double al = (dp(k) * u[k - 1] + dp(k - 1) * u[k]) * I_h12 +
-                          I_h0123 * (2. * dp(k) * dp(k - 1) * I_h12 * (u[k] - u[k - 1]) * (h01_h112 - h23_h122) +
-                                     (dp(k) * au[k - 1] * h23_h122 - dp(k - 1) * au[k] * h01_h112));
-        EL[k] = al; ER[k - 1] = al;
-      }
-    }
-    if (lane == 0) { EL[0] = u[0]; ER[0] = u[0]; EL[1] = u[0]; ER[n - 2] = u[n - 1]; EL[n - 1] = u[n - 1]; ER[n - 1] = u[n - 1]; }
-    wsync();
-    for (int k = lane + 1; k < n - 1; k += 64) {      // PPM_monotonicity
-      if (pcm(k) || (u[k + 1] - u[k]) * (u[k] - u[k - 1]) <= 0.) {
-        EL[k] = u[k]; ER[k] = u[k];
-      } else {
-        const double da = ER[k] - EL[k];
-        const double a6 = 6.0 * u[k] - 3.0 * (EL[k] + ER[k]);
-        if (da * a6 > da * da) EL[k] = 3.0 * u[k] - 2.0 * ER[k];
-        else if (da * a6 < -da * da) ER[k] = 3.0 * u[k] - 2.0 * EL[k];
-      }
-    }
-    wsync();
-  } else
-  // ---- PPM_H4: edge_values_explicit_h4 :222-363
-  {
-    const double hMinFrac = 1.e-5, hNeglect = h_neglect_edge;
-    for (int i = lane + 2; i <= n - 2; i += 64) {
-      double h0 = h[i - 2], h1 = h[i - 1], h2 = h[i], h3 = h[i + 1];
-      if (h0 + h1 == 0.0 || h1 + h2 == 0.0 || h2 + h3 == 0.0) {
-        const double h_min = hMinFrac * fmax(hNeglect, (h0 + h1) + (h2 + h3));
-        h0 = fmax(h_min, h[i - 2]); h1 = fmax(h_min, h[i - 1]); h2 = fmax(h_min, h[i]); h3 = fmax(h_min, h[i + 1]);
-      }
-      const double I_h12 = 1.0 / (h1 + h2);
-      const double I_den_et2 = 1.0 / (((h0 + h1) + h2) * (h0 + h1)); const double I_h012 = (h0 + h1) * I_den_et2;
-      const double I_den_et3 = 1.0 / ((h1 + (h2 + h3)) * (h2 + h3)); const double I_h123 = (h2 + h3) * I_den_et3;
-      const double et1 = (1.0 + (h1 * I_h012 + (h0 + h1) * I_h123)) * I_h12 * (h2 * (h2 + h3)) * u[i - 1] +
-                         (1.0 + (h2 * I_h123 + (h2 + h3) * I_h012)) * I_h12 * (h1 * (h0 + h1)) * u[i];
-      const double et2 = (h1 * (h2 * (h2 + h3)) * I_den_et2) * (u[i - 1] - u[i - 2]);
-      const double et3 = (h2 * (h1 * (h0 + h1)) * I_den_et3) * (u[i] - u[i + 1]);
-      const double ev = (et1 + (et2 + et3)) / ((h0 + h1) + (h2 + h3));
-      EL[i] = ev; ER[i - 1] = ev;
-    }
-    if (lane >= 62) {      // the end values, on the two lanes that have no second interior edge to do: one code path for both
-      const bool last = lane == 63;
-      double dz[4], ut[4], Cs[4];
-      for (int i = 0; i < 4; i++) { const int q = last ? n - 1 - i : i; dz[i] = fmax(hNeglect, h[q]); ut[i] = u[q]; }
-      end_value_h4(dz, ut, Cs);
-      const double inner = Cs[0] + dz[0] * (Cs[1] + dz[0] * (Cs[2] + dz[0] * Cs[3]));
-      if (last) { ER[n - 1] = Cs[0]; EL[n - 1] = inner; ER[n - 2] = inner; }
-      else { EL[0] = Cs[0]; ER[0] = inner; EL[1] = inner; }
-    }
-    wsync();
-  }
-  if (local == REMAP_PQM_IH4IH3) {
-    // ---- edge_slopes_implicit_h3 (regrid_edge_values.F90:803-972, answer_date >= 20190101): the same shape of system as the edge
-    // values', with h_neglect; the left slopes go to C1 (the solver's work array until then), the right ones to SR
-    const double hNeglect = h_neglect;
-    double *tri_l = c.u_sub, *tri_c = c.u_sub + (n + 1), *tri_u = c.uh_sub, *tri_b = c.uh_sub + (n + 1), *c1 = c.C1;
-    for (int i = lane; i < n - 1; i += 64) {
-      double h0 = fmax(h[i], hNeglect);
-      double h1 = fmax(h[i + 1], hNeglect);
-      const double I_h = 1.0 / (h0 + h1);
-      h0 = h0 * I_h; h1 = h1 * I_h;
-      const double h0h1 = h0 * h1, h0_2 = h0 * h0, h1_2 = h1 * h1;
-      const double h0_3 = h0_2 * h0, h1_3 = h1_2 * h1;
-      const double I_d = 1.0 / (4.0 * h0h1 * (h0 + h1) + h1_3 + h0_3);
-      tri_l[i + 1] = (h1 * ((h0_2 + h0h1) - h1_2)) * I_d;
-      tri_c[i + 1] = 2.0 * ((h0_2 + h1_2) * (h0 + h1)) * I_d;
-      tri_u[i + 1] = (h0 * ((h1_2 + h0h1) - h0_2)) * I_d;
-      tri_b[i + 1] = 12.0 * (h0h1 * I_d) * ((u[i + 1] - u[i]) * I_h);
-    }
-    if (lane >= 62) {      // the first (lane 62) and the last (lane 63) edge slope
-      const bool last = lane == 63;
-      double dz[4], ut[4], Cs[4];
-      for (int i = 0; i < 4; i++) { const int q = last ? n - 1 - i : i; dz[i] = fmax(hNeglect, h[q]); ut[i] = u[q]; }
-      end_value_h4(dz, ut, Cs);
-      const int row = last ? n : 0;
-      tri_b[row] = last ? -Cs[1] : Cs[1]; tri_c[row] = 1.0; tri_u[row] = 0.0; tri_l[row] = 0.0;
-    }
-    wsync();
-    if (lane == 0) {      // solve_diag_dominant_tridiag
-      const int N = n + 1;
-      double I_pivot = 1.0 / (tri_c[0] + tri_u[0]);
-      double d1 = tri_c[0] * I_pivot;
-      c1[0] = tri_u[0] * I_pivot;
-      tri_b[0] = tri_b[0] * I_pivot;
-      for (int k = 1; k < N - 1; k++) {
-        const double denom_t1 = tri_c[k] + d1 * tri_l[k];
-        I_pivot = 1.0 / (denom_t1 + tri_u[k]);
-        d1 = denom_t1 * I_pivot;
-        c1[k] = tri_u[k] * I_pivot;
-        tri_b[k] = (tri_b[k] - tri_l[k] * tri_b[k - 1]) * I_pivot;
-      }
-      I_pivot = 1.0 / (tri_c[N - 1] + d1 * tri_l[N - 1]);
-      tri_b[N - 1] = (tri_b[N - 1] - tri_l[N - 1] * tri_b[N - 2]) * I_pivot;
-      for (int k = N - 2; k >= 0; k--) tri_b[k] = tri_b[k] - c1[k] * tri_b[k + 1];
-    }
-    wsync();
-    for (int k = lane; k < n; k += 64) { c.C1[k] = tri_b[k]; c.SR[k] = tri_b[k + 1]; }
-    wsync();
-  }
-  if (local == REMAP_PQM_IH6IH5) {
-    w_ih65_system<true>(c, lane, n, h_neglect);      // edge_slopes_implicit_h5
-    for (int k = lane; k < n; k += 64) { c.C1[k] = c.uh_sub[k]; c.SR[k] = c.uh_sub[k + 1]; }
-    wsync();
-  }
-  // ---- PPM_reconstruction / PQM_limiter: bound_edge_values, check_discontinuous_edge_values, then the scheme's limiter
-  for (int k = lane; k < n; k += 64) {
-    const int km1 = (k - 1 > 0) ? k - 1 : 0, kp1 = (k + 1 < n - 1) ? k + 1 : n - 1;
-    double slope_x_h = 0.0;
-    if (((h[km1] + h[kp1]) + 2.0 * h[k]) > 0.0) {
-      const double sigma_l = (u[k] - u[km1]);
-      const double sigma_c = (u[kp1] - u[km1]) * (h[k] / ((h[km1] + h[kp1]) + 2.0 * h[k]));
-      const double sigma_r = (u[kp1] - u[k]);
-      if ((sigma_l * sigma_r) > 0.0) slope_x_h = fsign(min3(fabs(sigma_l), fabs(sigma_c), fabs(sigma_r)), sigma_c);
-    }
-    double el = EL[k], er = ER[k];
-    if ((u[km1] - el) * (el - u[k]) < 0.0) el = u[k] - fsign(fmin(fabs(slope_x_h), fabs(el - u[k])), slope_x_h);
-    if ((u[kp1] - er) * (er - u[k]) < 0.0) er = u[k] + fsign(fmin(fabs(slope_x_h), fabs(er - u[k])), slope_x_h);
-    el = fmax(fmin(el, fmax(u[km1], u[k])), fmin(u[km1], u[k]));
-    er = fmax(fmin(er, fmax(u[kp1], u[k])), fmin(u[kp1], u[k]));
-    EL[k] = el; ER[k] = er;
-  }
-  wsync();
-  for (int k = lane; k < n - 1; k += 64) {
-    if ((EL[k + 1] - ER[k]) * (u[k + 1] - u[k]) < 0.0) {
-      double u0_avg = 0.5 * (ER[k] + EL[k + 1]);
-      u0_avg = fmax(fmin(u0_avg, fmax(u[k], u[k + 1])), fmin(u[k], u[k + 1]));
-      ER[k] = u0_avg; EL[k + 1] = u0_avg;
-    }
-  }
-  wsync();
-  if (local == REMAP_PQM_IH4IH3 || local == REMAP_PQM_IH6IH5) {
-    // ---- PQM_limiter (PQM_functions.F90:103-337): a cell reads its own edge values and slopes and its neighbours' means and widths
-    const double hNeglect = h_neglect;
-    double *SL = c.C1, *SR = c.SR;
-    for (int k = lane; k < n; k += 64) {
-      double u0_l = u[k], u0_r = u[k], u1_l = 0.0, u1_r = 0.0;      // the boundary cells :331-335
-      if (k >= 1 && k < n - 1) {
-        u0_l = EL[k]; u0_r = ER[k]; u1_l = SL[k]; u1_r = SR[k];
-        const double h_l = h[k - 1], h_c = h[k], h_r = h[k + 1];
-        const double u_l = u[k - 1], u_c = u[k], u_r = u[k + 1];
-        const double sigma_l = 2.0 * (u_c - u_l) / (h_c + hNeglect);
-        const double sigma_c = 2.0 * (u_r - u_l) / (h_l + 2.0 * h_c + h_r + hNeglect);
-        const double sigma_r = 2.0 * (u_r - u_c) / (h_c + hNeglect);
-        double slope = 0.0;
-        if ((sigma_l * sigma_r) > 0.0) slope = fsign(min3(fabs(sigma_l), fabs(sigma_c), fabs(sigma_r)), sigma_c);
-        if (u1_l * slope <= 0.0) u1_l = slope;
-        if (u1_r * slope <= 0.0) u1_r = slope;
-        int inflexion = 0;      // 1: collapse the inflexion points onto the left edge, 2: onto the right edge
-        if ((u0_r - u_c) * (u_c - u0_l) <= 0.0) {      // a local extremum: flat
-          u0_l = u_c; u0_r = u_c; u1_l = 0.0; u1_r = 0.0;
-        } else if (pqm_bad_inflexion(pqm_quartic(u_c, h_c, u0_l, u0_r, u1_l, u1_r), slope, true)) {
-          inflexion = (fabs(sigma_l) < fabs(sigma_r)) ? 1 : 2;
-        }
-        if (inflexion == 1) {
-          u1_l = (10.0 * u_c - 2.0 * u0_r - 8.0 * u0_l) / (3.0 * h_c + hNeglect);
-          u1_r = (-10.0 * u_c + 6.0 * u0_r + 4.0 * u0_l) / (h_c + hNeglect);
-          if (u1_l * slope < 0.0) {
-            u1_l = 0.0;
-            u0_r = 5.0 * u_c - 4.0 * u0_l;
-            u1_r = 20.0 * (u_c - u0_l) / (h_c + hNeglect);
-          } else if (u1_r * slope < 0.0) {
-            u1_r = 0.0;
-            u0_l = (5.0 * u_c - 3.0 * u0_r) / 2.0;
-            u1_l = 10.0 * (-u_c + u0_r) / (3.0 * h_c + hNeglect);
-          }
-        } else if (inflexion == 2) {
-          u1_r = (-10.0 * u_c + 8.0 * u0_r + 2.0 * u0_l) / (3.0 * h_c + hNeglect);
-          u1_l = (10.0 * u_c - 4.0 * u0_r - 6.0 * u0_l) / (h_c + hNeglect);
-          if (u1_l * slope < 0.0) {
-            u1_l = 0.0;
-            u0_r = (5.0 * u_c - 3.0 * u0_l) / 2.0;
-            u1_r = 10.0 * (u_c - u0_l) / (3.0 * h_c + hNeglect);
-          } else if (u1_r * slope < 0.0) {
-            u1_r = 0.0;
-            u0_l = 5.0 * u_c - 4.0 * u0_r;
-            u1_l = 20.0 * (-u_c + u0_r) / (h_c + hNeglect);
-          }
-        }
-      }
-      EL[k] = u0_l; ER[k] = u0_r; SL[k] = u1_l; SR[k] = u1_r;
-    }
-    wsync();
-    if (extrap && lane >= 62) {      // PQM_boundary_extrapolation_v1 (PQM_functions.F90:502-831): lane 62 the top cell, lane 63 the bottom cell
-      const bool bottom = lane == 63;
-      double u0_l, u0_r, u1_l, u1_r, slope, um;
-      if (!bottom) {
-        const double h0 = h[0], h1 = h[1], u0 = u[0], u1 = u[1];
-        um = u0;
-        slope = 2.0 * (u1 - u0) / ((h0 + h1) + hNeglect);
-        slope = slope * h0;
-        u0_r = EL[1];                                   // ppoly_coef(i1,1)
-        u1_r = (h1 * SL[1]) / (h1 + hNeglect);          // ppoly_coef(i1,2) / (h1 + hNeglect)
-        double beta = 0.;
-        if (u1_r != 0.) beta = 2.0 * (u0_r - um) / ((h0 + hNeglect) * u1_r) - 1.0;
-        const double br = u0_r + beta * u0_r - um;
-        const double ar = um + beta * um - br;
-        u0_l = ar;
-        const double u_plm = um - 0.5 * slope;
-        if (fabs(um - u0_l) < fabs(um - u_plm)) {
-          u1_l = 2.0 * (br - ar * beta);
-          u1_l = u1_l / (h0 + hNeglect);
-        } else {
-          u0_l = u_plm;
-          u1_l = slope / (h0 + hNeglect);
-        }
-        if (pqm_bad_inflexion(pqm_quartic(um, h0, u0_l, u0_r, u1_l, u1_r), slope, false)) {
-          u1_l = (10.0 * um - 2.0 * u0_r - 8.0 * u0_l) / (3.0 * h0 + hNeglect);
-          u1_r = (-10.0 * um + 6.0 * u0_r + 4.0 * u0_l) / (h0 + hNeglect);
-          if (u1_l * slope < 0.0) {
-            u1_l = 0.0;
-            u0_r = 5.0 * um - 4.0 * u0_l;
-            u1_r = 20.0 * (um - u0_l) / (h0 + hNeglect);
-          } else if (u1_r * slope < 0.0) {
-            u1_r = 0.0;
-            u0_l = (5.0 * um - 3.0 * u0_r) / 2.0;
-            u1_l = 10.0 * (-um + u0_r) / (3.0 * h0 + hNeglect);
-          }
-        }
-      } else {
-        const int i0 = n - 2, i1 = n - 1;
-        const double h0 = h[i0], h1 = h[i1], u0 = u[i0], u1 = u[i1];
-        um = u1;
-        slope = 2.0 * (u1 - u0) / (h0 + h1);
-        slope = slope * h1;
-        const Quartic q0 = pqm_quartic(u0, h0, EL[i0], ER[i0], SL[i0], SR[i0]);      // ppoly_coef(i0,:), a = EL[i0]
-        u0_l = EL[i0] + q0.b + q0.c + q0.d + q0.e;
-        u1_l = (q0.b + 2 * q0.c + 3 * q0.d + 4 * q0.e) / h0;
-        double beta = 0.;
-        if (um - u0_l != 0.) beta = 0.5 * h1 * u1_l / (um - u0_l) - 1.0;
-        const double br = beta * um + um - u0_l;
-        const double ar = u0_l;
-        if (1 + beta != 0.) u0_r = (ar + 2 * br + beta * br) / ((1 + beta) * (1 + beta));
-        else u0_r = um + 0.5 * slope;
-        const double u_plm = um + 0.5 * slope;
-        if (fabs(um - u0_r) < fabs(um - u_plm)) {
-          u1_r = 2.0 * (br - ar * beta) / ((1 + beta) * (1 + beta) * (1 + beta));
-          u1_r = u1_r / h1;
-        } else {
-          u0_r = u_plm;
-          u1_r = slope / h1;
-        }
-        if (pqm_bad_inflexion(pqm_quartic(um, h1, u0_l, u0_r, u1_l, u1_r), slope, false)) {
-          u1_r = (-10.0 * um + 8.0 * u0_r + 2.0 * u0_l) / (3.0 * h1);
-          u1_l = (10.0 * um - 4.0 * u0_r - 6.0 * u0_l) / h1;
-          if (u1_l * slope < 0.0) {
-            u1_l = 0.0;
-            u0_r = (5.0 * um - 3.0 * u0_l) / 2.0;
-            u1_r = 10.0 * (um - u0_l) / (3.0 * h1);
-          } else if (u1_r * slope < 0.0) {
-            u1_r = 0.0;
-            u0_l = 5.0 * um - 4.0 * u0_r;
-            u1_l = 20.0 * (-um + u0_r) / h1;
-          }
-        }
-      }
-      const int kb = bottom ? n - 1 : 0;      // (the two lanes read cells 1 and n-2 and write cells 0 and n-1: n >= 5 here)
-      EL[kb] = u0_l; ER[kb] = u0_r; SL[kb] = u1_l; SR[kb] = u1_r;
-    }
+  // PPM_reconstruction / PQM_reconstruction: the bounds, then the scheme's limiter and boundary extrapolation
+  w_bound_and_check(c, lane, n);
+  if (pqm) {
+    w_pqm_limit(c, lane, n, h_neglect);
+    if (extrap && lane >= 62) w_pqm_boundary_extrapolation(c, lane == 63, n, h_neglect);      // lane 62 the top cell, lane 63 the bottom cell
     wsync();
     return INT_PQM;
   }
-  for (int k = lane; k < n; k += 64) {
-    double edge_l, edge_r;
-    if (k >= 1 && k < n - 1) {
-      const double u_l = u[k - 1], u_c = u[k], u_r = u[k + 1];
-      edge_l = EL[k]; edge_r = ER[k];
-      if ((u_r - u_c) * (u_c - u_l) <= 0.0) {
-        edge_l = u_c; edge_r = u_c;
-      } else {
-        const double expr1 = 3.0 * (edge_r - edge_l) * ((u_c - edge_l) + (u_c - edge_r));
-        const double expr2 = (edge_r - edge_l) * (edge_r - edge_l);
-        if (expr1 > expr2) {
-          edge_l = u_c + 2.0 * (u_c - edge_r);
-          edge_l = fmax(fmin(edge_l, fmax(u_l, u_c)), fmin(u_l, u_c));
-        } else if (expr1 < -expr2) {
-          edge_r = u_c + 2.0 * (u_c - edge_l);
-          edge_r = fmax(fmin(edge_r, fmax(u_r, u_c)), fmin(u_r, u_c));
-        }
-      }
-      if (fabs(edge_r - edge_l) < fmax(1.e-60, DBL_EPSILON * fabs(u_c))) { edge_l = u_c; edge_r = u_c; }
-    } else {
-      edge_l = u[k]; edge_r = u[k];
-    }
-    EL[k] = edge_l; ER[k] = edge_r;
-    c.C1[k] = 4.0 * (u[k] - edge_l) + 2.0 * (u[k] - edge_r);
-  }
-  wsync();
-  if (extrap && lane == 0) {      // PPM_boundary_extrapolation, PPM_functions.F90:162-316
-    int i0 = 0, i1 = 1;
-    double h0 = h[i0], h1 = h[i1], u0 = u[i0], u1 = u[i1];
-    double b = c.C1[i1];
-    double u1_r = b * ((h0 + h_neglect) / (h1 + h_neglect));
-    double slope = 2.0 * (u1 - u0);
-    if (fabs(u1_r) > fabs(slope)) u1_r = slope;
-    double u0_r = EL[i1];
-    double u0_l = 3.0 * u0 + 0.5 * u1_r - 2.0 * u0_r;
-    double exp1 = (u0_r - u0_l) * (u0 - 0.5 * (u0_l + u0_r));
-    double exp2 = (u0_r - u0_l) * (u0_r - u0_l) / 6.0;
-    if (exp1 > exp2) u0_l = 3.0 * u0 - 2.0 * u0_r;
-    if (exp1 < -exp2) u0_r = 3.0 * u0 - 2.0 * u0_l;
-    EL[i0] = u0_l; ER[i0] = u0_r;
-    c.C1[i0] = 6.0 * u0 - 4.0 * u0_l - 2.0 * u0_r;
-    i0 = n - 2; i1 = n - 1;
-    h0 = h[i0]; h1 = h[i1]; u0 = u[i0]; u1 = u[i1];
-    b = c.C1[i0];
-    const double cc = 3.0 * ((ER[i0] - u[i0]) + (EL[i0] - u[i0]));      // ppoly_coef(i0,3)
-    double u1_l = (b + 2 * cc);
-    u1_l = u1_l * ((h1 + h_neglect) / (h0 + h_neglect));
-    slope = 2.0 * (u1 - u0);
-    if (fabs(u1_l) > fabs(slope)) u1_l = slope;
-    u0_l = ER[i0];
-    u0_r = 3.0 * u1 - 0.5 * u1_l - 2.0 * u0_l;
-    exp1 = (u0_r - u0_l) * (u1 - 0.5 * (u0_l + u0_r));
-    exp2 = (u0_r - u0_l) * (u0_r - u0_l) / 6.0;
-    if (exp1 > exp2) u0_l = 3.0 * u1 - 2.0 * u0_r;
-    if (exp1 < -exp2) u0_r = 3.0 * u1 - 2.0 * u0_l;
-    EL[i1] = u0_l; ER[i1] = u0_r;
-    c.C1[i1] = 6.0 * u1 - 4.0 * u0_l - 2.0 * u0_r;
-  }
+  w_ppm_limit(c, lane, n);
+  if (extrap && lane == 0) w_ppm_boundary_extrapolation(c, n, h_neglect);
   wsync();
   return INT_PPM;
 }
@@ -1131,34 +1220,14 @@ __device__ __forceinline__ double w_average_value_ppoly(const WCol &c, int metho
     }
     return a + xa * (q.b + xa * (q.c + xa * (q.d + xa * q.e)));
   }
-  if (xb > xa) {
-    if (method == INT_PCM) return c.u0[i0];
-    if (method == INT_PLM) return (c.EL[i0] + c.C1[i0] * 0.5 * (xb + xa));
-    const double mx = 0.5 * (xa + xb);
-    const double a_L = c.EL[i0], a_R = c.ER[i0], u_c = c.u0[i0];
-    const double a_c = 0.5 * ((u_c - a_L) + (u_c - a_R));
-    if (mx < 0.5) {
-      const double xa2b2ab = (xa * xa + xb * xb) + xa * xb;
-      return a_L + ((a_R - a_L) * mx + a_c * (3. * (xb + xa) - 2. * xa2b2ab));
-    } else {
-      const double Ya = 1. - xa, Yb = 1. - xb;
-      const double my = 0.5 * (Ya + Yb);
-      const double Ya2b2ab = (Ya * Ya + Yb * Yb) + Ya * Yb;
-      return a_R + ((a_L - a_R) * my + a_c * (3. * (Yb + Ya) - 2. * Ya2b2ab));
-    }
-  } else {
-    if (method == INT_PCM) return c.EL[i0];
+  if (method == INT_PCM) return (xb > xa) ? c.u0[i0] : c.EL[i0];
+  if (method == INT_PLM) {
+    if (xb > xa) return (c.EL[i0] + c.C1[i0] * 0.5 * (xb + xa));
     const double a_L = c.EL[i0], a_R = c.ER[i0];
-    const double Ya = 1. - xa;
-    if (method == INT_PLM) {
-      if (xa < 0.5) return a_L + xa * (a_R - a_L);
-      return a_R + Ya * (a_L - a_R);
-    }
-    const double u_c = c.u0[i0];
-    const double a_c = 3. * ((u_c - a_L) + (u_c - a_R));
-    if (xa < 0.5) return a_L + xa * ((a_R - a_L) + a_c * Ya);
-    return a_R + Ya * ((a_L - a_R) + a_c * xa);
+    if (xa < 0.5) return a_L + xa * (a_R - a_L);
+    return a_R + (1. - xa) * (a_L - a_R);
   }
+  return average_ppm(c.EL[i0], c.ER[i0], c.u0[i0], xa, xb);
 }
 
 // The field-dependent part of remap_via_sub_cells :653-766; the result replaces u0.
@@ -1269,88 +1338,6 @@ struct SRemapArgs {
   double *side;            // NF arrays of the fields' size: values of target cells that lie below what the lane has read so far
   long side_stride;        // doubles between the side arrays of two fields
 };
-
-struct EdgeW { double A1, A2, B, Cc, Hs; };
-// the thickness-only factors of edge_values_explicit_h4 (regrid_edge_values.F90:262-300) at the interface above cell i
-__device__ __forceinline__ EdgeW edge_weights_h4(double h0, double h1, double h2, double h3, double hNeglect) {
-  const double hMinFrac = 1.e-5;
-  if (h0 + h1 == 0.0 || h1 + h2 == 0.0 || h2 + h3 == 0.0) {
-    const double h_min = hMinFrac * fmax(hNeglect, (h0 + h1) + (h2 + h3));
-    h0 = fmax(h_min, h0); h1 = fmax(h_min, h1); h2 = fmax(h_min, h2); h3 = fmax(h_min, h3);
-  }
-  const double I_h12 = 1.0 / (h1 + h2);
-  const double I_den_et2 = 1.0 / (((h0 + h1) + h2) * (h0 + h1)); const double I_h012 = (h0 + h1) * I_den_et2;
-  const double I_den_et3 = 1.0 / ((h1 + (h2 + h3)) * (h2 + h3)); const double I_h123 = (h2 + h3) * I_den_et3;
-  EdgeW w;
-  w.A1 = (1.0 + (h1 * I_h012 + (h0 + h1) * I_h123)) * I_h12 * (h2 * (h2 + h3));
-  w.A2 = (1.0 + (h2 * I_h123 + (h2 + h3) * I_h012)) * I_h12 * (h1 * (h0 + h1));
-  w.B = (h1 * (h2 * (h2 + h3)) * I_den_et2);
-  w.Cc = (h2 * (h1 * (h0 + h1)) * I_den_et3);
-  w.Hs = (h0 + h1) + (h2 + h3);
-  return w;
-}
-__device__ __forceinline__ double edge_value_h4(const EdgeW &w, double um2, double um1, double u0, double up1) {
-  const double et1 = w.A1 * um1 + w.A2 * u0;
-  const double et2 = w.B * (um1 - um2);
-  const double et3 = w.Cc * (u0 - up1);
-  return (et1 + (et2 + et3)) / w.Hs;
-}
-// the slope of bound_edge_values (regrid_edge_values.F90:71-82) with hr = h(k) / ((h(km1) + h(kp1)) + 2 h(k)) or a negative hr for "no slope"
-__device__ __forceinline__ double bound_slope(double ukm1, double uk, double ukp1, double hr) {
-  double slope_x_h = 0.0;
-  if (hr >= 0.0) {
-    const double sigma_l = (uk - ukm1);
-    const double sigma_c = (ukp1 - ukm1) * hr;
-    const double sigma_r = (ukp1 - uk);
-    if ((sigma_l * sigma_r) > 0.0) slope_x_h = fsign(min3(fabs(sigma_l), fabs(sigma_c), fabs(sigma_r)), sigma_c);
-  }
-  return slope_x_h;
-}
-__device__ __forceinline__ double bound_left(double EL, double ukm1, double uk, double slope) {
-  if ((ukm1 - EL) * (EL - uk) < 0.0) EL = uk - fsign(fmin(fabs(slope), fabs(EL - uk)), slope);
-  return fmax(fmin(EL, fmax(ukm1, uk)), fmin(ukm1, uk));
-}
-__device__ __forceinline__ double bound_right(double ER, double ukp1, double uk, double slope) {
-  if ((ukp1 - ER) * (ER - uk) < 0.0) ER = uk + fsign(fmin(fabs(slope), fabs(ER - uk)), slope);
-  return fmax(fmin(ER, fmax(ukp1, uk)), fmin(ukp1, uk));
-}
-// PPM_limiter_standard for an interior cell (PPM_functions.F90:84-121)
-__device__ __forceinline__ void ppm_limit_cell(double u_l, double u_c, double u_r, double &edge_l, double &edge_r) {
-  if ((u_r - u_c) * (u_c - u_l) <= 0.0) {
-    edge_l = u_c; edge_r = u_c;
-  } else {
-    const double expr1 = 3.0 * (edge_r - edge_l) * ((u_c - edge_l) + (u_c - edge_r));
-    const double expr2 = (edge_r - edge_l) * (edge_r - edge_l);
-    if (expr1 > expr2) {
-      edge_l = u_c + 2.0 * (u_c - edge_r);
-      edge_l = fmax(fmin(edge_l, fmax(u_l, u_c)), fmin(u_l, u_c));
-    } else if (expr1 < -expr2) {
-      edge_r = u_c + 2.0 * (u_c - edge_l);
-      edge_r = fmax(fmin(edge_r, fmax(u_r, u_c)), fmin(u_r, u_c));
-    }
-  }
-  if (fabs(edge_r - edge_l) < fmax(1.e-60, DBL_EPSILON * fabs(u_c))) { edge_l = u_c; edge_r = u_c; }
-}
-// average_value_ppoly for INT_PPM (MOM_remapping.F90:998-1099)
-__device__ __forceinline__ double average_ppm(double a_L, double a_R, double u_c, double xa, double xb) {
-  if (xb > xa) {
-    const double mx = 0.5 * (xa + xb);
-    const double a_c = 0.5 * ((u_c - a_L) + (u_c - a_R));
-    if (mx < 0.5) {
-      const double xa2b2ab = (xa * xa + xb * xb) + xa * xb;
-      return a_L + ((a_R - a_L) * mx + a_c * (3. * (xb + xa) - 2. * xa2b2ab));
-    } else {
-      const double Ya = 1. - xa, Yb = 1. - xb;
-      const double my = 0.5 * (Ya + Yb);
-      const double Ya2b2ab = (Ya * Ya + Yb * Yb) + Ya * Yb;
-      return a_R + ((a_L - a_R) * my + a_c * (3. * (Yb + Ya) - 2. * Ya2b2ab));
-    }
-  }
-  const double Ya = 1. - xa;
-  const double a_c = 3. * ((u_c - a_L) + (u_c - a_R));
-  if (xa < 0.5) return a_L + xa * ((a_R - a_L) + a_c * Ya);
-  return a_R + Ya * ((a_L - a_R) + a_c * xa);
-}
 
 // waves per SIMD the register allocation aims at: one field fits 128 VGPRs (4 waves: 13.7 / 6.0 ms for 4 tracers / u and v at
 // 1440x1080x75 against 15.2 / 6.6 with 3), two fields need 168 (3 waves: 10.0 ms for 4 tracers; 19 ms when squeezed into 128); four
@@ -1616,18 +1603,14 @@ __global__ __launch_bounds__(64, NF == 1 ? 4 : 3) void ale_remap_stream_kernel(S
           const double ukp2 = (m + 2 <= n - 1) ? up2[f] : up1[f];
           slope_n = bound_slope(uc[f], up1[f], ukp2, hr_n);
           el_next = bound_left(Vn[f], uc[f], up1[f], slope_n);
-          if ((el_next - erB) * (up1[f] - uc[f]) < 0.0) {      // check_discontinuous_edge_values :141-159
-            double u0_avg = 0.5 * (erB + el_next);
-            u0_avg = fmax(fmin(u0_avg, fmax(uc[f], up1[f])), fmin(uc[f], up1[f]));
+          if (edges_discontinuous(uc[f], up1[f], erB, el_next)) {
+            const double u0_avg = bounded_edge_average(uc[f], up1[f], erB, el_next);
             erB = u0_avg; el_next = u0_avg;
           }
         }
         double eL = elC[f], eR = erB;
         if (m == 0 || m == n - 1) { eL = uc[f]; eR = uc[f]; }
         else ppm_limit_cell(um1[f], uc[f], up1[f], eL, eR);
-#if defined(SR_EXP) && SR_EXP == 2
-        eL = uc[f]; eR = uc[f];      // (experiment: no reconstruction)
-#endif
         aL[f] = eL; aR[f] = eR; ucell[f] = uc[f];
         elC[f] = el_next; slope_c[f] = slope_n;
       }
@@ -1649,9 +1632,6 @@ __global__ __launch_bounds__(64, NF == 1 ? 4 : 3) void ale_remap_stream_kernel(S
         } else break;
       }
       h0_eff_cur = eff;
-#if defined(SR_EXP) && SR_EXP == 1
-      h0_eff_cur = hcell;      // (experiment: no look-ahead)
-#endif
     }
     // ---- the sub-cells of this source cell ----
     for (int it = 0; it < ns && i_sub < ns; it++)
@@ -1756,6 +1736,18 @@ bool scheme_provided(int scheme) {
           scheme == REMAP_WENO_HYBGEN || scheme == REMAP_PQM_IH4IH3 || scheme == REMAP_PQM_IH6IH5);
 }
 
+// What ALE_remap_tracers and ALE_remap_velocities ask of the remapping control structure; the entries word the last two refusals themselves
+int check_remapping_cs(const mom6hip_ctx_t *ctx, const mom6hip_remapping_cs_t *cs, const char *answer_date_text, const char *bounds_text) {
+  M6_REQUIRE(scheme_provided(cs->remapping_scheme),
+             "MOM_remapping, build_reconstructions_1d: The selected remapping method is invalid "
+             "(libmom6hip provides PCM, PLM, PLM_HYBGEN, PPM_H4, PPM_IH4, PPM_HYBGEN, WENO_HYBGEN, PPM_CW, PQM_IH4IH3 and PQM_IH6IH5)");
+  // (edge_values_implicit_h6 and edge_slopes_implicit_h5 read the six cells at either end of a column, whatever its length)
+  M6_REQUIRE(cs->remapping_scheme != REMAP_PQM_IH6IH5 || ctx->g.nk >= 6 || ctx->g.nk <= 4, "PQM_IH6IH5 needs at least six layers (or at most four, where build_reconstructions_1d takes a lower scheme)");
+  M6_REQUIRE(cs->answer_date >= 20190101, "%s", answer_date_text);
+  M6_REQUIRE(!cs->force_bounds_in_subcell, "%s", bounds_text);
+  return 0;
+}
+
 // MOM6HIP_ALE_STREAM: 0 = never the streaming kernel; 1 = one field a launch; 2 (default) = two fields a launch (read at every
 // call: the tests switch between the forms)
 int stream_fields() { const char *e = getenv("MOM6HIP_ALE_STREAM"); return e ? atoi(e) : 2; }
@@ -1812,13 +1804,8 @@ extern "C" int mom6hip_ale_remap_tracers(mom6hip_ctx_t *ctx, const mom6hip_remap
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "ALE_remap_tracers: bad memspace");
   if (ntr <= 0) return 0;
   M6_REQUIRE(tr != nullptr && ntr <= 64, "ALE_remap_tracers: bad tracer list");
-  M6_REQUIRE(scheme_provided(cs->remapping_scheme),
-             "MOM_remapping, build_reconstructions_1d: The selected remapping method is invalid "
-             "(libmom6hip provides PCM, PLM, PLM_HYBGEN, PPM_H4, PPM_IH4, PPM_HYBGEN, WENO_HYBGEN, PPM_CW, PQM_IH4IH3 and PQM_IH6IH5)");
-  // (edge_values_implicit_h6 and edge_slopes_implicit_h5 read the six cells at either end of a column, whatever its length)
-  M6_REQUIRE(cs->remapping_scheme != REMAP_PQM_IH6IH5 || ctx->g.nk >= 6 || ctx->g.nk <= 4, "PQM_IH6IH5 needs at least six layers (or at most four, where build_reconstructions_1d takes a lower scheme)");
-  M6_REQUIRE(cs->answer_date >= 20190101, "ALE_remap_tracers: only REMAPPING_ANSWER_DATE >= 20190101 is provided");
-  M6_REQUIRE(!cs->force_bounds_in_subcell, "ALE_remap_tracers: REMAP_BOUND_INTERMEDIATE_VALUES is not provided");
+  if (const int rc = check_remapping_cs(ctx, cs, "ALE_remap_tracers: only REMAPPING_ANSWER_DATE >= 20190101 is provided",
+                                        "ALE_remap_tracers: REMAP_BOUND_INTERMEDIATE_VALUES is not provided")) return rc;
   M6_REQUIRE(ctx->g.mask2dT != nullptr, "ALE_remap_tracers: mask2dT is required");
   m6::GridDev &g = ctx->g;
   hipStream_t s = ctx->stream;
@@ -1935,12 +1922,8 @@ extern "C" int mom6hip_ale_remap_velocities(mom6hip_ctx_t *ctx, const mom6hip_re
                                             const double *h_old_v, const double *h_new_u, const double *h_new_v, double *u,
                                             double *v, int32_t memspace) {
   M6_REQUIRE(ctx && cs && h_old_u && h_old_v && h_new_u && h_new_v && u && v, "ALE_remap_velocities: null argument");
-  M6_REQUIRE(scheme_provided(cs->remapping_scheme),
-             "MOM_remapping, build_reconstructions_1d: The selected remapping method is invalid "
-             "(libmom6hip provides PCM, PLM, PLM_HYBGEN, PPM_H4, PPM_IH4, PPM_HYBGEN, WENO_HYBGEN, PPM_CW, PQM_IH4IH3 and PQM_IH6IH5)");
-  // (edge_values_implicit_h6 and edge_slopes_implicit_h5 read the six cells at either end of a column, whatever its length)
-  M6_REQUIRE(cs->remapping_scheme != REMAP_PQM_IH6IH5 || ctx->g.nk >= 6 || ctx->g.nk <= 4, "PQM_IH6IH5 needs at least six layers (or at most four, where build_reconstructions_1d takes a lower scheme)");
-  M6_REQUIRE(cs->answer_date >= 20190101 && !cs->force_bounds_in_subcell, "ALE_remap_velocities: unsupported remapping options");
+  if (const int rc = check_remapping_cs(ctx, cs, "ALE_remap_velocities: unsupported remapping options",
+                                        "ALE_remap_velocities: unsupported remapping options")) return rc;
   const m6::GridDev g = ctx->g;
   M6_REQUIRE(g.nk <= 128 && g.mask2dCu && g.mask2dCv, "ALE_remap_velocities: at most 128 layers; face masks are needed");
   const size_t bu = sizeof(double) * (size_t)g.nu3(), bv = sizeof(double) * (size_t)g.nv3();

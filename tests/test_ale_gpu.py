@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from mom6_amd import _abi, synth
-from mom6_amd.ale import ALE_remap_tracers, initialize_remapping
+from mom6_amd.ale import ALE_remap_tracers, ALE_remap_velocities, initialize_remapping
 from mom6_amd.tracer_advect import DeviceGrid
 from helpers import bits_equal, interior
 
@@ -99,6 +99,60 @@ def test_remap_stream_and_wave_kernels_agree(oracle, form, nk, monkeypatch):
     for m in range(len(tr)):
         got = d[m].cpu().numpy()
         assert bits_equal(ref[m], got), (form, nk, m, np.argwhere(ref[m] != got)[:5])
+    dg.close()
+
+
+SCHEMES = ["PCM", "PLM", "PLM_HYBGEN", "PPM_H4", "PPM_IH4", "PPM_HYBGEN", "WENO_HYBGEN", "PPM_CW", "PQM_IH4IH3", "PQM_IH6IH5"]
+
+
+@pytest.mark.parametrize("extrap", [False, True])
+@pytest.mark.parametrize("nk", [1, 6, 7, 64, 65])
+def test_remap_wave_kernel_at_the_lengths_where_it_changes_shape(oracle, nk, extrap, monkeypatch):
+    """The wave-per-column kernel (MOM6HIP_ALE_STREAM = 0, so PPM_H4 takes it too) with every scheme at the column lengths where its
+    work is laid out differently: 1 layer is build_reconstructions_1d's demotion to PCM; 6 and 7 are the shortest columns PQM_IH6IH5
+    takes, where the two biased rows and the two six-cell boundary systems of its tridiagonal systems overlap; at 64 and 65 a lane
+    takes a second cell, and the lanes 60-63 own an interior row and a special row.  The oracle's bits."""
+    monkeypatch.setenv("MOM6HIP_ALE_STREAM", "0")
+    g, h_old0, h_new, tr = remap_case(20, 6, nk, ntr=2, seed=300 + nk)
+    dg = DeviceGrid(g)
+    for scheme in SCHEMES:
+        h_old = h_old0
+        if scheme == "PQM_IH6IH5" or (scheme.startswith("PQM") and extrap):      # the floors of test_remap_tracers_parity, for its reasons
+            h_old = np.maximum(h_old0, 1.0e-3)
+        ref = [t.copy() for t in tr]
+        oracle.ale_remap_tracers(g, scheme, h_old, h_new, ref, boundary_extrapolation=extrap)
+        d = [torch.from_numpy(t.copy()).cuda() for t in tr]
+        ALE_remap_tracers(initialize_remapping(scheme, boundary_extrapolation=extrap), dg, torch.from_numpy(h_old).cuda(),
+                          torch.from_numpy(h_new).cuda(), d)
+        dg.sync()
+        for m in range(len(tr)):
+            got = d[m].cpu().numpy()
+            assert bits_equal(ref[m], got), (scheme, extrap, nk, m, np.argwhere(ref[m] != got)[:3])
+    dg.close()
+
+
+@pytest.mark.parametrize("scheme", ["PPM_IH4", "PQM_IH4IH3"])
+def test_remap_velocities_with_the_implicit_and_quartic_schemes(oracle, scheme):
+    """ALE_remap_velocities at the u and v points through the wave kernel with a tridiagonal scheme and boundary extrapolation (the other
+    tests remap velocities with PPM_H4, the Fortran drivers add PLM): the staggered column and mask indexing of the sub-cell kernel and
+    of the wave kernel with the edge-value (and edge-slope) systems.  8 layers, 24 x 10 with land; the oracle's bits."""
+    g, h_old, h_new, _ = remap_case(24, 10, 8, ntr=1, seed=77)
+    h_old = np.maximum(h_old, 1.0e-3)      # PQM_boundary_extrapolation_v1 divides by the widths of the bottom cells: as in test_remap_tracers_parity
+    hou, hov = oracle.ale_remap_set_h_vel(g, h_old)
+    hnu, hnv = oracle.ale_remap_set_h_vel(g, h_new)
+    rng = np.random.default_rng(78)
+    u0 = np.ascontiguousarray(rng.standard_normal(g.shape3(_abi.POS_U)))
+    v0 = np.ascontiguousarray(np.round(3.0 * rng.standard_normal(g.shape3(_abi.POS_V))))      # exact ties and extrema
+    u_o, v_o = u0.copy(), v0.copy()
+    oracle.ale_remap_velocities(g, scheme, hou, hov, hnu, hnv, u_o, v_o, boundary_extrapolation=True)
+    dg = DeviceGrid(g)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    u, v = T(u0.copy()), T(v0.copy())
+    ALE_remap_velocities(initialize_remapping(scheme, boundary_extrapolation=True), dg, T(hou), T(hov), T(hnu), T(hnv), u, v)
+    dg.sync()
+    for name, got, ref, was in (("u", u.cpu().numpy(), u_o, u0), ("v", v.cpu().numpy(), v_o, v0)):
+        assert bits_equal(ref, got), (scheme, name, np.argwhere(ref != got)[:3])
+        assert not bits_equal(ref, was), name
     dg.close()
 
 
