@@ -2,23 +2,33 @@
 // finite-volume pressure-gradient integrals of int_density_dz_generic_plm
 // (src/core/MOM_density_integrals.F90:369-769), PLM edge values of T and S (ALE_PLM_edge_values,
 // src/ALE/MOM_ALE.F90:1520-1579), Set_pbce_Bouss (src/core/MOM_PressureForce_Montgomery.F90:649-748) and the
-// Wright / linear equations of state (src/equation_of_state/MOM_EOS_Wright.F90:80-206, MOM_EOS_linear.F90).
+// Wright / linear equations of state (src/equation_of_state/MOM_EOS_Wright.F90:80-206, MOM_EOS_linear.F90);
+// PressureForce_FV_nonBouss (:89-452) and ALE_PLM_edge_values for a caller's own field.
 //
 // This operator is fp64-VALU bound, not HBM bound: 35 equation-of-state evaluations per cell-layer (5 for
 // the vertical Boole quadrature, 3x5 on each of the two faces), each ~45 flops and one IEEE division,
-// against ~64 B of algorithmic traffic.  Two kernels, both one lane per column with the k loop inside the
-// lane (the pressure anomaly pa and the interface heights e are running sums in k) and lanes along i:
-//   pgf_column_kernel  per h-point column: e (bottom-up), then top-down the PLM edge values of T and S with
-//                      a rolling k window, the vertical integrals dpa / intz_dpa (5 EOS evaluations), pbce
-//                      and eta.  Writes e, T_t, T_b, S_t, S_b, dpa, intz_dpa.
-//   pgf_face_kernel    per (I,j)/(i,J) face pair: the 15+15 EOS evaluations of intx_dpa / inty_dpa and the
-//                      PFu / PFv formulas (:794-811), carrying pa, intx_pa, inty_pa down the column.
-//   pgf_face_kernel_t  the same with the equation of state (WRIGHT), the mass weighting, the u_bc_accel fusion and the surface
-//                      pressure fixed at compile time: a layer is one straight-line region in which the scheduler interleaves
-//                      the 30 evaluations (9.7 -> 7.8 ms at 1440x1080x75, profiles/r07_pgf_face.txt).  The host picks the
-//                      instantiation; a combination without one runs pgf_face_kernel.
+// against ~64 B of algorithmic traffic.  Every form is a pair of kernels, both one lane per column with the k loop inside
+// the lane (the pressure anomaly pa and the interface heights e are running sums in k) and lanes along i:
+//   a column kernel    per h-point column: e and eta (column_heights), the vertical integrals dpa / intz_dpa and pbce
+//                      (pbce_bouss_eos).  pgf_column_kernel (PLM: the edge values of T and S from the rolling k window
+//                      PlmH / PlmQ, 5 EOS evaluations), pgf_pcm_column_kernel<MODE> (no reconstruction), pgfnb_column_kernel.
+//   a face kernel      per (I,j)/(i,J) face pair: intx_dpa / inty_dpa and the PFu / PFv formula (pgf_accel, :794-811),
+//                      carrying pa, intx_pa, inty_pa down the column.
+// The Boussinesq face kernels are two frames, and two on purpose:
+//   pgf_face_kernel<KIND>   every option read at run time; KIND picks the face integral: the PLM quadrature (15+15 EOS
+//                      evaluations, face_integral) or one of the three forms without a reconstruction (pcm_face_integral).
+//   pgf_face_kernel_t  the PLM quadrature with the equation of state (WRIGHT), the mass weighting, the u_bc_accel fusion and the
+//                      surface pressure fixed at compile time: a layer is one straight-line region in which the scheduler
+//                      interleaves the 30 evaluations (9.7 -> 7.8 ms at 1440x1080x75, profiles/r07_pgf_face.txt).  The host
+//                      picks the instantiation; a combination without one runs pgf_face_kernel<PGF_FACE_PLM>.  Its shape (both
+//                      faces computed by every lane, 32-bit byte offsets, no run-time option) is what made it faster; folding
+//                      the run-time frame into it would change the speed of every PLM run that is not WRIGHT, which is a
+//                      decision about performance and not one about the text.  The two frames share the integral
+//                      (face_integral_core), pgf_accel and bc_accel.
+// pgfnb_face_kernel is a third frame: its formula has no Z_to_H, it subtracts before it uses the running sums, and it reads
+// the interface pressures where the others read heights.
 // Splitting at the column kernel keeps the EOS count at the reference's 35 per cell (a single fused
-// kernel would have to recompute the neighbours' vertical integrals: 45).
+// kernel would have to recompute the neighbours' vertical integrals: 45; tools/experiments/pgf_fused_kernel_r04.txt).
 #include <cmath>
 
 #include "common.hpp"
@@ -63,6 +73,36 @@ __device__ double plm_extrapolate_slope(double h_l, double h_c, double h_neglect
   return 2.0 * (u_c - left_edge);
 }
 
+
+// ---- the rolling k window of ALE_PLM_edge_values (MOM_ALE.F90:1549-1576) ---------------------------------------------
+// A lane walks its column top down holding, for the 0-based level kk in hand, h and one scalar at kk-1 (m), kk (c), kk+1 (p),
+// kk+2 (q) and the scalar's slopes at kk-1, kk, kk+1 (Fortran slp(1) = slp(nz) = 0).  Levels outside the column read as 0.
+struct PlmCol { long o2, pl; int nz, extrap; double h_neglect; };
+struct PlmH { double m, c, p, q; };
+struct PlmQ { double m, c, p, q, sm, sc, sp; };
+__device__ __forceinline__ double plm_ld(const PlmCol &c, const double *a, int kk) { return (kk >= 0 && kk < c.nz) ? a[c.o2 + c.pl * kk] : 0.0; }
+__device__ __forceinline__ PlmH plm_prime_h(const PlmCol &c, const double *h) { return PlmH{0., plm_ld(c, h, 0), plm_ld(c, h, 1), plm_ld(c, h, 2)}; }
+__device__ __forceinline__ PlmQ plm_prime(const PlmCol &c, const PlmH &H, const double *a) {
+  PlmQ Q{0., plm_ld(c, a, 0), plm_ld(c, a, 1), plm_ld(c, a, 2), 0., 0., 0.};
+  if (c.nz >= 3) Q.sp = plm_slope_wa(H.c, H.p, H.q, c.h_neglect, Q.c, Q.p, Q.q);      // slp of level 1 (Fortran k=2)
+  return Q;
+}
+// the edge values of level kk: monotonized in the interior, extrapolated or flat in the top and bottom levels
+__device__ __forceinline__ void plm_edges(const PlmCol &c, const PlmH &H, const PlmQ &Q, int kk, double &Qt, double &Qb) {
+  double m;
+  if (kk >= 1 && kk <= c.nz - 2) m = plm_monotonized_slope(Q.m, Q.c, Q.p, Q.sm, Q.sc, Q.sp);
+  else if (c.extrap) m = kk == 0 ? -plm_extrapolate_slope(H.p, H.c, c.h_neglect, Q.p, Q.c) : plm_extrapolate_slope(H.m, H.c, c.h_neglect, Q.m, Q.c);
+  else { Qt = Q.c; Qb = Q.c; return; }
+  Qt = Q.c - 0.5 * m; Qb = Q.c + 0.5 * m;
+}
+// on to level kk+1: h first, then every scalar (its new slope, of level kk+2, needs h at kk+1, kk+2, kk+3)
+__device__ __forceinline__ void plm_advance_h(const PlmCol &c, PlmH &H, const double *h, int kk) { H.m = H.c; H.c = H.p; H.p = H.q; H.q = plm_ld(c, h, kk + 3); }
+__device__ __forceinline__ void plm_advance(const PlmCol &c, const PlmH &H, PlmQ &Q, const double *a, int kk) {
+  Q.m = Q.c; Q.c = Q.p; Q.p = Q.q; Q.q = plm_ld(c, a, kk + 3);
+  Q.sm = Q.sc; Q.sc = Q.sp;
+  Q.sp = (kk + 2 <= c.nz - 2) ? plm_slope_wa(H.c, H.p, H.q, c.h_neglect, Q.c, Q.p, Q.q) : 0.;      // zero at the bottom level and beyond
+}
+
 struct PgfArgs {
   m6::GridDev g;
   EosDev eos;
@@ -83,6 +123,59 @@ struct PgfArgs {
   int bc_inviscid;
 };
 
+
+// ---- the pieces the Boussinesq kernels share ---------------------------------------------------------------------------
+// :572 / :646-648: the interface heights bottom-up into p.e (nk+1 planes), eta (:842); returns the height of the sea surface
+__device__ __forceinline__ double column_heights(const PgfArgs &p, long o2, long pl, int nz) {
+  const m6::GridDev &g = p.g;
+  double ek = -g.bathyT[o2];
+  p.e[o2 + pl * nz] = ek;
+  for (int k = nz - 1; k >= 0; k--) {
+    ek = ek + p.h[o2 + pl * k] * g.H_to_Z;
+    p.e[o2 + pl * k] = ek;
+  }
+  if (p.eta) p.eta[o2] = ek * g.Z_to_H;
+  return ek;
+}
+// Set_pbce_Bouss with an equation of state, one layer (MOM_PressureForce_Montgomery.F90:702-729); rel = (e_K - e_bot) * Ihtot
+__device__ __forceinline__ double pbce_bouss_eos(const PgfArgs &p, int k, double T_m, double T_c, double S_m, double S_c, double press,
+                                                 double G_Rho0, double rel, double pbce_prev) {
+  if (k == 0) {
+    const double rho_in_situ = eos_density(p.eos, T_c, S_c, press);
+    return G_Rho0 * (p.GFS_scale * rho_in_situ) * p.g.H_to_Z;
+  }
+  const double T_int = 0.5 * (T_m + T_c), S_int = 0.5 * (S_m + S_c);
+  double dR_dT, dR_dS;
+  eos_density_derivs(p.eos, T_int, S_int, press, dR_dT, dR_dS);
+  return pbce_prev + G_Rho0 * rel * (dR_dT * (T_c - T_m) + dR_dS * (S_c - S_m));
+}
+// hWght scaled by the squared relative difference of the two thicknesses (MOM_density_integrals.F90:606-613); returns iDenom
+__device__ __forceinline__ double mass_weight_scale(double &hWght, double hL, double hR) {
+  const double rr = (hL - hR) / (hL + hR);
+  hWght = hWght * (rr * rr);
+  return 1. / (hWght * (hR + hL) + hL * hR);
+}
+// the four weights of the thickness-weighted interpolation across a face (MOM_EOS_Wright.F90:560-573 and its kin)
+struct MassWt { double LL, LR, RR, RL; };
+__device__ __forceinline__ MassWt mass_weights(double hWght, double hL, double hR) {
+  if (hWght > 0.) {
+    const double iDenom = mass_weight_scale(hWght, hL, hR);
+    return MassWt{(hWght * hL + hR * hL) * iDenom, (hWght * hR) * iDenom, (hWght * hR + hR * hL) * iDenom, (hWght * hL) * iDenom};
+  }
+  return MassWt{1.0, 0.0, 1.0, 0.0};
+}
+// PFu / PFv of one face between the column in hand (c) and its neighbour (n), MOM_PressureForce_FV.F90:794-811
+__device__ __forceinline__ double pgf_accel(const m6::GridDev &g, double pa_c, double h_c, double iz_c, double pa_n, double h_n, double iz_n,
+                                            double int_pa, double ec_Kp1, double en_Kp1, double int_dpa, double f, double h_neglect) {
+  return (((pa_c * h_c + iz_c) - (pa_n * h_n + iz_n)) + ((h_n - h_c) * int_pa - (en_Kp1 - ec_Kp1) * int_dpa * g.Z_to_H)) *
+         (f / ((h_c + h_n) + h_neglect));
+}
+// the RK2 step's u_bc_accel = (CAu + PFu) + diffu, or (CAu + PFu) with its -0 turned into +0 where there is no diffu
+__device__ __forceinline__ double bc_accel(double ca, double pf, double df, bool inviscid) {
+  const double a = ca + pf;
+  return inviscid ? ((a == 0.0) ? 0.0 : a) : a + df;
+}
+
 // ---- column kernel -------------------------------------------------------------------------------
 #ifndef PGF_COL_OCC
 #define PGF_COL_OCC 4      // waves per SIMD the register allocation aims at (tools/build_variant.sh for experiments)
@@ -97,16 +190,7 @@ __global__ __launch_bounds__(64, PGF_COL_OCC) void pgf_column_kernel(PgfArgs p) 
   if (i > g.iec + 1) return;
   const int nz = g.nk;
   const long o2 = g.h2(i, j), pl = (long)g.nih * g.njh;
-  const double h_neglect = g.H_subroundoff;
-  // :572 / :646-648, bottom-up
-  double ek = -g.bathyT[o2];
-  p.e[o2 + pl * nz] = ek;
-  for (int k = nz - 1; k >= 0; k--) {
-    ek = ek + p.h[o2 + pl * k] * g.H_to_Z;
-    p.e[o2 + pl * k] = ek;
-  }
-  const double e_top = ek, e_bot = -g.bathyT[o2];
-  if (p.eta) p.eta[o2] = e_top * g.Z_to_H;      // :842
+  const double e_top = column_heights(p, o2, pl, nz), e_bot = -g.bathyT[o2];
 
   const double G_e = g.g_Earth, rho_0 = p.rho_ref, rho_ref = p.rho_ref;
   const double GxRho = G_e * rho_0;
@@ -114,42 +198,15 @@ __global__ __launch_bounds__(64, PGF_COL_OCC) void pgf_column_kernel(PgfArgs p) 
   const double Rho0xG = p.rho_ref * g.g_Earth, G_Rho0 = g.g_Earth / g.Rho0;
   const double Ihtot = g.H_to_Z / ((e_top - e_bot) + g.dZ_subroundoff);
 
-  // rolling window over k (0-based level kk): values at kk-1 (m), kk (c), kk+1 (p), kk+2 (q)
-  auto ld = [&](const double *a, int kk) -> double { return (kk >= 0 && kk < nz) ? a[o2 + pl * kk] : 0.0; };
-  double h_m = 0., h_c = ld(p.h, 0), h_p = ld(p.h, 1), h_q = ld(p.h, 2);
-  double T_m = 0., T_c = ld(p.T, 0), T_p = ld(p.T, 1), T_q = ld(p.T, 2);
-  double S_m = 0., S_c = ld(p.S, 0), S_p = ld(p.S, 1), S_q = ld(p.S, 2);
-  // slp at kk-1, kk, kk+1 (Fortran slp(1) = slp(nz) = 0)
-  double sT_m = 0., sT_c = 0., sT_p = 0., sS_m = 0., sS_c = 0., sS_p = 0.;
-  if (nz >= 3) {   // slp of level 1 (Fortran k=2)
-    sT_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, T_c, T_p, T_q);
-    sS_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, S_c, S_p, S_q);
-  }
+  const PlmCol col{o2, pl, nz, p.boundary_extrap, g.H_subroundoff};
+  PlmH H = plm_prime_h(col, p.h);
+  PlmQ WT = plm_prime(col, H, p.T), WS = plm_prime(col, H, p.S);
   double e_K = e_top, pbce_prev = 0.0;
   for (int kk = 0; kk < nz; kk++) {
     const long o3 = o2 + pl * kk;
-    // ---- ALE_PLM_edge_values :1549-1576 ----
     double Tt, Tb, St, Sb;
-    if (kk >= 1 && kk <= nz - 2) {
-      const double mT = plm_monotonized_slope(T_m, T_c, T_p, sT_m, sT_c, sT_p);
-      Tt = T_c - 0.5 * mT; Tb = T_c + 0.5 * mT;
-      const double mS = plm_monotonized_slope(S_m, S_c, S_p, sS_m, sS_c, sS_p);
-      St = S_c - 0.5 * mS; Sb = S_c + 0.5 * mS;
-    } else if (p.boundary_extrap) {
-      if (kk == 0) {
-        const double mT = -plm_extrapolate_slope(h_p, h_c, h_neglect, T_p, T_c);
-        Tt = T_c - 0.5 * mT; Tb = T_c + 0.5 * mT;
-        const double mS = -plm_extrapolate_slope(h_p, h_c, h_neglect, S_p, S_c);
-        St = S_c - 0.5 * mS; Sb = S_c + 0.5 * mS;
-      } else {
-        const double mT = plm_extrapolate_slope(h_m, h_c, h_neglect, T_m, T_c);
-        Tt = T_c - 0.5 * mT; Tb = T_c + 0.5 * mT;
-        const double mS = plm_extrapolate_slope(h_m, h_c, h_neglect, S_m, S_c);
-        St = S_c - 0.5 * mS; Sb = S_c + 0.5 * mS;
-      }
-    } else {
-      Tt = T_c; Tb = T_c; St = S_c; Sb = S_c;
-    }
+    plm_edges(col, H, WT, kk, Tt, Tb);
+    plm_edges(col, H, WS, kk, St, Sb);
     p.T_t[o3] = Tt; p.T_b[o3] = Tb; p.S_t[o3] = St; p.S_b[o3] = Sb;
 
     // ---- vertical integrals, MOM_density_integrals.F90:519-554 ----
@@ -169,48 +226,28 @@ __global__ __launch_bounds__(64, PGF_COL_OCC) void pgf_column_kernel(PgfArgs p) 
     const double iz = 0.5 * G_e * (dz * dz) * (rho_anom - C1_90 * (16.0 * (r5[3] - r5[1]) + 7.0 * (r5[4] - r5[0])));
     p.intz_dpa[o3] = iz * g.Z_to_H;      // MOM_PressureForce_FV.F90:772
 
-    // ---- Set_pbce_Bouss :702-729 ----
     if (p.pbce) {
-      const double press = -Rho0xG * (e_K - p.Z_ref);
-      double pb;
-      if (kk == 0) {
-        const double rho_in_situ = eos_density(p.eos, T_c, S_c, press);
-        pb = G_Rho0 * (p.GFS_scale * rho_in_situ) * g.H_to_Z;
-      } else {
-        const double T_int = 0.5 * (T_m + T_c), S_int = 0.5 * (S_m + S_c);
-        double dR_dT, dR_dS;
-        eos_density_derivs(p.eos, T_int, S_int, press, dR_dT, dR_dS);
-        pb = pbce_prev + G_Rho0 * ((e_K - e_bot) * Ihtot) * (dR_dT * (T_c - T_m) + dR_dS * (S_c - S_m));
-      }
-      p.pbce[o3] = pb;
-      pbce_prev = pb;
+      pbce_prev = pbce_bouss_eos(p, kk, WT.m, WT.c, WS.m, WS.c, -Rho0xG * (e_K - p.Z_ref), G_Rho0, (e_K - e_bot) * Ihtot, pbce_prev);
+      p.pbce[o3] = pbce_prev;
     }
-
-    // ---- advance the window ----
     e_K = e_Kp1;
-    h_m = h_c; h_c = h_p; h_p = h_q; h_q = ld(p.h, kk + 3);
-    T_m = T_c; T_c = T_p; T_p = T_q; T_q = ld(p.T, kk + 3);
-    S_m = S_c; S_c = S_p; S_p = S_q; S_q = ld(p.S, kk + 3);
-    sT_m = sT_c; sT_c = sT_p; sS_m = sS_c; sS_c = sS_p;
-    // slope of the new level kk+2 (needs levels kk+1, kk+2, kk+3); zero at the bottom level and beyond
-    if (kk + 2 <= nz - 2) {
-      sT_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, T_c, T_p, T_q);
-      sS_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, S_c, S_p, S_q);
-    } else {
-      sT_p = 0.; sS_p = 0.;
-    }
+    plm_advance_h(col, H, p.h, kk);
+    plm_advance(col, H, WT, p.T, kk);
+    plm_advance(col, H, WS, p.S, kk);
   }
 }
 
-// ---- face kernel ---------------------------------------------------------------------------------
+// ---- the face integral of the PLM quadrature -----------------------------------------------------------------------------
 // what the face integrals read of one column in one layer
 struct PgfColK { double e_Kp1, Tt, Tb, St, Sb, dpa; };
-constexpr int PGF_RUNTIME = -1;      // a template option read from PgfArgs at run time (pgf_face_kernel)
+constexpr int PGF_RUNTIME = -1;      // a template option read from PgfArgs at run time (face_integral)
 
 // 15 EOS evaluations across one face between the columns L (left/south) and R (right/north), from values in registers.
 // FORM: EOS_FORM_RUNTIME or a MOM6HIP_EOS_* value; MASSW: PGF_RUNTIME (p.massw), 0 or 1.  With both fixed at compile time the
 // 15 evaluations are one straight-line region (the m and n loops unroll; the only branch, on hWght, lies ahead of them).
-template <int FORM, int MASSW, bool FENCE = false>
+// The weighted edge values keep int_density_dz_generic_plm's association ((hWght*hR)*TtR + (hWght*hL + hR*hL)*TtL) * iDenom, which
+// rounds differently from mass_weights' wtT_L * TL + wtT_R * TR.
+template <int FORM, int MASSW>
 __device__ __forceinline__ double face_integral_core(const PgfArgs &p, const PgfColK &L, const PgfColK &R, double bathyL, double bathyR,
                                                      double eL_K, double eR_K) {
   const m6::GridDev &g = p.g;
@@ -226,9 +263,7 @@ __device__ __forceinline__ double face_integral_core(const PgfArgs &p, const Pgf
   if (hWght > 0.) {
     const double hL = (eL_K - eL_Kp1) + g.dZ_subroundoff;
     const double hR = (eR_K - eR_Kp1) + g.dZ_subroundoff;
-    const double rr = (hL - hR) / (hL + hR);
-    hWght = hWght * (rr * rr);
-    const double iDenom = 1. / (hWght * (hR + hL) + hL * hR);
+    const double iDenom = mass_weight_scale(hWght, hL, hR);
     Ttl = ((hWght * hR) * TtR + (hWght * hL + hR * hL) * TtL) * iDenom;
     Ttr = ((hWght * hL) * TtL + (hWght * hR + hR * hL) * TtR) * iDenom;
     Tbl = ((hWght * hR) * TbR + (hWght * hL + hR * hL) * TbL) * iDenom;
@@ -265,7 +300,6 @@ __device__ __forceinline__ double face_integral_core(const PgfArgs &p, const Pgf
       r[n - 1] = eos_density_anomaly<FORM>(p.eos, Tn, Sn, pn, rho_ref);
     }
     intz[m - 1] = G_e * dz_x * (C1_90 * (7.0 * (r[0] + r[4]) + 32.0 * (r[1] + r[3]) + 12.0 * r[2]));
-    if (FENCE) __builtin_amdgcn_sched_barrier(0);
   }
   return C1_90 * (7.0 * (intz[0] + intz[4]) + 32.0 * (intz[1] + intz[3]) + 12.0 * intz[2]);
 }
@@ -281,97 +315,23 @@ __device__ __forceinline__ double face_integral(const PgfArgs &p, long oL3, long
   return face_integral_core<EOS_FORM_RUNTIME, PGF_RUNTIME>(p, L, R, p.g.bathyT[oL2], p.g.bathyT[oR2], eL_K, eR_K);
 }
 
-__global__ __launch_bounds__(64, PGF_FACE_OCC) void pgf_face_kernel(PgfArgs p) {
-  const m6::GridDev &g = p.g;
-  const int i = g.isc - 1 + blockIdx.x * 64 + threadIdx.x;      // I (x face) / i (y face)
-  const int j = g.jsc - 1 + blockIdx.y;                         // j (x face) / J (y face)
-  if (i > g.iec) return;
-  const bool do_x = (j >= g.jsc), do_y = (i >= g.isc);          // j <= jec and i <= iec by the grid size
-  if (!do_x && !do_y) return;
-  const int nz = g.nk;
-  const long pl = (long)g.nih * g.njh, plU = (long)(g.nih + 1) * g.njh, plV = (long)g.nih * (g.njh + 1);
-  const long oc = g.h2(i, j), oe = oc + 1, on = oc + g.nih;
-  const double h_neglect = g.H_subroundoff, I_Rho0 = 1.0 / g.Rho0;
-  const double rg = p.rho_ref * g.g_Earth;
-  auto pa0 = [&](long o2) -> double {
-    double v = rg * (p.e[o2] - p.Z_ref);
-    if (p.p_atm) v = v + p.p_atm[o2];
-    return v;
-  };
-  double pa_c = pa0(oc), pa_e = do_x ? pa0(oe) : 0.0, pa_n = do_y ? pa0(on) : 0.0;
-  double intx_pa = 0.5 * (pa_c + pa_e), inty_pa = 0.5 * (pa_c + pa_n);
-  const double fx = do_x ? (2.0 * I_Rho0 * g.IdxCu[g.u2(i, j)]) : 0.0;
-  const double fy = do_y ? (2.0 * I_Rho0 * g.IdyCv[g.v2(i, j)]) : 0.0;
-  double ec_K = p.e[oc], ee_K = do_x ? p.e[oe] : 0.0, en_K = do_y ? p.e[on] : 0.0;
-  for (int k = 0; k < nz; k++) {
-    const long c3 = oc + pl * k;
-    const double ec_Kp1 = p.e[c3 + pl];
-    const double h_c = p.h[c3], dpa_c = p.dpa[c3], iz_c = p.intz_dpa[c3];
-    if (do_x) {
-      const long e3 = c3 + 1;
-      const double ee_Kp1 = p.e[e3 + pl];
-      const double h_e = p.h[e3];
-      const double intx_dpa = face_integral(p, c3, e3, oc, oe, ec_K, ec_Kp1, ee_K, ee_Kp1);
-      const double pfu = (((pa_c * h_c + iz_c) - (pa_e * h_e + p.intz_dpa[e3])) +
-                          ((h_e - h_c) * intx_pa - (ee_Kp1 - ec_Kp1) * intx_dpa * g.Z_to_H)) *
-                         (fx / ((h_c + h_e) + h_neglect));
-      p.PFu[g.u2(i, j) + plU * k] = pfu;
-      if (p.bc_u) {
-        const long n = g.u2(i, j) + plU * k;
-        double a = p.bc_CAu[n] + pfu;
-        if (p.bc_inviscid) a = (a == 0.0) ? 0.0 : a; else a = a + p.bc_diffu[n];
-        p.bc_u[n] = a;
-      }
-      intx_pa = intx_pa + intx_dpa;
-      pa_e = pa_e + p.dpa[e3];
-      ee_K = ee_Kp1;
-    }
-    if (do_y) {
-      const long n3 = c3 + g.nih;
-      const double en_Kp1 = p.e[n3 + pl];
-      const double h_n = p.h[n3];
-      const double inty_dpa = face_integral(p, c3, n3, oc, on, ec_K, ec_Kp1, en_K, en_Kp1);
-      const double pfv = (((pa_c * h_c + iz_c) - (pa_n * h_n + p.intz_dpa[n3])) +
-                          ((h_n - h_c) * inty_pa - (en_Kp1 - ec_Kp1) * inty_dpa * g.Z_to_H)) *
-                         (fy / ((h_c + h_n) + h_neglect));
-      p.PFv[g.v2(i, j) + plV * k] = pfv;
-      if (p.bc_v) {
-        const long n = g.v2(i, j) + plV * k;
-        double a = p.bc_CAv[n] + pfv;
-        if (p.bc_inviscid) a = (a == 0.0) ? 0.0 : a; else a = a + p.bc_diffv[n];
-        p.bc_v[n] = a;
-      }
-      inty_pa = inty_pa + inty_dpa;
-      pa_n = pa_n + p.dpa[n3];
-      en_K = en_Kp1;
-    }
-    pa_c = pa_c + dpa_c;
-    ec_K = ec_Kp1;
-  }
-}
-
 // ---- the face kernel with its options fixed at compile time ------------------------------------------------------------
 // FORM (a MOM6HIP_EOS_* value), MASSW (MASS_WEIGHT_IN_PRESSURE_GRADIENT), BC (the RK2 step's u_bc_accel: PGF_BC_OFF, _VISCOUS,
-// _INVISCID) and PATM (a surface pressure) are template parameters; mom6hip_pressureforce_fv_bouss picks the instantiation and
-// keeps pgf_face_kernel for every combination that has none.  The results are pgf_face_kernel's bit for bit; what changes is
+// _INVISCID) and PATM (a surface pressure) are template parameters; mom6hip_pressureforce_fv_bouss picks the instantiation and keeps
+// pgf_face_kernel<PGF_FACE_PLM> for every combination that has none.  The results are that kernel's bit for bit; what changes is
 // the shape of the code:
 //   - both faces of a point are computed by every lane (a lane without an x or a y face, on the first row or in the first
 //     column, takes its own column as the neighbour and stores nothing), so a layer is one straight-line region: its 30 EOS
 //     evaluations, each a serial chain ending in an IEEE division, are interleaved by the scheduler instead of being run one
 //     after the other in basic blocks of their own;
 //   - array elements are addressed by 32-bit byte offsets from the uniform array pointers (pgf_ld);
-//   - optionally (PGF_FACE_PF, off by default: it measured no faster) the loads are a layer ahead: what the evaluations need
-//     first (the interface heights and the edge values of T and S of the three columns, 1) or everything (2) is loaded for layer
-//     k+1 before layer k's arithmetic.
-// Defaults as measured at 1440x1080x75 (profiles/r07_pgf_face.txt): no layer-ahead loads, 3 waves per SIMD (152 VGPRs, no scratch).
+// The PFu / PFv formula is written out here and is pgf_accel's: called through pgf_accel (by value, by reference, inlined early or
+// late, inside or ahead of the store's branch) the compiler sinks the loads of h and intz_dpa in another order and commutes one
+// addition, which is not the measured kernel (profiles/pressure_force_one_text.txt, note (a)).
+// Loads a layer ahead and scheduling fences between the faces were tried and gained nothing: tools/experiments/pgf_face_layer_ahead_r07.txt.
+// Defaults as measured at 1440x1080x75 (profiles/r07_pgf_face.txt): 3 waves per SIMD (152 VGPRs, no scratch).
 #ifndef PGF_FACE_T_OCC
 #define PGF_FACE_T_OCC 3
-#endif
-#ifndef PGF_FACE_PF
-#define PGF_FACE_PF 0
-#endif
-#ifndef PGF_FACE_FENCE
-#define PGF_FACE_FENCE 0      // 1: no scheduling across the two faces; 2: nor across the three groups of five evaluations of a face
 #endif
 constexpr int PGF_BC_OFF = 0, PGF_BC_VISCOUS = 1, PGF_BC_INVISCID = 2;
 struct PgfColLate { double h, iz; };      // what only the PFu / PFv formulas read
@@ -419,57 +379,24 @@ __global__ __launch_bounds__(64, PGF_FACE_T_OCC) void pgf_face_kernel_t(PgfArgs 
   double bathy_c = 0., bathy_e = 0., bathy_n = 0.;
   if (MASSW) { bathy_c = g.bathyT[oc]; bathy_e = g.bathyT[oe]; bathy_n = g.bathyT[on]; }
   double ec_K = p.e[oc], ee_K = p.e[oe], en_K = p.e[on];
-#if PGF_FACE_PF >= 1
-  PgfColK c = pgf_load_col(p, c3, pl), e = pgf_load_col(p, e3, pl), n = pgf_load_col(p, n3, pl);
-#endif
-#if PGF_FACE_PF == 2
-  PgfColLate lc = pgf_load_late(p, c3), le = pgf_load_late(p, e3), ln = pgf_load_late(p, n3);
-  double cau = 0., cav = 0., dfu = 0., dfv = 0.;
-  if (BC != PGF_BC_OFF) { cau = pgf_ld(p.bc_CAu, u3); cav = pgf_ld(p.bc_CAv, v3); }
-  if (BC == PGF_BC_VISCOUS) { dfu = pgf_ld(p.bc_diffu, u3); dfv = pgf_ld(p.bc_diffv, v3); }
-#endif
   for (int k = 0; k < nz; k++) {
-    // the next layer's loads (the last layer loads itself again: no branch in the loop)
-    const unsigned dn = (k + 1 < nz) ? pl : 0u, dnU = (k + 1 < nz) ? plU : 0u, dnV = (k + 1 < nz) ? plV : 0u;
-    (void)dn; (void)dnU; (void)dnV;
-#if PGF_FACE_PF >= 1
-    const PgfColK c1 = pgf_load_col(p, c3 + dn, pl), e1 = pgf_load_col(p, e3 + dn, pl), n1 = pgf_load_col(p, n3 + dn, pl);
-#else
     const PgfColK c = pgf_load_col(p, c3, pl), e = pgf_load_col(p, e3, pl), n = pgf_load_col(p, n3, pl);
-#endif
-#if PGF_FACE_PF == 2
-    const PgfColLate lc1 = pgf_load_late(p, c3 + dn), le1 = pgf_load_late(p, e3 + dn), ln1 = pgf_load_late(p, n3 + dn);
-    double cau1 = 0., cav1 = 0., dfu1 = 0., dfv1 = 0.;
-    if (BC != PGF_BC_OFF) { cau1 = pgf_ld(p.bc_CAu, u3 + dnU); cav1 = pgf_ld(p.bc_CAv, v3 + dnV); }
-    if (BC == PGF_BC_VISCOUS) { dfu1 = pgf_ld(p.bc_diffu, u3 + dnU); dfv1 = pgf_ld(p.bc_diffv, v3 + dnV); }
-#else
     // read only by the formulas behind the evaluations: in flight while those run
     const PgfColLate lc = pgf_load_late(p, c3), le = pgf_load_late(p, e3), ln = pgf_load_late(p, n3);
     double cau = 0., cav = 0., dfu = 0., dfv = 0.;
     if (BC != PGF_BC_OFF) { cau = pgf_ld(p.bc_CAu, u3); cav = pgf_ld(p.bc_CAv, v3); }
     if (BC == PGF_BC_VISCOUS) { dfu = pgf_ld(p.bc_diffu, u3); dfv = pgf_ld(p.bc_diffv, v3); }
-#endif
-    const double intx_dpa = face_integral_core<FORM, MASSW ? 1 : 0, PGF_FACE_FENCE == 2>(p, c, e, bathy_c, bathy_e, ec_K, ee_K);
-#if PGF_FACE_FENCE
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    const double inty_dpa = face_integral_core<FORM, MASSW ? 1 : 0, PGF_FACE_FENCE == 2>(p, c, n, bathy_c, bathy_n, ec_K, en_K);
-#if PGF_FACE_FENCE
-    __builtin_amdgcn_sched_barrier(0);
-#endif
+    const double intx_dpa = face_integral_core<FORM, MASSW ? 1 : 0>(p, c, e, bathy_c, bathy_e, ec_K, ee_K);
+    const double inty_dpa = face_integral_core<FORM, MASSW ? 1 : 0>(p, c, n, bathy_c, bathy_n, ec_K, en_K);
     const double h_c = lc.h, iz_c = lc.iz, ec_Kp1 = c.e_Kp1;
     {
       const double ee_Kp1 = e.e_Kp1, h_e = le.h;
-      const double pfu = (((pa_c * h_c + iz_c) - (pa_e * h_e + le.iz)) +
+      const double pfu = (((pa_c * h_c + iz_c) - (pa_e * h_e + le.iz)) +      // pgf_accel, written out (see above)
                           ((h_e - h_c) * intx_pa - (ee_Kp1 - ec_Kp1) * intx_dpa * g.Z_to_H)) *
                          (fx / ((h_c + h_e) + h_neglect));
       if (do_x) {
         pgf_st(p.PFu, u3, pfu);
-        if (BC != PGF_BC_OFF) {
-          double a = cau + pfu;
-          if (BC == PGF_BC_INVISCID) a = (a == 0.0) ? 0.0 : a; else a = a + dfu;
-          pgf_st(p.bc_u, u3, a);
-        }
+        if (BC != PGF_BC_OFF) pgf_st(p.bc_u, u3, bc_accel(cau, pfu, dfu, BC == PGF_BC_INVISCID));
       }
       intx_pa = intx_pa + intx_dpa;
       pa_e = pa_e + e.dpa;
@@ -482,11 +409,7 @@ __global__ __launch_bounds__(64, PGF_FACE_T_OCC) void pgf_face_kernel_t(PgfArgs 
                          (fy / ((h_c + h_n) + h_neglect));
       if (do_y) {
         pgf_st(p.PFv, v3, pfv);
-        if (BC != PGF_BC_OFF) {
-          double a = cav + pfv;
-          if (BC == PGF_BC_INVISCID) a = (a == 0.0) ? 0.0 : a; else a = a + dfv;
-          pgf_st(p.bc_v, v3, a);
-        }
+        if (BC != PGF_BC_OFF) pgf_st(p.bc_v, v3, bc_accel(cav, pfv, dfv, BC == PGF_BC_INVISCID));
       }
       inty_pa = inty_pa + inty_dpa;
       pa_n = pa_n + n.dpa;
@@ -495,17 +418,11 @@ __global__ __launch_bounds__(64, PGF_FACE_T_OCC) void pgf_face_kernel_t(PgfArgs 
     pa_c = pa_c + c.dpa;
     ec_K = ec_Kp1;
     c3 += pl; e3 += pl; n3 += pl; u3 += plU; v3 += plV;
-#if PGF_FACE_PF >= 1
-    c = c1; e = e1; n = n1;
-#endif
-#if PGF_FACE_PF == 2
-    lc = lc1; le = le1; ln = ln1; cau = cau1; cav = cav1; dfu = dfu1; dfv = dfv1;
-#endif
   }
 }
 
 // the instantiations of pgf_face_kernel_t: EQN_OF_STATE = WRIGHT with every combination of the other three options (the RK2 step
-// of the benchmark runs <WRIGHT, false, PGF_BC_VISCOUS or _OFF, false>); null: pgf_face_kernel
+// of the benchmark runs <WRIGHT, false, PGF_BC_VISCOUS or _OFF, false>); null: pgf_face_kernel<PGF_FACE_PLM>
 using PgfFaceKernel = void (*)(PgfArgs);
 template <int FORM>
 PgfFaceKernel pgf_face_pick_form(bool massw, int bc, bool patm) {
@@ -533,28 +450,13 @@ __global__ __launch_bounds__(64) void plm_edge_kernel(PlmEdgeArgs p) {
   if (i > g.iec + 1) return;
   const int nz = g.nk;
   const long o2 = g.h2(i, j), pl = (long)g.nih * g.njh;
-  const double h_neglect = g.H_subroundoff;
-  auto ld = [&](const double *a, int kk) -> double { return (kk >= 0 && kk < nz) ? a[o2 + pl * kk] : 0.0; };
-  double h_m = 0., h_c = ld(p.h, 0), h_p = ld(p.h, 1), h_q = ld(p.h, 2);
-  double Q_m = 0., Q_c = ld(p.Q, 0), Q_p = ld(p.Q, 1), Q_q = ld(p.Q, 2);
-  double s_m = 0., s_c = 0., s_p = 0.;
-  if (nz >= 3) s_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, Q_c, Q_p, Q_q);
+  const PlmCol col{o2, pl, nz, p.bdry_extrap, g.H_subroundoff};
+  PlmH H = plm_prime_h(col, p.h);
+  PlmQ W = plm_prime(col, H, p.Q);
   for (int kk = 0; kk < nz; kk++) {
-    double Qt, Qb;
-    if (kk >= 1 && kk <= nz - 2) {
-      const double m = plm_monotonized_slope(Q_m, Q_c, Q_p, s_m, s_c, s_p);
-      Qt = Q_c - 0.5 * m; Qb = Q_c + 0.5 * m;
-    } else if (p.bdry_extrap) {
-      const double m = kk == 0 ? -plm_extrapolate_slope(h_p, h_c, h_neglect, Q_p, Q_c) : plm_extrapolate_slope(h_m, h_c, h_neglect, Q_m, Q_c);
-      Qt = Q_c - 0.5 * m; Qb = Q_c + 0.5 * m;
-    } else {
-      Qt = Q_c; Qb = Q_c;
-    }
-    p.Q_t[o2 + pl * kk] = Qt; p.Q_b[o2 + pl * kk] = Qb;
-    h_m = h_c; h_c = h_p; h_p = h_q; h_q = ld(p.h, kk + 3);
-    Q_m = Q_c; Q_c = Q_p; Q_p = Q_q; Q_q = ld(p.Q, kk + 3);
-    s_m = s_c; s_c = s_p;
-    s_p = (kk + 2 <= nz - 2) ? plm_slope_wa(h_c, h_p, h_q, h_neglect, Q_c, Q_p, Q_q) : 0.;
+    plm_edges(col, H, W, kk, p.Q_t[o2 + pl * kk], p.Q_b[o2 + pl * kk]);
+    plm_advance_h(col, H, p.h, kk);
+    plm_advance(col, H, W, p.Q, kk);
   }
 }
 
@@ -562,10 +464,10 @@ __global__ __launch_bounds__(64) void plm_edge_kernel(PlmEdgeArgs p) {
 // MODE 0: int_density_dz -> int_density_dz_linear (MOM_EOS_linear.F90:259-424); 1: int_density_dz_wright
 // (MOM_EOS_Wright.F90:389-640); 2: no equation of state, the layered form with GV%Rlay (:775-789).
 // The same split as the PLM pair: pgf_pcm_column_kernel forms e, dpa, intz_dpa (x Z_to_H), pbce and eta per column;
-// pgf_pcm_face_kernel the face integrals and PFu / PFv.  With a bulk mixed layer (nkmb > 0) the T and S of a layer below it
+// pgf_face_kernel<MODE> the face integrals and PFu / PFv.  With a bulk mixed layer (nkmb > 0) the T and S of a layer below it
 // are the buffer layer's wherever GV%Rlay(k) is lighter than the buffer layer's coordinate density (tv_tmp, :650-670);
 // the selection is re-derived per column in both kernels (one EOS evaluation) rather than stored as two 3-D arrays.
-constexpr int PCM_LINEAR = 0, PCM_WRIGHT = 1, PCM_NOEOS = 2;
+constexpr int PCM_LINEAR = 0, PCM_WRIGHT = 1, PCM_NOEOS = 2, PGF_FACE_PLM = 3;      // the last: the kind of face integral with a reconstruction
 
 struct PcmCol {      // tv_tmp of one column: which layers take the buffer layer's T and S
   double T_bl, S_bl, Rho_cv_BL;
@@ -618,14 +520,7 @@ __global__ __launch_bounds__(64) void pgf_pcm_column_kernel(PgfArgs p) {
   if (i > g.iec + 1) return;
   const int nz = g.nk;
   const long o2 = g.h2(i, j), pl = (long)g.nih * g.njh;
-  double ek = -g.bathyT[o2];
-  p.e[o2 + pl * nz] = ek;
-  for (int k = nz - 1; k >= 0; k--) {
-    ek = ek + p.h[o2 + pl * k] * g.H_to_Z;
-    p.e[o2 + pl * k] = ek;
-  }
-  const double e_top = ek, e_bot = -g.bathyT[o2];
-  if (p.eta) p.eta[o2] = e_top * g.Z_to_H;
+  const double e_top = column_heights(p, o2, pl, nz), e_bot = -g.bathyT[o2];
   const double G_e = g.g_Earth, rho_ref = p.rho_ref;
   const double GxRho = G_e * p.rho_ref, I_Rho = 1.0 / p.rho_ref;      // rho_0 = CS%Rho0 (:766)
   const double Rho0xG = p.rho_ref * g.g_Earth, G_Rho0 = g.g_Earth / g.Rho0;
@@ -663,16 +558,7 @@ __global__ __launch_bounds__(64) void pgf_pcm_column_kernel(PgfArgs p) {
         if (k == 0) pb = p.g_prime[0] * g.H_to_Z;
         else pb = pbce_prev + (p.g_prime[k] * g.H_to_Z) * ((e_K - e_bot) * Ihtot_lay);
       } else {
-        const double press = -Rho0xG * (e_K - p.Z_ref);
-        if (k == 0) {
-          const double rho_in_situ = eos_density(p.eos, T_c, S_c, press);
-          pb = G_Rho0 * (p.GFS_scale * rho_in_situ) * g.H_to_Z;
-        } else {
-          const double T_int = 0.5 * (T_m + T_c), S_int = 0.5 * (S_m + S_c);
-          double dR_dT, dR_dS;
-          eos_density_derivs(p.eos, T_int, S_int, press, dR_dT, dR_dS);
-          pb = pbce_prev + G_Rho0 * ((e_K - e_bot) * Ihtot_eos) * (dR_dT * (T_c - T_m) + dR_dS * (S_c - S_m));
-        }
+        pb = pbce_bouss_eos(p, k, T_m, T_c, S_m, S_c, -Rho0xG * (e_K - p.Z_ref), G_Rho0, (e_K - e_bot) * Ihtot_eos, pbce_prev);
       }
       p.pbce[o3] = pb;
       pbce_prev = pb;
@@ -704,19 +590,13 @@ __device__ __forceinline__ double pcm_face_integral(const PgfArgs &p, const PcmC
       const double raR = (R0 - rho_ref) + (dRdT * TR + dRdS * SR);
       return G_e * C1_6 * (dzL * (2.0 * raL + raR) + dzR * (2.0 * raR + raL));
     }
-    const double hL = (eL_K - eL_Kp1) + g.dZ_subroundoff;
-    const double hR = (eR_K - eR_Kp1) + g.dZ_subroundoff;
-    const double rr = (hL - hR) / (hL + hR);
-    hWght = hWght * (rr * rr);
-    const double iDenom = 1.0 / (hWght * (hR + hL) + hL * hR);
-    const double hWt_LL = (hWght * hL + hR * hL) * iDenom, hWt_LR = (hWght * hR) * iDenom;
-    const double hWt_RR = (hWght * hR + hR * hL) * iDenom, hWt_RL = (hWght * hL) * iDenom;
+    const MassWt w = mass_weights(hWght, (eL_K - eL_Kp1) + g.dZ_subroundoff, (eR_K - eR_Kp1) + g.dZ_subroundoff);
     double intz[5];
     intz[0] = p.dpa[L3]; intz[4] = p.dpa[R3];
 #pragma unroll
     for (int m = 2; m <= 4; m++) {
       const double wt_L = 0.25 * (double)(5 - m), wt_R = 1.0 - wt_L;
-      const double wtT_L = wt_L * hWt_LL + wt_R * hWt_RL, wtT_R = wt_L * hWt_LR + wt_R * hWt_RR;
+      const double wtT_L = wt_L * w.LL + wt_R * w.RL, wtT_R = wt_L * w.LR + wt_R * w.RR;
       const double dz = wt_L * (eL_K - eL_Kp1) + wt_R * (eR_K - eR_Kp1);
       const double rho_anom = (R0 - rho_ref) + (dRdT * (wtT_L * TL + wtT_R * TR) + dRdS * (wtT_L * SL + wtT_R * SR));
       intz[m - 1] = G_e * rho_anom * dz;
@@ -724,18 +604,7 @@ __device__ __forceinline__ double pcm_face_integral(const PgfArgs &p, const PcmC
     return C1_90 * (7.0 * (intz[0] + intz[4]) + 32.0 * (intz[1] + intz[3]) + 12.0 * intz[2]);
   }
   // MOM_EOS_Wright.F90:560-599
-  double hWt_LL, hWt_LR, hWt_RR, hWt_RL;
-  if (hWght > 0.) {
-    const double hL = (eL_K - eL_Kp1) + g.dZ_subroundoff;
-    const double hR = (eR_K - eR_Kp1) + g.dZ_subroundoff;
-    const double rr = (hL - hR) / (hL + hR);
-    hWght = hWght * (rr * rr);
-    const double iDenom = 1.0 / (hWght * (hR + hL) + hL * hR);
-    hWt_LL = (hWght * hL + hR * hL) * iDenom; hWt_LR = (hWght * hR) * iDenom;
-    hWt_RR = (hWght * hR + hR * hL) * iDenom; hWt_RL = (hWght * hL) * iDenom;
-  } else {
-    hWt_LL = 1.0; hWt_LR = 0.0; hWt_RR = 1.0; hWt_RL = 0.0;
-  }
+  const MassWt w = mass_weights(hWght, (eL_K - eL_Kp1) + g.dZ_subroundoff, (eR_K - eR_Kp1) + g.dZ_subroundoff);
   const WrightTerms wL = wright_terms(TL, SL), wR = wright_terms(TR, SR);
   const double GxRho = G_e * p.rho_ref, I_Rho = 1.0 / p.rho_ref;
   double intz[5], unused;
@@ -743,7 +612,7 @@ __device__ __forceinline__ double pcm_face_integral(const PgfArgs &p, const PcmC
 #pragma unroll
   for (int m = 2; m <= 4; m++) {
     const double wt_L = 0.25 * (double)(5 - m), wt_R = 1.0 - wt_L;
-    const double wtT_L = wt_L * hWt_LL + wt_R * hWt_RL, wtT_R = wt_L * hWt_LR + wt_R * hWt_RR;
+    const double wtT_L = wt_L * w.LL + wt_R * w.RL, wtT_R = wt_L * w.LR + wt_R * w.RR;
     const double al0 = wtT_L * wL.al0 + wtT_R * wR.al0;
     const double p0 = wtT_L * wL.p0 + wtT_R * wR.p0;
     const double lambda = wtT_L * wL.lambda + wtT_R * wR.lambda;
@@ -754,13 +623,24 @@ __device__ __forceinline__ double pcm_face_integral(const PgfArgs &p, const PcmC
   return C1_90 * (7.0 * (intz[0] + intz[4]) + 32.0 * (intz[1] + intz[3]) + 12.0 * intz[2]);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(64) void pgf_pcm_face_kernel(PgfArgs p) {
+// ---- the face kernel with every option read at run time ----------------------------------------------------------------
+// the integral of layer k across the face between the columns at L3 and R3, by kind
+template <int KIND>
+__device__ __forceinline__ double face_integral_of(const PgfArgs &p, const PcmCol &cL, const PcmCol &cR, long L3, long R3, long oL2, long oR2,
+                                                   int k, double eL_K, double eL_Kp1, double eR_K, double eR_Kp1) {
+  if constexpr (KIND == PGF_FACE_PLM) return face_integral(p, L3, R3, oL2, oR2, eL_K, eL_Kp1, eR_K, eR_Kp1);
+  else return pcm_face_integral<KIND>(p, cL, cR, L3, R3, oL2, oR2, k, eL_K, eL_Kp1, eR_K, eR_Kp1);
+}
+// KIND: the face integral, PGF_FACE_PLM (face_integral, after pgf_column_kernel) or a PCM_* mode (pcm_face_integral, after
+// pgf_pcm_column_kernel<KIND>).  The u_bc_accel lines are behind p.bc_u / p.bc_v, which the host sets on the PLM branch only.
+// The PLM kind keeps its waves-per-SIMD target; the PCM modes have none, as before (a target of 0 sets none).
+template <int KIND>
+__global__ __launch_bounds__(64, KIND == PGF_FACE_PLM ? PGF_FACE_OCC : 0) void pgf_face_kernel(PgfArgs p) {
   const m6::GridDev &g = p.g;
-  const int i = g.isc - 1 + blockIdx.x * 64 + threadIdx.x;
-  const int j = g.jsc - 1 + blockIdx.y;
+  const int i = g.isc - 1 + blockIdx.x * 64 + threadIdx.x;      // I (x face) / i (y face)
+  const int j = g.jsc - 1 + blockIdx.y;                         // j (x face) / J (y face)
   if (i > g.iec) return;
-  const bool do_x = (j >= g.jsc), do_y = (i >= g.isc);
+  const bool do_x = (j >= g.jsc), do_y = (i >= g.isc);          // j <= jec and i <= iec by the grid size
   if (!do_x && !do_y) return;
   const int nz = g.nk;
   const long pl = (long)g.nih * g.njh, plU = (long)(g.nih + 1) * g.njh, plV = (long)g.nih * (g.njh + 1);
@@ -773,7 +653,7 @@ __global__ __launch_bounds__(64) void pgf_pcm_face_kernel(PgfArgs p) {
     return v;
   };
   PcmCol cc, ce, cn; cc.nkmb = ce.nkmb = cn.nkmb = 0;
-  if (MODE != PCM_NOEOS) {
+  if constexpr (KIND == PCM_LINEAR || KIND == PCM_WRIGHT) {
     cc = pcm_col(p, oc, pl);
     if (do_x) ce = pcm_col(p, oe, pl);
     if (do_y) cn = pcm_col(p, on, pl);
@@ -788,25 +668,25 @@ __global__ __launch_bounds__(64) void pgf_pcm_face_kernel(PgfArgs p) {
     const double ec_Kp1 = p.e[c3 + pl];
     const double h_c = p.h[c3], dpa_c = p.dpa[c3], iz_c = p.intz_dpa[c3];
     if (do_x) {
-      const long e3 = c3 + 1;
+      const long e3 = c3 + 1, n = g.u2(i, j) + plU * k;
       const double ee_Kp1 = p.e[e3 + pl];
       const double h_e = p.h[e3];
-      const double intx_dpa = pcm_face_integral<MODE>(p, cc, ce, c3, e3, oc, oe, k, ec_K, ec_Kp1, ee_K, ee_Kp1);
-      p.PFu[g.u2(i, j) + plU * k] = (((pa_c * h_c + iz_c) - (pa_e * h_e + p.intz_dpa[e3])) +
-                                     ((h_e - h_c) * intx_pa - (ee_Kp1 - ec_Kp1) * intx_dpa * g.Z_to_H)) *
-                                    (fx / ((h_c + h_e) + h_neglect));
+      const double intx_dpa = face_integral_of<KIND>(p, cc, ce, c3, e3, oc, oe, k, ec_K, ec_Kp1, ee_K, ee_Kp1);
+      const double pfu = pgf_accel(g, pa_c, h_c, iz_c, pa_e, h_e, p.intz_dpa[e3], intx_pa, ec_Kp1, ee_Kp1, intx_dpa, fx, h_neglect);
+      p.PFu[n] = pfu;
+      if (p.bc_u) p.bc_u[n] = bc_accel(p.bc_CAu[n], pfu, p.bc_inviscid ? 0.0 : p.bc_diffu[n], p.bc_inviscid != 0);
       intx_pa = intx_pa + intx_dpa;
       pa_e = pa_e + p.dpa[e3];
       ee_K = ee_Kp1;
     }
     if (do_y) {
-      const long n3 = c3 + g.nih;
+      const long n3 = c3 + g.nih, n = g.v2(i, j) + plV * k;
       const double en_Kp1 = p.e[n3 + pl];
       const double h_n = p.h[n3];
-      const double inty_dpa = pcm_face_integral<MODE>(p, cc, cn, c3, n3, oc, on, k, ec_K, ec_Kp1, en_K, en_Kp1);
-      p.PFv[g.v2(i, j) + plV * k] = (((pa_c * h_c + iz_c) - (pa_n * h_n + p.intz_dpa[n3])) +
-                                     ((h_n - h_c) * inty_pa - (en_Kp1 - ec_Kp1) * inty_dpa * g.Z_to_H)) *
-                                    (fy / ((h_c + h_n) + h_neglect));
+      const double inty_dpa = face_integral_of<KIND>(p, cc, cn, c3, n3, oc, on, k, ec_K, ec_Kp1, en_K, en_Kp1);
+      const double pfv = pgf_accel(g, pa_c, h_c, iz_c, pa_n, h_n, p.intz_dpa[n3], inty_pa, ec_Kp1, en_Kp1, inty_dpa, fy, h_neglect);
+      p.PFv[n] = pfv;
+      if (p.bc_v) p.bc_v[n] = bc_accel(p.bc_CAv[n], pfv, p.bc_inviscid ? 0.0 : p.bc_diffv[n], p.bc_inviscid != 0);
       inty_pa = inty_pa + inty_dpa;
       pa_n = pa_n + p.dpa[n3];
       en_K = en_Kp1;
@@ -844,40 +724,15 @@ __global__ __launch_bounds__(64) void pgfnb_column_kernel(PgfArgs p) {
     const double Pa_to_H = 1.0 / (g.g_Earth * p.H_to_RZ);
     p.eta[o2] = p.p_atm ? (p_bot - p_top) * Pa_to_H : p_bot * Pa_to_H;
   }
-  auto ld = [&](const double *a, int kk) -> double { return (kk >= 0 && kk < nz) ? a[o2 + pl * kk] : 0.0; };
-  double h_m = 0., h_c = ld(p.h, 0), h_p = ld(p.h, 1), h_q = ld(p.h, 2);
-  double T_m = 0., T_c = ld(p.T, 0), T_p = ld(p.T, 1), T_q = ld(p.T, 2);
-  double S_m = 0., S_c = ld(p.S, 0), S_p = ld(p.S, 1), S_q = ld(p.S, 2);
-  double sT_m = 0., sT_c = 0., sT_p = 0., sS_m = 0., sS_c = 0., sS_p = 0.;
-  if (nz >= 3) {
-    sT_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, T_c, T_p, T_q);
-    sS_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, S_c, S_p, S_q);
-  }
+  const PlmCol col{o2, pl, nz, p.boundary_extrap, h_neglect};
+  PlmH H = plm_prime_h(col, p.h);
+  PlmQ WT = plm_prime(col, H, p.T), WS = plm_prime(col, H, p.S);
   double p_K = p_top;
   for (int kk = 0; kk < nz; kk++) {
     const long o3 = o2 + pl * kk;
-    // ---- TS_PLM_edge_values (ALE_PLM_edge_values, MOM_ALE.F90:1549-1576) ----
-    double Tt, Tb, St, Sb;
-    if (kk >= 1 && kk <= nz - 2) {
-      const double mT = plm_monotonized_slope(T_m, T_c, T_p, sT_m, sT_c, sT_p);
-      Tt = T_c - 0.5 * mT; Tb = T_c + 0.5 * mT;
-      const double mS = plm_monotonized_slope(S_m, S_c, S_p, sS_m, sS_c, sS_p);
-      St = S_c - 0.5 * mS; Sb = S_c + 0.5 * mS;
-    } else if (p.boundary_extrap) {
-      if (kk == 0) {
-        const double mT = -plm_extrapolate_slope(h_p, h_c, h_neglect, T_p, T_c);
-        Tt = T_c - 0.5 * mT; Tb = T_c + 0.5 * mT;
-        const double mS = -plm_extrapolate_slope(h_p, h_c, h_neglect, S_p, S_c);
-        St = S_c - 0.5 * mS; Sb = S_c + 0.5 * mS;
-      } else {
-        const double mT = plm_extrapolate_slope(h_m, h_c, h_neglect, T_m, T_c);
-        Tt = T_c - 0.5 * mT; Tb = T_c + 0.5 * mT;
-        const double mS = plm_extrapolate_slope(h_m, h_c, h_neglect, S_m, S_c);
-        St = S_c - 0.5 * mS; Sb = S_c + 0.5 * mS;
-      }
-    } else {
-      Tt = T_c; Tb = T_c; St = S_c; Sb = S_c;
-    }
+    double Tt, Tb, St, Sb;      // TS_PLM_edge_values
+    plm_edges(col, H, WT, kk, Tt, Tb);
+    plm_edges(col, H, WS, kk, St, Sb);
     p.T_t[o3] = Tt; p.T_b[o3] = Tb; p.S_t[o3] = St; p.S_b[o3] = Sb;
     // ---- the vertical integrals :1556-1574 (the weights run the other way than in int_density_dz) ----
     const double p_Kp1 = p.e[o3 + pl];
@@ -895,16 +750,9 @@ __global__ __launch_bounds__(64) void pgfnb_column_kernel(PgfArgs p) {
     p.dpa[o3] = dp * alpha_anom;
     p.intz_dpa[o3] = 0.5 * (dp * dp) * (alpha_anom - C1_90 * (16.0 * (a5[3] - a5[1]) + 7.0 * (a5[4] - a5[0])));
     p_K = p_Kp1;
-    h_m = h_c; h_c = h_p; h_p = h_q; h_q = ld(p.h, kk + 3);
-    T_m = T_c; T_c = T_p; T_p = T_q; T_q = ld(p.T, kk + 3);
-    S_m = S_c; S_c = S_p; S_p = S_q; S_q = ld(p.S, kk + 3);
-    sT_m = sT_c; sT_c = sT_p; sS_m = sS_c; sS_c = sS_p;
-    if (kk + 2 <= nz - 2) {
-      sT_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, T_c, T_p, T_q);
-      sS_p = plm_slope_wa(h_c, h_p, h_q, h_neglect, S_c, S_p, S_q);
-    } else {
-      sT_p = 0.; sS_p = 0.;
-    }
+    plm_advance_h(col, H, p.h, kk);
+    plm_advance(col, H, WT, p.T, kk);
+    plm_advance(col, H, WS, p.S, kk);
   }
   // :299-306: za at the sea surface, summed from the bottom
   double za = alpha_ref * p_bot - g.g_Earth * g.bathyT[o2];
@@ -937,19 +785,9 @@ __device__ __forceinline__ double face_integral_nb(const PgfArgs &p, long L3, lo
   const int nz = p.g.nk;
   const double C1_90 = 1.0 / 90.0;
   const double PT_L = p.e[L3], PB_L = p.e[L3 + pl], PT_R = p.e[R3], PB_R = p.e[R3 + pl];
-  double hWght = 0.0, hWt_LL, hWt_LR, hWt_RR, hWt_RL;
+  double hWght = 0.0;
   if (p.massw) hWght = max3(0., p.e[oL2 + pl * nz] - PT_R, p.e[oR2 + pl * nz] - PT_L);
-  if (hWght > 0.) {
-    const double hL = (PB_L - PT_L) + dp_neglect;
-    const double hR = (PB_R - PT_R) + dp_neglect;
-    const double rr = (hL - hR) / (hL + hR);
-    hWght = hWght * (rr * rr);
-    const double iDenom = 1.0 / (hWght * (hR + hL) + hL * hR);
-    hWt_LL = (hWght * hL + hR * hL) * iDenom; hWt_LR = (hWght * hR) * iDenom;
-    hWt_RR = (hWght * hR + hR * hL) * iDenom; hWt_RL = (hWght * hL) * iDenom;
-  } else {
-    hWt_LL = 1.0; hWt_LR = 0.0; hWt_RR = 1.0; hWt_RL = 0.0;
-  }
+  const MassWt w = mass_weights(hWght, (PB_L - PT_L) + dp_neglect, (PB_R - PT_R) + dp_neglect);
   const double TtL = p.T_t[L3], TtR = p.T_t[R3], TbL = p.T_b[L3], TbR = p.T_b[R3];
   const double StL = p.S_t[L3], StR = p.S_t[R3], SbL = p.S_b[L3], SbR = p.S_b[R3];
   double intp[5];
@@ -957,7 +795,7 @@ __device__ __forceinline__ double face_integral_nb(const PgfArgs &p, long L3, lo
 #pragma unroll
   for (int m = 2; m <= 4; m++) {
     const double wt_L = 0.25 * (double)(5 - m), wt_R = 1.0 - wt_L;
-    const double wtT_L = wt_L * hWt_LL + wt_R * hWt_RL, wtT_R = wt_L * hWt_LR + wt_R * hWt_RR;
+    const double wtT_L = wt_L * w.LL + wt_R * w.RL, wtT_R = wt_L * w.LR + wt_R * w.RR;
     const double P_top = wt_L * PT_L + wt_R * PT_R;
     const double P_bot = wt_L * PB_L + wt_R * PB_R;
     const double T_top = wtT_L * TtL + wtT_R * TtR;
@@ -1054,11 +892,60 @@ extern "C" int mom6hip_calculate_density(mom6hip_ctx_t *ctx, const mom6hip_eos_t
   M6_HIP(hipGetLastError());
   return st.finish();
 }
+namespace {
 
-extern "C" int mom6hip_pressureforce_fv_bouss(mom6hip_ctx_t *ctx, const mom6hip_pressureforce_cs_t *cs,
-                                              const mom6hip_eos_t *eos, const double *h, const double *T,
-                                              const double *S, const double *p_atm, double *PFu, double *PFv,
-                                              double *pbce, double *eta, int32_t memspace) {
+// ---- what the two PressureForce_FV entries share on the host ---------------------------------------------------------------
+// The common PgfArgs fill: the staged arrays and the scratch (whose order decides its layout), the constants, and the extras
+// of the branches without a reconstruction (mode: a PCM_* value, or -1), which every other caller gets nulled.
+int pgf_fill(mom6hip_ctx_t *ctx, m6::Stager &st, PgfArgs &a, const mom6hip_pressureforce_cs_t *cs, const mom6hip_eos_t *eos, const double *h,
+             const double *T, const double *S, const double *p_atm, double *PFu, double *PFv, double *pbce, double *eta, bool edges,
+             bool nonbouss, double H_to_RZ, int mode) {
+  const m6::GridDev &g = ctx->g;
+  const bool use_EOS = (eos != nullptr);
+  const size_t bH = (size_t)g.nh3() * 8, bU = (size_t)g.nu3() * 8, bV = (size_t)g.nv3() * 8;
+  const size_t bH2 = (size_t)g.nih * g.njh * 8;
+  a.Rlay = a.g_prime = nullptr; a.nkmb = 0; a.P_Ref = 0.0;
+  if (!nonbouss) {
+    if (cs->Rlay && (mode == PCM_NOEOS || cs->nkmb > 0)) {
+      a.Rlay = ctx->tables[m6::TABLE_PGF_RLAY].get(cs->Rlay, (size_t)g.nk);
+      if (!a.Rlay) return 1;
+    }
+    if (mode == PCM_NOEOS && pbce) {
+      a.g_prime = ctx->tables[m6::TABLE_PGF_GPRIME].get(cs->g_prime, (size_t)g.nk + 1);
+      if (!a.g_prime) return 1;
+    }
+    a.nkmb = use_EOS ? cs->nkmb : 0; a.P_Ref = cs->P_Ref;
+  }
+  a.bc_CAu = a.bc_CAv = a.bc_diffu = a.bc_diffv = nullptr; a.bc_u = a.bc_v = nullptr; a.bc_inviscid = 0;
+  a.g = g;
+  a.eos = use_EOS ? EosDev{eos->form, eos->Rho_T0_S0, eos->dRho_dT, eos->dRho_dS} : EosDev{0, 0., 0., 0.};
+  a.h = st.in(h, bH); a.T = use_EOS ? st.in(T, bH) : nullptr; a.S = use_EOS ? st.in(S, bH) : nullptr; a.p_atm = st.in(p_atm, bH2);
+  a.PFu = st.inout(PFu, bU); a.PFv = st.inout(PFv, bV); a.pbce = st.inout(pbce, bH); a.eta = st.inout(eta, bH2);
+  a.e = (double *)st.scratch(bH + bH2);
+  a.T_t = a.T_b = a.S_t = a.S_b = nullptr;
+  if (edges) {
+    a.T_t = (double *)st.scratch(bH); a.T_b = (double *)st.scratch(bH);
+    a.S_t = (double *)st.scratch(bH); a.S_b = (double *)st.scratch(bH);
+  }
+  a.dpa = (double *)st.scratch(bH); a.intz_dpa = (double *)st.scratch(bH);
+  a.za0 = nonbouss ? (double *)st.scratch(bH2) : nullptr;
+  if (st.failed()) return 1;
+  a.rho_ref = cs->Rho0; a.Z_ref = cs->Z_ref; a.GFS_scale = cs->GFS_scale; a.H_to_RZ = H_to_RZ;
+  a.boundary_extrap = cs->boundary_extrap; a.massw = cs->useMassWghtInterp;
+  return 0;
+}
+
+// the launch geometry: a lane per column, rows along y; the column kernels cover the compute domain and a rim of one, the face
+// kernels the faces between those columns
+struct PgfGrids { dim3 gc, gf; };
+PgfGrids pgf_grids(const m6::GridDev &g) {
+  const int ncol_i = g.iec - g.isc + 3, ncol_j = g.jec - g.jsc + 3;
+  return PgfGrids{dim3((ncol_i + 63) / 64, ncol_j), dim3((ncol_i - 1 + 63) / 64, ncol_j - 1)};
+}
+
+// the argument checks of PressureForce_FV_Bouss; use_ALE: the PLM pair, otherwise mode is the PCM_* form
+int pgf_check_bouss(mom6hip_ctx_t *ctx, const mom6hip_pressureforce_cs_t *cs, const mom6hip_eos_t *eos, const double *h, const double *T,
+                    const double *S, const double *PFu, const double *PFv, const double *pbce, int32_t memspace, bool &use_ALE_out, int &mode_out) {
   M6_REQUIRE(ctx != nullptr && cs != nullptr, "MOM_PressureForce_FV_Bouss: Module must be initialized before it is used.");
   M6_REQUIRE(h && PFu && PFv, "PressureForce_FV_Bouss: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "PressureForce_FV_Bouss: bad memspace");
@@ -1090,38 +977,41 @@ extern "C" int mom6hip_pressureforce_fv_bouss(mom6hip_ctx_t *ctx, const mom6hip_
   M6_REQUIRE(g.nk >= 2 || !use_ALE, "PressureForce_FV_Bouss: at least 2 layers are needed");
   M6_REQUIRE(g.isc - g.isd >= 1 && g.ied - g.iec >= 1 && g.jsc - g.jsd >= 1 && g.jed - g.jec >= 1,
              "PressureForce_FV_Bouss: needs a halo of at least 1");
-  hipStream_t s = ctx->stream;
-  const size_t bH = (size_t)g.nh3() * 8, bU = (size_t)g.nu3() * 8, bV = (size_t)g.nv3() * 8;
-  const size_t bH2 = (size_t)g.nih * g.njh * 8;
-  PgfArgs a;
-  a.Rlay = a.g_prime = nullptr;
-  a.bc_CAu = a.bc_CAv = a.bc_diffu = a.bc_diffv = nullptr; a.bc_u = a.bc_v = nullptr; a.bc_inviscid = 0;
-  if (cs->Rlay && (mode == PCM_NOEOS || cs->nkmb > 0)) {
-    a.Rlay = ctx->tables[m6::TABLE_PGF_RLAY].get(cs->Rlay, (size_t)g.nk);
-    if (!a.Rlay) return 1;
-  }
-  if (mode == PCM_NOEOS && pbce) {
-    a.g_prime = ctx->tables[m6::TABLE_PGF_GPRIME].get(cs->g_prime, (size_t)g.nk + 1);
-    if (!a.g_prime) return 1;
-  }
+  use_ALE_out = use_ALE; mode_out = mode;
+  return 0;
+}
+
+int pgf_check_nonbouss(mom6hip_ctx_t *ctx, const mom6hip_pressureforce_cs_t *cs, const mom6hip_eos_t *eos, const double *h, const double *T,
+                       const double *S, const double *PFu, const double *PFv, double H_to_RZ, int32_t memspace) {
+  M6_REQUIRE(ctx != nullptr && cs != nullptr, "MOM_PressureForce_FV_nonBouss: Module must be initialized before it is used.");
+  M6_REQUIRE(h && T && S && PFu && PFv, "PressureForce_FV_nonBouss: null argument");
+  M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "PressureForce_FV_nonBouss: bad memspace");
+  if (check_eos(eos)) return 2;
+  M6_REQUIRE(cs->use_ALE && cs->reconstruct && cs->Recon_Scheme == 1,
+             "PressureForce_FV_nonBouss: only ALE with RECONSTRUCT_FOR_PRESSURE=True and PRESSURE_RECONSTRUCTION_SCHEME=1 is provided");
+  M6_REQUIRE(cs->GFS_scale == 1.0, "PressureForce_FV_nonBouss: GFS_scale < 1 is not provided");
+  M6_REQUIRE(H_to_RZ > 0.0, "PressureForce_FV_nonBouss: H_to_RZ must be positive");
+  m6::GridDev &g = ctx->g;
+  M6_REQUIRE(g.bathyT && g.IdxCu && g.IdyCv, "PressureForce_FV_nonBouss: a required grid metric is missing");
+  M6_REQUIRE(g.nk >= 2, "PressureForce_FV_nonBouss: at least 2 layers are needed");
+  M6_REQUIRE(g.isc - g.isd >= 1 && g.ied - g.iec >= 1 && g.jsc - g.jsd >= 1 && g.jed - g.jec >= 1,
+             "PressureForce_FV_nonBouss: needs a halo of at least 1");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int mom6hip_pressureforce_fv_bouss(mom6hip_ctx_t *ctx, const mom6hip_pressureforce_cs_t *cs,
+                                              const mom6hip_eos_t *eos, const double *h, const double *T,
+                                              const double *S, const double *p_atm, double *PFu, double *PFv,
+                                              double *pbce, double *eta, int32_t memspace) {
+  bool use_ALE; int mode;
+  if (int rc = pgf_check_bouss(ctx, cs, eos, h, T, S, PFu, PFv, pbce, memspace, use_ALE, mode)) return rc;
   m6::Stager st(ctx, memspace);
-  a.g = g;
-  a.eos = use_EOS ? EosDev{eos->form, eos->Rho_T0_S0, eos->dRho_dT, eos->dRho_dS} : EosDev{0, 0., 0., 0.};
-  a.h = st.in(h, bH); a.T = use_EOS ? st.in(T, bH) : nullptr; a.S = use_EOS ? st.in(S, bH) : nullptr; a.p_atm = st.in(p_atm, bH2);
-  a.PFu = st.inout(PFu, bU); a.PFv = st.inout(PFv, bV); a.pbce = st.inout(pbce, bH); a.eta = st.inout(eta, bH2);
-  a.e = (double *)st.scratch(bH + bH2);
-  a.T_t = a.T_b = a.S_t = a.S_b = nullptr;
-  if (use_ALE) {
-    a.T_t = (double *)st.scratch(bH); a.T_b = (double *)st.scratch(bH);
-    a.S_t = (double *)st.scratch(bH); a.S_b = (double *)st.scratch(bH);
-  }
-  a.dpa = (double *)st.scratch(bH); a.intz_dpa = (double *)st.scratch(bH);
-  if (st.failed()) return 1;
-  a.rho_ref = cs->Rho0; a.Z_ref = cs->Z_ref; a.GFS_scale = cs->GFS_scale; a.za0 = nullptr; a.H_to_RZ = 0.0;
-  a.boundary_extrap = cs->boundary_extrap; a.massw = cs->useMassWghtInterp;
-  a.nkmb = use_EOS ? cs->nkmb : 0; a.P_Ref = cs->P_Ref;
-  const int ncol_i = g.iec - g.isc + 3, ncol_j = g.jec - g.jsc + 3;
-  const dim3 gc((ncol_i + 63) / 64, ncol_j), gf((ncol_i - 1 + 63) / 64, ncol_j - 1);
+  PgfArgs a;
+  if (int rc = pgf_fill(ctx, st, a, cs, eos, h, T, S, p_atm, PFu, PFv, pbce, eta, use_ALE, false, 0.0, mode)) return rc;
+  const PgfGrids gr = pgf_grids(ctx->g);
+  hipStream_t s = ctx->stream;
   if (use_ALE) {
     if (ctx->bc_fuse && memspace == MOM6HIP_MEM_DEVICE) {
       mom6hip_ctx::BcAccelFuse *f = ctx->bc_fuse;
@@ -1129,19 +1019,19 @@ extern "C" int mom6hip_pressureforce_fv_bouss(mom6hip_ctx_t *ctx, const mom6hip_
       a.bc_inviscid = f->inviscid;
       f->done = true;
     }
-    hipLaunchKernelGGL(pgf_column_kernel, gc, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pgf_column_kernel, gr.gc, dim3(64), 0, s, a);
     const PgfFaceKernel face_t = pgf_face_pick(a);
     ctx->pgf_face_launches[face_t ? 1 : 0]++;
-    { m6::KTimer kt(ctx, MOM6HIP_KT_PGF_FACE); hipLaunchKernelGGL(face_t ? face_t : pgf_face_kernel, gf, dim3(64), 0, s, a); }
+    { m6::KTimer kt(ctx, MOM6HIP_KT_PGF_FACE); hipLaunchKernelGGL(face_t ? face_t : pgf_face_kernel<PGF_FACE_PLM>, gr.gf, dim3(64), 0, s, a); }
   } else if (mode == PCM_LINEAR) {
-    hipLaunchKernelGGL(pgf_pcm_column_kernel<PCM_LINEAR>, gc, dim3(64), 0, s, a);
-    hipLaunchKernelGGL(pgf_pcm_face_kernel<PCM_LINEAR>, gf, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pgf_pcm_column_kernel<PCM_LINEAR>, gr.gc, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pgf_face_kernel<PCM_LINEAR>, gr.gf, dim3(64), 0, s, a);
   } else if (mode == PCM_WRIGHT) {
-    hipLaunchKernelGGL(pgf_pcm_column_kernel<PCM_WRIGHT>, gc, dim3(64), 0, s, a);
-    hipLaunchKernelGGL(pgf_pcm_face_kernel<PCM_WRIGHT>, gf, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pgf_pcm_column_kernel<PCM_WRIGHT>, gr.gc, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pgf_face_kernel<PCM_WRIGHT>, gr.gf, dim3(64), 0, s, a);
   } else {
-    hipLaunchKernelGGL(pgf_pcm_column_kernel<PCM_NOEOS>, gc, dim3(64), 0, s, a);
-    hipLaunchKernelGGL(pgf_pcm_face_kernel<PCM_NOEOS>, gf, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pgf_pcm_column_kernel<PCM_NOEOS>, gr.gc, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pgf_face_kernel<PCM_NOEOS>, gr.gf, dim3(64), 0, s, a);
   }
   M6_HIP(hipGetLastError());
   return st.finish();
@@ -1157,41 +1047,13 @@ extern "C" int mom6hip_pressureforce_fv_nonbouss(mom6hip_ctx_t *ctx, const mom6h
                                                  const mom6hip_eos_t *eos, const double *h, const double *T,
                                                  const double *S, const double *p_atm, double H_to_RZ, double *PFu,
                                                  double *PFv, double *pbce, double *eta, int32_t memspace) {
-  M6_REQUIRE(ctx != nullptr && cs != nullptr, "MOM_PressureForce_FV_nonBouss: Module must be initialized before it is used.");
-  M6_REQUIRE(h && T && S && PFu && PFv, "PressureForce_FV_nonBouss: null argument");
-  M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "PressureForce_FV_nonBouss: bad memspace");
-  if (check_eos(eos)) return 2;
-  M6_REQUIRE(cs->use_ALE && cs->reconstruct && cs->Recon_Scheme == 1,
-             "PressureForce_FV_nonBouss: only ALE with RECONSTRUCT_FOR_PRESSURE=True and PRESSURE_RECONSTRUCTION_SCHEME=1 is provided");
-  M6_REQUIRE(cs->GFS_scale == 1.0, "PressureForce_FV_nonBouss: GFS_scale < 1 is not provided");
-  M6_REQUIRE(H_to_RZ > 0.0, "PressureForce_FV_nonBouss: H_to_RZ must be positive");
-  m6::GridDev &g = ctx->g;
-  M6_REQUIRE(g.bathyT && g.IdxCu && g.IdyCv, "PressureForce_FV_nonBouss: a required grid metric is missing");
-  M6_REQUIRE(g.nk >= 2, "PressureForce_FV_nonBouss: at least 2 layers are needed");
-  M6_REQUIRE(g.isc - g.isd >= 1 && g.ied - g.iec >= 1 && g.jsc - g.jsd >= 1 && g.jed - g.jec >= 1,
-             "PressureForce_FV_nonBouss: needs a halo of at least 1");
-  hipStream_t s = ctx->stream;
-  const size_t bH = (size_t)g.nh3() * 8, bU = (size_t)g.nu3() * 8, bV = (size_t)g.nv3() * 8;
-  const size_t bH2 = (size_t)g.nih * g.njh * 8;
+  if (int rc = pgf_check_nonbouss(ctx, cs, eos, h, T, S, PFu, PFv, H_to_RZ, memspace)) return rc;
   m6::Stager st(ctx, memspace);
   PgfArgs a;
-  a.bc_CAu = a.bc_CAv = a.bc_diffu = a.bc_diffv = nullptr; a.bc_u = a.bc_v = nullptr; a.bc_inviscid = 0;
-  a.g = g;
-  a.eos = EosDev{eos->form, eos->Rho_T0_S0, eos->dRho_dT, eos->dRho_dS};
-  a.h = st.in(h, bH); a.T = st.in(T, bH); a.S = st.in(S, bH); a.p_atm = st.in(p_atm, bH2);
-  a.PFu = st.inout(PFu, bU); a.PFv = st.inout(PFv, bV); a.pbce = st.inout(pbce, bH); a.eta = st.inout(eta, bH2);
-  a.e = (double *)st.scratch(bH + bH2);
-  a.T_t = (double *)st.scratch(bH); a.T_b = (double *)st.scratch(bH);
-  a.S_t = (double *)st.scratch(bH); a.S_b = (double *)st.scratch(bH);
-  a.dpa = (double *)st.scratch(bH); a.intz_dpa = (double *)st.scratch(bH);
-  a.za0 = (double *)st.scratch(bH2);
-  if (st.failed()) return 1;
-  a.rho_ref = cs->Rho0; a.Z_ref = cs->Z_ref; a.GFS_scale = cs->GFS_scale; a.H_to_RZ = H_to_RZ;
-  a.Rlay = a.g_prime = nullptr; a.nkmb = 0; a.P_Ref = 0.0;
-  a.boundary_extrap = cs->boundary_extrap; a.massw = cs->useMassWghtInterp;
-  const int ncol_i = g.iec - g.isc + 3, ncol_j = g.jec - g.jsc + 3;
-  hipLaunchKernelGGL(pgfnb_column_kernel, dim3((ncol_i + 63) / 64, ncol_j), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(pgfnb_face_kernel, dim3((ncol_i - 1 + 63) / 64, ncol_j - 1), dim3(64), 0, s, a);
+  if (int rc = pgf_fill(ctx, st, a, cs, eos, h, T, S, p_atm, PFu, PFv, pbce, eta, true, true, H_to_RZ, -1)) return rc;
+  const PgfGrids gr = pgf_grids(ctx->g);
+  hipLaunchKernelGGL(pgfnb_column_kernel, gr.gc, dim3(64), 0, ctx->stream, a);
+  hipLaunchKernelGGL(pgfnb_face_kernel, gr.gf, dim3(64), 0, ctx->stream, a);
   M6_HIP(hipGetLastError());
   return st.finish();
 }
@@ -1210,8 +1072,7 @@ extern "C" int mom6hip_ale_plm_edge_values(mom6hip_ctx_t *ctx, const double *h, 
   PlmEdgeArgs a;
   a.g = g; a.h = st.in(h, bH); a.Q = st.in(Q, bH); a.Q_t = st.inout(Q_t, bH); a.Q_b = st.inout(Q_b, bH); a.bdry_extrap = bdry_extrap;
   M6_REQUIRE(!st.failed(), "ALE_PLM_edge_values: staging failed");
-  const int ncol_i = g.iec - g.isc + 3, ncol_j = g.jec - g.jsc + 3;
-  hipLaunchKernelGGL(plm_edge_kernel, dim3((ncol_i + 63) / 64, ncol_j), dim3(64), 0, ctx->stream, a);
+  hipLaunchKernelGGL(plm_edge_kernel, pgf_grids(g).gc, dim3(64), 0, ctx->stream, a);
   M6_HIP(hipGetLastError());
   return st.finish();
 }

@@ -95,20 +95,16 @@ def test_one_layer_is_refused():
     dg.close()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("p_surf_on", [False, True], ids=["no_p_surf", "p_surf"])
-@pytest.mark.parametrize("massw", [False, True], ids=["plain", "massw"])
-@pytest.mark.parametrize("viscous", [True, False], ids=["viscous", "inviscid"])
-def test_rk2_step_with_bc_accel_fused_equals_oracle(oracle, viscous, massw, p_surf_on):
-    """step_MOM_dyn_split_RK2 from its second step on hands u_bc_accel = (CAu_pred + PFu) + diffu to the face kernel: with
-    horizontal and vertical viscosity pgf_face_kernel_t<WRIGHT, massw, viscous, p_surf>, without either <.., inviscid, ..>"""
+def _rk2_steps_equal_oracle(orc, shapes, viscous, form, pf, p_surf_on, want):
+    """three steps of step_MOM_dyn_split_RK2 with EQN_OF_STATE = form and the PressureForce options pf (the oracle's names) on each
+    shape: u, v, h, uh, eta_av are the oracle's bit for bit, and the face kernel launch counter moved by want = (run-time PLM
+    kernel, pgf_face_kernel_t)"""
     import torch
     from mom6_amd.dynamics_split_rk2 import initialize_dyn_split_RK2, step_MOM_dyn_split_RK2
     from mom6_amd.pressure_force import pgf_face_launches
     from mom6_amd.tracer_advect import DeviceGrid
     from mom6_amd.vert_friction import vertvisc_type
-    orc = oracle
-    for (ni, nj, nk) in [(70, 12, 2), (30, 10, 75)]:
+    for (ni, nj, nk) in shapes:
         g = synth.make_grid(ni, nj, nk, seed=ni + 1)
         d = {k: v.numpy() for k, v in synth.make_dynamics_state(g, seed=3, umax=0.1, eta_amp=0.2).items()}
         taux = np.ascontiguousarray(0.1 * g.mask2dCu); tauy = g.zeros2(_abi.POS_V)
@@ -123,7 +119,7 @@ def test_rk2_step_with_bc_accel_fused_equals_oracle(oracle, viscous, massw, p_su
                        hor_visc=orc.hor_visc_cs(g, dt, biharmonic=1, Smagorinsky_Ah=1, Smag_bi_const=0.06, Ah_vel_scale=0.01))
             lkw = dict(vertvisc=dict(KV=1.0e-3, HBBL=10.0),
                        hor_visc=dict(BIHARMONIC=True, SMAGORINSKY_AH=True, SMAG_BI_CONST=0.06, AH_VEL_SCALE=0.01))
-        ref = orc.DynState(g, d["u"], d["v"], d["h"], d["T"], d["S"], dt, pressureforce=dict(useMassWghtInterp=massw), **okw)
+        ref = orc.DynState(g, d["u"], d["v"], d["h"], d["T"], d["S"], dt, eos_form=form, pressureforce=dict(pf), **okw)
         p_surf = None
         if p_surf_on:
             p_surf = np.ascontiguousarray(1.0e5 + 200.0 * rng.standard_normal(g.shape2(_abi.POS_H)))
@@ -133,8 +129,8 @@ def test_rk2_step_with_bc_accel_fused_equals_oracle(oracle, viscous, massw, p_su
         u, v, h, Tt, Ss = (T(d[k]) for k in ("u", "v", "h", "T", "S"))
         Z = lambda pos, k3=True: torch.zeros(g.shape3(pos) if k3 else g.shape2(pos), dtype=torch.float64, device="cuda")
         uh, vh, uhtr, vhtr, eta_av = Z(_abi.POS_U), Z(_abi.POS_V), Z(_abi.POS_U), Z(_abi.POS_V), Z(_abi.POS_H, False)
-        CS = initialize_dyn_split_RK2(u, v, h, uh, vh, dt, dg, coriolis=dict(bound_coriolis=True),
-                                      pressure_force=dict(useMassWghtInterp=massw), **lkw)
+        CS = initialize_dyn_split_RK2(u, v, h, uh, vh, dt, dg, coriolis=dict(bound_coriolis=True), EQN_OF_STATE=form,
+                                      pressure_force=dict(pf), **lkw)
         visc = vertvisc_type(**{n: T(a) for n, a in va.items()}) if viscous else None
         tx, ty = T(taux), T(tauy)
         before = pgf_face_launches(dg)
@@ -146,7 +142,32 @@ def test_rk2_step_with_bc_accel_fused_equals_oracle(oracle, viscous, massw, p_su
                                    calc_dtbt=(n == 0))
         dg.sync()
         after = pgf_face_launches(dg)
-        assert (after[0] - before[0], after[1] - before[1]) == (0, nstep), (before, after)
+        assert (after[0] - before[0], after[1] - before[1]) == (want[0] * nstep, want[1] * nstep), (before, after)
         for name, a, b in (("u", u, ref.u), ("v", v, ref.v), ("h", h, ref.h), ("uh", uh, ref.uh), ("eta_av", eta_av, ref.eta_av)):
-            assert bits_equal(a.cpu().numpy(), b), (viscous, massw, p_surf_on, (ni, nj, nk), name)
+            assert bits_equal(a.cpu().numpy(), b), (form, pf, viscous, p_surf_on, (ni, nj, nk), name)
         dg.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("p_surf_on", [False, True], ids=["no_p_surf", "p_surf"])
+@pytest.mark.parametrize("massw", [False, True], ids=["plain", "massw"])
+@pytest.mark.parametrize("viscous", [True, False], ids=["viscous", "inviscid"])
+def test_rk2_step_with_bc_accel_fused_equals_oracle(oracle, viscous, massw, p_surf_on):
+    """step_MOM_dyn_split_RK2 from its second step on hands u_bc_accel = (CAu_pred + PFu) + diffu to the face kernel: with
+    horizontal and vertical viscosity pgf_face_kernel_t<WRIGHT, massw, viscous, p_surf>, without either <.., inviscid, ..>"""
+    _rk2_steps_equal_oracle(oracle, [(70, 12, 2), (30, 10, 75)], viscous, "WRIGHT", dict(useMassWghtInterp=massw), p_surf_on, (0, 1))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("viscous", [True, False], ids=["viscous", "inviscid"])
+def test_rk2_step_with_bc_accel_fused_in_the_run_time_kernel_equals_oracle(oracle, viscous):
+    """EQN_OF_STATE = UNESCO has no pgf_face_kernel_t: the run-time face kernel with the PLM quadrature forms u_bc_accel, in its
+    viscous and its inviscid form (nk = 2: the layer loop's first layer, then its last; 70: a full wave and a partial one)"""
+    _rk2_steps_equal_oracle(oracle, [(70, 12, 2), (30, 10, 5)], viscous, "UNESCO", {}, False, (1, 0))
+
+
+@pytest.mark.gpu
+def test_rk2_step_without_reconstruction_equals_oracle(oracle):
+    """RECONSTRUCT_FOR_PRESSURE = False with EQN_OF_STATE = LINEAR: the run-time face kernel with the analytic integral of the linear
+    form, which is not handed u_bc_accel (the step forms it) and is not counted as a PLM launch"""
+    _rk2_steps_equal_oracle(oracle, [(70, 12, 2)], True, "LINEAR", dict(reconstruct=False), False, (0, 0))

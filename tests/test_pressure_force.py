@@ -153,7 +153,7 @@ def test_gpu_parity(oracle, form, opts):
     from mom6_amd.tracer_advect import DeviceGrid
     extrap, massw = opts
     for (ni, nj, nk, topo) in [(70, 21, 5, (True, False)), (44, 40, 2, (True, True)), (10, 8, 8, (False, False)),
-                               (130, 9, 3, (True, False))]:
+                               (130, 9, 3, (True, False)), (70, 9, 3, (True, False)), (70, 9, 4, (True, False))]:
         g, st = pgf_case(ni, nj, nk, seed=ni, reentrant_x=topo[0], reentrant_y=topo[1])
         E = oracle.eos(form, 1000.0, -0.2, 0.8)
         cs = oracle.pressureforce_cs(g, boundary_extrap=extrap, useMassWghtInterp=massw)
@@ -184,7 +184,7 @@ def test_gpu_ale_plm_edge_values(oracle, extrap):
     import torch
     from mom6_amd.ale import ALE_PLM_edge_values, TS_PLM_edge_values
     from mom6_amd.tracer_advect import DeviceGrid
-    for (ni, nj, nk) in [(70, 21, 5), (10, 8, 2), (33, 9, 12)]:
+    for (ni, nj, nk) in [(70, 21, 5), (10, 8, 2), (33, 9, 12), (70, 9, 3), (70, 9, 4)]:
         g, st = pgf_case(ni, nj, nk, seed=3 * ni)
         want = oracle.ale_plm_edge_values(g, st["h"], st["T"], extrap)
         dg = DeviceGrid(g)
@@ -214,7 +214,8 @@ def test_gpu_parity_nonbouss(oracle, form, opts):
     from mom6_amd.pressure_force import PressureForce, PressureForce_init, EOS_init
     from mom6_amd.tracer_advect import DeviceGrid
     extrap, massw = opts
-    for (ni, nj, nk, topo) in [(70, 21, 5, (True, False)), (44, 40, 2, (True, True)), (10, 8, 8, (False, False)), (130, 9, 75, (True, False))]:
+    for (ni, nj, nk, topo) in [(70, 21, 5, (True, False)), (44, 40, 2, (True, True)), (10, 8, 8, (False, False)), (130, 9, 75, (True, False)),
+                               (70, 9, 3, (True, False)), (70, 9, 4, (True, False))]:
         g, st = pgf_case(ni, nj, nk, seed=ni, reentrant_x=topo[0], reentrant_y=topo[1])
         hm = np.ascontiguousarray(st["h"] * g.Rho0)
         E = oracle.eos(form, 1000.0, -0.2, 0.8)
