@@ -1036,8 +1036,11 @@ int mom6hip_set_viscous_ml(mom6hip_ctx_t *ctx, const mom6hip_set_visc_cs_t *cs, 
  * and refused by the entry points that have none.
  * USE_HORIZONTAL_BOUNDARY_DIFFUSION (unsupported[1]) is taken by mom6hip_tracer_hordiff_hbd with its own control structure, and
  * refused by the entry points that have none.
- * Not provided (refused by name, any nonzero `unsupported`): KHTR_USE_EBT_STRUCT, offline khdt arrays, the df_x / df_y flux
- * diagnostics.
+ * KHTR_USE_EBT_STRUCT (unsupported[5], CS%KhTr_use_ebt_struct) is taken by mom6hip_tracer_hordiff_neutral and mom6hip_tracer_hordiff_hbd:
+ * the interface coefficients of the neutral and the boundary-diffusion branch decay with fields->ebt_struct (:428-462, :503-518), with
+ * FULL_DEPTH_KHTR_MIN (full_depth_khtr_min) floored by KHTR_MIN in the boundary-diffusion branch.  The along-layer and the epipycnal
+ * branch read level 1 only: they accept the switch and ignore the field.  Refused: the switch with fields->ebt_struct NULL.
+ * Not provided (refused by name, any nonzero `unsupported`): offline khdt arrays, the df_x / df_y flux diagnostics.
  */
 typedef struct mom6hip_tracer_hor_diff_cs {
   double KhTr;             /* KHTR [L2 T-1] (0: tracer_hordiff returns at once unless use_variable_mixing) */
@@ -1051,10 +1054,12 @@ typedef struct mom6hip_tracer_hor_diff_cs {
   int32_t check_diffusive_CFL;  /* CHECK_DIFFUSIVE_CFL (0) */
   int32_t initialized;
   int32_t unsupported[8];  /* use_neutral_diffusion, use_hor_bnd_diffusion, Diffuse_ML_interior, (free), (free),
-                              KhTr_use_ebt_struct, offline (do_online = false), flux diagnostics */
+                              KhTr_use_ebt_struct (KHTR_USE_EBT_STRUCT: needs fields->ebt_struct), offline (do_online = false),
+                              flux diagnostics */
   int32_t use_variable_mixing;  /* VarMix%use_variable_mixing (0): the diffusivities of :236-281 */
   int32_t Resoln_scaled_KhTr;   /* VarMix%Resoln_scaled_KhTr (0): needs Res_fn_h */
-  int32_t reserved1[4];
+  int32_t full_depth_khtr_min;  /* FULL_DEPTH_KHTR_MIN (0; read with KHTR_USE_EBT_STRUCT and KHTR_MIN > 0) */
+  int32_t reserved1[3];
 } mom6hip_tracer_hor_diff_cs_t;
 
 /* the fields of MEKE and VarMix tracer_hordiff reads with use_variable_mixing, in the memory space of the call (NULL: not
@@ -1065,7 +1070,8 @@ typedef struct mom6hip_hordiff_fields {
   const double *Res_fn_h;           /* VarMix%Res_fn_h (RESOLN_SCALED_KHTR), h points 2-D */
   const double *Rd_dx_h;            /* VarMix%Rd_dx_h (KHTR_PASSIVITY_COEFF > 0), h points 2-D */
   const double *h_ML;               /* visc%h_ML (NDIFF_INTERIOR_ONLY: the boundary-layer depth neutral diffusion stays below), h points 2-D */
-  void *reserved[4];
+  const double *ebt_struct;         /* VarMix%ebt_struct (KHTR_USE_EBT_STRUCT), h points, nk levels, valid halo of 1 */
+  void *reserved[3];
 } mom6hip_hordiff_fields_t;
 
 typedef struct mom6hip_hordiff_stats {
@@ -1092,8 +1098,13 @@ int mom6hip_tracer_hordiff_varmix(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_d
  * neutral_surface_flux (:2297) and the update of every tracer (:605-1019), for both values of NDIFF_ANSWER_DATE.
  * NDIFF_INTERIOR_ONLY (interior_only): the surfaces are kept below the surface boundary layer visc%h_ML (fields->h_ML) -- boundary_k_range
  * (src/tracer/MOM_hor_bnd_diffusion.F90:609) for every column and the limits of the walk (:1508-1521).
+ * NDIFF_TAPERING (unsupported[2], with NDIFF_INTERIOR_ONLY): the fluxes are tapered linearly across the transition zone between the two
+ * boundary-layer depths of a face (compute_tapering_coeffs :1022).  KHTR_USE_EBT_STRUCT (unsupported[3], the same parameter as
+ * cs->unsupported[5]): Coef_h (:670-684) from fields->ebt_struct, inside the fluxes (:2406-2441).
+ * Refused: NDIFF_TAPERING without NDIFF_INTERIOR_ONLY (the reference never reads the parameter then), unsupported[3] that differs from
+ * cs->unsupported[5].
  * Not provided (refused by name, any nonzero `unsupported`): NDIFF_CONTINUOUS = False (the discontinuous reconstructions),
- * NDIFF_TAPERING, KHTR_USE_EBT_STRUCT, NDIFF_USE_UNMASKED_TRANSPORT_BUG, the flux / tendency diagnostics.
+ * NDIFF_USE_UNMASKED_TRANSPORT_BUG, the flux / tendency diagnostics.
  */
 typedef struct mom6hip_neutral_diffusion_cs {
   double ref_pres;             /* NDIFF_REF_PRES [R L2 T-2] (-1, the default: the pressure of the interface) */
@@ -1103,8 +1114,8 @@ typedef struct mom6hip_neutral_diffusion_cs {
   int32_t recalc_neutral_surf; /* tracer_hor_diff_CS%recalc_neutral_surf, RECALC_NEUTRAL_SURF (0) */
   int32_t initialized;
   int32_t interior_only;       /* NDIFF_INTERIOR_ONLY (0): needs fields->h_ML */
-  int32_t unsupported[8];      /* .not.continuous_reconstruction, (free), tapering, KhTh_use_ebt_struct,
-                                  use_unmasked_transport_bug, diagnostics, (free), (free) */
+  int32_t unsupported[8];      /* .not.continuous_reconstruction, (free), tapering (NDIFF_TAPERING), KhTh_use_ebt_struct
+                                  (KHTR_USE_EBT_STRUCT), use_unmasked_transport_bug, diagnostics, (free), (free) */
 } mom6hip_neutral_diffusion_cs_t;
 
 /* tracer_hordiff with cs->unsupported[0] (CS%use_neutral_diffusion) set: the branch :474-534.  tr[idx_T] and tr[idx_S] are tv%T

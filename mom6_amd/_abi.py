@@ -159,15 +159,16 @@ class TracerHorDiffCS(C.Structure):
     _fields_ = [("KhTr", C.c_double), ("max_diff_CFL", C.c_double), ("KhTr_Slope_Cff", C.c_double), ("KhTr_fac", C.c_double), ("KhTr_min", C.c_double),
                 ("KhTr_max", C.c_double), ("KhTr_passivity_coeff", C.c_double), ("KhTr_passivity_min", C.c_double), ("check_diffusive_CFL", C.c_int32),
                 ("initialized", C.c_int32), ("unsupported", C.c_int32 * 8), ("use_variable_mixing", C.c_int32), ("Resoln_scaled_KhTr", C.c_int32),
-                ("reserved1", C.c_int32 * 4)]
+                ("full_depth_khtr_min", C.c_int32), ("reserved1", C.c_int32 * 3)]
 
 
 HORDIFF_FIELDS = ("MEKE_Kh", "L2u", "L2v", "SN_u", "SN_v", "Res_fn_h", "Rd_dx_h", "h_ML")
+HORDIFF_EBT_FIELD = "ebt_struct"      # VarMix%ebt_struct: read with KHTR_USE_EBT_STRUCT only
 
 
 class HorDiffFields(C.Structure):
     """mom6hip_hordiff_fields_t (include/mom6hip.h)."""
-    _fields_ = [(n, C.c_void_p) for n in HORDIFF_FIELDS] + [("reserved", C.c_void_p * 4)]
+    _fields_ = [(n, C.c_void_p) for n in HORDIFF_FIELDS + (HORDIFF_EBT_FIELD,)] + [("reserved", C.c_void_p * 3)]
 
 
 class NeutralDiffusionCS(C.Structure):

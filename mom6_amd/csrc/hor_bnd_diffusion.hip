@@ -666,6 +666,9 @@ __device__ int boundary_k_bot(int nk, const double *h, long stride, double hbl) 
 struct HBDArgs {
   m6::GridDev g;
   const double *h, *hbl, *khdt[2];
+  const double *ebt;           // KHTR_USE_EBT_STRUCT: VarMix%ebt_struct [layer][h points] (null: off)
+  double KhTr_min;             // KHTR_MIN, the floor of the interface coefficients below the first with FULL_DEPTH_KHTR_MIN
+  int full_depth_khtr_min;
   double I_numitts, h_neglect;
   int linear, limiter, limiter_remap, extrap, scheme;
   int *kmax[2], *nflx[2];      // per face
@@ -773,11 +776,20 @@ __global__ __launch_bounds__(64) void hbd_setup_kernel(HBDArgs A) {
   if (A.nflx[DIR][f] == 0) return;      // no fluxes through this face: khtr_ul_z is not read
   double h_vel[NKM], khtr_ul[NKM], dzl[2 * NKM + 2], khz[2 * NKM + 2];
   RemapWork<NKM> W;
-  const double c = A.I_numitts * A.khdt[DIR][f];      // Coef_x(I,j,K), the same at every interface
+  // Coef_x(I,j,K), MOM_tracer_hor_diff.F90:414-462: the same at every interface, or with KHTR_USE_EBT_STRUCT scaled below the first by
+  // the mean of ebt_struct in the two columns and, with FULL_DEPTH_KHTR_MIN, floored by KHTR_MIN (compared as the reference writes it)
+  const double c = A.I_numitts * A.khdt[DIR][f];
+  double ku = c;      // khtr_u(k)
   for (int k = 0; k < nk; k++) {
     const double h1 = A.h[cL + hpl * k], h2 = A.h[cR + hpl * k];
     h_vel[k] = (h1 + h2 == 0.) ? 0. : 2. * (h1 * h2) / (h1 + h2);      // harmonic_mean :409
-    khtr_ul[k] = c + 0.5 * (c - c);
+    double kn = c;      // khtr_u(k+1)
+    if (A.ebt) {
+      kn = c * 0.5 * (A.ebt[cL + hpl * k] + A.ebt[cR + hpl * k]);
+      if (A.full_depth_khtr_min) kn = max2(kn, A.KhTr_min);
+    }
+    khtr_ul[k] = ku + 0.5 * (kn - ku);
+    ku = kn;
   }
   for (int k = 0; k < km; k++) dzl[k] = dz[f + fpl * k];
   remapping_core_h<NKM>(W, A.scheme, A.extrap != 0, nk, h_vel, khtr_ul, km, dzl, khz, A.h_neglect);
@@ -886,9 +898,10 @@ bool hbd_scheme_provided(int scheme) {
 
 // USE_HORIZONTAL_BOUNDARY_DIFFUSION, MOM_tracer_hor_diff.F90:408-472: num_itts calls of hor_bnd_diffusion with Coef_x = I_numitts *
 // khdt_x at every interface, each after a group pass of the tracers.  h, h_ML, khdt_x / khdt_y and the tracers are device arrays.
+// ebt_struct is VarMix%ebt_struct with KHTR_USE_EBT_STRUCT and null without.
 int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_cs_t *hbd, const double *h, const double *h_ML,
-               const double *khdt_x, const double *khdt_y, int num_itts, double I_numitts, const std::vector<double *> &d_tr,
-               const std::vector<double> &cu, int *halo_updates) {
+               const double *ebt_struct, double KhTr_min, bool full_depth_khtr_min, const double *khdt_x, const double *khdt_y, int num_itts,
+               double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int *halo_updates) {
   M6_REQUIRE(hbd->initialized, "hor_bnd_diffusion: the control structure is not initialised");
   M6_REQUIRE(!hbd->debug, "hor_bnd_diffusion: HBD_DEBUG is not provided by libmom6hip");
   M6_REQUIRE(!hbd->diagnostics, "hor_bnd_diffusion: the hbd_* diagnostics are not provided by libmom6hip");
@@ -905,6 +918,7 @@ int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_c
   A.g = g; A.h = h; A.khdt[0] = khdt_x; A.khdt[1] = khdt_y; A.I_numitts = I_numitts; A.h_neglect = g.H_subroundoff;
   A.linear = hbd->linear; A.limiter = hbd->limiter; A.limiter_remap = hbd->limiter_remap; A.extrap = hbd->boundary_extrap;
   A.scheme = hbd->remap_scheme; A.t = nullptr; A.cu = 0.0;
+  A.ebt = ebt_struct; A.KhTr_min = KhTr_min; A.full_depth_khtr_min = full_depth_khtr_min ? 1 : 0;
   double *hbl = (double *)st.scratch(sizeof(double) * hpl);
   A.kmax[0] = (int *)st.scratch(sizeof(int) * upl); A.nflx[0] = (int *)st.scratch(sizeof(int) * upl);
   A.kmax[1] = (int *)st.scratch(sizeof(int) * vpl); A.nflx[1] = (int *)st.scratch(sizeof(int) * vpl);

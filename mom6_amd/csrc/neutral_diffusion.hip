@@ -13,12 +13,21 @@
 //                         surfaces and is kept in a register -- and nd_update_sym_kernel adds the four faces of a cell and updates the
 //                         tracer (:955-959).  With the older order (:927-938: surface by surface round the four faces) it leaves the
 //                         fluxes [surface][face] and nd_update_kernel accumulates them per layer in LDS.
+//   nd_coef_h_kernel      KHTR_USE_EBT_STRUCT: Coef_h (neutral_diffusion :670-684) of a wet column of the compute domain, straight from
+//                         khdt_x / khdt_y, I_numitts and VarMix%ebt_struct (the interface coefficients of MOM_tracer_hor_diff.F90:489-518
+//                         are formed in registers), as planes [interface][h points]; its halo is a group pass
+//   nd_taper_kernel       NDIFF_TAPERING: the four layer numbers of compute_tapering_coeffs (:1022) for one face -- boundary_k_range of
+//                         the two columns at the smaller and the larger of their boundary-layer depths; coeff_l / coeff_r are closed
+//                         forms of them
+// With either switch nd_flux_kernel forms khtr_ave (:2410-2417) from the coefficients of the interfaces klt, klb, krt, krb: a side's value
+// at klt is its value at klb of the sublayer above, so one is carried and a new one is formed only when the surface enters another cell.
 // A lane owns a column or a face and walks it: the walks are serial in the surface index and differ from lane to lane.  What a walk
 // reads at a depth of its own (the interfaces of a column) is stored as records, so that a gather is one or two sectors and not one a
 // number, and kept in registers while the walk stays in the cell: a step down a column loads one record.  What all lanes read at the
 // same step (the surfaces of a face) is stored as planes.  The blocks are dealt to the XCDs by their range of i (xcd_block).
 #include <cfloat>
 #include <cmath>
+#include <type_traits>
 
 #include "common.hpp"
 #include "eos.hpp"
@@ -173,7 +182,25 @@ struct NDArgs {
   long flx_stride;
   double cu[ND_BATCH];              // conc_underflow of the tracers
   int *bad;
+  const double *ebt;                // KHTR_USE_EBT_STRUCT: VarMix%ebt_struct [layer][h points] (null: off)
+  double *coef_h;                   // Coef_h [(nk+1)][h points]
+  ko_t *kt[2];                      // NDIFF_TAPERING: [k_min_l, k_max_l, k_min_r, k_max_r][faces of the direction] (null: off)
 };
+
+// boundary_k_range(SURFACE, ...), src/tracer/MOM_hor_bnd_diffusion.F90:609-647, for the column n2: k_bot (1-based) and zeta_bot
+__device__ __forceinline__ void boundary_k_range_surface(const double *__restrict__ h, long n2, long hpl, int nk, double hbl, int &k_bot,
+                                                         double &zeta_bot) {
+  k_bot = 1; zeta_bot = 0.;
+  if (hbl == 0.) return;
+  double hsum = 0., htot = 0.;
+  for (int k = 0; k < nk; k++) hsum = hsum + h[n2 + hpl * k];
+  if (hbl >= hsum) { k_bot = nk; zeta_bot = 1.; return; }
+  for (int k = 0; k < nk; k++) {
+    const double hk = h[n2 + hpl * k];
+    htot = htot + hk;
+    if (htot >= hbl) { k_bot = k + 1; zeta_bot = 1 - (htot - hbl) / hk; return; }
+  }
+}
 
 // Workgroups go round the eight XCDs by their index; a face reads the columns on its two sides, so the blocks of one range of i are given
 // to one XCD, row after row: the column a row's faces read on their far side is in that XCD's L2 when the next row asks for it.
@@ -198,18 +225,7 @@ __global__ __launch_bounds__(64) void nd_column_kernel(NDArgs A, int nbx, int nb
   if (A.interior) {      // boundary_k_range(SURFACE, ...), src/tracer/MOM_hor_bnd_diffusion.F90:609-647, for wet columns (:381-386)
     int k_bot = 1;
     double zeta_bot = 0.;
-    const double hbl = A.hbl[n2];
-    if (g.mask2dT[n2] > 0.0 && hbl != 0.) {
-      double hsum = 0., htot = 0.;
-      for (int k = 0; k < nk; k++) hsum = hsum + A.h[n2 + hpl * k];
-      if (hbl >= hsum) { k_bot = nk; zeta_bot = 1.; }
-      else
-        for (int k = 0; k < nk; k++) {
-          const double hk = A.h[n2 + hpl * k];
-          htot = htot + hk;
-          if (htot >= hbl) { k_bot = k + 1; zeta_bot = 1 - (htot - hbl) / hk; break; }
-        }
-    }
+    if (g.mask2dT[n2] > 0.0) boundary_k_range_surface(A.h, n2, hpl, nk, A.hbl[n2], k_bot, zeta_bot);
     A.kbot[n2] = k_bot; A.zbot[n2] = zeta_bot;
   }
   double P = A.p_surf ? A.p_surf[n2] : 0.;
@@ -327,6 +343,61 @@ __global__ __launch_bounds__(64) void nd_surfaces_kernel(NDArgs A, int nbx, int 
   }
 }
 
+// compute_tapering_coeffs :1044-1058 for one wet face: k_min and k_max of the left and of the right column
+template <int DIR>
+__global__ __launch_bounds__(64) void nd_taper_kernel(NDArgs A, int nbx, int nby) {
+  const m6::GridDev &g = A.g;
+  int bx, by;
+  if (!xcd_block(nbx, nby, bx, by)) return;
+  const int i = (DIR ? g.isc : g.isc - 1) + bx * 64 + threadIdx.x, j = (DIR ? g.jsc - 1 : g.jsc) + by, nk = g.nk;
+  if (i > g.iec) return;
+  const long f = DIR ? g.v2(i, j) : g.u2(i, j), pl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
+  if (!((DIR ? g.mask2dCv[f] : g.mask2dCu[f]) > 0.0)) return;      // (read by the wet faces only)
+  const long hpl = (long)g.nih * g.njh, cl = g.h2(i, j), cr = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const double bld_l = A.hbl[cl], bld_r = A.hbl[cr];
+  const double max_bld = max2(bld_l, bld_r), min_bld = min2(bld_l, bld_r);
+  int k[4];
+  double zeta;
+  boundary_k_range_surface(A.h, cl, hpl, nk, min_bld, k[0], zeta);
+  boundary_k_range_surface(A.h, cl, hpl, nk, max_bld, k[1], zeta);
+  boundary_k_range_surface(A.h, cr, hpl, nk, min_bld, k[2], zeta);
+  boundary_k_range_surface(A.h, cr, hpl, nk, max_bld, k[3], zeta);
+#pragma unroll
+  for (int q = 0; q < 4; q++) A.kt[DIR][f + pl * q] = (ko_t)k[q];
+}
+
+// coeff_l(K) / coeff_r(K) :1059-1073 of the interface K (1-based) from k_min and k_max of the column
+__device__ __forceinline__ double taper_coeff(int K, int k_min, int k_max) {
+  if (K <= k_min) return 0.0;
+  if (K <= k_max + 1) return ((double)(K - k_min) + 1.0) / ((double)(k_max - k_min) + 2.0);
+  return 1.0;
+}
+
+// Coef_h :670-684 of a wet column of the compute domain; Coef_x(I,j,K), Coef_y(i,J,K) as MOM_tracer_hor_diff.F90:489-518 forms them
+__global__ __launch_bounds__(64) void nd_coef_h_kernel(NDArgs A) {
+  const m6::GridDev &g = A.g;
+  const int i = g.isc + blockIdx.x * 64 + threadIdx.x, j = g.jsc + blockIdx.y, nk = g.nk;
+  if (i > g.iec) return;
+  const long n2 = g.h2(i, j), hpl = (long)g.nih * g.njh;
+  if (!(g.mask2dT[n2] > 0.)) return;
+  const int I = i, J = j;
+  const long uW = g.u2(I - 1, j), uE = g.u2(I, j), vS = g.v2(i, J - 1), vN = g.v2(i, J);
+  const long nW = g.h2(i - 1, j), nE = g.h2(i + 1, j), nS = g.h2(i, j - 1), nN = g.h2(i, j + 1);
+  const double normalize = 1.0 / ((g.mask2dCu[uW] + g.mask2dCu[uE]) + (g.mask2dCv[vS] + g.mask2dCv[vN]) + 1.0e-37);
+  const double nm = normalize * g.mask2dT[n2];
+  const double cW = A.scale * A.khdt[0][uW], cE = A.scale * A.khdt[0][uE], cS = A.scale * A.khdt[1][vS], cN = A.scale * A.khdt[1][vN];
+  const double *__restrict__ ebt = A.ebt;
+  double *__restrict__ coef_h = A.coef_h;
+  coef_h[n2] = nm * ((cW + cE) + (cS + cN));
+  for (int K = 1; K <= nk; K++) {
+    const long o = hpl * (K - 1);
+    const double e = ebt[n2 + o];
+    const double xW = cW * 0.5 * (ebt[nW + o] + e), xE = cE * 0.5 * (e + ebt[nE + o]);
+    const double yS = cS * 0.5 * (ebt[nS + o] + e), yN = cN * 0.5 * (e + ebt[nN + o]);
+    coef_h[n2 + hpl * K] = nm * ((xW + xE) + (yS + yN));
+  }
+}
+
 // the interface values of the batch's tracers (neutral_surface_flux :2373-2374) and the means of their cells, as records
 __global__ __launch_bounds__(64) void nd_tracer_cols_kernel(NDArgs A, int nbx, int nby) {
   const m6::GridDev &g = A.g;
@@ -345,9 +416,11 @@ __global__ __launch_bounds__(64) void nd_tracer_cols_kernel(NDArgs A, int nbx, i
   });
 }
 
-// neutral_surface_flux :2297 (continuous, no tapering: khtr_ave = 1).  SYM: the tendencies of the two cells of the face from its fluxes,
-// layer by layer (the order of the sums of neutral_diffusion :939-954: a face at a time, its surfaces top down); otherwise the fluxes
-template <int DIR, bool SYM>
+// neutral_surface_flux :2297 (continuous).  SYM: the tendencies of the two cells of the face from its fluxes, layer by layer (the order
+// of the sums of neutral_diffusion :939-954: a face at a time, its surfaces top down); otherwise the fluxes.  COEF: what coeff_l / coeff_r
+// are -- absent (khtr_ave = 1), the taper, Coef_h, or their product (:703-764); with Coef_h the fluxes carry the diffusivity (:834-878)
+enum { ND_COEF_NONE = 0, ND_COEF_TAPER = 1, ND_COEF_EBT = 2, ND_COEF_BOTH = 3 };
+template <int DIR, bool SYM, int COEF = ND_COEF_NONE>
 __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby) {
   const m6::GridDev &g = A.g;
   int bx, by;
@@ -405,6 +478,24 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby)
   double accL[ND_BATCH], accR[ND_BATCH];
 #pragma unroll
   for (int z = 0; z < ND_BATCH; z++) { accL[z] = 0.; accR[z] = 0.; }
+  // COEF: coeff_l / coeff_r at the interface K (0-based: the top of the cell K), and their values at the surface above
+  int kminL = 0, kmaxL = 0, kminR = 0, kmaxR = 0;
+  if constexpr ((COEF & ND_COEF_TAPER) != 0) {
+    const ko_t *__restrict__ kt = A.kt[DIR];
+    kminL = kt[f]; kmaxL = kt[f + pl]; kminR = kt[f + pl * 2]; kmaxR = kt[f + pl * 3];
+  }
+  auto coefL = [&](int K) -> double {
+    if constexpr (COEF == ND_COEF_TAPER) return taper_coeff(K + 1, kminL, kmaxL);
+    else if constexpr (COEF == ND_COEF_EBT) return A.coef_h[cl + hpl * K];
+    else return taper_coeff(K + 1, kminL, kmaxL) * A.coef_h[cl + hpl * K];
+  };
+  auto coefR = [&](int K) -> double {
+    if constexpr (COEF == ND_COEF_TAPER) return taper_coeff(K + 1, kminR, kmaxR);
+    else if constexpr (COEF == ND_COEF_EBT) return A.coef_h[cr + hpl * K];
+    else return taper_coeff(K + 1, kminR, kmaxR) * A.coef_h[cr + hpl * K];
+  };
+  double cLt = 0., cRt = 0.;
+  if constexpr (COEF != ND_COEF_NONE) { cLt = coefL(klt); cRt = coefR(krt); }
   if (SYM) {
     for (int z = 0; z < nb; z++) {
       for (int k = 0; k < klt; k++) tdL[A.flx_stride * z + f + pl * k] = 0.;
@@ -426,6 +517,12 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby)
     }
     if (klb != klt) enter(sl, cl, klt, klb);
     if (krb != krt) enter(sr, cr, krt, krb);
+    double khtr_ave = 1.0;
+    if constexpr (COEF != ND_COEF_NONE) {      // :2410-2417
+      const double cLb = (klb != klt) ? coefL(klb) : cLt, cRb = (krb != krt) ? coefR(krb) : cRt;
+      khtr_ave = 0.25 * ((cLb + cLt) + (cRb + cRt));
+      cLt = cLb; cRt = cRb;
+    }
 #pragma unroll
     for (int z = 0; z < ND_BATCH; z++) {
       const double T_left_bottom = (1. - pLb) * sl.i0[z] + pLb * sl.i1[z];
@@ -440,9 +537,10 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby)
         const double dT_layer = T_right_layer - T_left_layer;
         if (signum(1., dT_top) * signum(1., dT_bottom) <= 0. || signum(1., dT_ave) * signum(1., dT_layer) <= 0.) dT_ave = 0.;
         else dT_ave = dT_layer;
-        flx = dT_ave * he * 1.0;
+        flx = dT_ave * he * khtr_ave;
       }
-      if (SYM) { accL[z] = accL[z] + cf * flx; accR[z] = accR[z] - cf * flx; }
+      if (SYM && (COEF & ND_COEF_EBT) != 0) { accL[z] = accL[z] + flx; accR[z] = accR[z] - flx; }
+      else if (SYM) { accL[z] = accL[z] + cf * flx; accR[z] = accR[z] - cf * flx; }
       else if (z < nb) Flx[A.flx_stride * z + f + pl * ks] = flx;
       sl.top[z] = T_left_bottom; sr.top[z] = T_right_bottom;
     }
@@ -506,6 +604,8 @@ __global__ __launch_bounds__(256) void nd_update_sym_kernel(NDArgs A) {
 // :921-938, :955-959 (the order of 2024 and before): the cell's tendency from the fluxes of its four faces, surface by surface round the
 // faces E, W, N, S, accumulated per layer in LDS (the layer index is data: KoL / KoR), then the tracer.  (A thread per layer that walks
 // the runs of its four faces -- no LDS, full occupancy -- reads the fluxes as gathers and is slower: profiles/r04_experiments.txt.)
+// EBT: the fluxes carry the diffusivity (:834-848); otherwise they are multiplied by Coef_x(I,j,1), Coef_y(i,J,1) (:880-893)
+template <bool EBT>
 __global__ __launch_bounds__(64) void nd_update_kernel(NDArgs A) {
   extern __shared__ double acc[];      // [nk][64]
   const m6::GridDev &g = A.g;
@@ -540,10 +640,17 @@ __global__ __launch_bounds__(64) void nd_update_kernel(NDArgs A) {
 #pragma unroll
     for (int q = 0; q < NU; q++) {
       if (ks0 + q < nl) {
-        ACC(kE[q]) = ACC(kE[q]) + cE * fE[q];
-        ACC(kW[q]) = ACC(kW[q]) - cW * fW[q];
-        ACC(kN[q]) = ACC(kN[q]) + cN * fN[q];
-        ACC(kS[q]) = ACC(kS[q]) - cS * fS[q];
+        if (EBT) {
+          ACC(kE[q]) = ACC(kE[q]) + fE[q];
+          ACC(kW[q]) = ACC(kW[q]) - fW[q];
+          ACC(kN[q]) = ACC(kN[q]) + fN[q];
+          ACC(kS[q]) = ACC(kS[q]) - fS[q];
+        } else {
+          ACC(kE[q]) = ACC(kE[q]) + cE * fE[q];
+          ACC(kW[q]) = ACC(kW[q]) - cW * fW[q];
+          ACC(kN[q]) = ACC(kN[q]) + cN * fN[q];
+          ACC(kS[q]) = ACC(kS[q]) - cS * fS[q];
+        }
       }
     }
   }
@@ -561,16 +668,22 @@ __global__ __launch_bounds__(64) void nd_update_kernel(NDArgs A) {
 namespace m6 {
 
 // the neutral branch of tracer_hordiff (MOM_tracer_hor_diff.F90:474-534) on device arrays; khdt_x, khdt_y and the iteration count
-// are those tracer_hordiff has formed
+// are those tracer_hordiff has formed; ebt_struct is VarMix%ebt_struct with KHTR_USE_EBT_STRUCT (tracer_hordiff has checked that
+// nd->unsupported[3] says the same) and null without
 int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_eos_t *eos, const double *h,
-                   const double *p_surf, const double *h_ML, const double *khdt_x, const double *khdt_y, int num_itts, double I_numitts,
-                   const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S, int *halo_updates) {
+                   const double *p_surf, const double *h_ML, const double *ebt_struct, const double *khdt_x, const double *khdt_y, int num_itts,
+                   double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S,
+                   int *halo_updates) {
   static const char *names[8] = {"NDIFF_CONTINUOUS = False", "(free)", "NDIFF_TAPERING", "KHTR_USE_EBT_STRUCT",
                                  "NDIFF_USE_UNMASKED_TRANSPORT_BUG", "the neutral-diffusion diagnostics", "(free)", "(free)"};
   const int ntr = (int)d_tr.size();
   M6_REQUIRE(nd != nullptr && eos != nullptr, "tracer_hordiff: USE_NEUTRAL_DIFFUSION needs the neutral_diffusion control structure and tv%%eqn_of_state");
   M6_REQUIRE(nd->initialized, "neutral_diffusion: the control structure is not initialised");
-  for (int q = 0; q < 8; q++) M6_REQUIRE(!nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
+  // unsupported[2] (tapering) and [3] (KhTh_use_ebt_struct) are the switches of the two modes of the fluxes
+  for (int q = 0; q < 8; q++) M6_REQUIRE(q == 2 || q == 3 || !nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
+  const bool taper = nd->unsupported[2] != 0, ebt = ebt_struct != nullptr;
+  M6_REQUIRE(!taper || nd->interior_only, "neutral_diffusion: NDIFF_TAPERING is read with NDIFF_INTERIOR_ONLY only (the reference never reads it "
+             "otherwise): it is refused without");
   M6_REQUIRE(idx_T >= 0 && idx_T < ntr && idx_S >= 0 && idx_S < ntr, "tracer_hordiff: tv%%T and tv%%S must be among the tracers (idx_T, idx_S)");
   const m6::GridDev g = ctx->g;
   M6_REQUIRE(g.mask2dT && g.mask2dCu && g.mask2dCv && g.IareaT, "neutral_diffusion: mask2dT, mask2dCu, mask2dCv and IareaT are needed");
@@ -604,6 +717,17 @@ int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusi
   }
   M6_REQUIRE(!st.failed() && irec && faces && kos && trec && bad, "neutral_diffusion: out of device memory");
   A.irec = irec; A.trec = trec; A.bad = bad;
+  A.ebt = ebt_struct; A.coef_h = nullptr; A.kt[0] = A.kt[1] = nullptr;
+  if (ebt) {
+    A.coef_h = (double *)st.scratch(sizeof(double) * hpl * ((size_t)nk + 1));
+    M6_REQUIRE(!st.failed() && A.coef_h, "neutral_diffusion: out of device memory");
+  }
+  if (taper) {
+    ko_t *kt = (ko_t *)st.scratch(sizeof(ko_t) * fpl * 8);
+    M6_REQUIRE(!st.failed() && kt, "neutral_diffusion: out of device memory");
+    A.kt[0] = kt; A.kt[1] = kt + fpl * 4;
+  }
+  const int coef = (taper ? ND_COEF_TAPER : 0) | (ebt ? ND_COEF_EBT : 0);
   double *per = faces + fpl * ns * 6;
   for (int d = 0; d < 2; d++) {
     A.PoL[d] = faces + fpl * ns * (3 * d); A.PoR[d] = A.PoL[d] + fpl * ns; A.hEff[d] = A.PoR[d] + fpl * ns;
@@ -628,11 +752,32 @@ int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusi
     hipLaunchKernelGGL(nd_column_kernel, dim3(xcd_grid(nbc, nj + 2)), dim3(64), 0, s, A, nbc, nj + 2);
     hipLaunchKernelGGL(nd_surfaces_kernel<0>, dim3(xcd_grid(nbu, nj)), dim3(64), 0, s, A, nbu, nj);
     hipLaunchKernelGGL(nd_surfaces_kernel<1>, dim3(xcd_grid(nbv, nj + 1)), dim3(64), 0, s, A, nbv, nj + 1);
+    if (taper) {      // the layer numbers of the taper depend on h and CS%hbl only: once where the surfaces are formed
+      hipLaunchKernelGGL(nd_taper_kernel<0>, dim3(xcd_grid(nbu, nj)), dim3(64), 0, s, A, nbu, nj);
+      hipLaunchKernelGGL(nd_taper_kernel<1>, dim3(xcd_grid(nbv, nj + 1)), dim3(64), 0, s, A, nbv, nj + 1);
+    }
     return 0;
+  };
+  // the two flux kernels of a batch in the coefficient mode of the call
+  auto launch_flux = [&](auto sym, auto mode) {
+    hipLaunchKernelGGL((nd_flux_kernel<0, decltype(sym)::value, decltype(mode)::value>), dim3(xcd_grid(nbu, nj)), dim3(64), 0, s, A, nbu, nj);
+    hipLaunchKernelGGL((nd_flux_kernel<1, decltype(sym)::value, decltype(mode)::value>), dim3(xcd_grid(nbv, nj + 1)), dim3(64), 0, s, A, nbv, nj + 1);
+  };
+  auto launch_fluxes = [&](auto sym) {
+    if (coef == ND_COEF_NONE) launch_flux(sym, std::integral_constant<int, ND_COEF_NONE>());
+    else if (coef == ND_COEF_TAPER) launch_flux(sym, std::integral_constant<int, ND_COEF_TAPER>());
+    else if (coef == ND_COEF_EBT) launch_flux(sym, std::integral_constant<int, ND_COEF_EBT>());
+    else launch_flux(sym, std::integral_constant<int, ND_COEF_BOTH>());
   };
   if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;      // do_group_pass(CS%pass_t) :478
   (*halo_updates)++;
   if (int rc = calc_coeffs()) return rc;
+  if (ebt) {      // Coef_h :670-684 depends on khdt, I_numitts and ebt_struct only: once a call, not once an iteration
+    M6_HIP(hipMemsetAsync(A.coef_h, 0, sizeof(double) * hpl * ((size_t)nk + 1), s));
+    hipLaunchKernelGGL(nd_coef_h_kernel, dim3((ni + 63) / 64, nj), dim3(64), 0, s, A);
+    double *f1[1] = {A.coef_h}; int32_t p1[1] = {MOM6HIP_POS_H}, n1[1] = {nk + 1};
+    if (int rc = m6::group_pass(ctx, f1, p1, n1, 1)) return rc;      // pass_var(CS%Coef_h, G%Domain)
+  }
   for (int itt = 1; itt <= num_itts; itt++) {
     if (itt > 1) {
       if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;
@@ -645,13 +790,12 @@ int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusi
       for (int z = A.nb; z < ND_BATCH; z++) { A.t[z] = nullptr; A.cu[z] = 0.; }
       hipLaunchKernelGGL(nd_tracer_cols_kernel, dim3(xcd_grid(nbc, nj + 2)), dim3(64), 0, s, A, nbc, nj + 2);
       if (A.symmetric) {
-        hipLaunchKernelGGL((nd_flux_kernel<0, true>), dim3(xcd_grid(nbu, nj)), dim3(64), 0, s, A, nbu, nj);
-        hipLaunchKernelGGL((nd_flux_kernel<1, true>), dim3(xcd_grid(nbv, nj + 1)), dim3(64), 0, s, A, nbv, nj + 1);
+        launch_fluxes(std::true_type());
         hipLaunchKernelGGL(nd_update_sym_kernel, dim3((ni + 255) / 256, nj, nk * A.nb), dim3(256), 0, s, A);
       } else {
-        hipLaunchKernelGGL((nd_flux_kernel<0, false>), dim3(xcd_grid(nbu, nj)), dim3(64), 0, s, A, nbu, nj);
-        hipLaunchKernelGGL((nd_flux_kernel<1, false>), dim3(xcd_grid(nbv, nj + 1)), dim3(64), 0, s, A, nbv, nj + 1);
-        hipLaunchKernelGGL(nd_update_kernel, dim3((ni + 63) / 64, nj, A.nb), dim3(64), sizeof(double) * 64 * nk, s, A);
+        launch_fluxes(std::false_type());
+        if (ebt) hipLaunchKernelGGL(nd_update_kernel<true>, dim3((ni + 63) / 64, nj, A.nb), dim3(64), sizeof(double) * 64 * nk, s, A);
+        else hipLaunchKernelGGL(nd_update_kernel<false>, dim3((ni + 63) / 64, nj, A.nb), dim3(64), sizeof(double) * 64 * nk, s, A);
       }
     }
   }

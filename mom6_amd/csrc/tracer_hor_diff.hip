@@ -167,11 +167,12 @@ int epipycnal_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_epipycnal_cs_
                      const double *khdt_x, const double *khdt_y, int num_itts, const std::vector<double *> &d_tr,
                      const std::vector<double> &cu, int idx_T, int idx_S, int *halo_updates);
 int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_eos_t *eos, const double *h,
-                   const double *p_surf, const double *h_ML, const double *khdt_x, const double *khdt_y, int num_itts, double I_numitts,
-                   const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S, int *halo_updates);
+                   const double *p_surf, const double *h_ML, const double *ebt_struct, const double *khdt_x, const double *khdt_y, int num_itts,
+                   double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S,
+                   int *halo_updates);
 int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_cs_t *hbd, const double *h, const double *h_ML,
-               const double *khdt_x, const double *khdt_y, int num_itts, double I_numitts, const std::vector<double *> &d_tr,
-               const std::vector<double> &cu, int *halo_updates);
+               const double *ebt_struct, double KhTr_min, bool full_depth_khtr_min, const double *khdt_x, const double *khdt_y, int num_itts,
+               double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int *halo_updates);
 }
 
 static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
@@ -222,9 +223,18 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   M6_REQUIRE(cs != nullptr && h != nullptr, "tracer_hordiff: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "tracer_hordiff: bad memspace");
   // hbd: the call came through mom6hip_tracer_hordiff_hbd, which takes USE_HORIZONTAL_BOUNDARY_DIFFUSION
-  for (int q = 1; q < 8; q++) M6_REQUIRE(q == 2 || (q == 1 && hbd) || !cs->unsupported[q], "tracer_hordiff: %s is not provided by libmom6hip", names[q]);
+  // unsupported[5] (CS%KhTr_use_ebt_struct) is a switch every entry point takes: the neutral and the boundary-diffusion branch read
+  // fields->ebt_struct, the along-layer and the epipycnal branch read level 1 of the coefficients only and ignore the field
+  for (int q = 1; q < 8; q++)
+    M6_REQUIRE(q == 2 || q == 5 || (q == 1 && hbd) || !cs->unsupported[q], "tracer_hordiff: %s is not provided by libmom6hip", names[q]);
   M6_REQUIRE(!cs->unsupported[2] || epi != nullptr, "tracer_hordiff: %s is not provided by this entry point", names[2]);
   const bool use_neutral = cs->unsupported[0] != 0;      // CS%use_neutral_diffusion
+  const bool use_hbd = hbd && cs->unsupported[1];
+  const bool use_ebt = cs->unsupported[5] != 0 && (use_neutral || use_hbd);      // CS%KhTr_use_ebt_struct where ebt_struct is read
+  M6_REQUIRE(!use_ebt || (F && F->ebt_struct), "tracer_hordiff: KHTR_USE_EBT_STRUCT needs VarMix%%ebt_struct (fields->ebt_struct)");
+  M6_REQUIRE(!use_neutral || nd == nullptr || (nd->unsupported[3] != 0) == (cs->unsupported[5] != 0),
+             "tracer_hordiff: KHTR_USE_EBT_STRUCT of the neutral_diffusion control structure (unsupported[3]) differs from that of "
+             "tracer_hor_diff_CS (unsupported[5]); in the reference both are the one parameter");
   if (stats) { stats->num_itts = 0; stats->halo_updates = 0; stats->max_CFL = 0.0; }
   const bool use_VarMix = cs->use_variable_mixing != 0;
   if (ntr == 0 || (cs->KhTr <= 0.0 && !use_VarMix)) return 0;      // :197
@@ -305,16 +315,20 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   std::vector<double *> pf(d_tr);
   std::vector<int32_t> ppos(ntr, MOM6HIP_POS_H), pnk(ntr, g.nk);
   int halo_updates = 0;
-  if (hbd && cs->unsupported[1]) {      // :408-472, before the neutral or the along-layer branch
+  const double *d_ebt = use_ebt ? st.in(F->ebt_struct, bH) : nullptr;
+  if (use_hbd) {      // :408-472, before the neutral or the along-layer branch
     const double *d_hbl = (F && F->h_ML) ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
     M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
-    if (int rc = m6::hbd_branch(ctx, st, hbd, A.h, d_hbl, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, &halo_updates)) return rc;
+    if (int rc = m6::hbd_branch(ctx, st, hbd, A.h, d_hbl, d_ebt, cs->KhTr_min, cs->full_depth_khtr_min != 0, A.khdt_x, A.khdt_y, num_itts,
+                                A.scale, d_tr, cu, &halo_updates))
+      return rc;
   }
   if (use_neutral) {      // :474-534
     const double *d_ps = p_surf ? st.in(p_surf, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
     const double *d_hml = (nd && nd->interior_only && F && F->h_ML) ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
     M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
-    if (int rc = m6::neutral_branch(ctx, st, nd, eos, A.h, d_ps, d_hml, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, idx_T, idx_S, &halo_updates))
+    if (int rc = m6::neutral_branch(ctx, st, nd, eos, A.h, d_ps, d_hml, d_ebt, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, idx_T, idx_S,
+                                    &halo_updates))
       return rc;
   } else
   for (int itt = 1; itt <= num_itts; itt++) {      // :540-614

@@ -6,11 +6,13 @@
 !! RESOLN_SCALED_KHTR with VarMix%Res_fn_h, KHTR_PASSIVITY_COEFF / _MIN with VarMix%Rd_dx_h) on the GPU through libmom6hip
 !! (mom6hip_tracer_hordiff_varmix, HOST memspace), and with USE_NEUTRAL_DIFFUSION the continuous branch of MOM_neutral_diffusion
 !! (neutral_diffusion_init :138, neutral_diffusion_calc_coeffs :337, neutral_diffusion :605: NDIFF_REF_PRES, NDIFF_ANSWER_DATE,
-!! RECALC_NEUTRAL_SURF, NDIFF_INTERIOR_ONLY with visc%h_ML; mom6hip_tracer_hordiff_neutral), and with DIFFUSE_ML_TO_INTERIOR the
-!! epipycnal diffusion between the variable-density layers and the interior of a layered run (tracer_epipycnal_ML_diff :700,
-!! ML_KHTR_SCALE, HOR_DIFF_ANSWER_DATE, HOR_DIFF_LIMIT_BUG; mom6hip_tracer_hordiff_epipycnal).  NDIFF_CONTINUOUS = False,
-!! NDIFF_TAPERING, horizontal boundary diffusion, KHTR_USE_EBT_STRUCT, offline khdt arrays and the df_x / df_y flux diagnostics stop
-!! with a FATAL error.
+!! RECALC_NEUTRAL_SURF, NDIFF_INTERIOR_ONLY with visc%h_ML and NDIFF_TAPERING; mom6hip_tracer_hordiff_neutral), with
+!! USE_HORIZONTAL_BOUNDARY_DIFFUSION the horizontal boundary diffusion of MOM_hor_bnd_diffusion before either
+!! (mom6hip_tracer_hordiff_hbd), with KHTR_USE_EBT_STRUCT the interface coefficients of both that decay with VarMix%ebt_struct
+!! (FULL_DEPTH_KHTR_MIN), and with DIFFUSE_ML_TO_INTERIOR the epipycnal diffusion between the variable-density layers and the interior
+!! of a layered run (tracer_epipycnal_ML_diff :700, ML_KHTR_SCALE, HOR_DIFF_ANSWER_DATE, HOR_DIFF_LIMIT_BUG;
+!! mom6hip_tracer_hordiff_epipycnal).  NDIFF_CONTINUOUS = False, NDIFF_USE_UNMASKED_TRANSPORT_BUG, offline khdt arrays and the
+!! df_x / df_y flux diagnostics stop with a FATAL error.
 !!
 !! Compiled INSIDE a MOM6 source tree in place of src/tracer/MOM_tracer_hor_diff.F90; here against tests/fortran/stubs.
 module MOM_tracer_hor_diff
@@ -50,6 +52,8 @@ type, public :: tracer_hor_diff_CS ; private
   real    :: KhTr_passivity_min   !< Passivity minimum [nondim]
   real    :: max_diff_CFL         !< If positive, locally limit the diffusivity to this diffusive CFL [nondim].
   logical :: check_diffusive_CFL  !< If true, use enough iterations that the diffusive equations are stable.
+  logical :: KhTr_use_ebt_struct  !< If true, uses the equivalent barotropic structure as the vertical structure of the diffusivity.
+  logical :: full_depth_khtr_min  !< If true, KHTR_MIN is enforced throughout the whole water column.
   logical :: Diffuse_ML_interior, use_neutral_diffusion, use_hor_bnd_diffusion
   logical :: first_call = .true.
   logical :: recalc_neutral_surf  !< If true, recalculate the neutral surfaces if CFL has been exceeded
@@ -118,7 +122,14 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   ccs%KhTr_Slope_Cff = CS%KhTr_Slope_Cff ; ccs%KhTr_min = CS%KhTr_min ; ccs%KhTr_max = CS%KhTr_max
   ccs%KhTr_passivity_coeff = CS%KhTr_passivity_coeff ; ccs%KhTr_passivity_min = CS%KhTr_passivity_min
   ccs%check_diffusive_CFL = merge(1, 0, CS%check_diffusive_CFL) ; ccs%initialized = 1
-  ccs%unsupported(:) = 0 ; ccs%reserved1(:) = 0
+  ccs%unsupported(:) = 0 ; ccs%reserved1(:) = 0 ; ccs%full_depth_khtr_min = merge(1, 0, CS%full_depth_khtr_min)
+  if (CS%KhTr_use_ebt_struct) then      ! :428-462, :503-518
+    ccs%unsupported(6) = 1
+    if (CS%use_neutral_diffusion .or. CS%use_hor_bnd_diffusion) then
+      if (.not.allocated(VarMix%ebt_struct)) call MOM_error(FATAL, "tracer_hordiff (HIP): KHTR_USE_EBT_STRUCT needs VarMix%ebt_struct.")
+      fld%ebt_struct = c_loc(VarMix%ebt_struct)
+    endif
+  endif
   if (VarMix%use_variable_mixing) then      ! :219-224, :236-281
     ccs%use_variable_mixing = 1
     if (CS%KhTr_Slope_Cff > 0.) then
@@ -165,7 +176,7 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   if (mom6hip_resident()) then      ! GPU_RESIDENT_DYNAMICS: the shared device mirrors of the host arrays
     ctx = mom6hip_shared_context(G, GV)
     do m=1,Reg%ntr ; tr(m) = mom6hip_mirror(ctx, tr(m), int(size(h), c_int64_t), .true., .true.) ; enddo
-    call to_dev(p_surf, size(h(:,:,1))) ; call to_dev(fld%h_ML, size(h(:,:,1)))
+    call to_dev(p_surf, size(h(:,:,1))) ; call to_dev(fld%h_ML, size(h(:,:,1))) ; call to_dev(fld%ebt_struct, size(h))
     call to_dev(fld%MEKE_Kh, size(h(:,:,1))) ; call to_dev(fld%Res_fn_h, size(h(:,:,1))) ; call to_dev(fld%Rd_dx_h, size(h(:,:,1)))
     if (c_associated(fld%L2u)) then
       call to_dev(fld%L2u, size(VarMix%L2u)) ; call to_dev(fld%SN_u, size(VarMix%SN_u))
@@ -230,12 +241,20 @@ subroutine tracer_hor_diff_init(Time, G, GV, US, param_file, diag, EOS, diabatic
   call log_version(param_file, mdl, version, "")
   call get_param(param_file, mdl, "KHTR", CS%KhTr, "The background along-isopycnal tracer diffusivity.", &
                  units="m2 s-1", default=0.0, scale=US%m_to_L**2*US%T_to_s)
-  call get_param(param_file, mdl, "KHTR_USE_EBT_STRUCT", flag, default=.false.) ; call refuse(flag, "KHTR_USE_EBT_STRUCT")
+  call get_param(param_file, mdl, "KHTR_USE_EBT_STRUCT", CS%KhTr_use_ebt_struct, &
+                 "If true, uses the equivalent barotropic structure as the vertical structure of the tracer diffusivity.", &
+                 default=.false.)
   call get_param(param_file, mdl, "KHTR_SLOPE_CFF", CS%KhTr_Slope_Cff, &
                  "The scaling coefficient for along-isopycnal tracer diffusivity using a shear-based (Visbeck-like) "//&
                  "parameterization.  A non-zero value enables this param.", units="nondim", default=0.0)
   call get_param(param_file, mdl, "KHTR_MIN", CS%KhTr_Min, "The minimum along-isopycnal tracer diffusivity.", &
                  units="m2 s-1", default=0.0, scale=US%m_to_L**2*US%T_to_s)
+  CS%full_depth_khtr_min = .false.
+  if (CS%KhTr_use_ebt_struct .and. CS%KhTr_Min > 0.0) then
+    call get_param(param_file, mdl, "FULL_DEPTH_KHTR_MIN", CS%full_depth_khtr_min, &
+                   "If true, KHTR_MIN is enforced throughout the whole water column. Otherwise, KHTR_MIN is only enforced at the "//&
+                   "surface. This parameter is only available when KHTR_USE_EBT_STRUCT=True and KHTR_MIN>0.", default=.false.)
+  endif
   call get_param(param_file, mdl, "KHTR_MAX", CS%KhTr_Max, "The maximum along-isopycnal tracer diffusivity.", &
                  units="m2 s-1", default=0.0, scale=US%m_to_L**2*US%T_to_s)
   call get_param(param_file, mdl, "KHTR_PASSIVITY_COEFF", CS%KhTr_passivity_coeff, &
@@ -285,9 +304,12 @@ subroutine tracer_hor_diff_init(Time, G, GV, US, param_file, diag, EOS, diabatic
                    "surface and bottom boundary layers.", default=.false.)
     CS%nd%interior_only = merge(1, 0, flag)
     if (flag) then
-      call get_param(param_file, "MOM_neutral_diffusion", "NDIFF_TAPERING", flag, default=.false.)
-      call refuse(flag, "NDIFF_TAPERING")
+      call get_param(param_file, "MOM_neutral_diffusion", "NDIFF_TAPERING", flag, &
+                     "If true, neutral diffusion linearly decays to zero within a transition zone defined using boundary layer "//&
+                     "depths.    Only applicable when NDIFF_INTERIOR_ONLY=True", default=.false.)
+      CS%nd%unsupported(3) = merge(1, 0, flag)      ! CS%tapering
     endif
+    CS%nd%unsupported(4) = merge(1, 0, CS%KhTr_use_ebt_struct)      ! CS%KhTh_use_ebt_struct: the same parameter (:199)
     call get_param(param_file, "MOM_neutral_diffusion", "NDIFF_USE_UNMASKED_TRANSPORT_BUG", flag, default=.false.)
     call refuse(flag, "NDIFF_USE_UNMASKED_TRANSPORT_BUG")
     call get_param(param_file, "MOM_neutral_diffusion", "NDIFF_ANSWER_DATE", CS%nd%ndiff_answer_date, &

@@ -172,7 +172,8 @@ type, bind(c) :: mom6hip_tracer_hor_diff_cs_t
   integer(c_int32_t) :: check_diffusive_CFL, initialized
   integer(c_int32_t) :: unsupported(8)
   integer(c_int32_t) :: use_variable_mixing = 0, Resoln_scaled_KhTr = 0
-  integer(c_int32_t) :: reserved1(4)
+  integer(c_int32_t) :: full_depth_khtr_min = 0      !< FULL_DEPTH_KHTR_MIN
+  integer(c_int32_t) :: reserved1(3)
 end type mom6hip_tracer_hor_diff_cs_t
 
 !> mom6hip_hordiff_fields_t: the fields of MEKE and VarMix tracer_hordiff reads with variable mixing
@@ -180,7 +181,8 @@ type, bind(c) :: mom6hip_hordiff_fields_t
   type(c_ptr) :: MEKE_Kh = c_null_ptr, L2u = c_null_ptr, L2v = c_null_ptr, SN_u = c_null_ptr, SN_v = c_null_ptr
   type(c_ptr) :: Res_fn_h = c_null_ptr, Rd_dx_h = c_null_ptr
   type(c_ptr) :: h_ML = c_null_ptr      !< visc%h_ML (NDIFF_INTERIOR_ONLY)
-  type(c_ptr) :: reserved(4) = c_null_ptr
+  type(c_ptr) :: ebt_struct = c_null_ptr      !< VarMix%ebt_struct (KHTR_USE_EBT_STRUCT)
+  type(c_ptr) :: reserved(3) = c_null_ptr
 end type mom6hip_hordiff_fields_t
 
 !> mom6hip_neutral_diffusion_cs_t (neutral_diffusion_CS, src/tracer/MOM_neutral_diffusion.F90:38), the continuous branch
