@@ -17,6 +17,11 @@
 //    (ntr+2)*16 B per cell; unchanged values (land, inactive faces) are not written back.
 //  * domore_u/domore_v/domore_k stay on the device; only domore_k (nk ints) is read back per
 //    iteration for the exit test (the reference's sum_across_PEs at :305).
+//  * Said once: the flux of a tracer through a face (face_slopes, face_flux), the cell's tracer (cell_tracer, underflows) and the
+//    remaining transport (remaining_transport) serve the marching and the general kernels; with_group turns (tracers in the group,
+//    scheme) into template arguments.  mom6hip_advect_tracer_obc is a sequence of phases on one AdvCall: adv_check, adv_stage_in,
+//    adv_work_space, adv_registries, adv_setup; an iteration adv_group_pass, adv_sweep (adv_pass x and y), adv_count_remaining; adv_outputs.
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -150,6 +155,47 @@ __device__ __forceinline__ double ppm_flux(double Tp, double Tc, double Tm, doub
     return hh * (aL + 0.5 * CFL * ((aR - aL) + a6 * (1. - 2. / 3. * CFL)));
 }
 
+// The slopes the flux of one face needs, about its upwind cell c: PLM its own, CW84 those of c-1, c, c+1, H3 none.
+// T?? are the five cells c-2 .. c+2, mk_? the mask products of the two faces of c-1, c, c+1.  The outer two cells come by reference:
+// advect_x has them in LDS, and they are read where CW uses them, not before the call (and not at all by PLM and H3).
+template <int SCHEME>
+__device__ __forceinline__ void face_slopes(const double &Tmm, double Tm, double Tc, double Tp, const double &Tpp, double mk_m, double mk_c,
+                                            double mk_p, double &sm, double &sc, double &sp) {
+  sm = 0.; sc = 0.; sp = 0.;
+  if (SCHEME == CW) sm = plm_slope(Tc, Tm, Tmm, mk_m);
+  if (SCHEME != H3) sc = plm_slope(Tp, Tc, Tm, mk_c);
+  if (SCHEME == CW) sp = plm_slope(Tpp, Tp, Tc, mk_p);
+}
+
+// The flux of one tracer through one face from the upwind cell's values and slopes, :515-556 / :901-941
+template <int SCHEME>
+__device__ __forceinline__ double face_flux(double Tp, double Tc, double Tm, double sm, double sc, double sp, double mk_c,
+                                            double hh, double CFL) {
+  if (SCHEME == PLM) {
+    if (hh >= 0.0) return hh * (Tc + 0.5 * sc * (1. - CFL));
+    else           return hh * (Tc - 0.5 * sc * (1. - CFL));
+  }
+  return ppm_flux<SCHEME>(Tp, Tc, Tm, sm, sc, sp, mk_c, hh, CFL);
+}
+
+// What is left of the transport through a face, :632-635 / :1021-1024
+__device__ __forceinline__ double remaining_transport(double x, double hh, double neglect) {
+  double r = x - hh;
+  if (fabs(r) < neglect) r = 0.0;
+  return r;
+}
+
+// The tracer of a cell after the pass, :649-662 / :1040-1059.  `upd` is the caller's own guard: advect_x and the general
+// kernel pass do_i && Ihnew > 0, advect_y passes do_i, as the reference does.
+__device__ __forceinline__ double cell_tracer(bool upd, double t_old, double hlst, double fl_p, double fl_m, double Ihnew) {
+  double t_new = t_old;
+  if (upd) t_new = (t_old * hlst - (fl_p - fl_m)) * Ihnew;
+  return t_new;
+}
+
+// The user-controlled underflow, :683-687 / :1062-1066
+__device__ __forceinline__ bool underflows(double t, double cu) { return cu > 0.0 && fabs(t) < cu; }
+
 // New cell volume and the factors of the tracer update, :637-648 (x) / :1030-1039 (y).
 template <bool CLAMP0>
 __device__ __forceinline__ bool cell_volume(double hh_p, double hh_m, double h_old, double areaT,
@@ -282,9 +328,7 @@ __global__ void adv_vflags_prep_kernel(m6::GridDev g, const int *in, int *out, c
 
 // ---------------------------------------------------------------------------------------------
 // advect_x: one wavefront per (j,k) row.
-// FIRST tags the launches of iteration 1 (every row active); the code is identical, the separate
-// symbol keeps profiler statistics of the dense pass apart from the sparse later iterations.
-template <int NT, int SCHEME, bool FIRST>
+template <int NT, int SCHEME>
 __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
   const m6::GridDev &g = p.g;
   __shared__ double s_T[4][NT][XTW];
@@ -310,8 +354,8 @@ __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
     for (int i = p.is + lane; i <= p.ie; i += 64) {
 #pragma unroll
       for (int m = 0; m < NT; m++) if (p.cu[m] > 0.0) {
-        double t = p.tr[m][rowH + (i - g.isd)];
-        if (fabs(t) < p.cu[m] && changed(t, 0.0)) p.tr[m][rowH + (i - g.isd)] = 0.0;
+        const double t = p.tr[m][rowH + (i - g.isd)];
+        if (underflows(t, p.cu[m]) && changed(t, 0.0)) p.tr[m][rowH + (i - g.isd)] = 0.0;
       }
     }
     return;
@@ -373,33 +417,18 @@ __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
       any_limited |= lim;
       const int up = (hh >= 0.0) ? 0 : 1;        // i_up = i + up
       const int Pu = P + up;
-      if (SCHEME == PLM) {
-        const double mk = g.mask2dCu[row2U + (i + up - g.isd)] * g.mask2dCu[row2U + (i + up - 1 - g.isd)];
+      const double mk_c = g.mask2dCu[row2U + (i + up - g.isd)] * g.mask2dCu[row2U + (i + up - 1 - g.isd)];
+      double mk_m = 0.0, mk_p = 0.0;
+      if (SCHEME == CW) {
+        mk_m = g.mask2dCu[row2U + (i + up - 1 - g.isd)] * g.mask2dCu[row2U + (i + up - 2 - g.isd)];
+        mk_p = g.mask2dCu[row2U + (i + up + 1 - g.isd)] * g.mask2dCu[row2U + (i + up - g.isd)];
+      }
 #pragma unroll
-        for (int m = 0; m < NT; m++) {
-          const double Tc = sT[m][Pu];
-          const double sl = plm_slope(sT[m][Pu + 1], Tc, sT[m][Pu - 1], mk);
-          if (hh >= 0.0) flux[m] = hh * (Tc + 0.5 * sl * (1. - CFL));
-          else           flux[m] = hh * (Tc - 0.5 * sl * (1. - CFL));
-        }
-      } else {
-        const double mk_c = g.mask2dCu[row2U + (i + up - g.isd)] * g.mask2dCu[row2U + (i + up - 1 - g.isd)];
-        double mk_m = 0.0, mk_p = 0.0;
-        if (SCHEME == CW) {
-          mk_m = g.mask2dCu[row2U + (i + up - 1 - g.isd)] * g.mask2dCu[row2U + (i + up - 2 - g.isd)];
-          mk_p = g.mask2dCu[row2U + (i + up + 1 - g.isd)] * g.mask2dCu[row2U + (i + up - g.isd)];
-        }
-#pragma unroll
-        for (int m = 0; m < NT; m++) {
-          const double Tp = sT[m][Pu + 1], Tc = sT[m][Pu], Tm = sT[m][Pu - 1];
-          double sm = 0., sc = 0., sp = 0.;
-          if (SCHEME == CW) {
-            sm = plm_slope(Tc, Tm, sT[m][Pu - 2], mk_m);
-            sc = plm_slope(Tp, Tc, Tm, mk_c);
-            sp = plm_slope(sT[m][Pu + 2], Tp, Tc, mk_p);
-          }
-          flux[m] = ppm_flux<SCHEME>(Tp, Tc, Tm, sm, sc, sp, mk_c, hh, CFL);
-        }
+      for (int m = 0; m < NT; m++) {
+        const double Tp = sT[m][Pu + 1], Tc = sT[m][Pu], Tm = sT[m][Pu - 1];
+        double sm, sc, sp;
+        face_slopes<SCHEME>(sT[m][Pu - 2], Tm, Tc, Tp, sT[m][Pu + 2], mk_m, mk_c, mk_p, sm, sc, sp);
+        flux[m] = face_flux<SCHEME>(Tp, Tc, Tm, sm, sc, sp, mk_c, hh, CFL);
       }
     }
     // west-face values from the neighbouring lane (lane 0: carried from the previous chunk)
@@ -417,8 +446,7 @@ __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
 
     // remaining transport, :632-635
     if (face_ok && p.write_mass) {
-      double u_new = u_c - hh;
-      if (fabs(u_new) < g.uh_neglect[row2U + (i - g.isd)]) u_new = 0.0;
+      const double u_new = remaining_transport(u_c, hh, g.uh_neglect[row2U + (i - g.isd)]);
       if (changed(u_new, u_c)) p.uhr[rowU + (i - g.isd)] = u_new;
     }
     // cell volume and tracers, :636-662, and underflow :683-687
@@ -429,9 +457,8 @@ __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
 #pragma unroll
       for (int m = 0; m < NT; m++) {
         const double t_old = sT[m][P];
-        double t_new = t_old;
-        if (do_i && Ihnew > 0.0) t_new = (t_old * hlst - (flux[m] - fl_w[m])) * Ihnew;
-        if (p.cu[m] > 0.0 && fabs(t_new) < p.cu[m]) t_new = 0.0;
+        double t_new = cell_tracer(do_i && Ihnew > 0.0, t_old, hlst, flux[m], fl_w[m], Ihnew);
+        if (underflows(t_new, p.cu[m])) t_new = 0.0;
         if (changed(t_new, t_old)) p.tr[m][rowH + (i - g.isd)] = t_new;
       }
     }
@@ -470,9 +497,10 @@ __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
 // after the barrier a wave reads global memory only inside its own segment.  Each wave starts with one
 // face-only step at J = Ja-1 (recomputing the flux its southern neighbour also computes) so that no
 // flux has to cross a wave boundary.
-constexpr int YSEG_MAX = 8;
+constexpr int YSEG_MAX = 8;      // the waves a block may have: sizes the kernel's LDS and its launch bounds
+constexpr int YSEG = 4;          // the waves a block is given: measured best on MI355X (8: one block per CU; 1-2: too few waves)
 
-template <int NT, int SCHEME, bool FIRST>
+template <int NT, int SCHEME>
 #ifndef ADVY_OCC
 #define ADVY_OCC 2      // waves per SIMD the register allocation aims at (tools/build_variant.sh for experiments)
 #endif
@@ -600,28 +628,17 @@ __global__ __launch_bounds__(64 * YSEG_MAX, ADVY_OCC) void adv_y_kernel(AdvArgs 
 #pragma unroll
       for (int m = 0; m < NT; m++) {
         const double Tm = up ? t2[m] : t1[m], Tc = up ? t3[m] : t2[m], Tp = up ? t4[m] : t3[m];
-        if (SCHEME == PLM) {
-          const double sl = plm_slope(Tp, Tc, Tm, mk_c);
-          if (hh >= 0.0) flux[m] = hh * (Tc + 0.5 * sl * (1. - CFL));
-          else           flux[m] = hh * (Tc - 0.5 * sl * (1. - CFL));
-        } else {
-          double sm = 0., sc = 0., sp = 0.;
-          if (SCHEME == CW) {
-            const double Tmm = up ? t1[m] : t0[m], Tpp = up ? t5[m] : t4[m];
-            const double mk_m = up ? (m_c * m_s) : (m_s * m_ss);
-            const double mk_p = up ? (m_nn * m_n) : (m_n * m_c);
-            sm = plm_slope(Tc, Tm, Tmm, mk_m);
-            sc = plm_slope(Tp, Tc, Tm, mk_c);
-            sp = plm_slope(Tpp, Tp, Tc, mk_p);
-          }
-          flux[m] = ppm_flux<SCHEME>(Tp, Tc, Tm, sm, sc, sp, mk_c, hh, CFL);
-        }
+        const double Tmm = up ? t1[m] : t0[m], Tpp = up ? t5[m] : t4[m];      // (these four are read by CW only)
+        const double mk_m = up ? (m_c * m_s) : (m_s * m_ss);
+        const double mk_p = up ? (m_nn * m_n) : (m_n * m_c);
+        double sm, sc, sp;
+        face_slopes<SCHEME>(Tmm, Tm, Tc, Tp, Tpp, mk_m, mk_c, mk_p, sm, sc, sp);
+        flux[m] = face_flux<SCHEME>(Tp, Tc, Tm, sm, sc, sp, mk_c, hh, CFL);
       }
     }
     // remaining transport, :1021-1024 (every row J, active or not)
     if (own && p.write_mass && lane_ok) {
-      double v_new = v_c - hh;
-      if (fabs(v_new) < g.vh_neglect[col2V + (long)sH * (J - g.jsd)]) v_new = 0.0;
+      const double v_new = remaining_transport(v_c, hh, g.vh_neglect[col2V + (long)sH * (J - g.jsd)]);
       if (changed(v_new, v_c)) p.vhr[colV + (long)sH * (J - g.jsd)] = v_new;
     }
     // cell j = J, :1028-1059, and underflow :1062-1066
@@ -632,9 +649,8 @@ __global__ __launch_bounds__(64 * YSEG_MAX, ADVY_OCC) void adv_y_kernel(AdvArgs 
 #pragma unroll
       for (int m = 0; m < NT; m++) {
         const double t_old = t2[m];
-        double t_new = t_old;
-        if (do_i) t_new = (t_old * hlst - (flux[m] - fl_prev[m])) * Ihnew;
-        if (p.cu[m] > 0.0 && fabs(t_new) < p.cu[m]) t_new = 0.0;
+        double t_new = cell_tracer(do_i, t_old, hlst, flux[m], fl_prev[m], Ihnew);
+        if (underflows(t_new, p.cu[m])) t_new = 0.0;
         if (changed(t_new, t_old)) p.tr[m][colH + (long)sH * (j - g.jsd)] = t_new;
       }
     }
@@ -662,31 +678,19 @@ __global__ __launch_bounds__(64 * YSEG_MAX, ADVY_OCC) void adv_y_kernel(AdvArgs 
   for (; J <= Jb; J++) step(J, std::true_type{});
 }
 
-template <int NT, bool FIRST>
-void launch_x2(int scheme, dim3 grid, hipStream_t s, const AdvArgs &a) {
-  switch (scheme) {
-    case PLM: hipLaunchKernelGGL((adv_x_kernel<NT, PLM, FIRST>), grid, dim3(256), 0, s, a); break;
-    case H3:  hipLaunchKernelGGL((adv_x_kernel<NT, H3, FIRST>), grid, dim3(256), 0, s, a); break;
-    default:  hipLaunchKernelGGL((adv_x_kernel<NT, CW, FIRST>), grid, dim3(256), 0, s, a); break;
+// The run-time pair (tracers in the group 1..MAXG, scheme) as compile-time constants: f(Int<NT>, Int<SCHEME>).
+template <int N> using Int = std::integral_constant<int, N>;
+template <class F>
+void with_group(int n, int scheme, F &&f) {
+  auto with_scheme = [&](auto nt) {
+    if (scheme == PLM) f(nt, Int<PLM>{}); else if (scheme == H3) f(nt, Int<H3>{}); else f(nt, Int<CW>{});
+  };
+  switch (n) {
+    case 1: with_scheme(Int<1>{}); break;
+    case 2: with_scheme(Int<2>{}); break;
+    case 3: with_scheme(Int<3>{}); break;
+    default: with_scheme(Int<4>{}); break;
   }
-}
-template <int NT>
-void launch_x(int scheme, bool first, dim3 grid, hipStream_t s, const AdvArgs &a) {
-  if (first) launch_x2<NT, true>(scheme, grid, s, a); else launch_x2<NT, false>(scheme, grid, s, a);
-}
-template <int NT, bool FIRST>
-void launch_y2(int scheme, dim3 grid, int nseg, int seglen, hipStream_t s, const AdvArgs &a) {
-  const dim3 block(64 * nseg);
-  switch (scheme) {
-    case PLM: hipLaunchKernelGGL((adv_y_kernel<NT, PLM, FIRST>), grid, block, 0, s, a, seglen); break;
-    case H3:  hipLaunchKernelGGL((adv_y_kernel<NT, H3, FIRST>), grid, block, 0, s, a, seglen); break;
-    default:  hipLaunchKernelGGL((adv_y_kernel<NT, CW, FIRST>), grid, block, 0, s, a, seglen); break;
-  }
-}
-template <int NT>
-void launch_y(int scheme, bool first, dim3 grid, int nseg, int seglen, hipStream_t s, const AdvArgs &a) {
-  if (first) launch_y2<NT, true>(scheme, grid, nseg, seglen, s, a);
-  else launch_y2<NT, false>(scheme, grid, nseg, seglen, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -696,8 +700,8 @@ void launch_y(int scheme, bool first, dim3 grid, int nseg, int seglen, hipStream
 // the segment :441-462 / :823-846, the slopes of the three cells about the segment's face are formed again, each with the masks of its own two
 // faces (the loop index of :466 / :850 is the I / J of the mask expression: Fortran does not tell the cases apart) :463-473 / :847-856, an inflow carries the reservoir value with the whole remaining transport :580-627 / :965-1014); regional
 // configurations are small, and the marching kernels above stay as they are.  MOM6HIP_ADV_GENERIC=1 takes this path without OBC (tests).
-constexpr int GEN_MAXTR = 64;
-struct GenTr { double *t[GEN_MAXTR]; double cu[GEN_MAXTR]; int ntr; };
+constexpr int MAXTR = 64;      // the tracers of a call (the context's staging buffers; GenTr)
+struct GenTr { double *t[MAXTR]; double cu[MAXTR]; int ntr; };
 struct GenSeg {      // a segment of the direction of the pass that has a tracer registry
   int plus;          // OBC_DIRECTION_E | N: the cell outside is the second cell of its faces
   int specified, A, c0, c1;      // the face index (IsdB | JsdB) and the range across it (jsd:jed | isd:ied)
@@ -777,17 +781,13 @@ __global__ __launch_bounds__(256) void gen_flux_kernel(GenArgs p) {
   if (lim) atomicOr(&p.dom_new[row], 1);
   const int up = (hh >= 0.0) ? 0 : 1, cu = n + up;
   for (int m = 0; m < p.T.ntr; m++) {
-    double fl;
-    if (SCHEME == PLM) {
-      const double Tc = Tt(m, cu), sl = slope(m, cu);
-      if (hh >= 0.0) fl = hh * (Tc + 0.5 * sl * (1. - CFL));
-      else           fl = hh * (Tc - 0.5 * sl * (1. - CFL));
-    } else {
-      const double Tp = Tt(m, cu + 1), Tc = Tt(m, cu), Tm = Tt(m, cu - 1);
-      double sm = 0., sc = 0., sp = 0.;
-      if (SCHEME == CW) { sm = slope(m, cu - 1); sc = slope(m, cu); sp = slope(m, cu + 1); }
-      fl = ppm_flux<SCHEME>(Tp, Tc, Tm, sm, sc, sp, fmask(cu) * fmask(cu - 1), hh, CFL);
-    }
+    const double Tc = Tt(m, cu);
+    double Tp = 0., Tm = 0., sm = 0., sc = 0., sp = 0.;
+    if (SCHEME != PLM) { Tp = Tt(m, cu + 1); Tm = Tt(m, cu - 1); }
+    if (SCHEME == CW) sm = slope(m, cu - 1);
+    if (SCHEME != H3) sc = slope(m, cu);
+    if (SCHEME == CW) sp = slope(m, cu + 1);
+    const double fl = face_flux<SCHEME>(Tp, Tc, Tm, sm, sc, sp, fmask(cu) * fmask(cu - 1), hh, CFL);
     p.flux[p.fstride * m + f3] = fl;
   }
   // the inflows through the faces of the segments (two loops over the segments, as the reference)
@@ -832,9 +832,7 @@ __global__ __launch_bounds__(256) void gen_update_kernel(GenArgs p) {
   const long h2 = gen_h2<DIR>(g, n, c), h3 = h2 + hpl * k;
   if (active) {
     const double hh = p.hh[f3];
-    double r = p.xr[f3] - hh;      // :632-635 / :1021-1024
-    if (fabs(r) < p.neglect[f2]) r = 0.0;
-    p.xr[f3] = r;
+    p.xr[f3] = remaining_transport(p.xr[f3], hh, p.neglect[f2]);
     if (cell) {
       const double hh_m = p.hh[f3 - fstep], h_old = p.hprev[h3];
       double h_new, hlst, Ihnew;
@@ -844,14 +842,14 @@ __global__ __launch_bounds__(256) void gen_update_kernel(GenArgs p) {
       if (do_i && Ihnew > 0.0)
         for (int m = 0; m < p.T.ntr; m++) {
           const double t_old = p.T.t[m][h3];
-          p.T.t[m][h3] = (t_old * hlst - (p.flux[p.fstride * m + f3] - p.flux[p.fstride * m + f3 - fstep])) * Ihnew;
+          p.T.t[m][h3] = cell_tracer(true, t_old, hlst, p.flux[p.fstride * m + f3], p.flux[p.fstride * m + f3 - fstep], Ihnew);
         }
     }
   }
   if (cell)      // :683-687 / :1062-1066
     for (int m = 0; m < p.T.ntr; m++) if (p.T.cu[m] > 0.0) {
       const double t = p.T.t[m][h3];
-      if (fabs(t) < p.T.cu[m] && changed(t, 0.0)) p.T.t[m][h3] = 0.0;
+      if (underflows(t, p.T.cu[m]) && changed(t, 0.0)) p.T.t[m][h3] = 0.0;
     }
 }
 
@@ -882,104 +880,98 @@ struct Timer {
   }
 };
 
-}  // namespace
+// What one advect_tracer call carries from phase to phase (the pattern of BtCall in barotropic.hip).
+struct AdvCall {
+  mom6hip_ctx_t *ctx; const mom6hip_tracer_advect_cs_t *cs; const mom6hip_obc_t *obc; hipStream_t s; m6::GridDev g;
+  // the caller's arguments
+  const double *h_end, *uhtr, *vhtr, *conc_underflow;
+  double *const *tr; double *vol_prev, *uhr_out, *vhr_out;
+  int ntr, memspace, update_vol_prev;
+  // the switches and ranges of the call; bytes of an h-, u-, v-point array; elements of domore_u, domore_v
+  int is, ie, js, je, nz, stencil, max_iter;
+  bool x_first, generic;
+  size_t bH, bU, bV, nfu, nfv;
+  // device views of the caller's arrays; work space and flags
+  const double *d_in[4];      // h_end, uhtr, vhtr, vol_prev (or null)
+  std::vector<double *> d_tr;
+  double *hprev, *uhr, *vhr;
+  int *domore_u, *domore_v, *domore_v2, *domore_k;
+  // the general path: the segments with a registry by direction, their registries, the scratch of a pass (hh, then the fluxes)
+  std::vector<GenSeg> gsegs[2]; std::vector<GenReg> gregs;
+  GenSeg *d_gsegs[2]; GenReg *d_gregs; double *gen_scratch; size_t fmax_el; int *gen_flags;
+  // the iteration (:203): its number, the range still valid, what the statistics report
+  int itt, isv, iev, jsv, jev, halo_updates, remaining;
+  Timer *t_k; mom6hip_advect_timing_t tm;
+};
 
-extern "C" int mom6hip_advect_get_timing(mom6hip_ctx_t *ctx, mom6hip_advect_timing_t *t) {
-  M6_REQUIRE(ctx && t, "mom6hip_advect_get_timing: null argument");
-  *t = ctx->adv_timing;
+// the checks of the arguments, then the stencil, the sweep order and the iteration limit (:126-150)
+int adv_check(AdvCall &c, double dt, int x_first_in, int max_iter_in) {
+  const mom6hip_tracer_advect_cs_t *cs = c.cs; const m6::GridDev &g = c.g; const int ntr = c.ntr;
+  M6_REQUIRE(cs != nullptr, "advect_tracer: tracer_advect_init must be called before advect_tracer");
+  M6_REQUIRE(c.h_end && c.uhtr && c.vhtr && c.tr, "advect_tracer: null field pointer");
+  M6_REQUIRE(cs->scheme == PLM || cs->scheme == H3 || cs->scheme == CW,
+             "MOM_tracer_advect: Unknown TRACER_ADVECTION_SCHEME = %d", cs->scheme);
+  M6_REQUIRE(c.memspace == MOM6HIP_MEM_HOST || c.memspace == MOM6HIP_MEM_DEVICE, "advect_tracer: bad memspace");
+  M6_REQUIRE(ntr <= MAXTR, "advect_tracer: at most 64 tracers are supported");
+  M6_REQUIRE(dt > 0.0 && cs->dt > 0.0, "advect_tracer: dt must be positive");
+  for (int m = 0; m < ntr; m++) M6_REQUIRE(c.tr[m] != nullptr, "advect_tracer: tracer %d is null", m);
+
+  c.is = g.isc; c.ie = g.iec; c.js = g.jsc; c.je = g.jec; c.nz = g.nk;
+  c.bH = (size_t)g.nh3() * 8; c.bU = (size_t)g.nu3() * 8; c.bV = (size_t)g.nv3() * 8;
+  c.stencil = 2;
+  if (cs->scheme != PLM && !cs->use_huynh_stencil_bug) c.stencil = 3;
+  M6_REQUIRE(c.is - g.isd >= c.stencil && g.ied - c.ie >= c.stencil && c.js - g.jsd >= c.stencil && g.jed - c.je >= c.stencil,
+             "advect_tracer: halo (%d) narrower than the advection stencil (%d)", c.is - g.isd, c.stencil);
+  c.x_first = (c.ctx->host.first_direction % 2) == 0;
+  c.max_iter = 2 * (int)ceil(dt / cs->dt) + 1;
+  if (max_iter_in > 0) c.max_iter = max_iter_in;
+  if (x_first_in >= 0) c.x_first = x_first_in != 0;
   return 0;
 }
 
-extern "C" int mom6hip_advect_tracer(mom6hip_ctx_t *ctx, const double *h_end, const double *uhtr,
-                                     const double *vhtr, double dt, const mom6hip_tracer_advect_cs_t *cs,
-                                     double *const *tr, const double *conc_underflow, int32_t ntr,
-                                     int32_t x_first_in, double *vol_prev, int32_t max_iter_in,
-                                     int32_t update_vol_prev, double *uhr_out, double *vhr_out,
-                                     int32_t memspace, mom6hip_advect_stats_t *stats) {
-  return mom6hip_advect_tracer_obc(ctx, h_end, uhtr, vhtr, dt, cs, tr, conc_underflow, ntr, x_first_in, vol_prev, max_iter_in, update_vol_prev,
-                                   uhr_out, vhr_out, nullptr, memspace, stats);
+// device views of the caller's arrays
+int adv_stage_in(AdvCall &c) {
+  mom6hip_ctx_t *ctx = c.ctx; hipStream_t s = c.s;
+  const double *src[4] = {c.h_end, c.uhtr, c.vhtr, c.vol_prev};
+  const size_t bytes[4] = {c.bH, c.bU, c.bV, c.bH};
+  for (int q = 0; q < 4; q++) c.d_in[q] = src[q];
+  c.d_tr.assign(c.tr, c.tr + c.ntr);
+  if (c.memspace != MOM6HIP_MEM_HOST) return 0;
+  for (int q = 0; q < 4; q++) {
+    if (!src[q]) continue;      // (vol_prev absent)
+    if (ctx->stage[q].reserve(bytes[q])) return 1;
+    M6_HIP(hipMemcpyAsync(ctx->stage[q].p, src[q], bytes[q], hipMemcpyHostToDevice, s));
+    c.d_in[q] = (const double *)ctx->stage[q].p;
+  }
+  for (int m = 0; m < c.ntr; m++) {
+    if (ctx->tr_stage[m].reserve(c.bH)) return 1;
+    M6_HIP(hipMemcpyAsync(ctx->tr_stage[m].p, c.tr[m], c.bH, hipMemcpyHostToDevice, s));
+    c.d_tr[m] = (double *)ctx->tr_stage[m].p;
+  }
+  return 0;
 }
 
-// advect_tracer with OBC associated: of the OBC, advect_x / advect_y read the tracer registries of the segments (segment%tr_Reg); without
-// any the marching kernels run as for a closed domain, with one the general kernels (gen_flux_kernel, gen_update_kernel)
-extern "C" int mom6hip_advect_tracer_obc(mom6hip_ctx_t *ctx, const double *h_end, const double *uhtr,
-                                         const double *vhtr, double dt, const mom6hip_tracer_advect_cs_t *cs,
-                                         double *const *tr, const double *conc_underflow, int32_t ntr,
-                                         int32_t x_first_in, double *vol_prev, int32_t max_iter_in,
-                                         int32_t update_vol_prev, double *uhr_out, double *vhr_out, const mom6hip_obc_t *obc,
-                                         int32_t memspace, mom6hip_advect_stats_t *stats) {
-  M6_REQUIRE(ctx != nullptr, "advect_tracer: null context (tracer_advect_init must be called before advect_tracer)");
-  if (stats) memset(stats, 0, sizeof(*stats));
-  M6_REQUIRE(ntr >= 0, "advect_tracer: ntr < 0");
-  if (ntr == 0) return 0;   // :124
-  M6_REQUIRE(cs != nullptr, "advect_tracer: tracer_advect_init must be called before advect_tracer");
-  M6_REQUIRE(h_end && uhtr && vhtr && tr, "advect_tracer: null field pointer");
-  M6_REQUIRE(cs->scheme == PLM || cs->scheme == H3 || cs->scheme == CW,
-             "MOM_tracer_advect: Unknown TRACER_ADVECTION_SCHEME = %d", cs->scheme);
-  M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "advect_tracer: bad memspace");
-  M6_REQUIRE(ntr <= 64, "advect_tracer: at most 64 tracers are supported");
-  M6_REQUIRE(dt > 0.0 && cs->dt > 0.0, "advect_tracer: dt must be positive");
-  for (int m = 0; m < ntr; m++) M6_REQUIRE(tr[m] != nullptr, "advect_tracer: tracer %d is null", m);
-
-  m6::GridDev &g = ctx->g;
-  hipStream_t s = ctx->stream;
-  const int is = g.isc, ie = g.iec, js = g.jsc, je = g.jec, nz = g.nk;
-  const size_t bH = (size_t)g.nh3() * 8, bU = (size_t)g.nu3() * 8, bV = (size_t)g.nv3() * 8;
-
-  int stencil = 2;
-  const bool usePPM = cs->scheme != PLM;
-  if (usePPM && !cs->use_huynh_stencil_bug) stencil = 3;
-  M6_REQUIRE(is - g.isd >= stencil && g.ied - ie >= stencil && js - g.jsd >= stencil && g.jed - je >= stencil,
-             "advect_tracer: halo (%d) narrower than the advection stencil (%d)", is - g.isd, stencil);
-  bool x_first = (ctx->host.first_direction % 2) == 0;
-  int max_iter = 2 * (int)ceil(dt / cs->dt) + 1;
-  if (max_iter_in > 0) max_iter = max_iter_in;
-  if (x_first_in >= 0) x_first = x_first_in != 0;
-
-  Timer t_all(ctx->timing, s), t_k(ctx->timing, s);
-  mom6hip_advect_timing_t tm = {};
-  t_all.start();
-
-  // ---- device views of the caller's arrays ----
-  const double *d_hend = h_end, *d_uhtr = uhtr, *d_vhtr = vhtr;
-  double *d_vol = vol_prev;
-  std::vector<double *> d_tr(ntr);
-  if (memspace == MOM6HIP_MEM_HOST) {
-    if (ctx->stage[0].reserve(bH) || ctx->stage[1].reserve(bU) || ctx->stage[2].reserve(bV)) return 1;
-    M6_HIP(hipMemcpyAsync(ctx->stage[0].p, h_end, bH, hipMemcpyHostToDevice, s));
-    M6_HIP(hipMemcpyAsync(ctx->stage[1].p, uhtr, bU, hipMemcpyHostToDevice, s));
-    M6_HIP(hipMemcpyAsync(ctx->stage[2].p, vhtr, bV, hipMemcpyHostToDevice, s));
-    d_hend = (double *)ctx->stage[0].p; d_uhtr = (double *)ctx->stage[1].p; d_vhtr = (double *)ctx->stage[2].p;
-    if (vol_prev) {
-      if (ctx->stage[3].reserve(bH)) return 1;
-      M6_HIP(hipMemcpyAsync(ctx->stage[3].p, vol_prev, bH, hipMemcpyHostToDevice, s));
-      d_vol = (double *)ctx->stage[3].p;
-    }
-    for (int m = 0; m < ntr; m++) {
-      if (ctx->tr_stage[m].reserve(bH)) return 1;
-      M6_HIP(hipMemcpyAsync(ctx->tr_stage[m].p, tr[m], bH, hipMemcpyHostToDevice, s));
-      d_tr[m] = (double *)ctx->tr_stage[m].p;
-    }
-  } else {
-    for (int m = 0; m < ntr; m++) d_tr[m] = tr[m];
-  }
-
-  // ---- work space ----
-  const size_t nfu = (size_t)g.njh * nz, nfv = (size_t)(g.njh + 1) * nz;
-  if (ctx->hprev.reserve(bH) || ctx->uhr.reserve(bU) || ctx->vhr.reserve(bV) ||
-      ctx->flags.reserve((nfu + 2 * nfv + nz) * sizeof(int)))
+// hprev, uhr, vhr; domore_u, two copies of domore_v (advect_y reads one and writes the other) and domore_k = 1
+int adv_work_space(AdvCall &c) {
+  mom6hip_ctx_t *ctx = c.ctx; const int nz = c.nz;
+  c.nfu = (size_t)c.g.njh * nz; c.nfv = (size_t)(c.g.njh + 1) * nz;
+  if (ctx->hprev.reserve(c.bH) || ctx->uhr.reserve(c.bU) || ctx->vhr.reserve(c.bV) ||
+      ctx->flags.reserve((c.nfu + 2 * c.nfv + nz) * sizeof(int)))
     return 1;
-  double *hprev = (double *)ctx->hprev.p, *uhr = (double *)ctx->uhr.p, *vhr = (double *)ctx->vhr.p;
-  int *domore_u = (int *)ctx->flags.p, *domore_v = domore_u + nfu, *domore_v2 = domore_v + nfv;
-  int *domore_k = domore_v2 + nfv;
-  M6_HIP(hipMemsetAsync(domore_u, 0, (nfu + 2 * nfv) * sizeof(int), s));
+  c.hprev = (double *)ctx->hprev.p; c.uhr = (double *)ctx->uhr.p; c.vhr = (double *)ctx->vhr.p;
+  c.domore_u = (int *)ctx->flags.p; c.domore_v = c.domore_u + c.nfu; c.domore_v2 = c.domore_v + c.nfv;
+  c.domore_k = c.domore_v2 + c.nfv;
+  M6_HIP(hipMemsetAsync(c.domore_u, 0, (c.nfu + 2 * c.nfv) * sizeof(int), c.s));
   for (int k = 0; k < nz; k++) ctx->h_domore_k[k] = 1;
-  M6_HIP(hipMemcpyAsync(domore_k, ctx->h_domore_k, nz * sizeof(int), hipMemcpyHostToDevice, s));
+  M6_HIP(hipMemcpyAsync(c.domore_k, ctx->h_domore_k, nz * sizeof(int), hipMemcpyHostToDevice, c.s));
+  return 0;
+}
 
-  // ---- the general path: the tracer registries of the segments (OBC%OBC_pe), or on request ----
-  bool generic = getenv("MOM6HIP_ADV_GENERIC") && atoi(getenv("MOM6HIP_ADV_GENERIC")) != 0;
-  std::vector<GenSeg> gsegs[2];
-  std::vector<GenReg> gregs;
+// The general path is taken for the tracer registries of the segments (OBC%OBC_pe), or on request: the segments that have one as
+// GenSeg by direction, their registered tracers as GenReg (a reservoir handed over as a host array is staged).
+int adv_registries(AdvCall &c) {
+  mom6hip_ctx_t *ctx = c.ctx; const mom6hip_obc_t *obc = c.obc; const m6::GridDev &g = c.g;
+  c.generic = getenv("MOM6HIP_ADV_GENERIC") && atoi(getenv("MOM6HIP_ADV_GENERIC")) != 0;
   ctx->adv_obc_n = 0;      // (the staged reservoirs of this call: counted from zero whatever a refused call left behind)
   if (obc && obc->OBC_pe) {
     M6_REQUIRE(obc->number_of_segments == 0 || obc->segment, "advect_tracer: OBC%%segment is required");
@@ -987,7 +979,7 @@ extern "C" int mom6hip_advect_tracer_obc(mom6hip_ctx_t *ctx, const double *h_end
       const mom6hip_obc_segment_t &S = obc->segment[n];
       if (!S.tr_Reg) continue;
       if (!(S.is_E_or_W || S.is_N_or_S)) continue;      // (not on this PE: read by neither advect_x nor advect_y)
-      generic = true;
+      c.generic = true;
       const int d = S.is_N_or_S ? 1 : 0;
       GenSeg q;
       q.plus = (S.direction == MOM6HIP_OBC_DIRECTION_E || S.direction == MOM6HIP_OBC_DIRECTION_N) ? 1 : 0;
@@ -996,249 +988,281 @@ extern "C" int mom6hip_advect_tracer_obc(mom6hip_ctx_t *ctx, const double *h_end
       q.b0 = d ? S.JsdB : S.jsd; q.nb = d ? (S.JedB - S.JsdB + 1) : (S.jed - S.jsd + 1);
       M6_REQUIRE(q.A >= (d ? g.jsd : g.isd) + 2 && q.A <= (d ? g.jed : g.ied) - 3 && q.c0 >= (d ? g.isd : g.jsd) && q.c1 <= (d ? g.ied : g.jed),
                  "advect_tracer: OBC segment %d lies outside the data domain", n + 1);
-      q.r0 = (int)gregs.size(); q.ntseg = S.ntseg;
+      q.r0 = (int)c.gregs.size(); q.ntseg = S.ntseg;
       for (int t = 0; t < S.ntseg; t++) {
         const mom6hip_obc_segment_tracer_t &R = S.tr_Reg[t];
-        M6_REQUIRE(R.ntr_index >= 1 && R.ntr_index <= ntr, "advect_tracer: the registry of OBC segment %d names tracer %d of %d", n + 1, R.ntr_index, ntr);
+        M6_REQUIRE(R.ntr_index >= 1 && R.ntr_index <= c.ntr, "advect_tracer: the registry of OBC segment %d names tracer %d of %d", n + 1, R.ntr_index, c.ntr);
         GenReg r; r.m = R.ntr_index - 1; r.conc = R.OBC_inflow_conc; r.tres = nullptr;
         if (R.tres) {
-          const size_t bytes = (size_t)q.na * q.nb * nz * 8;
-          if (memspace == MOM6HIP_MEM_HOST) {
+          const size_t bytes = (size_t)q.na * q.nb * c.nz * 8;
+          if (c.memspace == MOM6HIP_MEM_HOST) {
             M6_REQUIRE(ctx->adv_obc_n < 64 && ctx->adv_obc[ctx->adv_obc_n].reserve(bytes) == 0, "advect_tracer: out of device memory for the tracer reservoirs");
-            M6_HIP(hipMemcpyAsync(ctx->adv_obc[ctx->adv_obc_n].p, R.tres, bytes, hipMemcpyHostToDevice, s));
+            M6_HIP(hipMemcpyAsync(ctx->adv_obc[ctx->adv_obc_n].p, R.tres, bytes, hipMemcpyHostToDevice, c.s));
             r.tres = (const double *)ctx->adv_obc[ctx->adv_obc_n++].p;
           } else r.tres = R.tres;
         }
-        gregs.push_back(r);
+        c.gregs.push_back(r);
       }
       // the slopes about a segment are formed again with the tracer values of that moment: two segments with registries within three
       // cells of each other on a line would make the order of the reference's loop over the segments matter
-      for (const GenSeg &o : gsegs[d])
+      for (const GenSeg &o : c.gsegs[d])
         M6_REQUIRE(o.c1 < q.c0 || o.c0 > q.c1 || abs(o.A - q.A) > 3, "advect_tracer: OBC segments with tracer registries closer than four cells are not provided");
-      gsegs[d].push_back(q);
+      c.gsegs[d].push_back(q);
     }
   }
-  ctx->adv_obc_n = 0;
-  M6_REQUIRE(!generic || ntr <= GEN_MAXTR, "advect_tracer: at most %d tracers on the general path", GEN_MAXTR);
-  GenSeg *d_gsegs[2] = {nullptr, nullptr};
-  GenReg *d_gregs = nullptr;
-  double *gen_scratch = nullptr;
-  int *gen_flags = nullptr;
-  const size_t fmax_el = (size_t)(g.nu3() > g.nv3() ? g.nu3() : g.nv3());
-  if (generic) {
-    const size_t bs0 = sizeof(GenSeg) * (gsegs[0].size() + 1), bs1 = sizeof(GenSeg) * (gsegs[1].size() + 1), br = sizeof(GenReg) * (gregs.size() + 1);
-    if (ctx->adv_gen.reserve(bs0 + bs1 + br + 64 + nfu * sizeof(int) + fmax_el * 8 * ((size_t)ntr + 1))) return 1;
-    char *q = (char *)ctx->adv_gen.p;
-    gen_scratch = (double *)q; q += fmax_el * 8 * ((size_t)ntr + 1);
-    d_gsegs[0] = (GenSeg *)q; q += bs0; d_gsegs[1] = (GenSeg *)q; q += bs1; d_gregs = (GenReg *)q; q += br;
-    q = (char *)(((uintptr_t)q + 15) & ~(uintptr_t)15);
-    gen_flags = (int *)q;
-    if (!gsegs[0].empty()) M6_HIP(hipMemcpyAsync(d_gsegs[0], gsegs[0].data(), sizeof(GenSeg) * gsegs[0].size(), hipMemcpyHostToDevice, s));
-    if (!gsegs[1].empty()) M6_HIP(hipMemcpyAsync(d_gsegs[1], gsegs[1].data(), sizeof(GenSeg) * gsegs[1].size(), hipMemcpyHostToDevice, s));
-    if (!gregs.empty()) M6_HIP(hipMemcpyAsync(d_gregs, gregs.data(), sizeof(GenReg) * gregs.size(), hipMemcpyHostToDevice, s));
-    M6_HIP(hipStreamSynchronize(s));      // (the host vectors are read by the copies)
-  }
-  auto gen_args = [&](int d, GenArgs &a) {
-    a.g = g; a.T.ntr = ntr;
-    for (int m = 0; m < ntr; m++) { a.T.t[m] = d_tr[m]; a.T.cu[m] = conc_underflow ? conc_underflow[m] : 0.0; }
-    a.hprev = hprev; a.xr = d ? vhr : uhr; a.hh = gen_scratch; a.flux = gen_scratch + fmax_el; a.fstride = (long)fmax_el;
-    a.domore_k = domore_k; a.neglect = d ? g.vh_neglect : g.uh_neglect;
-    a.nseg = (int)gsegs[d].size(); a.segs = d_gsegs[d]; a.regs = d_gregs;
-    a.obc_any = obc ? (d ? (obc->specified_v_BCs_exist_globally || obc->open_v_BCs_exist_globally)
-                         : (obc->specified_u_BCs_exist_globally || obc->open_u_BCs_exist_globally)) : 0;
-    a.obc_open = obc ? (d ? obc->open_v_BCs_exist_globally : obc->open_u_BCs_exist_globally) : 0;
-  };
+  M6_REQUIRE(!c.generic || c.ntr <= MAXTR, "advect_tracer: at most %d tracers on the general path", MAXTR);
+  // the general path's device memory: the scratch of a pass, the tables above, the flags gen_xflags_kernel reads
+  hipStream_t s = c.s;
+  c.fmax_el = (size_t)(g.nu3() > g.nv3() ? g.nu3() : g.nv3());
+  if (!c.generic) return 0;
+  const size_t bs0 = sizeof(GenSeg) * (c.gsegs[0].size() + 1), bs1 = sizeof(GenSeg) * (c.gsegs[1].size() + 1), br = sizeof(GenReg) * (c.gregs.size() + 1);
+  if (c.ctx->adv_gen.reserve(bs0 + bs1 + br + 64 + c.nfu * sizeof(int) + c.fmax_el * 8 * ((size_t)c.ntr + 1))) return 1;
+  char *q = (char *)c.ctx->adv_gen.p;
+  c.gen_scratch = (double *)q; q += c.fmax_el * 8 * ((size_t)c.ntr + 1);
+  c.d_gsegs[0] = (GenSeg *)q; q += bs0; c.d_gsegs[1] = (GenSeg *)q; q += bs1; c.d_gregs = (GenReg *)q; q += br;
+  q = (char *)(((uintptr_t)q + 15) & ~(uintptr_t)15);
+  c.gen_flags = (int *)q;
+  for (int d = 0; d < 2; d++)
+    if (!c.gsegs[d].empty()) M6_HIP(hipMemcpyAsync(c.d_gsegs[d], c.gsegs[d].data(), sizeof(GenSeg) * c.gsegs[d].size(), hipMemcpyHostToDevice, s));
+  if (!c.gregs.empty()) M6_HIP(hipMemcpyAsync(c.d_gregs, c.gregs.data(), sizeof(GenReg) * c.gregs.size(), hipMemcpyHostToDevice, s));
+  M6_HIP(hipStreamSynchronize(s));      // (the host vectors are read by the copies)
+  return 0;
+}
 
-  // ---- :152-178 ----
-  t_k.start();
-  {
-    dim3 grid((g.nih + 1 + 255) / 256, g.njh + 1, nz);
-    hipLaunchKernelGGL(adv_setup_kernel, grid, dim3(256), 0, s, g, d_hend, d_uhtr, d_vhtr, (const double *)d_vol,
-                       hprev, uhr, vhr);
+// uhr, vhr, hprev :152-178
+int adv_setup(AdvCall &c) {
+  const m6::GridDev &g = c.g;
+  c.t_k->start();
+  hipLaunchKernelGGL(adv_setup_kernel, dim3((g.nih + 1 + 255) / 256, g.njh + 1, c.nz), dim3(256), 0, c.s, g, c.d_in[0], c.d_in[1], c.d_in[2],
+                     c.d_in[3], c.hprev, c.uhr, c.vhr);
+  M6_HIP(hipGetLastError());
+  c.tm.ms_setup += c.t_k->stop();
+  return 0;
+}
+
+// the arguments of the general kernels in direction d, but for the range and the flags of the pass
+void gen_args(const AdvCall &c, int d, GenArgs &a) {
+  const m6::GridDev &g = c.g; const mom6hip_obc_t *obc = c.obc;
+  a.g = g; a.T.ntr = c.ntr;
+  for (int m = 0; m < c.ntr; m++) { a.T.t[m] = c.d_tr[m]; a.T.cu[m] = c.conc_underflow ? c.conc_underflow[m] : 0.0; }
+  a.hprev = c.hprev; a.xr = d ? c.vhr : c.uhr; a.hh = c.gen_scratch; a.flux = c.gen_scratch + c.fmax_el; a.fstride = (long)c.fmax_el;
+  a.domore_k = c.domore_k; a.neglect = d ? g.vh_neglect : g.uh_neglect;
+  a.nseg = (int)c.gsegs[d].size(); a.segs = c.d_gsegs[d]; a.regs = c.d_gregs;
+  a.obc_any = obc ? (d ? (obc->specified_v_BCs_exist_globally || obc->open_v_BCs_exist_globally)
+                       : (obc->specified_u_BCs_exist_globally || obc->open_u_BCs_exist_globally)) : 0;
+  a.obc_open = obc ? (d ? obc->open_v_BCs_exist_globally : obc->open_u_BCs_exist_globally) : 0;
+}
+
+// the arguments of the marching kernels for tracer group grp, but for the range and the v flags of the pass; returns the group's tracers
+int group_args(const AdvCall &c, int grp, int ngroups, AdvArgs &a) {
+  a.g = c.g; a.hprev = c.hprev; a.uhr = c.uhr; a.vhr = c.vhr;
+  a.domore_u = c.domore_u; a.domore_k = c.domore_k;
+  const int m0 = grp * MAXG;
+  const int n = (c.ntr - m0 < MAXG) ? c.ntr - m0 : MAXG;
+  a.any_cu = 0;
+  for (int m = 0; m < MAXG; m++) {
+    a.tr[m] = (m < n) ? c.d_tr[m0 + m] : nullptr;
+    a.cu[m] = (m < n && c.conc_underflow) ? c.conc_underflow[m0 + m] : 0.0;
+    if (a.cu[m] > 0.0) a.any_cu = 1;
+  }
+  a.write_mass = (grp == ngroups - 1);   // earlier groups must see the pre-pass hprev/uhr/vhr/flags
+  return n;
+}
+
+// advect_x (dir 0, :329) or advect_y (dir 1, :705) over the range given: the general kernels once, or the marching kernel once a group
+// of MAXG tracers.  advect_y reads domore_v and writes domore_v2 (cleared over its rows by adv_vflags_prep_kernel), and the two swap.
+int adv_pass(AdvCall &c, int dir, int is, int ie, int js, int je) {
+  const m6::GridDev &g = c.g; hipStream_t s = c.s; const int nz = c.nz, scheme = c.cs->scheme;
+  c.t_k->start();
+  if (dir) hipLaunchKernelGGL(adv_vflags_prep_kernel, dim3(64), dim3(256), 0, s, g, (const int *)c.domore_v, c.domore_v2,
+                              (const int *)c.domore_k, js, je);
+  int32_t &n_pass = dir ? c.tm.n_y : c.tm.n_x;
+  if (c.generic) {
+    GenArgs a; gen_args(c, dir, a);
+    a.is = is; a.ie = ie; a.js = js; a.je = je;
+    a.dom_in = dir ? c.domore_v : c.domore_u; a.dom_new = dir ? c.domore_v2 : c.gen_flags;
+    if (!dir) M6_HIP(hipMemsetAsync(c.gen_flags, 0, c.nfu * sizeof(int), s));
+    // a thread a face: x has ie - is + 2 faces a row, y je - js + 2 rows of faces
+    const dim3 grid = dir ? dim3((ie - is + 1 + 255) / 256, je - js + 2, nz) : dim3((ie - is + 2 + 255) / 256, je - js + 1, nz);
+    with_group(1, scheme, [&](auto, auto sc) {      // (the general kernels take every tracer: only the scheme is a constant)
+      constexpr int SCHEME = decltype(sc)::value;
+      if (dir) hipLaunchKernelGGL((gen_flux_kernel<1, SCHEME>), grid, dim3(256), 0, s, a);
+      else     hipLaunchKernelGGL((gen_flux_kernel<0, SCHEME>), grid, dim3(256), 0, s, a);
+    });
+    if (dir) hipLaunchKernelGGL(gen_update_kernel<1>, grid, dim3(256), 0, s, a);
+    else     hipLaunchKernelGGL(gen_update_kernel<0>, grid, dim3(256), 0, s, a);
+    if (!dir) hipLaunchKernelGGL(gen_xflags_kernel, dim3(64), dim3(256), 0, s, g, c.domore_u, (const int *)c.gen_flags, (const int *)c.domore_k, js, je);
     M6_HIP(hipGetLastError());
-  }
-  tm.ms_setup += t_k.stop();
-
-  int itt = 1;
-  const int ngroups = (ntr + MAXG - 1) / MAXG;
-  auto group_args = [&](int grp, AdvArgs &a) -> int {
-    a.g = g; a.hprev = hprev; a.uhr = uhr; a.vhr = vhr;
-    a.domore_u = domore_u; a.domore_k = domore_k;
-    const int m0 = grp * MAXG;
-    const int n = (ntr - m0 < MAXG) ? ntr - m0 : MAXG;
-    a.any_cu = 0;
-    for (int m = 0; m < MAXG; m++) {
-      a.tr[m] = (m < n) ? d_tr[m0 + m] : nullptr;
-      a.cu[m] = (m < n && conc_underflow) ? conc_underflow[m0 + m] : 0.0;
-      if (a.cu[m] > 0.0) a.any_cu = 1;
-    }
-    a.write_mass = (grp == ngroups - 1);   // earlier groups must see the pre-pass hprev/uhr/vhr/flags
-    return n;
-  };
-  auto run_x = [&](int xis, int xie, int xjs, int xje) -> int {
-    t_k.start();
-    if (generic) {
-      GenArgs a; gen_args(0, a);
-      a.is = xis; a.ie = xie; a.js = xjs; a.je = xje; a.dom_in = domore_u; a.dom_new = gen_flags;
-      M6_HIP(hipMemsetAsync(gen_flags, 0, nfu * sizeof(int), s));
-      const dim3 grid((xie - xis + 2 + 255) / 256, xje - xjs + 1, nz);
-      if (cs->scheme == PLM) hipLaunchKernelGGL((gen_flux_kernel<0, PLM>), grid, dim3(256), 0, s, a);
-      else if (cs->scheme == H3) hipLaunchKernelGGL((gen_flux_kernel<0, H3>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gen_flux_kernel<0, CW>), grid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL(gen_update_kernel<0>, grid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL(gen_xflags_kernel, dim3(64), dim3(256), 0, s, g, domore_u, (const int *)gen_flags, (const int *)domore_k, xjs, xje);
-      M6_HIP(hipGetLastError());
-      tm.n_x++;
-      { const double ms = t_k.stop(); tm.ms_x += ms; if (itt == 1) tm.ms_x1 += ms; }
-      return 0;
-    }
-    for (int grp = 0; grp < ngroups; grp++) {
-      AdvArgs a; const int n = group_args(grp, a);
-      a.is = xis; a.ie = xie; a.js = xjs; a.je = xje;
-      a.domore_v_in = domore_v; a.domore_v_out = domore_v;
-      dim3 grid((xje - xjs + 1 + 3) / 4, nz);
-      switch (n) {
-        case 1: launch_x<1>(cs->scheme, itt == 1, grid, s, a); break;
-        case 2: launch_x<2>(cs->scheme, itt == 1, grid, s, a); break;
-        case 3: launch_x<3>(cs->scheme, itt == 1, grid, s, a); break;
-        default: launch_x<4>(cs->scheme, itt == 1, grid, s, a); break;
-      }
-      M6_HIP(hipGetLastError());
-      tm.n_x++;
-    }
-    { const double ms = t_k.stop(); tm.ms_x += ms; if (itt == 1) tm.ms_x1 += ms; }
-    return 0;
-  };
-  auto run_y = [&](int yis, int yie, int yjs, int yje) -> int {
-    t_k.start();
-    hipLaunchKernelGGL(adv_vflags_prep_kernel, dim3(64), dim3(256), 0, s, g, (const int *)domore_v, domore_v2,
-                       (const int *)domore_k, yjs, yje);
-    if (generic) {
-      GenArgs a; gen_args(1, a);
-      a.is = yis; a.ie = yie; a.js = yjs; a.je = yje; a.dom_in = domore_v; a.dom_new = domore_v2;
-      const dim3 grid((yie - yis + 1 + 255) / 256, yje - yjs + 2, nz);
-      if (cs->scheme == PLM) hipLaunchKernelGGL((gen_flux_kernel<1, PLM>), grid, dim3(256), 0, s, a);
-      else if (cs->scheme == H3) hipLaunchKernelGGL((gen_flux_kernel<1, H3>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gen_flux_kernel<1, CW>), grid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL(gen_update_kernel<1>, grid, dim3(256), 0, s, a);
-      M6_HIP(hipGetLastError());
-      tm.n_y++;
-      { int *t = domore_v; domore_v = domore_v2; domore_v2 = t; }
-      { const double ms = t_k.stop(); tm.ms_y += ms; if (itt == 1) tm.ms_y1 += ms; }
-      return 0;
-    }
-    for (int grp = 0; grp < ngroups; grp++) {
-      AdvArgs a; const int n = group_args(grp, a);
-      a.is = yis; a.ie = yie; a.js = yjs; a.je = yje;
-      a.domore_v_in = domore_v; a.domore_v_out = domore_v2;
-      dim3 grid((yie - yis + 1 + 63) / 64, nz);
-      // segments of at least 8 faces, at most YSEG_MAX waves per column strip
-      const int nfaces = yje - yjs + 2;
-      int nseg_max = 4;   // measured best on MI355X (8: one block per CU; 1-2: too few waves)
-      if (const char *e = getenv("MOM6HIP_YSEG")) { int v = atoi(e); if (v >= 1 && v <= YSEG_MAX) nseg_max = v; }
-      int nseg = nfaces / 8; if (nseg < 1) nseg = 1; if (nseg > nseg_max) nseg = nseg_max;
-      const int seglen = (nfaces + nseg - 1) / nseg;
-      switch (n) {
-        case 1: launch_y<1>(cs->scheme, itt == 1, grid, nseg, seglen, s, a); break;
-        case 2: launch_y<2>(cs->scheme, itt == 1, grid, nseg, seglen, s, a); break;
-        case 3: launch_y<3>(cs->scheme, itt == 1, grid, nseg, seglen, s, a); break;
-        default: launch_y<4>(cs->scheme, itt == 1, grid, nseg, seglen, s, a); break;
-      }
-      M6_HIP(hipGetLastError());
-      tm.n_y++;
-    }
-    { int *t = domore_v; domore_v = domore_v2; domore_v2 = t; }
-    { const double ms = t_k.stop(); tm.ms_y += ms; if (itt == 1) tm.ms_y1 += ms; }
-    return 0;
-  };
-
-  int isv = is, iev = ie, jsv = js, jev = je;
-  int halo_updates = 0, remaining = nz;
-  for (itt = 1; itt <= max_iter; itt++) {
-    if (isv > is - stencil) {
-      // do_group_pass(CS%pass_uhr_vhr_t_hprev), :206
-      t_k.start();
-      {      // (one tile: the local wrap kernels; several: the native exchange or the host's group pass)
-        std::vector<double *> flds = {uhr, vhr, hprev};
-        std::vector<int32_t> pos = {MOM6HIP_POS_U, MOM6HIP_POS_V, MOM6HIP_POS_H}, nks = {nz, nz, nz};
-        for (int m = 0; m < ntr; m++) { flds.push_back(d_tr[m]); pos.push_back(MOM6HIP_POS_H); nks.push_back(nz); }
-        if (int rc = m6::group_pass(ctx, flds.data(), pos.data(), nks.data(), (int)flds.size())) return rc;
-      }
-      halo_updates++;
-      tm.ms_halo += t_k.stop();
-
-      int mh = is - g.isd;
-      if (g.ied - ie < mh) mh = g.ied - ie;
-      if (js - g.jsd < mh) mh = js - g.jsd;
-      if (g.jed - je < mh) mh = g.jed - je;
-      const int nsten_halo = mh / stencil;
-      isv = is - nsten_halo * stencil; jsv = js - nsten_halo * stencil;
-      iev = ie + nsten_halo * stencil; jev = je + nsten_halo * stencil;
-      if ((nsten_halo > 1) || (itt == 1)) {
-        t_k.start();
-        ScanArgs sa;
-        sa.g = g; sa.uhr = uhr; sa.vhr = vhr; sa.domore_u = domore_u; sa.domore_v = domore_v; sa.domore_k = domore_k;
-        sa.ju0 = jsv; sa.ju1 = jev; sa.iu0 = isv + stencil - 1; sa.iu1 = iev - stencil;
-        sa.jv0 = jsv + stencil - 1; sa.jv1 = jev - stencil; sa.iv0 = isv + stencil; sa.iv1 = iev - stencil;
-        hipLaunchKernelGGL(adv_scan_kernel, dim3(g.njh + 1, nz), dim3(256), 0, s, sa);
-        hipLaunchKernelGGL(adv_domore_k_kernel, dim3(nz), dim3(64), 0, s, g, (const int *)domore_u,
-                           (const int *)domore_v, domore_k, jsv, jev, jsv + stencil - 1, jev - stencil);
-        M6_HIP(hipGetLastError());
-        tm.ms_setup += t_k.stop();
-      }
-    }
-
-    isv += stencil; iev -= stencil; jsv += stencil; jev -= stencil;
-
-    if (x_first) {
-      if (run_x(isv, iev, jsv - stencil, jev + stencil)) return 1;
-      if (run_y(isv, iev, jsv, jev)) return 1;
-      hipLaunchKernelGGL(adv_domore_k_kernel, dim3(nz), dim3(64), 0, s, g, (const int *)domore_u,
-                         (const int *)domore_v, domore_k, jsv - stencil, jev + stencil, jsv - 1, jev);
-    } else {
-      if (run_y(isv - stencil, iev + stencil, jsv, jev)) return 1;
-      if (run_x(isv, iev, jsv, jev)) return 1;
-      hipLaunchKernelGGL(adv_domore_k_kernel, dim3(nz), dim3(64), 0, s, g, (const int *)domore_u,
-                         (const int *)domore_v, domore_k, jsv, jev, jsv - 1, jev);
-    }
-    M6_HIP(hipGetLastError());
-
-    if (itt >= max_iter) break;
-    if (isv > is - stencil) {
-      // sum_across_PEs(domore_k), :305 -- the one host read-back per iteration
-      if (m6::multi_tile(ctx)) {
-        // domore_k becomes the global count and is what the next iteration tests (:215, :252): reduced where it lies (an all-reduce on the
-        // communication stream with the native domain), the host's copy read back behind it
-        if (int rc = m6::sum_across_PEs_dev(ctx, domore_k, nz, ctx->h_domore_k)) return rc;
-      } else {
-        M6_HIP(hipMemcpyAsync(ctx->h_domore_k, domore_k, nz * sizeof(int), hipMemcpyDeviceToHost, s));
-        M6_HIP(hipStreamSynchronize(s));
-      }
-      remaining = 0;
-      for (int k = 0; k < nz; k++) remaining += ctx->h_domore_k[k];
-      if (remaining == 0) break;
-    }
-  }
-  if (itt > max_iter) itt = max_iter;
-
-  // ---- outputs ----
-  if (memspace == MOM6HIP_MEM_HOST) {
-    for (int m = 0; m < ntr; m++) M6_HIP(hipMemcpyAsync(tr[m], d_tr[m], bH, hipMemcpyDeviceToHost, s));
-    if (uhr_out) M6_HIP(hipMemcpyAsync(uhr_out, uhr, bU, hipMemcpyDeviceToHost, s));
-    if (vhr_out) M6_HIP(hipMemcpyAsync(vhr_out, vhr, bV, hipMemcpyDeviceToHost, s));
-    if (vol_prev && update_vol_prev) M6_HIP(hipMemcpyAsync(vol_prev, hprev, bH, hipMemcpyDeviceToHost, s));
+    n_pass++;
   } else {
-    if (uhr_out) M6_HIP(hipMemcpyAsync(uhr_out, uhr, bU, hipMemcpyDeviceToDevice, s));
-    if (vhr_out) M6_HIP(hipMemcpyAsync(vhr_out, vhr, bV, hipMemcpyDeviceToDevice, s));
-    if (vol_prev && update_vol_prev) M6_HIP(hipMemcpyAsync(vol_prev, hprev, bH, hipMemcpyDeviceToDevice, s));
+    dim3 grid((je - js + 1 + 3) / 4, nz), block(256);      // x: a wave a row, four rows a block
+    int seglen = 0;
+    if (dir) {      // y: a block a strip of 64 columns, its faces js-1 .. je cut into segments of at least 8, one a wave, at most YSEG
+      const int nfaces = je - js + 2;
+      int nseg = nfaces / 8; if (nseg < 1) nseg = 1; if (nseg > YSEG) nseg = YSEG;
+      seglen = (nfaces + nseg - 1) / nseg;
+      grid = dim3((ie - is + 1 + 63) / 64, nz); block = dim3(64 * nseg);
+    }
+    const int ngroups = (c.ntr + MAXG - 1) / MAXG;
+    for (int grp = 0; grp < ngroups; grp++) {
+      AdvArgs a; const int n = group_args(c, grp, ngroups, a);
+      a.is = is; a.ie = ie; a.js = js; a.je = je;
+      a.domore_v_in = c.domore_v; a.domore_v_out = dir ? c.domore_v2 : c.domore_v;
+      with_group(n, scheme, [&](auto nt, auto sc) {
+        constexpr int NT = decltype(nt)::value, SCHEME = decltype(sc)::value;
+        if (dir) hipLaunchKernelGGL((adv_y_kernel<NT, SCHEME>), grid, block, 0, s, a, seglen);
+        else     hipLaunchKernelGGL((adv_x_kernel<NT, SCHEME>), grid, block, 0, s, a);
+      });
+      M6_HIP(hipGetLastError());
+      n_pass++;
+    }
   }
-  if (stats || memspace == MOM6HIP_MEM_HOST) {
-    M6_HIP(hipMemcpyAsync(ctx->h_domore_k, domore_k, nz * sizeof(int), hipMemcpyDeviceToHost, s));
-    M6_HIP(hipStreamSynchronize(s));
-    remaining = 0;
-    for (int k = 0; k < nz; k++) remaining += ctx->h_domore_k[k];
+  if (dir) std::swap(c.domore_v, c.domore_v2);
+  const double ms = c.t_k->stop();
+  (dir ? c.tm.ms_y : c.tm.ms_x) += ms;
+  if (c.itt == 1) (dir ? c.tm.ms_y1 : c.tm.ms_x1) += ms;
+  return 0;
+}
+
+// do_group_pass(CS%pass_uhr_vhr_t_hprev) :206, the range that is valid after it, and domore_u / domore_v / domore_k again :215-231
+int adv_group_pass(AdvCall &c) {
+  const m6::GridDev &g = c.g; const int is = c.is, ie = c.ie, js = c.js, je = c.je, nz = c.nz, stencil = c.stencil;
+  c.t_k->start();
+  {      // (one tile: the local wrap kernels; several: the native exchange or the host's group pass)
+    std::vector<double *> flds = {c.uhr, c.vhr, c.hprev};
+    std::vector<int32_t> pos = {MOM6HIP_POS_U, MOM6HIP_POS_V, MOM6HIP_POS_H}, nks = {nz, nz, nz};
+    for (int m = 0; m < c.ntr; m++) { flds.push_back(c.d_tr[m]); pos.push_back(MOM6HIP_POS_H); nks.push_back(nz); }
+    if (int rc = m6::group_pass(c.ctx, flds.data(), pos.data(), nks.data(), (int)flds.size())) return rc;
   }
-  if (stats) { stats->iterations = itt; stats->halo_updates = halo_updates; stats->domore_remaining = remaining; }
-  if (ctx->timing) { tm.ms_total = t_all.stop(); ctx->adv_timing = tm; }
+  c.halo_updates++;
+  c.tm.ms_halo += c.t_k->stop();
+
+  const int nsten_halo = std::min({is - g.isd, g.ied - ie, js - g.jsd, g.jed - je}) / stencil;
+  c.isv = is - nsten_halo * stencil; c.jsv = js - nsten_halo * stencil;
+  c.iev = ie + nsten_halo * stencil; c.jev = je + nsten_halo * stencil;
+  if ((nsten_halo > 1) || (c.itt == 1)) {
+    const int isv = c.isv, iev = c.iev, jsv = c.jsv, jev = c.jev;
+    c.t_k->start();
+    ScanArgs sa;
+    sa.g = g; sa.uhr = c.uhr; sa.vhr = c.vhr; sa.domore_u = c.domore_u; sa.domore_v = c.domore_v; sa.domore_k = c.domore_k;
+    sa.ju0 = jsv; sa.ju1 = jev; sa.iu0 = isv + stencil - 1; sa.iu1 = iev - stencil;
+    sa.jv0 = jsv + stencil - 1; sa.jv1 = jev - stencil; sa.iv0 = isv + stencil; sa.iv1 = iev - stencil;
+    hipLaunchKernelGGL(adv_scan_kernel, dim3(g.njh + 1, nz), dim3(256), 0, c.s, sa);
+    hipLaunchKernelGGL(adv_domore_k_kernel, dim3(nz), dim3(64), 0, c.s, g, (const int *)c.domore_u,
+                       (const int *)c.domore_v, c.domore_k, jsv, jev, jsv + stencil - 1, jev - stencil);
+    M6_HIP(hipGetLastError());
+    c.tm.ms_setup += c.t_k->stop();
+  }
+  return 0;
+}
+
+// one iteration's two passes on the range a stencil narrower, and domore_k of the rows they worked on (:233-289)
+int adv_sweep(AdvCall &c) {
+  const int stencil = c.stencil;
+  c.isv += stencil; c.iev -= stencil; c.jsv += stencil; c.jev -= stencil;
+  const int isv = c.isv, iev = c.iev, jsv = c.jsv, jev = c.jev;
+  int ju0 = jsv, ju1 = jev;      // the rows of advect_x
+  if (c.x_first) {
+    ju0 = jsv - stencil; ju1 = jev + stencil;
+    if (int rc = adv_pass(c, 0, isv, iev, ju0, ju1)) return rc;
+    if (int rc = adv_pass(c, 1, isv, iev, jsv, jev)) return rc;
+  } else {
+    if (int rc = adv_pass(c, 1, isv - stencil, iev + stencil, jsv, jev)) return rc;
+    if (int rc = adv_pass(c, 0, isv, iev, jsv, jev)) return rc;
+  }
+  hipLaunchKernelGGL(adv_domore_k_kernel, dim3(c.nz), dim3(64), 0, c.s, c.g, (const int *)c.domore_u, (const int *)c.domore_v,
+                     c.domore_k, ju0, ju1, jsv - 1, jev);
+  M6_HIP(hipGetLastError());
+  return 0;
+}
+
+// c.remaining = sum(domore_k); across_PEs: sum_across_PEs(domore_k) first, :305 -- the one host read-back per iteration
+int adv_count_remaining(AdvCall &c, bool across_PEs) {
+  mom6hip_ctx_t *ctx = c.ctx; const int nz = c.nz;
+  if (across_PEs && m6::multi_tile(ctx)) {
+    // domore_k becomes the global count and is what the next iteration tests (:215, :252): reduced where it lies (an all-reduce on the
+    // communication stream with the native domain), the host's copy read back behind it
+    if (int rc = m6::sum_across_PEs_dev(ctx, c.domore_k, nz, ctx->h_domore_k)) return rc;
+  } else {
+    M6_HIP(hipMemcpyAsync(ctx->h_domore_k, c.domore_k, nz * sizeof(int), hipMemcpyDeviceToHost, c.s));
+    M6_HIP(hipStreamSynchronize(c.s));
+  }
+  c.remaining = 0;
+  for (int k = 0; k < nz; k++) c.remaining += ctx->h_domore_k[k];
+  return 0;
+}
+
+// the tracers, uhr, vhr and vol_prev back to the caller; the statistics
+int adv_outputs(AdvCall &c, mom6hip_advect_stats_t *stats) {
+  hipStream_t s = c.s;
+  const hipMemcpyKind kind = (c.memspace == MOM6HIP_MEM_HOST) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  if (c.memspace == MOM6HIP_MEM_HOST)
+    for (int m = 0; m < c.ntr; m++) M6_HIP(hipMemcpyAsync(c.tr[m], c.d_tr[m], c.bH, kind, s));
+  if (c.uhr_out) M6_HIP(hipMemcpyAsync(c.uhr_out, c.uhr, c.bU, kind, s));
+  if (c.vhr_out) M6_HIP(hipMemcpyAsync(c.vhr_out, c.vhr, c.bV, kind, s));
+  if (c.vol_prev && c.update_vol_prev) M6_HIP(hipMemcpyAsync(c.vol_prev, c.hprev, c.bH, kind, s));
+  if (stats || c.memspace == MOM6HIP_MEM_HOST)      // (the copies are complete behind it)
+    if (int rc = adv_count_remaining(c, false)) return rc;
+  if (stats) { stats->iterations = c.itt; stats->halo_updates = c.halo_updates; stats->domore_remaining = c.remaining; }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int mom6hip_advect_get_timing(mom6hip_ctx_t *ctx, mom6hip_advect_timing_t *t) {
+  M6_REQUIRE(ctx && t, "mom6hip_advect_get_timing: null argument");
+  *t = ctx->adv_timing;
+  return 0;
+}
+
+extern "C" int mom6hip_advect_tracer(mom6hip_ctx_t *ctx, const double *h_end, const double *uhtr, const double *vhtr, double dt,
+                                     const mom6hip_tracer_advect_cs_t *cs, double *const *tr, const double *conc_underflow, int32_t ntr,
+                                     int32_t x_first_in, double *vol_prev, int32_t max_iter_in, int32_t update_vol_prev, double *uhr_out,
+                                     double *vhr_out, int32_t memspace, mom6hip_advect_stats_t *stats) {
+  return mom6hip_advect_tracer_obc(ctx, h_end, uhtr, vhtr, dt, cs, tr, conc_underflow, ntr, x_first_in, vol_prev, max_iter_in, update_vol_prev,
+                                   uhr_out, vhr_out, nullptr, memspace, stats);
+}
+
+// advect_tracer with OBC associated: of the OBC, advect_x / advect_y read the tracer registries of the segments (segment%tr_Reg); without
+// any the marching kernels run as for a closed domain, with one the general kernels (gen_flux_kernel, gen_update_kernel)
+extern "C" int mom6hip_advect_tracer_obc(mom6hip_ctx_t *ctx, const double *h_end, const double *uhtr, const double *vhtr, double dt,
+                                         const mom6hip_tracer_advect_cs_t *cs, double *const *tr, const double *conc_underflow, int32_t ntr,
+                                         int32_t x_first_in, double *vol_prev, int32_t max_iter_in, int32_t update_vol_prev, double *uhr_out,
+                                         double *vhr_out, const mom6hip_obc_t *obc, int32_t memspace, mom6hip_advect_stats_t *stats) {
+  M6_REQUIRE(ctx != nullptr, "advect_tracer: null context (tracer_advect_init must be called before advect_tracer)");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  M6_REQUIRE(ntr >= 0, "advect_tracer: ntr < 0");
+  if (ntr == 0) return 0;   // :124
+  AdvCall c{};      // (every scalar and pointer zero until its phase sets it)
+  c.ctx = ctx; c.cs = cs; c.obc = obc; c.s = ctx->stream; c.g = ctx->g;
+  c.h_end = h_end; c.uhtr = uhtr; c.vhtr = vhtr; c.conc_underflow = conc_underflow; c.tr = tr; c.vol_prev = vol_prev;
+  c.uhr_out = uhr_out; c.vhr_out = vhr_out; c.ntr = ntr; c.memspace = memspace; c.update_vol_prev = update_vol_prev;
+  int rc = 0;
+  if ((rc = adv_check(c, dt, x_first_in, max_iter_in))) return rc;
+
+  Timer t_all(ctx->timing, c.s), t_k(ctx->timing, c.s);
+  c.t_k = &t_k;
+  t_all.start();
+  if ((rc = adv_stage_in(c))) return rc;
+  if ((rc = adv_work_space(c))) return rc;
+  if ((rc = adv_registries(c))) return rc;
+  if ((rc = adv_setup(c))) return rc;                        // :152-178
+
+  c.isv = c.is; c.iev = c.ie; c.jsv = c.js; c.jev = c.je;
+  c.remaining = c.nz;
+  for (c.itt = 1; c.itt <= c.max_iter; c.itt++) {            // :203
+    const bool narrow = c.isv > c.is - c.stencil;            // the halo that is valid is used up
+    if (narrow && (rc = adv_group_pass(c))) return rc;       // :206-231
+    if ((rc = adv_sweep(c))) return rc;                      // :233-289
+    if (c.itt >= c.max_iter) break;
+    if (c.isv > c.is - c.stencil) {                          // :303-307
+      if ((rc = adv_count_remaining(c, true))) return rc;
+      if (c.remaining == 0) break;
+    }
+  }
+  if (c.itt > c.max_iter) c.itt = c.max_iter;
+
+  if ((rc = adv_outputs(c, stats))) return rc;
+  if (ctx->timing) { c.tm.ms_total = t_all.stop(); ctx->adv_timing = c.tm; }
   return 0;
 }

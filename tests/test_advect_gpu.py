@@ -91,6 +91,45 @@ def test_parity_limiter_iterations(oracle, scheme, x_first):
     assert_same(g, ref1, out1, f"{scheme} limiter max_iter=1")
 
 
+def y_limited_case():
+    """70 x 33 x 2: two 64-column strips in advect_y, and the 34 faces J = jsc-1 .. jec make four wave segments of 9 (faces 0-8, 9-17,
+    18-26, 27-33 counted from jsc-1).  vhtr is raised to three times the volume of the cell south of the face at faces 8, 9, 10, 17,
+    18, 26 and 27 -- both sides of every segment boundary -- in the first column of each strip that has a wet face and a cell of real
+    thickness there, so a y-first sweep has to postpone transport (the limiter of :872-899) and flag the row for a later iteration."""
+    g, case = advect_case(ni=70, nj=33, nk=2, ntr=2, cfl=0.1)
+    h = g.halo
+    picked = []
+    for k, r in [(0, 8), (0, 9), (0, 10), (1, 17), (1, 18), (0, 26), (0, 27)]:
+        for strip in (range(0, 64), range(64, 70)):
+            for ii in strip:
+                thick = case["vol0"][k, h + r - 1, h + ii] > 1.0e-3 * g.areaT[h + r - 1, h + ii]
+                if thick and g.mask2dCv[h + r, h + ii] > 0.0:
+                    case["vhtr"][k, h + r, h + ii] = 3.0 * case["vol0"][k, h + r - 1, h + ii]
+                    picked.append((k, r, ii))
+                    break
+    return g, case, picked
+
+
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_parity_limiter_iterations_y(oracle, scheme):
+    # test_parity_limiter_iterations postpones transport in its x-first sweep only: here advect_y does, in the first pass of a y-first
+    # sweep (the dv_out[J] = 1 store) and in the sparse later iterations across the wave segments
+    g, case, picked = y_limited_case()
+    assert len(picked) >= 10, picked
+    ref = run_oracle(oracle, g, case, scheme, x_first=False)
+    ref1 = run_oracle(oracle, g, case, scheme, x_first=False, max_iter=1)
+    assert ref["stats"].iterations >= 2
+    assert ref1["stats"].domore_remaining > 0
+    for r in (ref, ref1):
+        assert all(np.isfinite(a).all() for a in r["tr"] + [r["uhr"], r["vhr"], r["vol"]])
+    out = run_hip(g, case, scheme, x_first=False)
+    print(f"{scheme}: picked={picked} oracle iterations={ref['stats'].iterations} halo_updates={ref['stats'].halo_updates} "
+          f"domore_remaining={ref['stats'].domore_remaining} (max_iter=1: {ref1['stats'].domore_remaining})")
+    assert_same(g, ref, out, f"{scheme} y limiter")
+    out1 = run_hip(g, case, scheme, x_first=False, max_iter=1)
+    assert_same(g, ref1, out1, f"{scheme} y limiter max_iter=1")
+
+
 @pytest.mark.parametrize("scheme", SCHEMES)
 def test_parity_tall_grid_many_segments(oracle, scheme):
     # 130 rows: advect_y splits the march over several waves per column strip (segment hand-over rows
