@@ -5,7 +5,9 @@ rotation).  New axes: x' = y, y' = -x, so on arrays indexed [j, i]
     rot(A) = A.T[::-1, :]          R[j', i'] = A[j = i', i = n_i - 1 - j']
 
 maps h -> h, q -> q, u-point arrays onto v'-point arrays and v-point arrays onto u'-point arrays; a vector (u, v) becomes
-u' = rot(v), v' = -rot(u); dx and dy metrics swap."""
+u' = rot(v), v' = -rot(u); dx and dy metrics swap.  A pair of face scalars (a_u, a_v) -- a diffusivity, a thickness, a length scale
+held at the u and at the v points -- swaps points the same way but keeps its sign: a_u' = rot(a_v), a_v' = rot(a_u) (the reference's
+rotate_array_pair)."""
 import numpy as np
 
 from mom6_amd import _abi
@@ -30,6 +32,16 @@ def unrot(a):
 def unrot_vector(up, vp):
     """(u, v) of the original frame from (u', v')"""
     return np.ascontiguousarray(-unrot(vp)), unrot(up)
+
+
+def rot_face(au, av):
+    """(a_u', a_v') of the turned frame, of two scalars held at the faces (no sign: L2u / L2v, Kv_bbl_u / Kv_bbl_v, ...)"""
+    return rot(av), rot(au)
+
+
+def unrot_face(aup, avp):
+    """(a_u, a_v) of the original frame from (a_u', a_v')"""
+    return unrot(avp), unrot(aup)
 
 
 _SWAP = {"dx": "dy", "dy": "dx", "Idx": "Idy", "Idy": "Idx"}
