@@ -9,215 +9,23 @@
 //   ale_sub_cells_kernel + ale_remap_wave_kernel   every scheme (PCM, PLM, PPM_H4, PPM_IH4, PPM_CW, PQM_IH4IH3, PQM_IH6IH5 and the
 //                                 three HYBGEN ones), with or without extrapolation: the sub-cell structure per column, then one
 //                                 WAVE per column with the column's arrays in LDS.
-// The per-cell pieces of the reconstructions (edge weights, bounds, limiters, the tridiagonal solver) are scalar functions that both
-// forms call; the wave path has one function per stage of a scheme and w_build_reconstructions chooses among them.
+// The per-cell pieces of the reconstructions (edge weights, bounds, limiters, the tridiagonal solver, the boundary extrapolations, the
+// PPM average) live in remap_pieces.hpp, which hor_bnd_diffusion.hip and pressure_force.hip share: scalar functions that both forms
+// call, here with fmin / fmax.  The wave path has one function per stage of a scheme and w_build_reconstructions chooses among them.
+// Five pieces of the wave path stay written out in their stage functions (the implicit-h4 row, the h4cw slope and edge, the cell of
+// PPM_monotonicity, the PCM / PLM branches of the average): calling the header's text for any of them changes ale_remap_wave_kernel's
+// instructions (profiles/remap_pieces.txt, section 3); the header's implicit_h4_row, h4cw_slope, h4cw_edge, ppm_monotonicity_cell and
+// average_value_ppoly are the same arithmetic for hor_bnd_diffusion.hip, and a fix to one goes to both.
 // Algorithmic traffic: read h_old, h_new once per launch + read/write each field = (16 / NF + 16) B per cell and field.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 
 #include "common.hpp"
+#define REMAP_PIECES_SELECT 0      // fmin / fmax: one v_min_f64 / v_max_f64 each (remap_pieces.hpp says why there are two flavours)
+#include "remap_pieces.hpp"
 
 namespace {
-
-constexpr int REMAP_PCM = 0, REMAP_PLM = 2, REMAP_PLM_HYBGEN = 3, REMAP_PPM_H4 = 4, REMAP_PPM_IH4 = 5, REMAP_PPM_HYBGEN = 6,
-              REMAP_WENO_HYBGEN = 7, REMAP_PQM_IH4IH3 = 8, REMAP_PQM_IH6IH5 = 9, REMAP_PPM_CW = 10;   // MOM_remapping.F90:50-59
-constexpr int INT_PCM = 0, INT_PLM = 1, INT_PPM = 3, INT_PQM = 5;   // :61-64
-
-__device__ __forceinline__ double max3(double a, double b, double c) { return fmax(fmax(a, b), c); }
-__device__ __forceinline__ double min3(double a, double b, double c) { return fmin(fmin(a, b), c); }
-__device__ __forceinline__ double fsign(double a, double b) { return copysign(fabs(a), b); }
-
-// ---- PLM_functions.F90 ----------------------------------------------------------------------------
-// PLM_slope_wa :22-65
-__device__ double plm_slope_wa(double h_l, double h_c, double h_r, double h_neglect, double u_l, double u_c, double u_r) {
-  const double sigma_r = u_r - u_c;
-  const double sigma_l = u_c - u_l;
-  const double sigma_c = 2.0 * (u_r - u_l) * (h_c / (h_l + 2.0 * h_c + h_r + h_neglect));
-  const double u_min = min3(u_l, u_c, u_r);
-  const double u_max = max3(u_l, u_c, u_r);
-  double slope = 0.0;
-  if ((sigma_l * sigma_r) > 0.0) slope = fsign(fmin(fabs(sigma_c), 2. * fmin(u_c - u_min, u_max - u_c)), sigma_c);
-  if (u_c - 0.5 * fabs(slope) < u_min || u_c + 0.5 * fabs(slope) > u_max) slope = slope * (1. - DBL_EPSILON);
-  if (fabs(slope) < 1.E-140) slope = 0.;
-  return slope;
-}
-
-// PLM_monotonized_slope :124-159
-__device__ double plm_monotonized_slope(double u_l, double u_c, double u_r, double s_l, double s_c, double s_r) {
-  const double almost_two = 2. * (1. - DBL_EPSILON);
-  const double e_r = u_l + 0.5 * s_l;
-  const double e_l = u_r - 0.5 * s_r;
-  double slp = fabs(s_c);
-  double edge = u_c - 0.5 * s_c;
-  if ((edge - e_r) * (u_c - edge) < 0.) {
-    edge = 0.5 * (edge + e_r);
-    slp = fmin(slp, fabs(edge - u_c) * almost_two);
-  }
-  edge = u_c + 0.5 * s_c;
-  if ((edge - u_c) * (e_l - edge) < 0.) {
-    edge = 0.5 * (edge + e_l);
-    slp = fmin(slp, fabs(edge - u_c) * almost_two);
-  }
-  return fsign(slp, s_c);
-}
-
-// PLM_extrapolate_slope :164-183
-__device__ double plm_extrapolate_slope(double h_l, double h_c, double h_neglect, double u_l, double u_c) {
-  const double hl = h_l + h_neglect;
-  const double hc = h_c + h_neglect;
-  const double left_edge = (u_l * hc + u_c * hl) / (hl + hc);
-  return 2.0 * (u_c - left_edge);
-}
-
-// ---- regrid_edge_values.F90 -----------------------------------------------------------------------
-// end_value_h4 :658-771
-__device__ void end_value_h4(const double dz[4], const double u[4], double Csys[4]) {
-  const double min_frac = 1.0e-6;
-  double h1 = dz[0], h2 = dz[1], h3 = dz[2], h4 = dz[3];
-  if ((h2 + h3) < min_frac * h1) h3 = min_frac * h1 - h2;
-  if ((h3 + h4) < min_frac * h1) h4 = min_frac * h1 - h3;
-  const double h12 = h1 + h2, h23 = h2 + h3, h34 = h3 + h4;
-  const double h123 = h12 + h3, h234 = h2 + h34, h1234 = h12 + h34;
-  const double I_denB3 = 1.0 / (h123 * h12 * h23);
-  const double I_h12 = (h123 * h23) * I_denB3;
-  const double I_h23 = (h12 * h123) * I_denB3;
-  const double I_h123 = (h12 * h23) * I_denB3;
-  const double I_denom = 1.0 / (h1234 * (h234 * h34));
-  const double I_h234 = (h1234 * h34) * I_denom;
-  const double I_h1234 = (h234 * h34) * I_denom;
-
-  const double W11 = -h1 * (I_h1234 + I_h123 + I_h12);
-  const double W21 = h1 * h12 * (I_h234 * I_h1234 + I_h23 * (I_h234 + I_h123));
-  const double W31 = -h1 * h12 * h123 * I_denom;
-  const double W12 = 2.0 * (I_h12 * (1.0 + (h1 + h12) * (I_h1234 + I_h123)) + h1 * I_h1234 * I_h123);
-  const double W22 = -2.0 * ((h1 * h12 * I_h1234) * (I_h23 * (I_h234 + I_h123)) +
-                             (h1 + h12) * (I_h1234 * I_h234 + I_h23 * (I_h234 + I_h123)));
-  const double W32 = 2.0 * ((h1 + h12) * h123 + h1 * h12) * I_denom;
-  const double W13 = -3.0 * I_h12 * I_h123 * (1.0 + I_h1234 * ((h1 + h12) + h123));
-  const double W23 = 3.0 * I_h23 * (I_h123 + I_h1234 * ((h1 + h12) + h123) * (I_h123 + I_h234));
-  const double W33 = -3.0 * ((h1 + h12) + h123) * I_denom;
-  const double W14 = 4.0 * I_h1234 * I_h123 * I_h12;
-  const double W24 = -4.0 * I_h1234 * (I_h23 * (I_h123 + I_h234));
-  const double W34 = 4.0 * I_denom;
-
-  Csys[0] = ((u[0] + W11 * (u[1] - u[0])) + W21 * (u[2] - u[1])) + W31 * (u[3] - u[2]);
-  Csys[1] = (W12 * (u[1] - u[0]) + W22 * (u[2] - u[1])) + W32 * (u[3] - u[2]);
-  Csys[2] = (W13 * (u[1] - u[0]) + W23 * (u[2] - u[1])) + W33 * (u[3] - u[2]);
-  Csys[3] = (W14 * (u[1] - u[0]) + W24 * (u[2] - u[1])) + W34 * (u[3] - u[2]);
-}
-
-struct EdgeW { double A1, A2, B, Cc, Hs; };
-// the thickness-only factors of edge_values_explicit_h4 (regrid_edge_values.F90:262-300) at the interface above cell i
-__device__ __forceinline__ EdgeW edge_weights_h4(double h0, double h1, double h2, double h3, double hNeglect) {
-  const double hMinFrac = 1.e-5;
-  if (h0 + h1 == 0.0 || h1 + h2 == 0.0 || h2 + h3 == 0.0) {
-    const double h_min = hMinFrac * fmax(hNeglect, (h0 + h1) + (h2 + h3));
-    h0 = fmax(h_min, h0); h1 = fmax(h_min, h1); h2 = fmax(h_min, h2); h3 = fmax(h_min, h3);
-  }
-  const double I_h12 = 1.0 / (h1 + h2);
-  const double I_den_et2 = 1.0 / (((h0 + h1) + h2) * (h0 + h1)); const double I_h012 = (h0 + h1) * I_den_et2;
-  const double I_den_et3 = 1.0 / ((h1 + (h2 + h3)) * (h2 + h3)); const double I_h123 = (h2 + h3) * I_den_et3;
-  EdgeW w;
-  w.A1 = (1.0 + (h1 * I_h012 + (h0 + h1) * I_h123)) * I_h12 * (h2 * (h2 + h3));
-  w.A2 = (1.0 + (h2 * I_h123 + (h2 + h3) * I_h012)) * I_h12 * (h1 * (h0 + h1));
-  w.B = (h1 * (h2 * (h2 + h3)) * I_den_et2);
-  w.Cc = (h2 * (h1 * (h0 + h1)) * I_den_et3);
-  w.Hs = (h0 + h1) + (h2 + h3);
-  return w;
-}
-__device__ __forceinline__ double edge_value_h4(const EdgeW &w, double um2, double um1, double u0, double up1) {
-  const double et1 = w.A1 * um1 + w.A2 * u0;
-  const double et2 = w.B * (um1 - um2);
-  const double et3 = w.Cc * (u0 - up1);
-  return (et1 + (et2 + et3)) / w.Hs;
-}
-// the slope of bound_edge_values (regrid_edge_values.F90:71-82) with hr = h(k) / ((h(km1) + h(kp1)) + 2 h(k)) or a negative hr for "no slope"
-__device__ __forceinline__ double bound_slope(double ukm1, double uk, double ukp1, double hr) {
-  double slope_x_h = 0.0;
-  if (hr >= 0.0) {
-    const double sigma_l = (uk - ukm1);
-    const double sigma_c = (ukp1 - ukm1) * hr;
-    const double sigma_r = (ukp1 - uk);
-    if ((sigma_l * sigma_r) > 0.0) slope_x_h = fsign(min3(fabs(sigma_l), fabs(sigma_c), fabs(sigma_r)), sigma_c);
-  }
-  return slope_x_h;
-}
-__device__ __forceinline__ double bound_left(double EL, double ukm1, double uk, double slope) {
-  if ((ukm1 - EL) * (EL - uk) < 0.0) EL = uk - fsign(fmin(fabs(slope), fabs(EL - uk)), slope);
-  return fmax(fmin(EL, fmax(ukm1, uk)), fmin(ukm1, uk));
-}
-__device__ __forceinline__ double bound_right(double ER, double ukp1, double uk, double slope) {
-  if ((ukp1 - ER) * (ER - uk) < 0.0) ER = uk + fsign(fmin(fabs(slope), fabs(ER - uk)), slope);
-  return fmax(fmin(ER, fmax(ukp1, uk)), fmin(ukp1, uk));
-}
-// check_discontinuous_edge_values :141-159 at the interface between cells k and k+1 (er the right edge of k, el_next the left edge of
-// k+1): the test, and the value both edges take when it holds
-__device__ __forceinline__ bool edges_discontinuous(double u_k, double u_kp1, double er, double el_next) {
-  return (el_next - er) * (u_kp1 - u_k) < 0.0;
-}
-__device__ __forceinline__ double bounded_edge_average(double u_k, double u_kp1, double er, double el_next) {
-  const double u0_avg = 0.5 * (er + el_next);
-  return fmax(fmin(u0_avg, fmax(u_k, u_kp1)), fmin(u_k, u_kp1));
-}
-
-// ---- regrid_solvers.F90 ---------------------------------------------------------------------------
-// solve_diag_dominant_tridiag :246-280 as a serial walk by one lane; the solution overwrites the right-hand side, c1 is work space
-__device__ void solve_diag_dominant_tridiag(const double *tri_l, const double *tri_c, const double *tri_u, double *tri_b, double *c1, int N) {
-  double I_pivot = 1.0 / (tri_c[0] + tri_u[0]);
-  double d1 = tri_c[0] * I_pivot;
-  c1[0] = tri_u[0] * I_pivot;
-  tri_b[0] = tri_b[0] * I_pivot;
-  for (int k = 1; k < N - 1; k++) {
-    const double denom_t1 = tri_c[k] + d1 * tri_l[k];
-    I_pivot = 1.0 / (denom_t1 + tri_u[k]);
-    d1 = denom_t1 * I_pivot;
-    c1[k] = tri_u[k] * I_pivot;
-    tri_b[k] = (tri_b[k] - tri_l[k] * tri_b[k - 1]) * I_pivot;
-  }
-  I_pivot = 1.0 / (tri_c[N - 1] + d1 * tri_l[N - 1]);
-  tri_b[N - 1] = (tri_b[N - 1] - tri_l[N - 1] * tri_b[N - 2]) * I_pivot;
-  for (int k = N - 2; k >= 0; k--) tri_b[k] = tri_b[k] - c1[k] * tri_b[k + 1];
-}
-
-// ---- PPM_functions.F90, MOM_remapping.F90 -----------------------------------------------------------
-// PPM_limiter_standard for an interior cell (PPM_functions.F90:84-121)
-__device__ __forceinline__ void ppm_limit_cell(double u_l, double u_c, double u_r, double &edge_l, double &edge_r) {
-  if ((u_r - u_c) * (u_c - u_l) <= 0.0) {
-    edge_l = u_c; edge_r = u_c;
-  } else {
-    const double expr1 = 3.0 * (edge_r - edge_l) * ((u_c - edge_l) + (u_c - edge_r));
-    const double expr2 = (edge_r - edge_l) * (edge_r - edge_l);
-    if (expr1 > expr2) {
-      edge_l = u_c + 2.0 * (u_c - edge_r);
-      edge_l = fmax(fmin(edge_l, fmax(u_l, u_c)), fmin(u_l, u_c));
-    } else if (expr1 < -expr2) {
-      edge_r = u_c + 2.0 * (u_c - edge_l);
-      edge_r = fmax(fmin(edge_r, fmax(u_r, u_c)), fmin(u_r, u_c));
-    }
-  }
-  if (fabs(edge_r - edge_l) < fmax(1.e-60, DBL_EPSILON * fabs(u_c))) { edge_l = u_c; edge_r = u_c; }
-}
-// average_value_ppoly for INT_PPM (MOM_remapping.F90:998-1099)
-__device__ __forceinline__ double average_ppm(double a_L, double a_R, double u_c, double xa, double xb) {
-  if (xb > xa) {
-    const double mx = 0.5 * (xa + xb);
-    const double a_c = 0.5 * ((u_c - a_L) + (u_c - a_R));
-    if (mx < 0.5) {
-      const double xa2b2ab = (xa * xa + xb * xb) + xa * xb;
-      return a_L + ((a_R - a_L) * mx + a_c * (3. * (xb + xa) - 2. * xa2b2ab));
-    } else {
-      const double Ya = 1. - xa, Yb = 1. - xb;
-      const double my = 0.5 * (Ya + Yb);
-      const double Ya2b2ab = (Ya * Ya + Yb * Yb) + Ya * Yb;
-      return a_R + ((a_L - a_R) * my + a_c * (3. * (Yb + Ya) - 2. * Ya2b2ab));
-    }
-  }
-  const double Ya = 1. - xa;
-  const double a_c = 3. * ((u_c - a_L) + (u_c - a_R));
-  if (xa < 0.5) return a_L + xa * ((a_R - a_L) + a_c * Ya);
-  return a_R + Ya * ((a_L - a_R) + a_c * xa);
-}
 
 // ---- ALE_regrid, z* (MOM_regridding.F90:763-889, :1174-1284; coord_zlike.F90:63-144) ------------------------------
 struct RegridArgs {
@@ -445,7 +253,7 @@ struct WCol {   // LDS arrays of one column (doubles first, then shorts); the fi
   double *SR;                              // PQM only (xd = nz doubles more a column): the right edge slopes; the left ones live in C1
   short *isrc_end, *isrc_max, *itgt_end;   // (+ last_thick at itgt_end[nz + 1])
 };
-__host__ __device__ inline int wcol_extra(int scheme, int nz) { return (scheme == REMAP_PQM_IH4IH3 || scheme == REMAP_PQM_IH6IH5) ? nz : 0; }
+__host__ __device__ inline int wcol_extra(int scheme, int nz) { return (scheme == MOM6HIP_REMAP_PQM_IH4IH3 || scheme == MOM6HIP_REMAP_PQM_IH6IH5) ? nz : 0; }
 __host__ __device__ inline size_t wcol_doubles(int nz, int xd) { return (size_t)sub_drows(nz) + 5 * nz + 2 * (2 * nz + 2) + xd; }
 __host__ __device__ inline size_t wcol_bytes(int nz, int xd) { return (wcol_doubles(nz, xd) * 8 + (size_t)sub_srows(nz) * 2 + 7) / 8 * 8; }
 __device__ inline WCol wcol_at(char *base, int nz, int xd) {
@@ -736,28 +544,6 @@ __device__ void w_take_interfaces(const double *X, double *left, double *right, 
   wsync();
 }
 
-// The cubic of end_value_h4 through the first (last = false) or the last four cells of the column, counted from the end, their widths
-// floored at hNeglect; returns the floored width of the end cell.  Lanes 62 and 63 call it in every h4 / h3 scheme: the two lanes that
-// have no second interior row to do, one code path for both ends
-__device__ double w_end_polynomial_h4(const WCol &c, bool last, int n, double hNeglect, double Cs[4]) {
-  double dz[4], ut[4];
-  for (int i = 0; i < 4; i++) { const int q = last ? n - 1 - i : i; dz[i] = fmax(hNeglect, c.h0[q]); ut[i] = c.u0[q]; }
-  end_value_h4(dz, ut, Cs);
-  return dz[0];
-}
-
-// PLM_boundary_extrapolation :272-307, by one lane
-__device__ void w_plm_boundary_extrapolation(const WCol &c, int n, double h_neglect) {
-  const double *h = c.h0, *u = c.u0;
-  double *EL = c.EL, *ER = c.ER;
-  double slope = -plm_extrapolate_slope(h[1], h[0], h_neglect, u[1], u[0]);
-  EL[0] = u[0] - 0.5 * slope; ER[0] = u[0] + 0.5 * slope;
-  c.C1[0] = ER[0] - EL[0];
-  slope = plm_extrapolate_slope(h[n - 2], h[n - 1], h_neglect, u[n - 2], u[n - 1]);
-  EL[n - 1] = u[n - 1] - 0.5 * slope; ER[n - 1] = u[n - 1] + 0.5 * slope;
-  c.C1[n - 1] = ER[n - 1] - EL[n - 1];
-}
-
 // PLM: PLM_reconstruction :190-260
 __device__ void w_plm(const WCol &c, int lane, int n, bool extrap, double h_neglect) {
   const double *h = c.h0, *u = c.u0;
@@ -786,7 +572,7 @@ __device__ void w_plm(const WCol &c, int lane, int n, bool extrap, double h_negl
     }
   }
   wsync();
-  if (extrap && lane == 0) w_plm_boundary_extrapolation(c, n, h_neglect);
+  if (extrap && lane == 0) plm_boundary_extrapolation(c.h0, c.u0, c.EL, c.ER, c.C1, n, h_neglect);
   wsync();
 }
 
@@ -808,7 +594,7 @@ __device__ void w_plm_hybgen(const WCol &c, int lane, int n, bool extrap, double
     c.ER[k] = u[k] + 0.5 * sl;
   }
   wsync();
-  if (extrap && lane == 0) w_plm_boundary_extrapolation(c, n, h_neglect);
+  if (extrap && lane == 0) plm_boundary_extrapolation(c.h0, c.u0, c.EL, c.ER, c.C1, n, h_neglect);
   wsync();
 }
 
@@ -876,7 +662,7 @@ __device__ void w_close_and_solve_h4(const WCol &c, int lane, int n, double hNeg
   if (lane >= 62) {
     const bool last = lane == 63;
     double Cs[4];
-    w_end_polynomial_h4(c, last, n, hNeglect, Cs);
+    end_polynomial_h4(c.h0, c.u0, last, n, hNeglect, Cs);
     const int row = last ? n : 0;
     tri_b[row] = slopes ? (last ? -Cs[1] : Cs[1]) : Cs[0];
     tri_c[row] = 1.0; tri_u[row] = 0.0; tri_l[row] = 0.0;
@@ -995,7 +781,7 @@ __device__ void w_edges_explicit_h4(const WCol &c, int lane, int n, double hNegl
   if (lane >= 62) {      // the end values: the first (lane 62) and the last (lane 63) two interfaces
     const bool last = lane == 63;
     double Cs[4];
-    const double dz0 = w_end_polynomial_h4(c, last, n, hNeglect, Cs);
+    const double dz0 = end_polynomial_h4(c.h0, c.u0, last, n, hNeglect, Cs);
     const double inner = Cs[0] + dz0 * (Cs[1] + dz0 * (Cs[2] + dz0 * Cs[3]));
     if (last) { ER[n - 1] = Cs[0]; EL[n - 1] = inner; ER[n - 2] = inner; }
     else { EL[0] = Cs[0]; ER[0] = inner; EL[1] = inner; }
@@ -1038,42 +824,6 @@ __device__ void w_ppm_limit(const WCol &c, int lane, int n) {
     c.C1[k] = 4.0 * (u[k] - edge_l) + 2.0 * (u[k] - edge_r);
   }
   wsync();
-}
-
-// PPM_boundary_extrapolation (PPM_functions.F90:162-316), by one lane
-__device__ void w_ppm_boundary_extrapolation(const WCol &c, int n, double h_neglect) {
-  const double *h = c.h0, *u = c.u0;
-  double *EL = c.EL, *ER = c.ER;
-  int i0 = 0, i1 = 1;
-  double h0 = h[i0], h1 = h[i1], u0 = u[i0], u1 = u[i1];
-  double b = c.C1[i1];
-  double u1_r = b * ((h0 + h_neglect) / (h1 + h_neglect));
-  double slope = 2.0 * (u1 - u0);
-  if (fabs(u1_r) > fabs(slope)) u1_r = slope;
-  double u0_r = EL[i1];
-  double u0_l = 3.0 * u0 + 0.5 * u1_r - 2.0 * u0_r;
-  double exp1 = (u0_r - u0_l) * (u0 - 0.5 * (u0_l + u0_r));
-  double exp2 = (u0_r - u0_l) * (u0_r - u0_l) / 6.0;
-  if (exp1 > exp2) u0_l = 3.0 * u0 - 2.0 * u0_r;
-  if (exp1 < -exp2) u0_r = 3.0 * u0 - 2.0 * u0_l;
-  EL[i0] = u0_l; ER[i0] = u0_r;
-  c.C1[i0] = 6.0 * u0 - 4.0 * u0_l - 2.0 * u0_r;
-  i0 = n - 2; i1 = n - 1;
-  h0 = h[i0]; h1 = h[i1]; u0 = u[i0]; u1 = u[i1];
-  b = c.C1[i0];
-  const double cc = 3.0 * ((ER[i0] - u[i0]) + (EL[i0] - u[i0]));      // ppoly_coef(i0,3)
-  double u1_l = (b + 2 * cc);
-  u1_l = u1_l * ((h1 + h_neglect) / (h0 + h_neglect));
-  slope = 2.0 * (u1 - u0);
-  if (fabs(u1_l) > fabs(slope)) u1_l = slope;
-  u0_l = ER[i0];
-  u0_r = 3.0 * u1 - 0.5 * u1_l - 2.0 * u0_l;
-  exp1 = (u0_r - u0_l) * (u1 - 0.5 * (u0_l + u0_r));
-  exp2 = (u0_r - u0_l) * (u0_r - u0_l) / 6.0;
-  if (exp1 > exp2) u0_l = 3.0 * u1 - 2.0 * u0_r;
-  if (exp1 < -exp2) u0_r = 3.0 * u1 - 2.0 * u0_l;
-  EL[i1] = u0_l; ER[i1] = u0_r;
-  c.C1[i1] = 6.0 * u1 - 4.0 * u0_l - 2.0 * u0_r;
 }
 
 // PQM_limiter (PQM_functions.F90:103-337): a cell reads its own edge values and slopes and its neighbours' means and widths
@@ -1165,30 +915,27 @@ __device__ void w_pqm_boundary_extrapolation(const WCol &c, bool bottom, int n, 
 
 // build_reconstructions_1d :257-386; returns the integration method (uniform over the wave)
 __device__ int w_build_reconstructions(const WCol &c, int lane, int scheme, bool extrap, int n, double h_neglect, double h_neglect_edge) {
-  int local = scheme;
-  if (n <= 1) local = REMAP_PCM;
-  else if (n <= 3) local = (local < REMAP_PLM) ? local : REMAP_PLM;
-  else if (n <= 4 && local != REMAP_PPM_CW) local = (local < REMAP_PPM_H4) ? local : REMAP_PPM_H4;      // :293
-  if (local == REMAP_PCM) {
+  const int local = remap_local_scheme(scheme, n);
+  if (local == MOM6HIP_REMAP_PCM) {
     for (int k = lane; k < n; k += 64) { c.EL[k] = c.u0[k]; c.ER[k] = c.u0[k]; c.C1[k] = 0.; }
     wsync();
     return INT_PCM;
   }
-  if (local == REMAP_PLM) { w_plm(c, lane, n, extrap, h_neglect); return INT_PLM; }
-  if (local == REMAP_PLM_HYBGEN) { w_plm_hybgen(c, lane, n, extrap, h_neglect); return INT_PLM; }
-  const bool pqm = local == REMAP_PQM_IH4IH3 || local == REMAP_PQM_IH6IH5;
+  if (local == MOM6HIP_REMAP_PLM) { w_plm(c, lane, n, extrap, h_neglect); return INT_PLM; }
+  if (local == MOM6HIP_REMAP_PLM_HYBGEN) { w_plm_hybgen(c, lane, n, extrap, h_neglect); return INT_PLM; }
+  const bool pqm = local == MOM6HIP_REMAP_PQM_IH4IH3 || local == MOM6HIP_REMAP_PQM_IH6IH5;
   // the edge values, and the edge slopes of the quartic schemes
-  if (local == REMAP_WENO_HYBGEN) w_edges_weno_hybgen(c, lane, n, h_neglect);
-  else if (local == REMAP_PPM_IH4 || local == REMAP_PQM_IH4IH3) w_edges_implicit_h4(c, lane, n, h_neglect_edge);
-  else if (local == REMAP_PQM_IH6IH5) {      // edge_values_implicit_h6
+  if (local == MOM6HIP_REMAP_WENO_HYBGEN) w_edges_weno_hybgen(c, lane, n, h_neglect);
+  else if (local == MOM6HIP_REMAP_PPM_IH4 || local == MOM6HIP_REMAP_PQM_IH4IH3) w_edges_implicit_h4(c, lane, n, h_neglect_edge);
+  else if (local == MOM6HIP_REMAP_PQM_IH6IH5) {      // edge_values_implicit_h6
     w_ih65_system<false>(c, lane, n, h_neglect_edge);
     w_take_interfaces(c.uh_sub, c.EL, c.ER, lane, n);
   }
-  else if (local == REMAP_PPM_HYBGEN) w_edges_h4cw(c, lane, n, true, h_neglect);
-  else if (local == REMAP_PPM_CW) w_edges_h4cw(c, lane, n, false, h_neglect_edge);
+  else if (local == MOM6HIP_REMAP_PPM_HYBGEN) w_edges_h4cw(c, lane, n, true, h_neglect);
+  else if (local == MOM6HIP_REMAP_PPM_CW) w_edges_h4cw(c, lane, n, false, h_neglect_edge);
   else w_edges_explicit_h4(c, lane, n, h_neglect_edge);
-  if (local == REMAP_PQM_IH4IH3) w_slopes_implicit_h3(c, lane, n, h_neglect);
-  if (local == REMAP_PQM_IH6IH5) {      // edge_slopes_implicit_h5
+  if (local == MOM6HIP_REMAP_PQM_IH4IH3) w_slopes_implicit_h3(c, lane, n, h_neglect);
+  if (local == MOM6HIP_REMAP_PQM_IH6IH5) {      // edge_slopes_implicit_h5
     w_ih65_system<true>(c, lane, n, h_neglect);
     w_take_interfaces(c.uh_sub, c.C1, c.SR, lane, n);
   }
@@ -1201,7 +948,7 @@ __device__ int w_build_reconstructions(const WCol &c, int lane, int scheme, bool
     return INT_PQM;
   }
   w_ppm_limit(c, lane, n);
-  if (extrap && lane == 0) w_ppm_boundary_extrapolation(c, n, h_neglect);
+  if (extrap && lane == 0) ppm_boundary_extrapolation(c.h0, c.u0, c.EL, c.ER, c.C1, n, h_neglect);
   wsync();
   return INT_PPM;
 }
@@ -1731,9 +1478,9 @@ __global__ __launch_bounds__(64 * WR_NCOL) void ale_remap_wave_kernel(WRemapArgs
 }
 
 bool scheme_provided(int scheme) {
-  if (scheme == REMAP_PCM || scheme == REMAP_PLM || scheme == REMAP_PPM_H4) return true;
-  return (scheme == REMAP_PPM_IH4 || scheme == REMAP_PPM_CW || scheme == REMAP_PLM_HYBGEN || scheme == REMAP_PPM_HYBGEN ||
-          scheme == REMAP_WENO_HYBGEN || scheme == REMAP_PQM_IH4IH3 || scheme == REMAP_PQM_IH6IH5);
+  if (scheme == MOM6HIP_REMAP_PCM || scheme == MOM6HIP_REMAP_PLM || scheme == MOM6HIP_REMAP_PPM_H4) return true;
+  return (scheme == MOM6HIP_REMAP_PPM_IH4 || scheme == MOM6HIP_REMAP_PPM_CW || scheme == MOM6HIP_REMAP_PLM_HYBGEN || scheme == MOM6HIP_REMAP_PPM_HYBGEN ||
+          scheme == MOM6HIP_REMAP_WENO_HYBGEN || scheme == MOM6HIP_REMAP_PQM_IH4IH3 || scheme == MOM6HIP_REMAP_PQM_IH6IH5);
 }
 
 // What ALE_remap_tracers and ALE_remap_velocities ask of the remapping control structure; the entries word the last two refusals themselves
@@ -1742,7 +1489,7 @@ int check_remapping_cs(const mom6hip_ctx_t *ctx, const mom6hip_remapping_cs_t *c
              "MOM_remapping, build_reconstructions_1d: The selected remapping method is invalid "
              "(libmom6hip provides PCM, PLM, PLM_HYBGEN, PPM_H4, PPM_IH4, PPM_HYBGEN, WENO_HYBGEN, PPM_CW, PQM_IH4IH3 and PQM_IH6IH5)");
   // (edge_values_implicit_h6 and edge_slopes_implicit_h5 read the six cells at either end of a column, whatever its length)
-  M6_REQUIRE(cs->remapping_scheme != REMAP_PQM_IH6IH5 || ctx->g.nk >= 6 || ctx->g.nk <= 4, "PQM_IH6IH5 needs at least six layers (or at most four, where build_reconstructions_1d takes a lower scheme)");
+  M6_REQUIRE(cs->remapping_scheme != MOM6HIP_REMAP_PQM_IH6IH5 || ctx->g.nk >= 6 || ctx->g.nk <= 4, "PQM_IH6IH5 needs at least six layers (or at most four, where build_reconstructions_1d takes a lower scheme)");
   M6_REQUIRE(cs->answer_date >= 20190101, "%s", answer_date_text);
   M6_REQUIRE(!cs->force_bounds_in_subcell, "%s", bounds_text);
   return 0;
@@ -1758,7 +1505,7 @@ int launch_wave_remap(mom6hip_ctx_t *ctx, WRemapArgs a) {
   const m6::GridDev &g = a.g;
   const int xs = (a.pos == MOM6HIP_POS_U) ? 1 : 0, ys = (a.pos == MOM6HIP_POS_V) ? 1 : 0;
   const int nf_stream = stream_fields();
-  if (nf_stream > 0 && a.scheme == REMAP_PPM_H4 && !a.extrap && g.nk >= 6) {
+  if (nf_stream > 0 && a.scheme == MOM6HIP_REMAP_PPM_H4 && !a.extrap && g.nk >= 6) {
     const size_t fbytes = sizeof(double) * (size_t)(g.nih + 1) * (g.njh + 1) * g.nk;      // (covers every staggering)
     M6_REQUIRE(ctx->ale_side.reserve(2 * fbytes) == 0, "ALE remap: out of device memory");
     SRemapArgs sa;

@@ -14,8 +14,10 @@
 //                      (which turns a -0.0 into +0.0 as the reference does)
 // One lane per face walks the serial depth loops of its column pair from private arrays (sized by the template's layer bound NKM).
 // The vertical reconstructions are those of remapping_core_h (src/ALE/MOM_remapping.F90:160) for PCM, PLM, PPM_H4, PPM_IH4 and
-// PPM_CW, with and without boundary extrapolation, force_bounds_in_subcell = .false.; they are restated here on their own and
-// leave the ALE kernels (ale_remap.hip) untouched.
+// PPM_CW, with and without boundary extrapolation, force_bounds_in_subcell = .false.  Their per-cell arithmetic lives in
+// remap_pieces.hpp, the text the ALE kernels (ale_remap.hip) use too, here with minima and maxima by compare-and-select; the column
+// drivers below are the serial loops over those pieces, on ALE's column layout (the edge values EL, ER and the slope column C1).
+// (Five pieces are called from here alone, and ale_remap.hip's wave path keeps the same arithmetic in place; the header names them.)
 // Algorithmic traffic per tracer and iteration: the flux kernels read h and the tracer of both columns of every wet face down to the
 // HBD grid's depth and write nflx_max planes of fluxes per direction; the update reads h and the fluxes and reads and writes every
 // layer of the tracer (>= 24 B per cell).
@@ -23,453 +25,152 @@
 #include <cmath>
 
 #include "common.hpp"
+#define REMAP_PIECES_SELECT 1      // m6::min2 / max2, as the oracle (remap_pieces.hpp says why there are two flavours)
+#include "remap_pieces.hpp"
 
 namespace {
 
 using m6::max2;
 using m6::min2;
 
-__device__ __forceinline__ double max3(double a, double b, double c) { return max2(max2(a, b), c); }
-__device__ __forceinline__ double min3(double a, double b, double c) { return min2(min2(a, b), c); }
-__device__ __forceinline__ double fsign(double a, double b) { return copysign(fabs(a), b); }
-
-enum { INT_PCM = 0, INT_PLM = 1, INT_PPM = 3 };
-
-// ---- reconstructions (E[s*n + k], coef[d*n + k]; k 0-based) ---------------------------------------------------------------
-#define E_(k, s) E[(s) * n + (k)]
-#define C_(k, d) coef[(d) * n + (k)]
-
-// PLM_slope_wa, src/ALE/PLM_functions.F90:22-65
-__device__ double plm_slope_wa(double h_l, double h_c, double h_r, double h_neglect, double u_l, double u_c, double u_r) {
-  const double sigma_r = u_r - u_c;
-  const double sigma_l = u_c - u_l;
-  const double sigma_c = 2.0 * (u_r - u_l) * (h_c / (h_l + 2.0 * h_c + h_r + h_neglect));
-  const double u_min = min3(u_l, u_c, u_r);
-  const double u_max = max3(u_l, u_c, u_r);
-  double slope;
-  if ((sigma_l * sigma_r) > 0.0) slope = fsign(min2(fabs(sigma_c), 2. * min2(u_c - u_min, u_max - u_c)), sigma_c);
-  else slope = 0.0;
-  if (u_c - 0.5 * fabs(slope) < u_min || u_c + 0.5 * fabs(slope) > u_max) slope = slope * (1. - DBL_EPSILON);
-  if (fabs(slope) < 1.E-140) slope = 0.;
-  return slope;
-}
-
-// PLM_monotonized_slope :124-159
-__device__ double plm_monotonized_slope(double u_l, double u_c, double u_r, double s_l, double s_c, double s_r) {
-  const double almost_two = 2. * (1. - DBL_EPSILON);
-  const double e_r = u_l + 0.5 * s_l;
-  const double e_l = u_r - 0.5 * s_r;
-  double slp = fabs(s_c);
-  double edge = u_c - 0.5 * s_c;
-  if ((edge - e_r) * (u_c - edge) < 0.) {
-    edge = 0.5 * (edge + e_r);
-    slp = min2(slp, fabs(edge - u_c) * almost_two);
-  }
-  edge = u_c + 0.5 * s_c;
-  if ((edge - u_c) * (e_l - edge) < 0.) {
-    edge = 0.5 * (edge + e_l);
-    slp = min2(slp, fabs(edge - u_c) * almost_two);
-  }
-  return fsign(slp, s_c);
-}
-
-// PLM_extrapolate_slope :164-183
-__device__ double plm_extrapolate_slope(double h_l, double h_c, double h_neglect, double u_l, double u_c) {
-  const double hl = h_l + h_neglect;
-  const double hc = h_c + h_neglect;
-  const double left_edge = (u_l * hc + u_c * hl) / (hl + hc);
-  return 2.0 * (u_c - left_edge);
-}
-
+// ---- the reconstructions of one column of n cells (k 0-based), serial loops over the pieces of remap_pieces.hpp ------------------------
 // PLM_reconstruction :190-260 (slp, mslp: work of n values each)
-__device__ void plm_reconstruction(int n, const double *h, const double *u, double *E, double *coef, double h_neglect, double *slp,
-                                   double *mslp) {
+__device__ void plm_reconstruction(int n, const double *h, const double *u, double *EL, double *ER, double *C1, double h_neglect,
+                                   double *slp, double *mslp) {
   const double almost_one = 1. - DBL_EPSILON;
   for (int k = 1; k < n - 1; k++) slp[k] = plm_slope_wa(h[k - 1], h[k], h[k + 1], h_neglect, u[k - 1], u[k], u[k + 1]);
   slp[0] = 0.; slp[n - 1] = 0.;
   for (int k = 1; k < n - 1; k++) mslp[k] = plm_monotonized_slope(u[k - 1], u[k], u[k + 1], slp[k - 1], slp[k], slp[k + 1]);
   mslp[0] = 0.; mslp[n - 1] = 0.;
-  E_(0, 0) = u[0]; E_(0, 1) = u[0]; C_(0, 0) = u[0]; C_(0, 1) = 0.;
+  EL[0] = u[0]; ER[0] = u[0]; C1[0] = 0.;
   for (int k = 1; k < n - 1; k++) {
     const double slope = mslp[k];
     const double u_l = u[k] - 0.5 * slope;
     const double u_r = u[k] + 0.5 * slope;
-    E_(k, 0) = u_l; E_(k, 1) = u_r;
-    C_(k, 0) = u_l;
-    C_(k, 1) = (u_r - u_l);
-    const double edge = C_(k, 1) + C_(k, 0);
+    EL[k] = u_l; ER[k] = u_r;
+    double c1 = (u_r - u_l);
+    const double edge = c1 + u_l;
     const double e_r = u[k + 1] - 0.5 * fsign(mslp[k + 1], slp[k + 1]);
-    if ((edge - u[k]) * (e_r - edge) < 0.) C_(k, 1) = C_(k, 1) * almost_one;
+    if ((edge - u[k]) * (e_r - edge) < 0.) c1 = c1 * almost_one;
+    C1[k] = c1;
   }
-  E_(n - 1, 0) = u[n - 1]; E_(n - 1, 1) = u[n - 1]; C_(n - 1, 0) = u[n - 1]; C_(n - 1, 1) = 0.;
-}
-
-// PLM_boundary_extrapolation :272-307
-__device__ void plm_boundary_extrapolation(int n, const double *h, const double *u, double *E, double *coef, double h_neglect) {
-  double slope = -plm_extrapolate_slope(h[1], h[0], h_neglect, u[1], u[0]);
-  E_(0, 0) = u[0] - 0.5 * slope;
-  E_(0, 1) = u[0] + 0.5 * slope;
-  C_(0, 0) = E_(0, 0);
-  C_(0, 1) = E_(0, 1) - E_(0, 0);
-  slope = plm_extrapolate_slope(h[n - 2], h[n - 1], h_neglect, u[n - 2], u[n - 1]);
-  E_(n - 1, 0) = u[n - 1] - 0.5 * slope;
-  E_(n - 1, 1) = u[n - 1] + 0.5 * slope;
-  C_(n - 1, 0) = E_(n - 1, 0);
-  C_(n - 1, 1) = E_(n - 1, 1) - E_(n - 1, 0);
+  EL[n - 1] = u[n - 1]; ER[n - 1] = u[n - 1]; C1[n - 1] = 0.;
 }
 
 // bound_edge_values (answer_date >= 20190101), src/ALE/regrid_edge_values.F90:44-110
-__device__ void bound_edge_values(int n, const double *h, const double *u, double *E) {
+__device__ void bound_edge_values(int n, const double *h, const double *u, double *EL, double *ER) {
   for (int k = 0; k < n; k++) {
     const int km1 = (k - 1 > 0) ? k - 1 : 0, kp1 = (k + 1 < n - 1) ? k + 1 : n - 1;
-    double slope_x_h = 0.0;
-    if (((h[km1] + h[kp1]) + 2.0 * h[k]) > 0.0) {
-      const double sigma_l = (u[k] - u[km1]);
-      const double sigma_c = (u[kp1] - u[km1]) * (h[k] / ((h[km1] + h[kp1]) + 2.0 * h[k]));
-      const double sigma_r = (u[kp1] - u[k]);
-      if ((sigma_l * sigma_r) > 0.0) slope_x_h = fsign(min3(fabs(sigma_l), fabs(sigma_c), fabs(sigma_r)), sigma_c);
-    }
-    if ((u[km1] - E_(k, 0)) * (E_(k, 0) - u[k]) < 0.0) E_(k, 0) = u[k] - fsign(min2(fabs(slope_x_h), fabs(E_(k, 0) - u[k])), slope_x_h);
-    if ((u[kp1] - E_(k, 1)) * (E_(k, 1) - u[k]) < 0.0) E_(k, 1) = u[k] + fsign(min2(fabs(slope_x_h), fabs(E_(k, 1) - u[k])), slope_x_h);
-    E_(k, 0) = max2(min2(E_(k, 0), max2(u[km1], u[k])), min2(u[km1], u[k]));
-    E_(k, 1) = max2(min2(E_(k, 1), max2(u[kp1], u[k])), min2(u[kp1], u[k]));
+    const double den = (h[km1] + h[kp1]) + 2.0 * h[k];
+    const double slope_x_h = bound_slope(u[km1], u[k], u[kp1], den > 0.0 ? h[k] / den : -1.0);
+    EL[k] = bound_left(EL[k], u[km1], u[k], slope_x_h);
+    ER[k] = bound_right(ER[k], u[kp1], u[k], slope_x_h);
   }
 }
 
 // check_discontinuous_edge_values :141-159
-__device__ void check_discontinuous_edge_values(int n, const double *u, double *E) {
+__device__ void check_discontinuous_edge_values(int n, const double *u, double *EL, double *ER) {
   for (int k = 0; k < n - 1; k++) {
-    if ((E_(k + 1, 0) - E_(k, 1)) * (u[k + 1] - u[k]) < 0.0) {
-      double u0_avg = 0.5 * (E_(k, 1) + E_(k + 1, 0));
-      u0_avg = max2(min2(u0_avg, max2(u[k], u[k + 1])), min2(u[k], u[k + 1]));
-      E_(k, 1) = u0_avg;
-      E_(k + 1, 0) = u0_avg;
+    if (edges_discontinuous(u[k], u[k + 1], ER[k], EL[k + 1])) {
+      const double u0_avg = bounded_edge_average(u[k], u[k + 1], ER[k], EL[k + 1]);
+      ER[k] = u0_avg; EL[k + 1] = u0_avg;
     }
   }
-}
-
-// end_value_h4 :658-771
-__device__ void end_value_h4(const double dz[4], const double u[4], double Csys[4]) {
-  const double min_frac = 1.0e-6;
-  double Wt[3][4];
-  double h1 = dz[0], h2 = dz[1], h3 = dz[2], h4 = dz[3];
-  if ((h2 + h3) < min_frac * h1) h3 = min_frac * h1 - h2;
-  if ((h3 + h4) < min_frac * h1) h4 = min_frac * h1 - h3;
-  const double h12 = h1 + h2, h23 = h2 + h3, h34 = h3 + h4;
-  const double h123 = h12 + h3, h234 = h2 + h34, h1234 = h12 + h34;
-  const double I_denB3 = 1.0 / (h123 * h12 * h23);
-  const double I_h12 = (h123 * h23) * I_denB3;
-  const double I_h23 = (h12 * h123) * I_denB3;
-  const double I_h123 = (h12 * h23) * I_denB3;
-  const double I_denom = 1.0 / (h1234 * (h234 * h34));
-  const double I_h234 = (h1234 * h34) * I_denom;
-  const double I_h1234 = (h234 * h34) * I_denom;
-  Wt[0][0] = -h1 * (I_h1234 + I_h123 + I_h12);
-  Wt[1][0] = h1 * h12 * (I_h234 * I_h1234 + I_h23 * (I_h234 + I_h123));
-  Wt[2][0] = -h1 * h12 * h123 * I_denom;
-  Wt[0][1] = 2.0 * (I_h12 * (1.0 + (h1 + h12) * (I_h1234 + I_h123)) + h1 * I_h1234 * I_h123);
-  Wt[1][1] = -2.0 * ((h1 * h12 * I_h1234) * (I_h23 * (I_h234 + I_h123)) + (h1 + h12) * (I_h1234 * I_h234 + I_h23 * (I_h234 + I_h123)));
-  Wt[2][1] = 2.0 * ((h1 + h12) * h123 + h1 * h12) * I_denom;
-  Wt[0][2] = -3.0 * I_h12 * I_h123 * (1.0 + I_h1234 * ((h1 + h12) + h123));
-  Wt[1][2] = 3.0 * I_h23 * (I_h123 + I_h1234 * ((h1 + h12) + h123) * (I_h123 + I_h234));
-  Wt[2][2] = -3.0 * ((h1 + h12) + h123) * I_denom;
-  Wt[0][3] = 4.0 * I_h1234 * I_h123 * I_h12;
-  Wt[1][3] = -4.0 * I_h1234 * (I_h23 * (I_h123 + I_h234));
-  Wt[2][3] = 4.0 * I_denom;
-  Csys[0] = ((u[0] + Wt[0][0] * (u[1] - u[0])) + Wt[1][0] * (u[2] - u[1])) + Wt[2][0] * (u[3] - u[2]);
-  Csys[1] = (Wt[0][1] * (u[1] - u[0]) + Wt[1][1] * (u[2] - u[1])) + Wt[2][1] * (u[3] - u[2]);
-  Csys[2] = (Wt[0][2] * (u[1] - u[0]) + Wt[1][2] * (u[2] - u[1])) + Wt[2][2] * (u[3] - u[2]);
-  Csys[3] = (Wt[0][3] * (u[1] - u[0]) + Wt[1][3] * (u[2] - u[1])) + Wt[2][3] * (u[3] - u[2]);
-}
-
-__device__ void end_values_h4(int n, const double *h, const double *u, double hNeglect, double &top, double &top_r, double &bot,
-                              double &bot_l) {
-  double dz[4], ut[4], C[4];
-  for (int i = 0; i < 4; i++) { dz[i] = max2(hNeglect, h[i]); ut[i] = u[i]; }
-  end_value_h4(dz, ut, C);
-  top = C[0]; top_r = C[0] + dz[0] * (C[1] + dz[0] * (C[2] + dz[0] * C[3]));
-  for (int i = 0; i < 4; i++) { dz[i] = max2(hNeglect, h[n - 1 - i]); ut[i] = u[n - 1 - i]; }
-  end_value_h4(dz, ut, C);
-  bot = C[0]; bot_l = C[0] + dz[0] * (C[1] + dz[0] * (C[2] + dz[0] * C[3]));
 }
 
 // edge_values_explicit_h4 (answer_date >= 20190101) :222-363, n >= 4
-__device__ void edge_values_explicit_h4(int n, const double *h, const double *u, double *E, double hNeglect) {
-  const double hMinFrac = 1.e-5;
+__device__ void edge_values_explicit_h4(int n, const double *h, const double *u, double *EL, double *ER, double hNeglect) {
   for (int i = 2; i <= n - 2; i++) {
-    double h0 = h[i - 2], h1 = h[i - 1], h2 = h[i], h3 = h[i + 1];
-    if (h0 + h1 == 0.0 || h1 + h2 == 0.0 || h2 + h3 == 0.0) {
-      const double h_min = hMinFrac * max2(hNeglect, (h0 + h1) + (h2 + h3));
-      h0 = max2(h_min, h[i - 2]);
-      h1 = max2(h_min, h[i - 1]);
-      h2 = max2(h_min, h[i]);
-      h3 = max2(h_min, h[i + 1]);
-    }
-    const double I_h12 = 1.0 / (h1 + h2);
-    const double I_den_et2 = 1.0 / (((h0 + h1) + h2) * (h0 + h1)); const double I_h012 = (h0 + h1) * I_den_et2;
-    const double I_den_et3 = 1.0 / ((h1 + (h2 + h3)) * (h2 + h3)); const double I_h123 = (h2 + h3) * I_den_et3;
-    const double et1 = (1.0 + (h1 * I_h012 + (h0 + h1) * I_h123)) * I_h12 * (h2 * (h2 + h3)) * u[i - 1] +
-                       (1.0 + (h2 * I_h123 + (h2 + h3) * I_h012)) * I_h12 * (h1 * (h0 + h1)) * u[i];
-    const double et2 = (h1 * (h2 * (h2 + h3)) * I_den_et2) * (u[i - 1] - u[i - 2]);
-    const double et3 = (h2 * (h1 * (h0 + h1)) * I_den_et3) * (u[i] - u[i + 1]);
-    E_(i, 0) = (et1 + (et2 + et3)) / ((h0 + h1) + (h2 + h3));
-    E_(i - 1, 1) = E_(i, 0);
+    const EdgeW w = edge_weights_h4(h[i - 2], h[i - 1], h[i], h[i + 1], hNeglect);
+    const double ev = edge_value_h4(w, u[i - 2], u[i - 1], u[i], u[i + 1]);
+    EL[i] = ev; ER[i - 1] = ev;
   }
-  double t, tr, b, bl;
-  end_values_h4(n, h, u, hNeglect, t, tr, b, bl);
-  E_(0, 0) = t; E_(0, 1) = tr; E_(1, 0) = E_(0, 1);
-  E_(n - 1, 1) = b; E_(n - 1, 0) = bl; E_(n - 2, 1) = E_(n - 1, 0);
+  double Cs[4];
+  double dz0 = end_polynomial_h4(h, u, false, n, hNeglect, Cs);
+  EL[0] = Cs[0]; ER[0] = Cs[0] + dz0 * (Cs[1] + dz0 * (Cs[2] + dz0 * Cs[3])); EL[1] = ER[0];
+  dz0 = end_polynomial_h4(h, u, true, n, hNeglect, Cs);
+  ER[n - 1] = Cs[0]; EL[n - 1] = Cs[0] + dz0 * (Cs[1] + dz0 * (Cs[2] + dz0 * Cs[3])); ER[n - 2] = EL[n - 1];
 }
 
-// edge_values_implicit_h4 (answer_date >= 20190101) :491-654 with solve_diag_dominant_tridiag (regrid_solvers.F90:246-280), n >= 4;
-// w: work of 6 (n + 1) values
-__device__ void edge_values_implicit_h4(int n, const double *h, const double *u, double *E, double hNeglect, double *w) {
+// edge_values_implicit_h4 (answer_date >= 20190101) :491-654, n >= 4; w: work of 5 (n + 1) values
+__device__ void edge_values_implicit_h4(int n, const double *h, const double *u, double *EL, double *ER, double hNeglect, double *w) {
   const int m = n + 1;
-  double *tri_l = w, *tri_c = w + m, *tri_u = tri_c + m, *tri_b = tri_u + m, *tri_x = tri_b + m, *c1 = tri_x + m;
-  for (int i = 0; i < 6 * m; i++) w[i] = 0.0;
+  double *tri_l = w, *tri_c = w + m, *tri_u = tri_c + m, *tri_b = tri_u + m, *c1 = tri_b + m;
   for (int i = 0; i < n - 1; i++) {
-    double h0 = max2(h[i], hNeglect);
-    double h1 = max2(h[i + 1], hNeglect);
-    if (fabs(h0) < 1.0e-12 * fabs(h1)) h0 = 1.0e-12 * h1;
-    if (fabs(h1) < 1.0e-12 * fabs(h0)) h1 = 1.0e-12 * h0;
-    const double I_h2 = 1.0 / ((h0 + h1) * (h0 + h1));
-    const double alpha = (h1 * h1) * I_h2;
-    const double beta = (h0 * h0) * I_h2;
-    const double abmix = (h0 * h1) * I_h2;
-    const double a = 2.0 * alpha * (alpha + 2.0 * beta + 3.0 * abmix);
-    const double b = 2.0 * beta * (beta + 2.0 * alpha + 3.0 * abmix);
-    tri_c[i + 1] = 2.0 * abmix;
-    tri_l[i + 1] = alpha;
-    tri_u[i + 1] = beta;
-    tri_b[i + 1] = a * u[i] + b * u[i + 1];
+    const TriRow r = implicit_h4_row(h[i], h[i + 1], u[i], u[i + 1], hNeglect);
+    tri_c[i + 1] = r.c; tri_l[i + 1] = r.l; tri_u[i + 1] = r.u; tri_b[i + 1] = r.b;
   }
-  double t, tr, bt, bl;
-  end_values_h4(n, h, u, hNeglect, t, tr, bt, bl);
-  tri_b[0] = t; tri_c[0] = 1.0; tri_u[0] = 0.0;
-  tri_b[n] = bt; tri_c[n] = 1.0; tri_l[n] = 0.0;
-  double I_pivot = 1.0 / (tri_c[0] + tri_u[0]);
-  double d1 = tri_c[0] * I_pivot;
-  c1[0] = tri_u[0] * I_pivot;
-  tri_x[0] = tri_b[0] * I_pivot;
-  for (int k = 1; k < m - 1; k++) {
-    const double denom_t1 = tri_c[k] + d1 * tri_l[k];
-    I_pivot = 1.0 / (denom_t1 + tri_u[k]);
-    d1 = denom_t1 * I_pivot;
-    c1[k] = tri_u[k] * I_pivot;
-    tri_x[k] = (tri_b[k] - tri_l[k] * tri_x[k - 1]) * I_pivot;
-  }
-  I_pivot = 1.0 / (tri_c[m - 1] + d1 * tri_l[m - 1]);
-  tri_x[m - 1] = (tri_b[m - 1] - tri_l[m - 1] * tri_x[m - 2]) * I_pivot;
-  for (int k = m - 2; k >= 0; k--) tri_x[k] = tri_x[k] - c1[k] * tri_x[k + 1];
-  E_(0, 0) = tri_x[0];
-  for (int i = 1; i < n; i++) { E_(i, 0) = tri_x[i]; E_(i - 1, 1) = tri_x[i]; }
-  E_(n - 1, 1) = tri_x[n];
+  double Cs[4];
+  end_polynomial_h4(h, u, false, n, hNeglect, Cs);
+  tri_b[0] = Cs[0]; tri_c[0] = 1.0; tri_u[0] = 0.0; tri_l[0] = 0.0;
+  end_polynomial_h4(h, u, true, n, hNeglect, Cs);
+  tri_b[n] = Cs[0]; tri_c[n] = 1.0; tri_u[n] = 0.0; tri_l[n] = 0.0;
+  solve_diag_dominant_tridiag(tri_l, tri_c, tri_u, tri_b, c1, m);
+  for (int k = 0; k < n; k++) { EL[k] = tri_b[k]; ER[k] = tri_b[k + 1]; }
 }
 
-// edge_values_explicit_h4cw :381-470, n >= 4; w: work of 8 (n + 2) values (1-based as in the reference)
-__device__ void edge_values_explicit_h4cw(int n, const double *h, const double *u, double *E, double hNeglect, double *w) {
-  const int m = n + 2;
-  double *dp = w, *au = dp + m, *al = au + m, *ar = al + m, *h112 = ar + m, *h122 = h112 + m, *I_h12 = h122 + m, *h2_h123 = I_h12 + m;
-  for (int i = 0; i < 8 * m; i++) w[i] = 0.0;
-#define U1(k) u[(k) - 1]
-  for (int k = 1; k <= n; k++) dp[k] = max2(h[k - 1], hNeglect);
-  for (int k = 2; k <= n; k++) {
-    h112[k] = 2. * dp[k - 1] + dp[k];
-    h122[k] = dp[k - 1] + 2. * dp[k];
-    I_h12[k] = 1.0 / (dp[k - 1] + dp[k]);
+// edge_values_explicit_h4cw :381-470 and PPM_monotonicity (PPM_functions.F90:132-158), n >= 4; au: work of n values
+__device__ void edge_values_explicit_h4cw(int n, const double *h, const double *u, double *EL, double *ER, double hNeglect, double *au) {
+  auto dp = [&](int k) { return max2(h[k], hNeglect); };
+  au[0] = 0.; au[n - 1] = 0.;
+  for (int k = 1; k <= n - 2; k++) au[k] = h4cw_slope(dp(k - 1), dp(k), dp(k + 1), u[k - 1], u[k], u[k + 1]);
+  for (int k = 2; k <= n - 2; k++) {
+    const double al = h4cw_edge(dp(k - 2), dp(k - 1), dp(k), dp(k + 1), u[k - 1], u[k], au[k - 1], au[k]);
+    EL[k] = al; ER[k - 1] = al;
   }
-  for (int k = 2; k <= n - 1; k++) h2_h123[k] = dp[k] / (dp[k] + (dp[k - 1] + dp[k + 1]));
-  au[1] = 0.;
-  for (int k = 2; k <= n - 1; k++) {
-    const double slk = U1(k) - U1(k - 1);
-    const double srk = U1(k + 1) - U1(k);
-    if (slk * srk > 0.) {
-      const double sck = h2_h123[k] * (h112[k] * srk * I_h12[k + 1] + h122[k + 1] * slk * I_h12[k]);
-      au[k] = fsign(min3(fabs(2.0 * slk), fabs(sck), fabs(2.0 * srk)), sck);
-    } else {
-      au[k] = 0.;
-    }
-  }
-  au[n] = 0.;
-  al[1] = U1(1); ar[1] = U1(1); al[2] = U1(1);
-  for (int k = 3; k <= n - 1; k++) {
-    const double I_h0123 = 1.0 / ((dp[k - 2] + dp[k - 1]) + (dp[k] + dp[k + 1]));
-    const double h01_h112 = (dp[k - 2] + dp[k - 1]) / (2.0 * dp[k - 1] + dp[k]);
-    const double h23_h122 = (dp[k] + dp[k + 1]) / (dp[k - 1] + 2.0 * dp[k]);
-    al[k] = (dp[k] * U1(k - 1) + dp[k - 1] * U1(k)) * I_h12[k] +
-            I_h0123 * (2. * dp[k] * dp[k - 1] * I_h12[k] * (U1(k) - U1(k - 1)) * (h01_h112 - h23_h122) +
-                       (dp[k] * au[k - 1] * h23_h122 - dp[k - 1] * au[k] * h01_h112));
-    ar[k - 1] = al[k];
-  }
-  ar[n - 1] = U1(n); al[n] = U1(n); ar[n] = U1(n);
-  for (int k = 1; k <= n; k++) { E_(k - 1, 0) = al[k]; E_(k - 1, 1) = ar[k]; }
-#undef U1
+  EL[0] = u[0]; ER[0] = u[0]; EL[1] = u[0]; ER[n - 2] = u[n - 1]; EL[n - 1] = u[n - 1]; ER[n - 1] = u[n - 1];
 }
-
-// PPM_monotonicity, src/ALE/PPM_functions.F90:132-158
-__device__ void ppm_monotonicity(int n, const double *u, double *E) {
+__device__ void ppm_monotonicity(int n, const double *u, double *EL, double *ER) {
   for (int k = 1; k < n - 1; k++) {
-    if ((u[k + 1] - u[k]) * (u[k] - u[k - 1]) <= 0.) {
-      E_(k, 0) = u[k];
-      E_(k, 1) = u[k];
-    } else {
-      const double da = E_(k, 1) - E_(k, 0);
-      const double a6 = 6.0 * u[k] - 3.0 * (E_(k, 0) + E_(k, 1));
-      if (da * a6 > da * da) E_(k, 0) = 3.0 * u[k] - 2.0 * E_(k, 1);
-      else if (da * a6 < -da * da) E_(k, 1) = 3.0 * u[k] - 2.0 * E_(k, 0);
-    }
+    double edge_l = EL[k], edge_r = ER[k];
+    ppm_monotonicity_cell(u[k - 1], u[k], u[k + 1], edge_l, edge_r);
+    EL[k] = edge_l; ER[k] = edge_r;
   }
 }
 
 // PPM_reconstruction with PPM_limiter_standard :28-128
-__device__ void ppm_reconstruction(int n, const double *h, const double *u, double *E, double *coef) {
-  bound_edge_values(n, h, u, E);
-  check_discontinuous_edge_values(n, u, E);
-  for (int k = 1; k < n - 1; k++) {
-    const double u_l = u[k - 1], u_c = u[k], u_r = u[k + 1];
-    double edge_l = E_(k, 0), edge_r = E_(k, 1);
-    if ((u_r - u_c) * (u_c - u_l) <= 0.0) {
-      edge_l = u_c; edge_r = u_c;
-    } else {
-      const double expr1 = 3.0 * (edge_r - edge_l) * ((u_c - edge_l) + (u_c - edge_r));
-      const double expr2 = (edge_r - edge_l) * (edge_r - edge_l);
-      if (expr1 > expr2) {
-        edge_l = u_c + 2.0 * (u_c - edge_r);
-        edge_l = max2(min2(edge_l, max2(u_l, u_c)), min2(u_l, u_c));
-      } else if (expr1 < -expr2) {
-        edge_r = u_c + 2.0 * (u_c - edge_l);
-        edge_r = max2(min2(edge_r, max2(u_r, u_c)), min2(u_r, u_c));
-      }
-    }
-    if (fabs(edge_r - edge_l) < max2(1.e-60, DBL_EPSILON * fabs(u_c))) { edge_l = u_c; edge_r = u_c; }
-    E_(k, 0) = edge_l; E_(k, 1) = edge_r;
-  }
-  E_(0, 0) = u[0]; E_(0, 1) = u[0];
-  E_(n - 1, 0) = u[n - 1]; E_(n - 1, 1) = u[n - 1];
+__device__ void ppm_reconstruction(int n, const double *h, const double *u, double *EL, double *ER, double *C1) {
+  bound_edge_values(n, h, u, EL, ER);
+  check_discontinuous_edge_values(n, u, EL, ER);
   for (int k = 0; k < n; k++) {
-    const double edge_l = E_(k, 0), edge_r = E_(k, 1);
-    C_(k, 0) = edge_l;
-    C_(k, 1) = 4.0 * (u[k] - edge_l) + 2.0 * (u[k] - edge_r);
-    C_(k, 2) = 3.0 * ((edge_r - u[k]) + (edge_l - u[k]));
+    double edge_l = u[k], edge_r = u[k];      // the boundary cells are piecewise constant
+    if (k >= 1 && k < n - 1) {
+      edge_l = EL[k]; edge_r = ER[k];
+      ppm_limit_cell(u[k - 1], u[k], u[k + 1], edge_l, edge_r);
+    }
+    EL[k] = edge_l; ER[k] = edge_r;
+    C1[k] = 4.0 * (u[k] - edge_l) + 2.0 * (u[k] - edge_r);
   }
 }
-
-// PPM_boundary_extrapolation :162-316
-__device__ void ppm_boundary_extrapolation(int n, const double *h, const double *u, double *E, double *coef, double hNeglect) {
-  int i0 = 0, i1 = 1;
-  double h0 = h[i0], h1 = h[i1], u0 = u[i0], u1 = u[i1];
-  double b = C_(i1, 1);
-  double u1_r = b * ((h0 + hNeglect) / (h1 + hNeglect));
-  double slope = 2.0 * (u1 - u0);
-  if (fabs(u1_r) > fabs(slope)) u1_r = slope;
-  double u0_r = E_(i1, 0);
-  double u0_l = 3.0 * u0 + 0.5 * u1_r - 2.0 * u0_r;
-  double exp1 = (u0_r - u0_l) * (u0 - 0.5 * (u0_l + u0_r));
-  double exp2 = (u0_r - u0_l) * (u0_r - u0_l) / 6.0;
-  if (exp1 > exp2) u0_l = 3.0 * u0 - 2.0 * u0_r;
-  if (exp1 < -exp2) u0_r = 3.0 * u0 - 2.0 * u0_l;
-  E_(i0, 0) = u0_l; E_(i0, 1) = u0_r;
-  C_(i0, 0) = u0_l;
-  C_(i0, 1) = 6.0 * u0 - 4.0 * u0_l - 2.0 * u0_r;
-  C_(i0, 2) = 3.0 * (u0_r + u0_l - 2.0 * u0);
-
-  i0 = n - 2; i1 = n - 1;
-  h0 = h[i0]; h1 = h[i1]; u0 = u[i0]; u1 = u[i1];
-  b = C_(i0, 1);
-  const double c = C_(i0, 2);
-  double u1_l = (b + 2 * c);
-  u1_l = u1_l * ((h1 + hNeglect) / (h0 + hNeglect));
-  slope = 2.0 * (u1 - u0);
-  if (fabs(u1_l) > fabs(slope)) u1_l = slope;
-  u0_l = E_(i0, 1);
-  u0_r = 3.0 * u1 - 0.5 * u1_l - 2.0 * u0_l;
-  exp1 = (u0_r - u0_l) * (u1 - 0.5 * (u0_l + u0_r));
-  exp2 = (u0_r - u0_l) * (u0_r - u0_l) / 6.0;
-  if (exp1 > exp2) u0_l = 3.0 * u1 - 2.0 * u0_r;
-  if (exp1 < -exp2) u0_r = 3.0 * u1 - 2.0 * u0_l;
-  E_(i1, 0) = u0_l; E_(i1, 1) = u0_r;
-  C_(i1, 0) = u0_l;
-  C_(i1, 1) = 6.0 * u1 - 4.0 * u0_l - 2.0 * u0_r;
-  C_(i1, 2) = 3.0 * (u0_r + u0_l - 2.0 * u1);
-}
-
-// average_value_ppoly, src/ALE/MOM_remapping.F90:998-1099 (PCM, PLM, PPM)
-__device__ double average_value_ppoly(int n, const double *u0, const double *E, const double *coef, int method, int i0, double xa, double xb) {
-  double u_ave = 0.0;
-  if (xb > xa) {
-    if (method == INT_PCM) {
-      u_ave = u0[i0];
-    } else if (method == INT_PLM) {
-      u_ave = (C_(i0, 0) + C_(i0, 1) * 0.5 * (xb + xa));
-    } else {
-      const double mx = 0.5 * (xa + xb);
-      const double a_L = E_(i0, 0), a_R = E_(i0, 1), u_c = u0[i0];
-      const double a_c = 0.5 * ((u_c - a_L) + (u_c - a_R));
-      if (mx < 0.5) {
-        const double xa2b2ab = (xa * xa + xb * xb) + xa * xb;
-        u_ave = a_L + ((a_R - a_L) * mx + a_c * (3. * (xb + xa) - 2. * xa2b2ab));
-      } else {
-        const double Ya = 1. - xa, Yb = 1. - xb;
-        const double my = 0.5 * (Ya + Yb);
-        const double Ya2b2ab = (Ya * Ya + Yb * Yb) + Ya * Yb;
-        u_ave = a_R + ((a_L - a_R) * my + a_c * (3. * (Yb + Ya) - 2. * Ya2b2ab));
-      }
-    }
-  } else {
-    if (method == INT_PCM) {
-      u_ave = C_(i0, 0);
-    } else if (method == INT_PLM) {
-      const double a_L = E_(i0, 0), a_R = E_(i0, 1);
-      const double Ya = 1. - xa;
-      if (xa < 0.5) u_ave = a_L + xa * (a_R - a_L);
-      else u_ave = a_R + Ya * (a_L - a_R);
-    } else {
-      const double a_L = E_(i0, 0), a_R = E_(i0, 1), u_c = u0[i0];
-      const double a_c = 3. * ((u_c - a_L) + (u_c - a_R));
-      const double Ya = 1. - xa;
-      if (xa < 0.5) u_ave = a_L + xa * ((a_R - a_L) + a_c * Ya);
-      else u_ave = a_R + Ya * ((a_L - a_R) + a_c * xa);
-    }
-  }
-  return u_ave;
-}
-#undef E_
-#undef C_
 
 // the private work space of one remapping_core_h of at most NKM source and 2 NKM + 2 target cells
 template <int NKM>
 struct RemapWork {
   static constexpr int N1M = 2 * NKM + 2, NS = NKM + N1M + 3;
-  double E[2 * NKM], coef[3 * NKM], w[8 * (NKM + 2)];
+  double EL[NKM], ER[NKM], C1[NKM], w[5 * (NKM + 1)];
   double h_sub[NS], uh_sub[NS], u_sub[NS], h0_eff[NKM + 2];
   int isub_src[NS], isrc_start[NKM + 2], isrc_end[NKM + 2], isrc_max[NKM + 2], itgt_start[N1M + 2], itgt_end[N1M + 2];
 };
 
 // build_reconstructions_1d (:257-386) for the schemes provided; returns the integration method
 template <int NKM>
-__device__ int build_reconstructions(RemapWork<NKM> &W, int scheme, bool extrap, int n0, const double *h0, const double *u0,
+__device__ int build_reconstructions(RemapWork<NKM> &W, int scheme, bool extrap, int n, const double *h0, const double *u0,
                                      double h_neglect, double h_neglect_edge) {
-  const int n = n0;
-  for (int i = 0; i < 2 * n0; i++) W.E[i] = 0.0;
-  for (int i = 0; i < 3 * n0; i++) W.coef[i] = 0.0;
-  int local = scheme;
-  if (n0 <= 1) local = MOM6HIP_REMAP_PCM;
-  else if (n0 <= 3) local = (local < MOM6HIP_REMAP_PLM) ? local : MOM6HIP_REMAP_PLM;
-  else if (n0 <= 4 && local != MOM6HIP_REMAP_PPM_CW) local = (local < MOM6HIP_REMAP_PPM_H4) ? local : MOM6HIP_REMAP_PPM_H4;
+  const int local = remap_local_scheme(scheme, n);
   if (local == MOM6HIP_REMAP_PCM) {
-    for (int k = 0; k < n; k++) { W.coef[k] = u0[k]; W.E[k] = u0[k]; W.E[n + k] = u0[k]; }
+    for (int k = 0; k < n; k++) { W.EL[k] = u0[k]; W.ER[k] = u0[k]; W.C1[k] = 0.; }
     return INT_PCM;
   }
   if (local == MOM6HIP_REMAP_PLM) {
-    plm_reconstruction(n, h0, u0, W.E, W.coef, h_neglect, W.w, W.w + n);
-    if (extrap) plm_boundary_extrapolation(n, h0, u0, W.E, W.coef, h_neglect);
+    plm_reconstruction(n, h0, u0, W.EL, W.ER, W.C1, h_neglect, W.w, W.w + n);
+    if (extrap) plm_boundary_extrapolation(h0, u0, W.EL, W.ER, W.C1, n, h_neglect);
     return INT_PLM;
   }
-  if (local == MOM6HIP_REMAP_PPM_H4) edge_values_explicit_h4(n, h0, u0, W.E, h_neglect_edge);
-  else if (local == MOM6HIP_REMAP_PPM_IH4) edge_values_implicit_h4(n, h0, u0, W.E, h_neglect_edge, W.w);
-  else { edge_values_explicit_h4cw(n, h0, u0, W.E, h_neglect_edge, W.w); ppm_monotonicity(n, u0, W.E); }
-  ppm_reconstruction(n, h0, u0, W.E, W.coef);
-  if (extrap) ppm_boundary_extrapolation(n, h0, u0, W.E, W.coef, h_neglect);
+  if (local == MOM6HIP_REMAP_PPM_H4) edge_values_explicit_h4(n, h0, u0, W.EL, W.ER, h_neglect_edge);
+  else if (local == MOM6HIP_REMAP_PPM_IH4) edge_values_implicit_h4(n, h0, u0, W.EL, W.ER, h_neglect_edge, W.w);
+  else { edge_values_explicit_h4cw(n, h0, u0, W.EL, W.ER, h_neglect_edge, W.w); ppm_monotonicity(n, u0, W.EL, W.ER); }
+  ppm_reconstruction(n, h0, u0, W.EL, W.ER, W.C1);
+  if (extrap) ppm_boundary_extrapolation(h0, u0, W.EL, W.ER, W.C1, n, h_neglect);
   return INT_PPM;
 }
 
@@ -477,8 +178,7 @@ __device__ int build_reconstructions(RemapWork<NKM> &W, int scheme, bool extrap,
 template <int NKM>
 __device__ void remap_via_sub_cells(RemapWork<NKM> &W, int n0, const double *h0, const double *u0, int n1, const double *h1, int method,
                                     double *u1) {
-  const int n = n0, ns = n0 + n1 + 1;
-  const double *E = W.E;
+  const int ns = n0 + n1 + 1;
   double *h_sub = W.h_sub, *uh_sub = W.uh_sub, *u_sub = W.u_sub, *h0_eff = W.h0_eff;
   int *isub_src = W.isub_src, *isrc_start = W.isrc_start, *isrc_end = W.isrc_end, *isrc_max = W.isrc_max;
   int *itgt_start = W.itgt_start, *itgt_end = W.itgt_end;
@@ -532,7 +232,7 @@ __device__ void remap_via_sub_cells(RemapWork<NKM> &W, int n0, const double *h0,
   double xa = 0., xb;
   dh0_eff = 0.;
   uh_sub[1] = 0.;
-  u_sub[1] = E[0];
+  u_sub[1] = W.EL[0];
   for (int i_sub = 2; i_sub <= n0 + n1; i_sub++) {
     dh = h_sub[i_sub];
     i0 = isub_src[i_sub];
@@ -540,7 +240,7 @@ __device__ void remap_via_sub_cells(RemapWork<NKM> &W, int n0, const double *h0,
     if (h0_eff[i0] > 0.) {
       xb = dh0_eff / h0_eff[i0];
       xb = min2(1., xb);
-      u_sub[i_sub] = average_value_ppoly(n0, u0, E, W.coef, method, i0 - 1, xa, xb);
+      u_sub[i_sub] = average_value_ppoly(method, U0(i0), W.EL[i0 - 1], W.ER[i0 - 1], W.C1[i0 - 1], xa, xb);
     } else {
       xb = 1.;
       u_sub[i_sub] = U0(i0);
@@ -549,8 +249,8 @@ __device__ void remap_via_sub_cells(RemapWork<NKM> &W, int n0, const double *h0,
     if (isub_src[i_sub + 1] != i0) { dh0_eff = 0.; xa = 0.; }
     else { xa = xb; }
   }
-  u_sub[ns] = E[n + n0 - 1];
-  uh_sub[ns] = E[n + n0 - 1] * h_sub[ns];
+  u_sub[ns] = W.ER[n0 - 1];
+  uh_sub[ns] = W.ER[n0 - 1] * h_sub[ns];
   for (i0 = 1; i0 <= i0_last_thick_cell; i0++) {      // adjust_thickest_subcell
     i_max = isrc_max[i0];
     dh_max = h_sub[i_max];

@@ -3,7 +3,9 @@
 // (src/core/MOM_density_integrals.F90:369-769), PLM edge values of T and S (ALE_PLM_edge_values,
 // src/ALE/MOM_ALE.F90:1520-1579), Set_pbce_Bouss (src/core/MOM_PressureForce_Montgomery.F90:649-748) and the
 // Wright / linear equations of state (src/equation_of_state/MOM_EOS_Wright.F90:80-206, MOM_EOS_linear.F90);
-// PressureForce_FV_nonBouss (:89-452) and ALE_PLM_edge_values for a caller's own field.
+// PressureForce_FV_nonBouss (:89-452) and ALE_PLM_edge_values for a caller's own field.  The PLM slopes (PLM_slope_wa,
+// PLM_monotonized_slope, PLM_extrapolate_slope) are those of remap_pieces.hpp, the text the remapping kernels use, with minima and
+// maxima by compare-and-select.
 //
 // This operator is fp64-VALU bound, not HBM bound: 35 equation-of-state evaluations per cell-layer (5 for
 // the vertical Boole quadrature, 3x5 on each of the two faces), each ~45 flops and one IEEE division,
@@ -33,46 +35,14 @@
 
 #include "common.hpp"
 #include "eos.hpp"
+#define REMAP_PIECES_SELECT 1      // m6::min2 / max2, as it has always used (remap_pieces.hpp says why there are two flavours)
+#include "remap_pieces.hpp"
 
 namespace {
 
 using m6::max2;
 using m6::min2;
 using namespace m6::eos;
-__device__ __forceinline__ double max3(double a, double b, double c) { return max2(max2(a, b), c); }
-__device__ __forceinline__ double min3(double a, double b, double c) { return min2(min2(a, b), c); }
-__device__ __forceinline__ double fsign(double a, double b) { return copysign(fabs(a), b); }
-
-// ---- PLM_functions.F90 ---------------------------------------------------------------------------
-__device__ double plm_slope_wa(double h_l, double h_c, double h_r, double h_neglect, double u_l, double u_c, double u_r) {
-  const double sigma_r = u_r - u_c;
-  const double sigma_l = u_c - u_l;
-  const double sigma_c = 2.0 * (u_r - u_l) * (h_c / (h_l + 2.0 * h_c + h_r + h_neglect));
-  const double u_min = min3(u_l, u_c, u_r);
-  const double u_max = max3(u_l, u_c, u_r);
-  double slope = 0.0;
-  if ((sigma_l * sigma_r) > 0.0) slope = fsign(min2(fabs(sigma_c), 2. * min2(u_c - u_min, u_max - u_c)), sigma_c);
-  if (u_c - 0.5 * fabs(slope) < u_min || u_c + 0.5 * fabs(slope) > u_max) slope = slope * (1. - 2.220446049250313e-16);
-  if (fabs(slope) < 1.E-140) slope = 0.;
-  return slope;
-}
-__device__ double plm_monotonized_slope(double u_l, double u_c, double u_r, double s_l, double s_c, double s_r) {
-  const double almost_two = 2. * (1. - 2.220446049250313e-16);
-  const double e_r = u_l + 0.5 * s_l;
-  const double e_l = u_r - 0.5 * s_r;
-  double slp = fabs(s_c);
-  double edge = u_c - 0.5 * s_c;
-  if ((edge - e_r) * (u_c - edge) < 0.) { edge = 0.5 * (edge + e_r); slp = min2(slp, fabs(edge - u_c) * almost_two); }
-  edge = u_c + 0.5 * s_c;
-  if ((edge - u_c) * (e_l - edge) < 0.) { edge = 0.5 * (edge + e_l); slp = min2(slp, fabs(edge - u_c) * almost_two); }
-  return fsign(slp, s_c);
-}
-__device__ double plm_extrapolate_slope(double h_l, double h_c, double h_neglect, double u_l, double u_c) {
-  const double hl = h_l + h_neglect, hc = h_c + h_neglect;
-  const double left_edge = (u_l * hc + u_c * hl) / (hl + hc);
-  return 2.0 * (u_c - left_edge);
-}
-
 
 // ---- the rolling k window of ALE_PLM_edge_values (MOM_ALE.F90:1549-1576) ---------------------------------------------
 // A lane walks its column top down holding, for the 0-based level kk in hand, h and one scalar at kk-1 (m), kk (c), kk+1 (p),

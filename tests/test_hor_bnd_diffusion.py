@@ -136,7 +136,12 @@ OPTS = [("default", {}), ("no_limiter", dict(APPLY_LIMITER=False)), ("limiter_re
         if (s, e) != ("PLM", False)] + \
        [("along_layer_nk2", dict(nk=2, thin=False)), ("neutral_interior", dict(neutral=True)), ("neutral_cfl", dict(neutral=True, KhTr=2.0e7, max_diff_CFL=2.5)),
         ("nk40", dict(nk=40, ni=12, nj=8, HBD_REMAPPING_SCHEME="PPM_H4")), ("nk75", dict(nk=75, ni=10, nj=6)),
-        ("nk100", dict(nk=100, ni=10, nj=6, HBD_REMAPPING_SCHEME="PPM_IH4", HBD_BOUNDARY_EXTRAP=True))]
+        ("nk100", dict(nk=100, ni=10, nj=6, HBD_REMAPPING_SCHEME="PPM_IH4", HBD_BOUNDARY_EXTRAP=True))] + \
+       [  # the shortest columns of the serial drivers: where build_reconstructions_1d takes a lower scheme, and loops of a single turn
+        ("nk4_cw_extrap", dict(nk=4, ni=10, nj=6, HBD_REMAPPING_SCHEME="PPM_CW", HBD_BOUNDARY_EXTRAP=True)),      # kept; one interior al
+        ("nk4_ih4", dict(nk=4, ni=10, nj=6, HBD_REMAPPING_SCHEME="PPM_IH4")),      # taken as PPM_H4: one interior edge, both ends on the same cells
+        ("nk5_ih4_extrap", dict(nk=5, ni=10, nj=6, HBD_REMAPPING_SCHEME="PPM_IH4", HBD_BOUNDARY_EXTRAP=True)),      # the smallest implicit solve, 6 rows
+        ("nk3_h4_extrap", dict(nk=3, ni=10, nj=6, HBD_REMAPPING_SCHEME="PPM_H4", HBD_BOUNDARY_EXTRAP=True))]      # taken as PLM, extrapolated as PLM
 HBD_KEYS = ("HBD_LINEAR_TRANSITION", "APPLY_LIMITER", "APPLY_LIMITER_REMAP", "HBD_BOUNDARY_EXTRAP", "HBD_REMAPPING_SCHEME")
 
 
