@@ -1103,8 +1103,9 @@ int mom6hip_tracer_hordiff_varmix(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_d
  * cs->unsupported[5]): Coef_h (:670-684) from fields->ebt_struct, inside the fluxes (:2406-2441).
  * Refused: NDIFF_TAPERING without NDIFF_INTERIOR_ONLY (the reference never reads the parameter then), unsupported[3] that differs from
  * cs->unsupported[5].
- * Not provided (refused by name, any nonzero `unsupported`): NDIFF_CONTINUOUS = False (the discontinuous reconstructions),
- * NDIFF_USE_UNMASKED_TRANSPORT_BUG, the flux / tendency diagnostics.
+ * NDIFF_CONTINUOUS = False (unsupported[0], the discontinuous reconstructions) is taken by mom6hip_tracer_hordiff_neutral_discontinuous
+ * with mom6hip_ndiff_discontinuous_cs_t, and refused by name without that struct.
+ * Not provided (refused by name, any nonzero `unsupported`): NDIFF_USE_UNMASKED_TRANSPORT_BUG, the flux / tendency diagnostics.
  */
 typedef struct mom6hip_neutral_diffusion_cs {
   double ref_pres;             /* NDIFF_REF_PRES [R L2 T-2] (-1, the default: the pressure of the interface) */
@@ -1186,6 +1187,46 @@ int mom6hip_tracer_hordiff_hbd(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff
                                const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_hordiff_fields_t *fields, const double *h,
                                const mom6hip_eos_t *eos, const double *p_surf, double dt, double *const *tr, const double *conc_underflow,
                                int32_t ntr, int32_t idx_T, int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats);
+
+/*
+ * NDIFF_CONTINUOUS = False (nd->unsupported[0]): the parameters neutral_diffusion_init reads for the discontinuous reconstructions
+ * (:219-277).  Provided: build_reconstructions_1d of T, S and every tracer with NDIFF_REMAPPING_SCHEME PLM, PPM_H4 or PPM_IH4
+ * (REMAPPING_ANSWER_DATE >= 20190101, no NDIFF_BOUNDARY_EXTRAP), mark_unstable_cells (:1841),
+ * find_neutral_surface_positions_discontinuous (:1604) with NEUTRAL_POS_METHOD 1, 2 or 3 and DELTA_RHO_FORM full, mid_pressure or
+ * local_pressure, HARD_FAIL_HEFF both ways (True: a negative sublayer thickness is returned as an error with the reference's message),
+ * the discontinuous branch of neutral_surface_flux (:2442-2471) and the update of the tracers over 4 nk surfaces, with NDIFF_REF_PRES,
+ * NDIFF_INTERIOR_ONLY, RECALC_NEUTRAL_SURF and both forms of NDIFF_ANSWER_DATE as the continuous branch takes them.
+ * Refused by name: any other scheme, NDIFF_BOUNDARY_EXTRAP, REMAPPING_ANSWER_DATE < 20190101, NEUTRAL_POS_METHOD 0 or 4,
+ * NEUTRAL_POS_METHOD 2 with DELTA_RHO_FORM full (the reference reads derivatives it never sets), and NDIFF_TAPERING or
+ * KHTR_USE_EBT_STRUCT with this branch.  NDIFF_DEBUG only prints and is ignored.
+ */
+#define MOM6HIP_DELTA_RHO_FULL 0
+#define MOM6HIP_DELTA_RHO_MID_PRESSURE 1
+#define MOM6HIP_DELTA_RHO_LOCAL_PRESSURE 2
+typedef struct mom6hip_ndiff_discontinuous_cs {
+  double drho_tol;             /* NDIFF_DRHO_TOL [R] (1e-10) */
+  double x_tol;                /* NDIFF_X_TOL (0) */
+  double reserved0[2];
+  int32_t remap_scheme;        /* NDIFF_REMAPPING_SCHEME as MOM6HIP_REMAP_* (MOM6HIP_REMAP_PLM, the reference's default) */
+  int32_t boundary_extrap;     /* NDIFF_BOUNDARY_EXTRAP (0; refused if set) */
+  int32_t remap_answer_date;   /* REMAPPING_ANSWER_DATE (99991231; refused below 20190101) */
+  int32_t neutral_pos_method;  /* NEUTRAL_POS_METHOD (3) */
+  int32_t delta_rho_form;      /* DELTA_RHO_FORM as MOM6HIP_DELTA_RHO_* (mid_pressure) */
+  int32_t max_iter;            /* NDIFF_MAX_ITER (10) */
+  int32_t hard_fail_heff;      /* HARD_FAIL_HEFF (1) */
+  int32_t initialized;
+  int32_t reserved1[4];
+} mom6hip_ndiff_discontinuous_cs_t;
+
+/* mom6hip_tracer_hordiff_hbd with the parameters of the discontinuous reconstructions: ndd is read when nd->unsupported[0]
+ * (NDIFF_CONTINUOUS = False) is set and may be NULL otherwise; hbd may be NULL when cs->unsupported[1] is 0.  Without ndd -- through
+ * any other entry point -- nd->unsupported[0] stays refused. */
+int mom6hip_tracer_hordiff_neutral_discontinuous(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs,
+                                                 const mom6hip_hor_bnd_diffusion_cs_t *hbd, const mom6hip_neutral_diffusion_cs_t *nd,
+                                                 const mom6hip_ndiff_discontinuous_cs_t *ndd, const mom6hip_hordiff_fields_t *fields,
+                                                 const double *h, const mom6hip_eos_t *eos, const double *p_surf, double dt, double *const *tr,
+                                                 const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S, int32_t memspace,
+                                                 mom6hip_hordiff_stats_t *stats);
 
 /* ---- MOM_hor_visc ----------------------------------------------------------------------------- */
 

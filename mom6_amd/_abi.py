@@ -190,6 +190,18 @@ class HorBndDiffusionCS(C.Structure):
                 ("reserved", C.c_int32 * 8)]
 
 
+class NdiffDiscontinuousCS(C.Structure):
+    """mom6hip_ndiff_discontinuous_cs_t (include/mom6hip.h)."""
+    _fields_ = [("drho_tol", C.c_double), ("x_tol", C.c_double), ("reserved0", C.c_double * 2), ("remap_scheme", C.c_int32),
+                ("boundary_extrap", C.c_int32), ("remap_answer_date", C.c_int32), ("neutral_pos_method", C.c_int32),
+                ("delta_rho_form", C.c_int32), ("max_iter", C.c_int32), ("hard_fail_heff", C.c_int32), ("initialized", C.c_int32),
+                ("reserved1", C.c_int32 * 4)]
+
+
+# NDIFF_REMAPPING_SCHEME values and DELTA_RHO_FORM names the discontinuous neutral branch provides
+NDIFF_REMAPPING_SCHEMES = ("PLM", "PPM_H4", "PPM_IH4")
+DELTA_RHO_FORMS = {"full": 0, "mid_pressure": 1, "local_pressure": 2}
+
 # HBD_REMAPPING_SCHEME values mom6hip_tracer_hordiff_hbd provides
 HBD_REMAPPING_SCHEMES = ("PCM", "PLM", "PPM_H4", "PPM_IH4", "PPM_CW")
 

@@ -667,18 +667,47 @@ __global__ __launch_bounds__(64) void nd_update_kernel(NDArgs A) {
 
 namespace m6 {
 
+int neutral_disc_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_ndiff_discontinuous_cs_t *ndd,
+                        const mom6hip_eos_t *eos, const double *h, const double *p_surf, const double *h_ML, const double *khdt_x,
+                        const double *khdt_y, int num_itts, double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu,
+                        int idx_T, int idx_S, int *halo_updates);
+
+// the update of a batch's tracers from the tendencies (symmetric) or the fluxes its flux kernels left, for the discontinuous branch
+// (neutral_diffusion_disc.hip), whose surfaces, fluxes and tendencies are laid out as nd_flux_kernel's: ns = 4 nk there
+int nd_launch_update(mom6hip_ctx_t *ctx, const double *h, double scale, int ns, bool symmetric, unsigned char *const *KoL,
+                     unsigned char *const *KoR, double *const *Flx, double *const *tend, long flx_stride, const double *const *khdt,
+                     double *const *t, const double *cu, int nb) {
+  NDArgs A = {};
+  const m6::GridDev g = ctx->g;
+  A.g = g; A.h = h; A.scale = scale; A.ns = ns; A.symmetric = symmetric; A.flx_stride = flx_stride; A.nb = nb;
+  for (int d = 0; d < 2; d++) {
+    A.KoL[d] = KoL[d]; A.KoR[d] = KoR[d]; A.Flx[d] = Flx[d]; A.khdt[d] = khdt[d];
+    A.tend[d][0] = tend[2 * d]; A.tend[d][1] = tend[2 * d + 1];
+  }
+  for (int z = 0; z < ND_BATCH; z++) { A.t[z] = z < nb ? t[z] : nullptr; A.cu[z] = z < nb ? cu[z] : 0.; }
+  const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1, nk = g.nk;
+  if (symmetric) hipLaunchKernelGGL(nd_update_sym_kernel, dim3((ni + 255) / 256, nj, nk * nb), dim3(256), 0, ctx->stream, A);
+  else hipLaunchKernelGGL(nd_update_kernel<false>, dim3((ni + 63) / 64, nj, nb), dim3(64), sizeof(double) * 64 * nk, ctx->stream, A);
+  M6_HIP(hipGetLastError());
+  return 0;
+}
+
 // the neutral branch of tracer_hordiff (MOM_tracer_hor_diff.F90:474-534) on device arrays; khdt_x, khdt_y and the iteration count
 // are those tracer_hordiff has formed; ebt_struct is VarMix%ebt_struct with KHTR_USE_EBT_STRUCT (tracer_hordiff has checked that
 // nd->unsupported[3] says the same) and null without
 int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_eos_t *eos, const double *h,
                    const double *p_surf, const double *h_ML, const double *ebt_struct, const double *khdt_x, const double *khdt_y, int num_itts,
                    double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S,
-                   int *halo_updates) {
+                   int *halo_updates, const mom6hip_ndiff_discontinuous_cs_t *ndd) {
   static const char *names[8] = {"NDIFF_CONTINUOUS = False", "(free)", "NDIFF_TAPERING", "KHTR_USE_EBT_STRUCT",
                                  "NDIFF_USE_UNMASKED_TRANSPORT_BUG", "the neutral-diffusion diagnostics", "(free)", "(free)"};
   const int ntr = (int)d_tr.size();
   M6_REQUIRE(nd != nullptr && eos != nullptr, "tracer_hordiff: USE_NEUTRAL_DIFFUSION needs the neutral_diffusion control structure and tv%%eqn_of_state");
   M6_REQUIRE(nd->initialized, "neutral_diffusion: the control structure is not initialised");
+  if (nd->unsupported[0] && ndd) {      // NDIFF_CONTINUOUS = False with its parameters: neutral_diffusion_disc.hip
+    for (int q = 4; q < 8; q++) M6_REQUIRE(!nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
+    return neutral_disc_branch(ctx, st, nd, ndd, eos, h, p_surf, h_ML, khdt_x, khdt_y, num_itts, I_numitts, d_tr, cu, idx_T, idx_S, halo_updates);
+  }
   // unsupported[2] (tapering) and [3] (KhTh_use_ebt_struct) are the switches of the two modes of the fluxes
   for (int q = 0; q < 8; q++) M6_REQUIRE(q == 2 || q == 3 || !nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
   const bool taper = nd->unsupported[2] != 0, ebt = ebt_struct != nullptr;

@@ -169,7 +169,7 @@ int epipycnal_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_epipycnal_cs_
 int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_eos_t *eos, const double *h,
                    const double *p_surf, const double *h_ML, const double *ebt_struct, const double *khdt_x, const double *khdt_y, int num_itts,
                    double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S,
-                   int *halo_updates);
+                   int *halo_updates, const mom6hip_ndiff_discontinuous_cs_t *ndd);
 int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_cs_t *hbd, const double *h, const double *h_ML,
                const double *ebt_struct, double KhTr_min, bool full_depth_khtr_min, const double *khdt_x, const double *khdt_y, int num_itts,
                double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int *halo_updates);
@@ -178,7 +178,8 @@ int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_c
 static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
                         const mom6hip_epipycnal_cs_t *epi, const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos,
                         const double *p_surf, double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
-                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_hor_bnd_diffusion_cs_t *hbd = nullptr);
+                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_hor_bnd_diffusion_cs_t *hbd = nullptr,
+                        const mom6hip_ndiff_discontinuous_cs_t *ndd = nullptr);
 
 extern "C" int mom6hip_tracer_hordiff_neutral(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
                                               const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, const double *p_surf,
@@ -212,10 +213,27 @@ extern "C" int mom6hip_tracer_hordiff_hbd(mom6hip_ctx_t *ctx, const mom6hip_trac
   return hordiff_impl(ctx, cs, nd, nullptr, F, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, stats, hbd);
 }
 
+// the same with the parameters of NDIFF_CONTINUOUS = False; hbd is read with USE_HORIZONTAL_BOUNDARY_DIFFUSION only
+extern "C" int mom6hip_tracer_hordiff_neutral_discontinuous(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs,
+                                                            const mom6hip_hor_bnd_diffusion_cs_t *hbd, const mom6hip_neutral_diffusion_cs_t *nd,
+                                                            const mom6hip_ndiff_discontinuous_cs_t *ndd, const mom6hip_hordiff_fields_t *F,
+                                                            const double *h, const mom6hip_eos_t *eos, const double *p_surf, double dt,
+                                                            double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
+                                                            int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats) {
+  M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
+  M6_REQUIRE(!(cs->unsupported[1] && cs->unsupported[2]),
+             "MOM_tracer_hor_diff: USE_HORIZONTAL_BOUNDARY_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!");      // :1735
+  M6_REQUIRE(!cs->unsupported[2], "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR is not provided by this entry point (mom6hip_tracer_hordiff_epipycnal takes it)");
+  M6_REQUIRE(!cs->unsupported[1] || hbd != nullptr, "tracer_hordiff: USE_HORIZONTAL_BOUNDARY_DIFFUSION needs its control structure (mom6hip_hor_bnd_diffusion_cs_t)");
+  return hordiff_impl(ctx, cs, nd, nullptr, F, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, stats,
+                      cs->unsupported[1] ? hbd : nullptr, ndd);
+}
+
 static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
                         const mom6hip_epipycnal_cs_t *epi, const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos,
                         const double *p_surf, double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
-                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_hor_bnd_diffusion_cs_t *hbd) {
+                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_hor_bnd_diffusion_cs_t *hbd,
+                        const mom6hip_ndiff_discontinuous_cs_t *ndd) {
   static const char *names[8] = {"USE_NEUTRAL_DIFFUSION", "USE_HORIZONTAL_BOUNDARY_DIFFUSION", "DIFFUSE_ML_TO_INTERIOR",
                                  "(free)", "(free)", "KHTR_USE_EBT_STRUCT", "offline khdt (do_online = false)",
                                  "the df_x / df_y flux diagnostics"};
@@ -328,7 +346,7 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
     const double *d_hml = (nd && nd->interior_only && F && F->h_ML) ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
     M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
     if (int rc = m6::neutral_branch(ctx, st, nd, eos, A.h, d_ps, d_hml, d_ebt, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, idx_T, idx_S,
-                                    &halo_updates))
+                                    &halo_updates, ndd))
       return rc;
   } else
   for (int itt = 1; itt <= num_itts; itt++) {      // :540-614

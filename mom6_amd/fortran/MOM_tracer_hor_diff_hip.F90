@@ -11,7 +11,9 @@
 !! (mom6hip_tracer_hordiff_hbd), with KHTR_USE_EBT_STRUCT the interface coefficients of both that decay with VarMix%ebt_struct
 !! (FULL_DEPTH_KHTR_MIN), and with DIFFUSE_ML_TO_INTERIOR the epipycnal diffusion between the variable-density layers and the interior
 !! of a layered run (tracer_epipycnal_ML_diff :700, ML_KHTR_SCALE, HOR_DIFF_ANSWER_DATE, HOR_DIFF_LIMIT_BUG;
-!! mom6hip_tracer_hordiff_epipycnal).  NDIFF_CONTINUOUS = False, NDIFF_USE_UNMASKED_TRANSPORT_BUG, offline khdt arrays and the
+!! mom6hip_tracer_hordiff_epipycnal).  NDIFF_CONTINUOUS = False goes to mom6hip_tracer_hordiff_neutral_discontinuous with the
+!! parameters of MOM_neutral_diffusion.F90:219-277 (the interface takes hbd and ndd by reference: CS%hbd stands in where HBD is off).
+!! NDIFF_USE_UNMASKED_TRANSPORT_BUG, offline khdt arrays and the
 !! df_x / df_y flux diagnostics stop with a FATAL error.
 !!
 !! Compiled INSIDE a MOM6 source tree in place of src/tracer/MOM_tracer_hor_diff.F90; here against tests/fortran/stubs.
@@ -58,6 +60,7 @@ type, public :: tracer_hor_diff_CS ; private
   logical :: first_call = .true.
   logical :: recalc_neutral_surf  !< If true, recalculate the neutral surfaces if CFL has been exceeded
   type(mom6hip_neutral_diffusion_cs_t) :: nd   !< neutral_diffusion_CS as the library reads it
+  type(mom6hip_ndiff_discontinuous_cs_t) :: ndd !< its parameters of NDIFF_CONTINUOUS = False (MOM_neutral_diffusion.F90:219-277)
   type(mom6hip_epipycnal_cs_t) :: epi          !< the parameters of tracer_epipycnal_ML_diff as the library reads them
   type(mom6hip_hor_bnd_diffusion_cs_t) :: hbd  !< hbd_CS (USE_HORIZONTAL_BOUNDARY_DIFFUSION) as the library reads it
   type(mom6hip_eos_t) :: eos                   !< the equation of state tracer_hor_diff_init was given
@@ -186,6 +189,11 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
       rc = mom6hip_tracer_hordiff_epipycnal(ctx, ccs, CS%epi, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
                                             CS%eos, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
                                             int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats)
+    elseif (CS%use_neutral_diffusion .and. CS%nd%unsupported(1) /= 0) then      ! NDIFF_CONTINUOUS = False (CS%hbd is read with HBD only)
+      rc = mom6hip_tracer_hordiff_neutral_discontinuous(ctx, ccs, CS%hbd, CS%nd, CS%ndd, fld, &
+                                      mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
+                                      CS%eos, p_surf, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
+                                      int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats)
     elseif (CS%use_hor_bnd_diffusion) then
       rc = mom6hip_tracer_hordiff_hbd(ctx, ccs, CS%hbd, CS%nd, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
                                       CS%eos, p_surf, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
@@ -198,6 +206,10 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   elseif (CS%Diffuse_ML_interior) then
     rc = mom6hip_tracer_hordiff_epipycnal(mom6hip_shared_context(G, GV), ccs, CS%epi, fld, c_loc(h), CS%eos, dt, tr, c_loc(cu), &
                                           int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats)
+  elseif (CS%use_neutral_diffusion .and. CS%nd%unsupported(1) /= 0) then
+    rc = mom6hip_tracer_hordiff_neutral_discontinuous(mom6hip_shared_context(G, GV), ccs, CS%hbd, CS%nd, CS%ndd, fld, c_loc(h), CS%eos, &
+                                    p_surf, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), &
+                                    MOM6HIP_MEM_HOST, stats)
   elseif (CS%use_hor_bnd_diffusion) then
     rc = mom6hip_tracer_hordiff_hbd(mom6hip_shared_context(G, GV), ccs, CS%hbd, CS%nd, fld, c_loc(h), CS%eos, p_surf, dt, tr, c_loc(cu), &
                                     int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats)
@@ -295,7 +307,7 @@ subroutine tracer_hor_diff_init(Time, G, GV, US, param_file, diag, EOS, diabatic
   if (CS%use_neutral_diffusion) then
     call get_param(param_file, "MOM_neutral_diffusion", "NDIFF_CONTINUOUS", flag, &
                    "If true, uses a continuous reconstruction of T and S when finding neutral surfaces.", default=.true.)
-    call refuse(.not.flag, "NDIFF_CONTINUOUS = False")
+    CS%nd%unsupported(1) = merge(0, 1, flag)      ! .not.CS%continuous_reconstruction
     call get_param(param_file, "MOM_neutral_diffusion", "NDIFF_REF_PRES", CS%nd%ref_pres, &
                    "The reference pressure (Pa) used for the derivatives of the equation of state. If negative (default), "//&
                    "local pressure is used.", units="Pa", default=-1., scale=US%Pa_to_RL2_T2)
@@ -314,6 +326,7 @@ subroutine tracer_hor_diff_init(Time, G, GV, US, param_file, diag, EOS, diabatic
     call refuse(flag, "NDIFF_USE_UNMASKED_TRANSPORT_BUG")
     call get_param(param_file, "MOM_neutral_diffusion", "NDIFF_ANSWER_DATE", CS%nd%ndiff_answer_date, &
                    "The vintage of the order of arithmetic to use for the neutral diffusion.", default=20240101)
+    if (CS%nd%unsupported(1) /= 0) call ndiff_discontinuous_init()
     call mom6hip_read_eos(param_file, CS%eos, "neutral_diffusion_init")
     CS%nd%initialized = 1
   endif
@@ -369,6 +382,73 @@ contains
     call refuse(flag, "HBD_DEBUG")
     CS%hbd%initialized = 1
   end subroutine hor_bnd_diffusion_init
+
+  !> neutral_diffusion_init :219-277: the parameters read with NDIFF_CONTINUOUS = False, names, units and defaults
+  subroutine ndiff_discontinuous_init()
+    character(len=40) :: nd_mdl = "MOM_neutral_diffusion"
+    character(len=80) :: string
+    integer :: default_answer_date
+    logical :: debug
+    call refuse(CS%nd%unsupported(3) /= 0, "NDIFF_TAPERING with NDIFF_CONTINUOUS = False")
+    call refuse(CS%KhTr_use_ebt_struct, "KHTR_USE_EBT_STRUCT with NDIFF_CONTINUOUS = False")
+    call get_param(param_file, nd_mdl, "DEFAULT_ANSWER_DATE", default_answer_date, &
+                   "This sets the default value for the various _ANSWER_DATE parameters.", default=99991231)
+    call get_param(param_file, nd_mdl, "NDIFF_BOUNDARY_EXTRAP", flag, &
+                   "Extrapolate at the top and bottommost cells, otherwise assume boundaries are piecewise constant", default=.false.)
+    call refuse(flag, "NDIFF_BOUNDARY_EXTRAP = True")
+    call get_param(param_file, nd_mdl, "NDIFF_REMAPPING_SCHEME", string, &
+                   "This sets the reconstruction scheme used for vertical remapping for all variables.", default="PLM")
+    select case (trim(string))
+      case ("PLM") ; CS%ndd%remap_scheme = MOM6HIP_REMAP_PLM
+      case ("PPM_H4") ; CS%ndd%remap_scheme = MOM6HIP_REMAP_PPM_H4
+      case ("PPM_IH4") ; CS%ndd%remap_scheme = MOM6HIP_REMAP_PPM_IH4
+      case default ; call refuse(.true., "NDIFF_REMAPPING_SCHEME = "//trim(string))
+    end select
+    call get_param(param_file, nd_mdl, "REMAPPING_ANSWER_DATE", CS%ndd%remap_answer_date, &
+                   "The vintage of the expressions and order of arithmetic to use for remapping.", default=default_answer_date, &
+                   do_not_log=.not.GV%Boussinesq)
+    if (.not.GV%Boussinesq) CS%ndd%remap_answer_date = max(CS%ndd%remap_answer_date, 20230701)
+    call refuse(CS%ndd%remap_answer_date < 20190101, "REMAPPING_ANSWER_DATE < 20190101 with NDIFF_CONTINUOUS = False")
+    call get_param(param_file, nd_mdl, "NEUTRAL_POS_METHOD", CS%ndd%neutral_pos_method, &
+                   "Method used to find the neutral position                 \n"// &
+                   "1. Delta_rho varies linearly, find 0 crossing            \n"// &
+                   "2. Alpha and beta vary linearly from top to bottom,      \n"// &
+                   "   Newton's method for neutral position                  \n"// &
+                   "3. Full nonlinear equation of state, use regula falsi    \n"// &
+                   "   for neutral position", default=3)
+    if (CS%ndd%neutral_pos_method > 4 .or. CS%ndd%neutral_pos_method < 0) call MOM_error(FATAL, "Invalid option for NEUTRAL_POS_METHOD")
+    call refuse(CS%ndd%neutral_pos_method == 0 .or. CS%ndd%neutral_pos_method == 4, "NEUTRAL_POS_METHOD = 0 or 4")
+    call get_param(param_file, nd_mdl, "DELTA_RHO_FORM", string, &
+                   "Determine how the difference in density is calculated    \n"// &
+                   "  full       : Difference of in-situ densities           \n"// &
+                   "  no_pressure: Calculated from dRdT, dRdS, but no        \n"// &
+                   "               pressure dependence", default="mid_pressure")
+    select case (trim(string))
+      case ("full") ; CS%ndd%delta_rho_form = MOM6HIP_DELTA_RHO_FULL
+      case ("mid_pressure") ; CS%ndd%delta_rho_form = MOM6HIP_DELTA_RHO_MID_PRESSURE
+      case ("local_pressure") ; CS%ndd%delta_rho_form = MOM6HIP_DELTA_RHO_LOCAL_PRESSURE
+      case default ; call MOM_error(FATAL, "delta_rho_form is not recognized")
+    end select
+    call refuse(CS%ndd%neutral_pos_method == 2 .and. CS%ndd%delta_rho_form == MOM6HIP_DELTA_RHO_FULL, &
+                "NEUTRAL_POS_METHOD = 2 with DELTA_RHO_FORM = full (the reference reads density derivatives this form never sets)")
+    if (CS%ndd%neutral_pos_method > 1) then
+      call get_param(param_file, nd_mdl, "NDIFF_DRHO_TOL", CS%ndd%drho_tol, &
+                     "Sets the convergence criterion for finding the neutral position within a layer in kg m-3.", &
+                     units="kg m-3", default=1.e-10, scale=US%kg_m3_to_R)
+      call get_param(param_file, nd_mdl, "NDIFF_X_TOL", CS%ndd%x_tol, &
+                     "Sets the convergence criterion for a change in nondimensional position within a layer.", &
+                     units="nondim", default=0.)
+      call get_param(param_file, nd_mdl, "NDIFF_MAX_ITER", CS%ndd%max_iter, &
+                     "The maximum number of iterations to be done before exiting the iterative loop to find the neutral surface", &
+                     default=10)
+    endif
+    call get_param(param_file, nd_mdl, "DEBUG", debug, default=.false., do_not_log=.true.)
+    call get_param(param_file, nd_mdl, "NDIFF_DEBUG", debug, &
+                   "Turns on verbose output for discontinuous neutral diffusion routines.", default=debug)      ! (only prints: ignored)
+    call get_param(param_file, nd_mdl, "HARD_FAIL_HEFF", flag, "Bring down the model if a problem with heff is detected", default=.true.)
+    CS%ndd%hard_fail_heff = merge(1, 0, flag)
+    CS%ndd%initialized = 1
+  end subroutine ndiff_discontinuous_init
 
   subroutine refuse(on, name)
     logical,          intent(in) :: on

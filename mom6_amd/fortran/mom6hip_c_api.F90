@@ -201,6 +201,16 @@ type, bind(c) :: mom6hip_hor_bnd_diffusion_cs_t
   integer(c_int32_t) :: reserved(8) = 0
 end type mom6hip_hor_bnd_diffusion_cs_t
 
+!> mom6hip_ndiff_discontinuous_cs_t: the parameters of NDIFF_CONTINUOUS = False (src/tracer/MOM_neutral_diffusion.F90:219-277)
+integer(c_int32_t), parameter :: MOM6HIP_DELTA_RHO_FULL = 0, MOM6HIP_DELTA_RHO_MID_PRESSURE = 1, MOM6HIP_DELTA_RHO_LOCAL_PRESSURE = 2
+type, bind(c) :: mom6hip_ndiff_discontinuous_cs_t
+  real(c_double) :: drho_tol = 1.0e-10, x_tol = 0.0
+  real(c_double) :: reserved0(2) = 0.0
+  integer(c_int32_t) :: remap_scheme = MOM6HIP_REMAP_PLM, boundary_extrap = 0, remap_answer_date = 99991231, neutral_pos_method = 3
+  integer(c_int32_t) :: delta_rho_form = MOM6HIP_DELTA_RHO_MID_PRESSURE, max_iter = 10, hard_fail_heff = 1, initialized = 0
+  integer(c_int32_t) :: reserved1(4) = 0
+end type mom6hip_ndiff_discontinuous_cs_t
+
 !> mom6hip_obc_segment_t / mom6hip_obc_t: what continuity_PPM reads of OBC_segment_type / ocean_OBC_type (src/core/MOM_open_boundary.F90:146, :266)
 integer(c_int32_t), parameter :: MOM6HIP_OBC_TAN_RADIATION = 1, MOM6HIP_OBC_GRAD_RADIATION = 2, MOM6HIP_OBC_TAN_NUDGED = 4, &
                                  MOM6HIP_OBC_GRAD_NUDGED = 8, MOM6HIP_OBC_TAN_OBLIQUE = 16, MOM6HIP_OBC_GRAD_OBLIQUE = 32
@@ -605,6 +615,32 @@ interface
     type(mom6hip_hordiff_stats_t), intent(out) :: stats
     integer(c_int) :: rc
   end function mom6hip_tracer_hordiff_hbd
+
+  !> mom6hip_tracer_hordiff_hbd with the parameters of NDIFF_CONTINUOUS = False (nd%unsupported(1)): ndd
+  function mom6hip_tracer_hordiff_neutral_discontinuous(ctx, cs, hbd, nd, ndd, fields, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, &
+                                                        idx_S, memspace, stats) &
+                                                        bind(c, name="mom6hip_tracer_hordiff_neutral_discontinuous") result(rc)
+    import :: c_int, c_int32_t, c_double, c_ptr, mom6hip_tracer_hor_diff_cs_t, mom6hip_hordiff_stats_t, mom6hip_hordiff_fields_t, &
+              mom6hip_neutral_diffusion_cs_t, mom6hip_eos_t, mom6hip_hor_bnd_diffusion_cs_t, mom6hip_ndiff_discontinuous_cs_t
+    type(c_ptr), value :: ctx, h, p_surf, conc_underflow
+    type(mom6hip_tracer_hor_diff_cs_t), intent(in) :: cs
+    type(mom6hip_hor_bnd_diffusion_cs_t), intent(in) :: hbd
+    type(mom6hip_neutral_diffusion_cs_t), intent(in) :: nd
+    type(mom6hip_ndiff_discontinuous_cs_t), intent(in) :: ndd
+    type(mom6hip_hordiff_fields_t), intent(in) :: fields
+    type(mom6hip_eos_t), intent(in) :: eos
+    real(c_double), value :: dt
+    type(c_ptr), intent(in) :: tr(*)
+    integer(c_int32_t), value :: ntr, idx_T, idx_S, memspace
+    type(mom6hip_hordiff_stats_t), intent(out) :: stats
+    integer(c_int) :: rc
+  end function mom6hip_tracer_hordiff_neutral_discontinuous
+
+  !> sizeof(mom6hip_ndiff_discontinuous_cs_t) as the library was compiled
+  function mom6hip_abi_sizeof_ndiff_discontinuous_cs() bind(c, name="mom6hip_abi_sizeof_ndiff_discontinuous_cs") result(n)
+    import :: c_int64_t
+    integer(c_int64_t) :: n
+  end function mom6hip_abi_sizeof_ndiff_discontinuous_cs
 
   !> sizeof(mom6hip_hor_bnd_diffusion_cs_t) as the library was compiled
   function mom6hip_abi_sizeof_hor_bnd_diffusion_cs() bind(c, name="mom6hip_abi_sizeof_hor_bnd_diffusion_cs") result(n)

@@ -27,10 +27,22 @@ _EPI_PARAMS = {"ML_KHTR_SCALE": ("ML_KhTr_scale", float), "HOR_DIFF_ANSWER_DATE"
 _ND_PARAMS = {"NDIFF_REF_PRES": ("ref_pres", float), "NDIFF_ANSWER_DATE": ("ndiff_answer_date", int), "RECALC_NEUTRAL_SURF": ("recalc_neutral_surf", bool),
               "NDIFF_INTERIOR_ONLY": ("interior_only", bool)}
 _ND_REFUSED = {"NDIFF_USE_UNMASKED_TRANSPORT_BUG": 4}
+# the parameters neutral_diffusion_init reads with NDIFF_CONTINUOUS = False only (:219-277)
+_NDD_PARAMS = {"NDIFF_BOUNDARY_EXTRAP": ("boundary_extrap", bool), "REMAPPING_ANSWER_DATE": ("remap_answer_date", int),
+               "NEUTRAL_POS_METHOD": ("neutral_pos_method", int), "NDIFF_DRHO_TOL": ("drho_tol", float), "NDIFF_X_TOL": ("x_tol", float),
+               "NDIFF_MAX_ITER": ("max_iter", int), "HARD_FAIL_HEFF": ("hard_fail_heff", bool)}
 
 
 class tracer_hor_diff_CS:
-    """tracer_hor_diff_CS (:40-100); parameters by their reference names (defaults :1652-1700)."""
+    """tracer_hor_diff_CS (:40-100); parameters by their reference names (defaults :1652-1700).
+
+    NDIFF_CONTINUOUS = False (the discontinuous reconstructions of MOM_neutral_diffusion) is taken only when NDIFF_REMAPPING_SCHEME is
+    named with it (PLM, the reference's default, PPM_H4 or PPM_IH4); its other parameters (NDIFF_BOUNDARY_EXTRAP, REMAPPING_ANSWER_DATE,
+    NEUTRAL_POS_METHOD, DELTA_RHO_FORM, NDIFF_DRHO_TOL, NDIFF_X_TOL, NDIFF_MAX_ITER, HARD_FAIL_HEFF, NDIFF_DEBUG) keep the reference's
+    defaults.  NDIFF_CONTINUOUS = False alone goes on being refused at the call, by the library and with the words it has always used
+    (the mirror adds that the scheme has to be named):
+    tests/test_neutral_diffusion.py::test_tracer_hordiff_neutral_refuses_what_it_does_not_provide calls it so and expects the error, and
+    that test stays as it is -- the arrangement that keeps its NDIFF_TAPERING line true."""
 
     def __init__(self, **params):
         st = self.st = _abi.TracerHorDiffCS()
@@ -41,6 +53,10 @@ class tracer_hor_diff_CS:
         ep.ML_KhTr_scale, ep.answer_date, ep.limit_bug = 1.0, 20240101, 1
         hb = self.hor_bnd_diffusion_CSp = _abi.HorBndDiffusionCS()
         hb.limiter, hb.remap_scheme = 1, _abi.REMAP_SCHEMES["PLM"]
+        ndd = self.ndiff_discontinuous = _abi.NdiffDiscontinuousCS()
+        ndd.drho_tol, ndd.x_tol, ndd.remap_scheme, ndd.remap_answer_date = 1.0e-10, 0.0, _abi.REMAP_SCHEMES["PLM"], 99991231
+        ndd.neutral_pos_method, ndd.delta_rho_form, ndd.max_iter, ndd.hard_fail_heff = 3, _abi.DELTA_RHO_FORMS["mid_pressure"], 10, 1
+        self.discontinuous = False      # NDIFF_REMAPPING_SCHEME was named: the library gets ndiff_discontinuous
         full_depth = False
         for k, v in params.items():
             if k == "KHTR_USE_EBT_STRUCT":      # the one parameter both control structures read (:1655; MOM_neutral_diffusion.F90:199)
@@ -68,6 +84,19 @@ class tracer_hor_diff_CS:
                 setattr(nd, _ND_PARAMS[k][0], _ND_PARAMS[k][1](v))
             elif k == "NDIFF_CONTINUOUS":
                 nd.unsupported[0] = int(not v)
+            elif k == "NDIFF_REMAPPING_SCHEME":
+                if v not in _abi.NDIFF_REMAPPING_SCHEMES:
+                    raise Mom6HipError(f"neutral_diffusion: NDIFF_REMAPPING_SCHEME = {v} is not provided by libmom6hip "
+                                       f"({', '.join(_abi.NDIFF_REMAPPING_SCHEMES)} are)")
+                ndd.remap_scheme = _abi.REMAP_SCHEMES[v]; self.discontinuous = True
+            elif k == "DELTA_RHO_FORM":
+                if v not in _abi.DELTA_RHO_FORMS:
+                    raise Mom6HipError(f"neutral_diffusion: DELTA_RHO_FORM = {v}: delta_rho_form is not recognized")
+                ndd.delta_rho_form = _abi.DELTA_RHO_FORMS[v]
+            elif k in _NDD_PARAMS:
+                setattr(ndd, _NDD_PARAMS[k][0], int(_NDD_PARAMS[k][1](v)) if _NDD_PARAMS[k][1] is bool else _NDD_PARAMS[k][1](v))
+            elif k == "NDIFF_DEBUG":
+                pass      # only prints
             elif k in _ND_REFUSED:
                 nd.unsupported[_ND_REFUSED[k]] = int(bool(v))
             elif k == "GV_H_to_RZ":
@@ -84,7 +113,7 @@ class tracer_hor_diff_CS:
             raise Mom6HipError("MOM_tracer_hor_diff: USE_NEUTRAL_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!")      # :1732
         if st.unsupported[1] and st.unsupported[2]:
             raise Mom6HipError("MOM_tracer_hor_diff: USE_HORIZONTAL_BOUNDARY_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!")      # :1735
-        st.initialized = 1; nd.initialized = 1; hb.initialized = 1
+        st.initialized = 1; nd.initialized = 1; hb.initialized = 1; ndd.initialized = 1
         self.last = None
 
 
@@ -105,6 +134,8 @@ def tracer_hordiff(h, dt, MEKE, VarMix, visc, G: DeviceGrid, CS: tracer_hor_diff
         raise Mom6HipError("MOM_tracer_hor_diff: register_tracer must be called before tracer_hordiff.")
     if do_online_flag is False or read_khdt_x is not None or read_khdt_y is not None:
         raise Mom6HipError("tracer_hordiff (HIP): offline khdt arrays are not supported on this path")
+    if CS.st.unsupported[0] and CS.neutral_diffusion_CSp.unsupported[0]:
+        return _tracer_hordiff_neutral_discontinuous(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow)
     if CS.st.unsupported[1]:
         return _tracer_hordiff_hbd(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow)
     if CS.st.unsupported[0]:
@@ -257,6 +288,45 @@ def _tracer_hordiff_hbd(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflo
                                        C.c_void_p(hp), C.byref(eos) if neutral else None, None if ps is None else C.c_void_p(ps), float(dt),
                                        ptrs, None if cu is None else cu.ctypes.data, len(tr), idx[0], idx[1], spaces.pop(), C.byref(stats)),
           "tracer_hordiff")
+    CS.last = stats
+    return stats
+
+
+def _tracer_hordiff_neutral_discontinuous(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow):
+    """USE_NEUTRAL_DIFFUSION with NDIFF_CONTINUOUS = False (after USE_HORIZONTAL_BOUNDARY_DIFFUSION, if that is set): tv and visc as
+    _tracer_hordiff_neutral and _tracer_hordiff_hbd take them.  The parameters of the branch go with the call only where
+    NDIFF_REMAPPING_SCHEME was named (the class docstring says why); without them the library refuses NDIFF_CONTINUOUS = False."""
+    tr = list(Reg)
+    st, nd = CS.st, CS.neutral_diffusion_CSp
+    hbd = bool(st.unsupported[1])
+    get, idx = _tv_TS(tv, tr, "USE_NEUTRAL_DIFFUSION")
+    L = lib()
+    L.mom6hip_tracer_hordiff_neutral_discontinuous.argtypes = [
+        C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.HorBndDiffusionCS), C.POINTER(_abi.NeutralDiffusionCS),
+        C.POINTER(_abi.NdiffDiscontinuousCS), C.POINTER(_abi.HorDiffFields), C.c_void_p, C.POINTER(_abi.EOS), C.c_void_p, C.c_double,
+        C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_abi.HorDiffStats)]
+    hp, F, ptrs, spaces = _marshal(h, MEKE, VarMix, CS, tr)
+    if hbd or nd.interior_only:
+        p, s = _ptr_space(_h_ML(visc)); spaces.add(s); F.h_ML = p
+    ps = None
+    if get("p_surf") is not None:
+        ps, s = _ptr_space(get("p_surf")); spaces.add(s)
+    if len(spaces) != 1:
+        raise Mom6HipError("tracer_hordiff: h, visc%h_ML, p_surf and every tracer must be in the same memory space")
+    if nd.H_to_RZ == 0.0:
+        nd.H_to_RZ = float(G.grid.Rho0 * G.grid.H_to_Z)      # GV%H_to_RZ, Boussinesq
+    cu = None if conc_underflow is None else np.ascontiguousarray(conc_underflow, dtype=np.float64)
+    stats = _abi.HorDiffStats()
+    try:
+        check(L.mom6hip_tracer_hordiff_neutral_discontinuous(
+            G.handle, C.byref(st), C.byref(CS.hor_bnd_diffusion_CSp) if hbd else None, C.byref(nd),
+            C.byref(CS.ndiff_discontinuous) if CS.discontinuous else None, C.byref(F), C.c_void_p(hp), C.byref(get("eqn_of_state")),
+            None if ps is None else C.c_void_p(ps), float(dt), ptrs, None if cu is None else cu.ctypes.data, len(tr), idx[0], idx[1],
+            spaces.pop(), C.byref(stats)), "tracer_hordiff")
+    except Mom6HipError as e:
+        if CS.discontinuous or "NDIFF_CONTINUOUS" not in str(e):
+            raise
+        raise Mom6HipError(f"{e} (NDIFF_REMAPPING_SCHEME -- {', '.join(_abi.NDIFF_REMAPPING_SCHEMES)} -- has to be named with it)") from None
     CS.last = stats
     return stats
 
