@@ -1328,9 +1328,16 @@ typedef struct mom6hip_visc_hooks {
  * state (slopes from the density gradients, vert_fill_TS, the slope-limited "safe" streamfunction) or without one (layer
  * densities), with stored slopes (VarMix%slope_x/y) or its own, Boussinesq; the work done against the stratification into
  * MEKE%GM_src (:1196-1209, :1552-1622); the transports into uhtr / vhtr and the thickness tendency (:607-620).
- * Refused: KHTH_USE_FGNV_STREAMFUNCTION, DETANGLE_INTERFACES, KH_ETA_CONST / KH_ETA_VEL_SCALE, USE_STANLEY_GM, MEKE_GEOMETRIC,
- * MEKE_GM_SRC_ALT, READ_KHTH, KHTH_USE_EBT_STRUCT, the QG Leith GM coefficient, DEPTH_SCALED_KHTH, USE_KH_IN_MEKE, SKEB,
- * KHTH_MAX_CFL <= 0, non-Boussinesq, tv%p_surf. */
+ * Also provided: KHTH_USE_FGNV_STREAMFUNCTION (the elliptic streamfunction of Ferrari et al., 2010) and DEPTH_SCALED_KHTH (Depth_fn_u / _v).
+ * KHTH_USE_EBT_STRUCT (unsupported[7]) with FULL_DEPTH_KHTH_MIN: the diffusivity of interface K >= 2 is that of the face times the
+ * mean of ebt_struct of layer K-1 at its two cells, floored by KHTH_MIN with full_depth_khth_min (:306-324, :410-428).
+ * MEKE_GEOMETRIC (unsupported[4]): with MEKE_Kh_out given (MEKE%Kh allocated) the face term is alpha*mean(MEKE%MEKE)/(SN + epsilon)
+ * in place of the MEKE%Kh term (:262-268), and MEKE%Kh is written on the compute domain (:446-468, the form with the parentheses,
+ * MEKE_GEOMETRIC_ANSWER_DATE >= 20190101).  MEKE_GM_SRC_ALT (unsupported[5]): MEKE%GM_src is the sum over interfaces of
+ * -0.25*H_to_RZ*KH*Slope**2*h*N2 of the four faces of a cell (:1633-1652), not the work integral.
+ * Refused, by name: DETANGLE_INTERFACES, KH_ETA_CONST / KH_ETA_VEL_SCALE, USE_STANLEY_GM, READ_KHTH, the QG Leith GM coefficient
+ * (unsupported[0]), USE_KH_IN_MEKE, USE_GME, SKEB, KHTH_MAX_CFL <= 0, non-Boussinesq, tv%p_surf, MEKE_GEOMETRIC_ANSWER_DATE < 20190101,
+ * MEKE_GEOMETRIC without MEKE%MEKE or without SN_u / SN_v, KHTH_USE_EBT_STRUCT without ebt_struct. */
 typedef struct mom6hip_thickness_diffuse_cs {
   double Khth;             /* KHTH [L2 T-1] (0) */
   double Khth_Min;         /* KHTH_MIN (0) */
@@ -1341,8 +1348,9 @@ typedef struct mom6hip_thickness_diffuse_cs {
   double KHTH_Slope_Cff;   /* KHTH_SLOPE_CFF (0): the Visbeck term needs L2u, L2v, SN_u, SN_v */
   double KhTh_fac;         /* MEKE%KhTh_fac (1): MEKE_KHTH_FAC, with MEKE_Kh */
   double FGNV_scale;       /* FGNV_FILTER_SCALE (1): the coefficient of the vertical smoothing term of the streamfunction equation (:58) */
-  double N2_floor;         /* (FGNV_STRAT_FLOOR * OMEGA)**2 (:2337): the floor of N2 in the elliptic solve */
-  double reserved0[2];
+  double N2_floor;         /* (FGNV_STRAT_FLOOR * OMEGA)**2 (:2337): the floor of N2 in the elliptic solve; read as 0 without use_FGNV_streamfn (:2336) */
+  double MEKE_GEOMETRIC_alpha;    /* MEKE_GEOMETRIC_ALPHA (0.05), with MEKE_GEOMETRIC */
+  double MEKE_GEOMETRIC_epsilon;  /* MEKE_GEOMETRIC_EPSILON [T-1] (1e-7): the least Eady growth rate, with MEKE_GEOMETRIC */
   int32_t thickness_diffuse;   /* THICKNESSDIFFUSE (0): without it (or with nothing to diffuse with, :192-194) the call returns at once */
   int32_t use_GM_work_bug;     /* USE_GM_WORK_BUG (0) */
   int32_t nkml;                /* GV%nkml (0): the streamfunction goes linearly to zero over max(nkml, 1) layers */
@@ -1351,8 +1359,9 @@ typedef struct mom6hip_thickness_diffuse_cs {
                                   Visbeck term is added when KHTH_SLOPE_CFF > 0 and L2u ... SN_v are given (:205-207, :242-249) */
   int32_t use_FGNV_streamfn;   /* KHTH_USE_FGNV_STREAMFUNCTION (0): the streamfunction of Ferrari et al. (2010) (:1105-1124, streamfn_solver :1673);
                                   needs cg1 (and g_prime without an equation of state) */
-  int32_t unsupported[10];     /* (unused), detangle, Kh_eta, Stanley, MEKE_GEOMETRIC, GM_src_alt, read_khth, ebt_struct / QG Leith,
-                                  Use_KH_in_MEKE, non-Boussinesq / p_surf / SKEB: any nonzero is refused */
+  int32_t unsupported[10];     /* QG Leith GM, detangle, Kh_eta, Stanley, [4] MEKE_GEOMETRIC, [5] GM_src_alt (MEKE_GM_SRC_ALT), read_khth,
+                                  [7] khth_use_ebt_struct (VarMix%khth_use_ebt_struct), Use_KH_in_MEKE, non-Boussinesq / p_surf / SKEB:
+                                  [4], [5] and [7] are switches the call takes, any other nonzero is refused */
   /* fields of MEKE and VarMix, in the memory space of the call; NULL = not allocated / not in use */
   const double *MEKE_Kh;       /* MEKE%Kh, h points 2-D (valid halo of 1) */
   const double *L2u, *L2v, *SN_u, *SN_v;      /* VarMix%L2u ... (use_Visbeck), u / v points 2-D */
@@ -1363,6 +1372,13 @@ typedef struct mom6hip_thickness_diffuse_cs {
   const double *cg1;           /* VarMix%cg1, h points 2-D (valid halo of 1): the first baroclinic gravity wave speed, with use_FGNV_streamfn */
   const double *g_prime;       /* GV%g_prime(1:nk+1) (HOST array): dzN2 without an equation of state (:1095), with use_FGNV_streamfn */
   const double *Depth_fn_u, *Depth_fn_v;      /* VarMix%Depth_fn_u / _v (DEPTH_SCALED_KHTH, :284-289), u / v points 2-D */
+  const double *MEKE_MEKE;     /* MEKE%MEKE, h points 2-D (valid halo of 1): the eddy energy, with MEKE_GEOMETRIC */
+  const double *ebt_struct;    /* VarMix%ebt_struct, h points, nk levels (valid halo of 1), with unsupported[7] */
+  double *MEKE_Kh_out;         /* MEKE%Kh with MEKE_GEOMETRIC (MEKE_Kh is not read then): written on the compute domain */
+  int32_t full_depth_khth_min;    /* FULL_DEPTH_KHTH_MIN (0; read with KHTH_USE_EBT_STRUCT and KHTH_MIN > 0, :2245) */
+  int32_t MEKE_GEOM_answer_date;  /* MEKE_GEOMETRIC_ANSWER_DATE (99991231): below 20190101 is refused */
+  int32_t MEKE_src_answer_date;   /* MEKE_GM_SRC_ANSWER_DATE (20240101): from 20240601 on the four faces are summed in pairs */
+  int32_t MEKE_src_slope_bug;     /* MEKE_GM_SRC_ALT_SLOPE_BUG (1): only the positive slopes are limited */
 } mom6hip_thickness_diffuse_cs_t;
 
 /* thickness_diffuse(h, uhtr, vhtr, tv, dt, G, GV, US, MEKE, VarMix, CDp, CS, STOCH)                               :133

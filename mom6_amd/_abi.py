@@ -261,19 +261,22 @@ class HorViscCS(C.Structure):
 
 
 # ---- MOM_thickness_diffuse --------------------------------------------------------------------------------
-THICKNESS_DIFFUSE_UNSUPPORTED = ("unused_0", "detangle_interfaces", "Kh_eta", "use_stanley_gm", "MEKE_GEOMETRIC", "GM_src_alt", "read_khth",
+THICKNESS_DIFFUSE_UNSUPPORTED = ("use_QG_Leith_GM", "detangle_interfaces", "Kh_eta", "use_stanley_gm", "MEKE_GEOMETRIC", "GM_src_alt", "read_khth",
                                  "ebt_struct", "Use_KH_in_MEKE", "non_Boussinesq")
-THICKNESS_DIFFUSE_FIELDS = ("MEKE_Kh", "L2u", "L2v", "SN_u", "SN_v", "Res_fn_u", "Res_fn_v", "slope_x", "slope_y", "MEKE_GM_src", "Rlay", "cg1", "g_prime", "Depth_fn_u", "Depth_fn_v")
+THICKNESS_DIFFUSE_SWITCHES = ("MEKE_GEOMETRIC", "GM_src_alt", "ebt_struct")      # the slots of `unsupported` the library takes as switches
+THICKNESS_DIFFUSE_FIELDS = ("MEKE_Kh", "L2u", "L2v", "SN_u", "SN_v", "Res_fn_u", "Res_fn_v", "slope_x", "slope_y", "MEKE_GM_src", "Rlay", "cg1", "g_prime", "Depth_fn_u", "Depth_fn_v",
+                            "MEKE_MEKE", "ebt_struct", "MEKE_Kh_out")
 
 
 class ThicknessDiffuseCS(C.Structure):
     """mom6hip_thickness_diffuse_cs_t (include/mom6hip.h)."""
     _fields_ = ([(n, C.c_double) for n in ("Khth", "Khth_Min", "Khth_Max", "max_Khth_CFL", "slope_max", "kappa_smooth", "KHTH_Slope_Cff", "KhTh_fac",
                                             "FGNV_scale", "N2_floor")]
-                + [("reserved0", C.c_double * 2)]
+                + [("MEKE_GEOMETRIC_alpha", C.c_double), ("MEKE_GEOMETRIC_epsilon", C.c_double)]
                 + [(n, C.c_int32) for n in ("thickness_diffuse", "use_GM_work_bug", "nkml", "initialized", "use_variable_mixing", "use_FGNV_streamfn")]
                 + [("unsupported", C.c_int32 * 10)]
-                + [(n, C.c_void_p) for n in THICKNESS_DIFFUSE_FIELDS])
+                + [(n, C.c_void_p) for n in THICKNESS_DIFFUSE_FIELDS]
+                + [(n, C.c_int32) for n in ("full_depth_khth_min", "MEKE_GEOM_answer_date", "MEKE_src_answer_date", "MEKE_src_slope_bug")])
 
 
 MIXEDLAYER_RESTRAT_UNSUPPORTED = ("use_Bodner", "use_Stanley_ML", "non_Boussinesq")

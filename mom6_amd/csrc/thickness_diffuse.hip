@@ -13,6 +13,10 @@
 //                      only the values of the same interface, so they are one loop here and nothing per interface is stored.
 //                      The work against the stratification accumulates in the same sweep;
 //   td_update_kernel   uhtr, vhtr, h (:607-620) and MEKE%GM_src (:1552-1560).
+//   td_meke_kernel     with MEKE_GM_SRC_ALT, MEKE%GM_src from KH * Slope_PE**2 * hN2_PE that the faces leave behind per layer (:1633-1652);
+//                      with MEKE_GEOMETRIC, MEKE%Kh (:446-468).
+// The face kernels are instantiated <DIR, MODE>: KHTH_USE_EBT_STRUCT, MEKE_GEOMETRIC and MEKE_GM_SRC_ALT are compile-time modes, and
+// <DIR, 0> is the kernel without them (profiles/thickness_diffuse_geometric.txt).
 // Algorithmic traffic: read h, T, S; write/read T_f, S_f, e, pres, h_avail_rsum; write uhD, vhD; update h, uhtr, vhtr
 // (~200 B per cell and call; the call runs once per dynamics step, MOM.F90:1165).
 #include <cmath>
@@ -40,7 +44,36 @@ struct TDArgs {
   double FGNV_scale, N2_floor;
   const double *cg1, *g_prime;
   double *W_sfn, *W_s2r, *W_n2, *W_dkde, *W_dik;
+  // the compile-time modes of the face kernels (TD_EBT, TD_GEOM, TD_SRC_ALT); none of this is read by the instantiation <DIR, 0>
+  int src_slope_bug;
+  double ebt_floor, geom_alpha, geom_eps;
+  const double *ebt, *MEKE;      // VarMix%ebt_struct (h points, nk levels), MEKE%MEKE (h points)
+  double *PE;                    // KH(k) * Slope_PE(k)**2 * hN2_PE(k) of the direction of the launch, nk planes of faces (:1637-1640)
 };
+
+// KHTH_USE_EBT_STRUCT: KH of interface K >= 2 (:306-324 / :410-428); MEKE_GEOMETRIC: the face term (:262-268 / :363-369);
+// MEKE_GM_SRC_ALT: the face leaves KH * Slope_PE**2 * hN2_PE of every interface behind (:1022-1023, :1055-1061)
+enum { TD_EBT = 1, TD_GEOM = 2, TD_SRC_ALT = 4 };
+
+// KH_u(I,j,K), K >= 2, from KH_u(I,j,1) (:306-324); o is the offset of layer K-1 in an h-point array
+template <int MODE>
+__device__ __forceinline__ double td_KH_K(const TDArgs &A, double KH, long cL, long cR, long o) {
+  if constexpr (MODE & TD_EBT) {
+    const double *__restrict__ ebt = A.ebt + o;
+    const double KH_K = KH * 0.5 * (ebt[cL] + ebt[cR]);
+    return max2(KH_K, A.ebt_floor);      // (KHTH_MIN with FULL_DEPTH_KHTH_MIN, -infinity without)
+  } else {
+    return KH;
+  }
+}
+
+// KH_u(I,j,k) * Slope_x_PE(I,j,k)**2 * hN2_x_PE(I,j,k) (:1637) from the blended slope (:1055-1061) and hN2_PE = hA * max(N2_unlim, N2_floor) (:1023)
+__device__ __forceinline__ double td_PE_K(const TDArgs &A, double KH_K, double Slope, double hA, double N2_unlim) {
+  const double hN2_PE = hA * max2(N2_unlim, A.N2_floor);
+  double Slope_PE = min2(Slope, A.slope_max);
+  if (!A.src_slope_bug && Slope < -A.slope_max) Slope_PE = -A.slope_max;
+  return KH_K * (Slope_PE * Slope_PE) * hN2_PE;
+}
 
 __global__ __launch_bounds__(64) void td_column_kernel(TDArgs A) {
   const m6::GridDev &g = A.g;
@@ -109,7 +142,7 @@ __global__ __launch_bounds__(64) void td_column_kernel(TDArgs A) {
 #ifndef TD_FACE_OCC
 #define TD_FACE_OCC 3      // waves per SIMD the register allocation aims at (tools/build_variant.sh for experiments)
 #endif
-template <int DIR>
+template <int DIR, int MODE>
 __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
   const m6::GridDev &g = A.g;
   const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 64 + threadIdx.x;
@@ -124,7 +157,9 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
   const double KH_CFL = (0.25 * A.max_Khth_CFL) / (A.dt * (IdxC * IdxC + IdyC * IdyC));
   double Kh = A.Khth;
   if (A.use_Visbeck) Kh = Kh + A.KHTH_Slope_Cff * A.L2[f2] * A.SN[f2];
-  if (A.MEKE_Kh) Kh = Kh + A.KhTh_fac * sqrt(A.MEKE_Kh[cL] * A.MEKE_Kh[cR]);
+  if constexpr (MODE & TD_GEOM)
+    Kh = Kh + (DIR ? g.mask2dCv[f2] : g.mask2dCu[f2]) * A.geom_alpha * 0.5 * (A.MEKE[cL] + A.MEKE[cR]) / (A.SN[f2] + A.geom_eps);
+  else if (A.MEKE_Kh) Kh = Kh + A.KhTh_fac * sqrt(A.MEKE_Kh[cL] * A.MEKE_Kh[cR]);
   if (A.Res_fn) Kh = Kh * A.Res_fn[f2];
   if (A.Depth_fn) Kh = Kh * A.Depth_fn[f2];      // DEPTH_SCALED_KHTH :284-289
   if (A.Khth_Max > 0) Kh = max2(A.Khth_Min, min2(Kh, A.Khth_Max));
@@ -158,6 +193,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
     double TL_km1 = 0.0, TR_km1 = 0.0, SL_km1 = 0.0, SR_km1 = 0.0;
     if (use_EOS) { TL_km1 = A.T[cL + okm1]; TR_km1 = A.T[cR + okm1]; SL_km1 = A.S[cL + okm1]; SR_km1 = A.S[cR + okm1]; }
     double Sfn_unlim, slope2_Ratio = 0.0, drdi_k = 0.0;
+    double PE_K = 0.0;      // KH * Slope_PE**2 * hN2_PE, zero where the reference never sets the factors (:843-846)
     if (find_work && !use_EOS) {      // :824-828
       drdiA = 0.0; drdiB = 0.0;
       drdkL = A.Rlay[k - 1] - A.Rlay[k - 2]; drdkR = drdkL;
@@ -179,6 +215,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
     }
     if (find_work) drdi_k = drdiB;
     if (k > nk_linear) {
+      const double KH_K = td_KH_K<MODE>(A, KH, cL, cR, okm1);      // KH_u(I,j,K)
       if (use_EOS) {
         double hg2A = 0.0, hg2B = 0.0, haA = 0.0, haB = 0.0, drdz = 0.0, Slope;
         if (find_work || !present_slope) {      // :882-917 (Boussinesq)
@@ -212,7 +249,9 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
         // :939-943 with int_slope = 0
         Slope = (1.0 - 0.0) * Slope + 0.0 * ((eR_K - eL_K) * IdL);
         slope2_Ratio = (1.0 - 0.0) * slope2_Ratio;
-        Sfn_unlim = -(KH * dLf) * Slope;      // :956
+        if constexpr (MODE & TD_SRC_ALT)      // :1022-1023, :1055-1061
+          PE_K = td_PE_K(A, KH_K, Slope, 0.5 * (hg2A / haA + hg2B / haB), drdz * (g.g_Earth / g.Rho0));
+        Sfn_unlim = -(KH_K * dLf) * Slope;      // :956
         if (Sfn_unlim > 0.0) {                 // :959-975
           if (eL_K < e_botR) Sfn_unlim = 0.0;
           else if (e_botR > eL_Kp1) Sfn_unlim = Sfn_unlim * ((eL_K - e_botR) / ((eL_K - eL_Kp1) + dz_neglect));
@@ -224,7 +263,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
         double Slope;
         if (present_slope) Slope = A.slope[f2 + fpl * (K - 1)];
         else Slope = ((eL_K - eR_K) * IdL) * OBCmask;
-        Sfn_unlim = ((KH * dLf) * Slope);
+        Sfn_unlim = ((KH_K * dLf) * Slope);
       }
     } else {
       Sfn_unlim = 0.;
@@ -254,6 +293,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
       else hDk = -htot * fracR;
     }
     A.hD[f2 + fpl * (k - 1)] = hDk;
+    if constexpr (MODE & TD_SRC_ALT) A.PE[f2 + fpl * (k - 1)] = PE_K;
     htot = htot + hDk;
     if (find_work)      // :1196-1209
       Work = Work + G_scale * (htot * drdkDe - (hDk * drdi_k) * 0.25 * ((eL_K + eL_Kp1) + (eR_K + eR_Kp1)));
@@ -263,6 +303,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
   // ---- the top layer :1517-1590 (after the sweep the handed-down values are those of layer 1 and interface 2)
   const double hD1 = -htot;
   A.hD[f2] = hD1;
+  if constexpr (MODE & TD_SRC_ALT) A.PE[f2] = 0.0;      // Slope_PE(:,:,1) = 0
   if (find_work && use_EOS) {
     const double pres_u = 0.5 * (A.pres[cL] + A.pres[cR]);
     const double T_u = 0.5 * (TL_k + TR_k), S_u = 0.5 * (SL_k + SR_k);
@@ -279,7 +320,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_kernel(TDArgs A) {
 
 // The same column with KHTH_USE_FGNV_STREAMFUNCTION: the two sweeps of the reference apart, the elliptic solve between them; what the first hands
 // the second goes through planes of faces in global memory (td_face_kernel fuses the sweeps, which the solve forbids)
-template <int DIR>
+template <int DIR, int MODE>
 __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_fgnv_kernel(TDArgs A) {
   const m6::GridDev &g = A.g;
   const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 64 + threadIdx.x;
@@ -294,7 +335,9 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_fgnv_kernel(TDArgs A)
   const double KH_CFL = (0.25 * A.max_Khth_CFL) / (A.dt * (IdxC * IdxC + IdyC * IdyC));
   double Kh = A.Khth;
   if (A.use_Visbeck) Kh = Kh + A.KHTH_Slope_Cff * A.L2[f2] * A.SN[f2];
-  if (A.MEKE_Kh) Kh = Kh + A.KhTh_fac * sqrt(A.MEKE_Kh[cL] * A.MEKE_Kh[cR]);
+  if constexpr (MODE & TD_GEOM)
+    Kh = Kh + (DIR ? g.mask2dCv[f2] : g.mask2dCu[f2]) * A.geom_alpha * 0.5 * (A.MEKE[cL] + A.MEKE[cR]) / (A.SN[f2] + A.geom_eps);
+  else if (A.MEKE_Kh) Kh = Kh + A.KhTh_fac * sqrt(A.MEKE_Kh[cL] * A.MEKE_Kh[cR]);
   if (A.Res_fn) Kh = Kh * A.Res_fn[f2];
   if (A.Depth_fn) Kh = Kh * A.Depth_fn[f2];      // DEPTH_SCALED_KHTH :284-289
   if (A.Khth_Max > 0) Kh = max2(A.Khth_Min, min2(Kh, A.Khth_Max));
@@ -330,6 +373,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_fgnv_kernel(TDArgs A)
     if (use_EOS) { TL_km1 = A.T[cL + okm1]; TR_km1 = A.T[cR + okm1]; SL_km1 = A.S[cL + okm1]; SR_km1 = A.S[cR + okm1]; }
     double Sfn_unlim, slope2_Ratio = 0.0, drdi_k = 0.0, dzN2 = 0.0;
     drdkDe = 0.0;
+    double PE_K = 0.0;      // KH * Slope_PE**2 * hN2_PE, zero where the reference never sets the factors (:843-846)
     if (find_work && !use_EOS) {      // :824-828
       drdiA = 0.0; drdiB = 0.0;
       drdkL = A.Rlay[k - 1] - A.Rlay[k - 2]; drdkR = drdkL;
@@ -351,6 +395,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_fgnv_kernel(TDArgs A)
     }
     if (find_work) drdi_k = drdiB;
     if (k > nk_linear) {
+      const double KH_K = td_KH_K<MODE>(A, KH, cL, cR, okm1);      // KH_u(I,j,K)
       if (use_EOS) {
         double hg2A = 0.0, hg2B = 0.0, haA = 0.0, haB = 0.0, drdz = 0.0, Slope;
         {      // :982-1024 (use_FGNV_streamfn; Boussinesq)
@@ -391,7 +436,9 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_fgnv_kernel(TDArgs A)
         // :939-943 with int_slope = 0
         Slope = (1.0 - 0.0) * Slope + 0.0 * ((eR_K - eL_K) * IdL);
         slope2_Ratio = (1.0 - 0.0) * slope2_Ratio;
-        Sfn_unlim = -(KH * dLf) * Slope;      // :956
+        if constexpr (MODE & TD_SRC_ALT)      // :1022-1023, :1055-1061
+          PE_K = td_PE_K(A, KH_K, Slope, 0.5 * (hg2A / haA + hg2B / haB), drdz * (g.g_Earth / g.Rho0));
+        Sfn_unlim = -(KH_K * dLf) * Slope;      // :956
         if (Sfn_unlim > 0.0) {                 // :959-975
           if (eL_K < e_botR) Sfn_unlim = 0.0;
           else if (e_botR > eL_Kp1) Sfn_unlim = Sfn_unlim * ((eL_K - e_botR) / ((eL_K - eL_Kp1) + dz_neglect));
@@ -403,7 +450,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_fgnv_kernel(TDArgs A)
         double Slope;
         if (present_slope) Slope = A.slope[f2 + fpl * (K - 1)];
         else Slope = ((eL_K - eR_K) * IdL) * OBCmask;
-        Sfn_unlim = ((KH * dLf) * Slope);
+        Sfn_unlim = ((KH_K * dLf) * Slope);
         dzN2 = A.g_prime[K - 1];      // GV%g_prime(K) :1095
       }
     } else {
@@ -413,6 +460,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_fgnv_kernel(TDArgs A)
     {
       const long w = f2 + fpl * (K - 1);
       A.W_sfn[w] = Sfn_unlim; A.W_s2r[w] = slope2_Ratio; A.W_n2[w] = dzN2;
+      if constexpr (MODE & TD_SRC_ALT) A.PE[w] = PE_K;
       if (find_work) { A.W_dkde[w] = drdkDe; A.W_dik[w] = drdi_k; }
     }
     hL_k = hL_km1; hR_k = hR_km1; eL_Kp1 = eL_K; eR_Kp1 = eR_K;
@@ -500,6 +548,7 @@ __global__ __launch_bounds__(64, TD_FACE_OCC) void td_face_fgnv_kernel(TDArgs A)
   // ---- the top layer :1517-1590 (after the sweep the handed-down values are those of layer 1 and interface 2)
   const double hD1 = -htot;
   A.hD[f2] = hD1;
+  if constexpr (MODE & TD_SRC_ALT) A.PE[f2] = 0.0;      // Slope_PE(:,:,1) = 0
   if (find_work && use_EOS) {
     TL_k = A.T[cL]; TR_k = A.T[cR]; SL_k = A.S[cL]; SR_k = A.S[cR];
     const double pres_u = 0.5 * (A.pres[cL] + A.pres[cR]);
@@ -551,12 +600,68 @@ __global__ __launch_bounds__(256) void td_update_kernel(UpdArgs A) {
   }
 }
 
+struct SrcArgs {
+  m6::GridDev g;
+  const double *PE_u, *PE_v, *SN_u, *SN_v, *MEKE;
+  double *GM_src, *MEKE_Kh;
+  double alpha, eps;
+  int date_2024;
+};
+
+// MEKE_GM_SRC_ALT (:1633-1652): MEKE%GM_src of a cell from what its four faces left behind, summed k = nz ... 1; the faces are grouped
+// in pairs from MEKE_GM_SRC_ANSWER_DATE = 20240601 on.  MEKE_GEOMETRIC (:446-468, the form with the parentheses): MEKE%Kh of the cell.
+__global__ __launch_bounds__(256) void td_meke_kernel(SrcArgs A) {
+  const m6::GridDev &g = A.g;
+  const int i = g.isc + blockIdx.x * 64 + threadIdx.x, j = g.jsc + blockIdx.y * 4 + threadIdx.y;
+  if (i > g.iec || j > g.jec) return;
+  const long upl = (long)(g.nih + 1) * g.njh, vpl = (long)g.nih * (g.njh + 1), c = g.h2(i, j);
+  const long uE = g.u2(i, j), uW = g.u2(i - 1, j), vN = g.v2(i, j), vS = g.v2(i, j - 1);
+  if (A.GM_src) {
+    const double fac = -0.25 * (g.Rho0 * g.H_to_Z);      // -0.25 * GV%H_to_RZ
+    double src = 0.;
+    for (int k = g.nk - 1; k >= 0; k--) {
+      double PE_release_h;
+      if (A.date_2024) PE_release_h = fac * ((A.PE_u[uE + upl * k] + A.PE_u[uW + upl * k]) + (A.PE_v[vN + vpl * k] + A.PE_v[vS + vpl * k]));
+      else PE_release_h = fac * (A.PE_u[uE + upl * k] + A.PE_u[uW + upl * k] + A.PE_v[vN + vpl * k] + A.PE_v[vS + vpl * k]);
+      src = src + PE_release_h;
+    }
+    A.GM_src[c] = src;
+  }
+  if (A.MEKE_Kh) A.MEKE_Kh[c] = A.alpha * A.MEKE[c] / (0.25 * ((A.SN_u[uE] + A.SN_u[uW]) + (A.SN_v[vN] + A.SN_v[vS])) + A.eps);
+}
+
+template <int DIR, int MODE>
+void launch_face(const TDArgs &A, dim3 grid, hipStream_t s) {
+  if (A.use_FGNV) hipLaunchKernelGGL((td_face_fgnv_kernel<DIR, MODE>), grid, dim3(64), 0, s, A);
+  else hipLaunchKernelGGL((td_face_kernel<DIR, MODE>), grid, dim3(64), 0, s, A);
+}
+
+template <int DIR>
+void launch_face(int mode, const TDArgs &A, dim3 grid, hipStream_t s) {
+  switch (mode) {
+    case 0: launch_face<DIR, 0>(A, grid, s); break;
+    case 1: launch_face<DIR, 1>(A, grid, s); break;
+    case 2: launch_face<DIR, 2>(A, grid, s); break;
+    case 3: launch_face<DIR, 3>(A, grid, s); break;
+    case 4: launch_face<DIR, 4>(A, grid, s); break;
+    case 5: launch_face<DIR, 5>(A, grid, s); break;
+    case 6: launch_face<DIR, 6>(A, grid, s); break;
+    default: launch_face<DIR, 7>(A, grid, s); break;
+  }
+}
+
+// the slots of cs->unsupported that have become switches
+enum { TD_SLOT_GEOMETRIC = 4, TD_SLOT_SRC_ALT = 5, TD_SLOT_EBT = 7 };
+
 int check_cs(const mom6hip_thickness_diffuse_cs_t *cs) {
-  static const char *names[10] = {"(unused)", "DETANGLE_INTERFACES", "KH_ETA_CONST / KH_ETA_VEL_SCALE", "USE_STANLEY_GM",
-                                  "MEKE_GEOMETRIC", "MEKE_GM_SRC_ALT", "READ_KHTH", "KHTH_USE_EBT_STRUCT / QG Leith GM",
+  static const char *names[10] = {"the QG Leith GM coefficient (USE_QG_LEITH_GM)", "DETANGLE_INTERFACES", "KH_ETA_CONST / KH_ETA_VEL_SCALE",
+                                  "USE_STANLEY_GM", "MEKE_GEOMETRIC", "MEKE_GM_SRC_ALT", "READ_KHTH", "KHTH_USE_EBT_STRUCT",
                                   "USE_KH_IN_MEKE", "non-Boussinesq mode / tv%p_surf / SKEB"};
   M6_REQUIRE(cs->initialized, "MOM_thickness_diffuse: Module must be initialized before it is used.");
-  for (int n = 0; n < 10; n++) M6_REQUIRE(!cs->unsupported[n], "thickness_diffuse: %s is not provided by libmom6hip", names[n]);
+  for (int n = 0; n < 10; n++) {
+    if (n == TD_SLOT_GEOMETRIC || n == TD_SLOT_SRC_ALT || n == TD_SLOT_EBT) continue;
+    M6_REQUIRE(!cs->unsupported[n], "thickness_diffuse: %s is not provided by libmom6hip", names[n]);
+  }
   M6_REQUIRE(!cs->use_FGNV_streamfn || cs->cg1, "thickness_diffuse: cg1 must be associated when using FGNV streamfunction.");      // :860
   return 0;
 }
@@ -578,6 +683,17 @@ extern "C" int mom6hip_thickness_diffuse(mom6hip_ctx_t *ctx, const mom6hip_thick
   M6_REQUIRE(!cs->MEKE_GM_src || eos || cs->Rlay, "thickness_diffuse: the work without an equation of state needs GV%%Rlay");
   M6_REQUIRE((cs->slope_x != nullptr) == (cs->slope_y != nullptr), "thickness_diffuse: slope_x and slope_y come together");
   M6_REQUIRE((cs->Depth_fn_u != nullptr) == (cs->Depth_fn_v != nullptr), "thickness_diffuse: Depth_fn_u and Depth_fn_v come together");
+  // the three switches: what each reads must be there (the reference would dereference it)
+  const bool use_ebt = cs->use_variable_mixing && cs->unsupported[TD_SLOT_EBT];      // :209-214
+  const bool use_geom = cs->unsupported[TD_SLOT_GEOMETRIC] && cs->MEKE_Kh_out;      // :261-262 (allocated(MEKE%Kh))
+  const bool src_alt = cs->unsupported[TD_SLOT_SRC_ALT] && cs->MEKE_GM_src;         // :1022, :1633
+  M6_REQUIRE(!use_ebt || cs->ebt_struct, "thickness_diffuse: KHTH_USE_EBT_STRUCT needs VarMix%%ebt_struct");
+  M6_REQUIRE(!cs->unsupported[TD_SLOT_GEOMETRIC] || !cs->MEKE_Kh, "thickness_diffuse: with MEKE_GEOMETRIC MEKE%%Kh is passed as MEKE_Kh_out");
+  M6_REQUIRE(!use_geom || cs->MEKE_GEOM_answer_date >= 20190101,
+             "thickness_diffuse: MEKE_GEOMETRIC_ANSWER_DATE < 20190101 is not provided by libmom6hip");
+  M6_REQUIRE(!use_geom || cs->MEKE_MEKE, "thickness_diffuse: MEKE_GEOMETRIC needs MEKE%%MEKE");
+  M6_REQUIRE(!use_geom || (cs->SN_u && cs->SN_v), "thickness_diffuse: MEKE_GEOMETRIC needs VarMix%%SN_u and VarMix%%SN_v");
+  const int mode = (use_ebt ? TD_EBT : 0) | (use_geom ? TD_GEOM : 0) | (src_alt ? TD_SRC_ALT : 0);
   const m6::GridDev g = ctx->g;
   M6_REQUIRE(g.isc - g.isd >= 1 && g.jsc - g.jsd >= 1, "thickness_diffuse: the halo must be at least 1 point wide");
   M6_REQUIRE(g.areaT && g.IareaT && g.bathyT && g.IdxCu && g.IdyCu && g.IdxCv && g.IdyCv && g.dy_Cu && g.dx_Cv && g.mask2dCu && g.mask2dCv,
@@ -604,11 +720,18 @@ extern "C" int mom6hip_thickness_diffuse(mom6hip_ctx_t *ctx, const mom6hip_thick
   const double *Du = st.in(cs->Depth_fn_u, bU2), *Dv = st.in(cs->Depth_fn_v, bV2);
   const double *sx = st.in(cs->slope_x, bU2 * (nz + 1)), *sy = st.in(cs->slope_y, bV2 * (nz + 1));
   double *d_src = cs->MEKE_GM_src ? st.inout(cs->MEKE_GM_src, bH2) : nullptr;
+  A.ebt_floor = (cs->full_depth_khth_min && cs->Khth_Min > 0.0) ? cs->Khth_Min : -HUGE_VAL;      // (:2245: read only then)
+  A.src_slope_bug = cs->MEKE_src_slope_bug; A.geom_alpha = cs->MEKE_GEOMETRIC_alpha; A.geom_eps = cs->MEKE_GEOMETRIC_epsilon;
+  A.ebt = use_ebt ? st.in(cs->ebt_struct, bH) : nullptr;
+  A.MEKE = use_geom ? st.in(cs->MEKE_MEKE, bH2) : nullptr;
+  double *d_Kh = use_geom ? st.inout(cs->MEKE_Kh_out, bH2) : nullptr;
+  double *PE_u = src_alt ? (double *)st.scratch(bU) : nullptr, *PE_v = src_alt ? (double *)st.scratch(bV) : nullptr;
   A.e = (double *)st.scratch(bH2 * (nz + 1)); A.pres = (double *)st.scratch(bH2 * (nz + 1)); A.rsum = (double *)st.scratch(bH2 * (nz + 1));
   A.T = eos ? (double *)st.scratch(bH) : nullptr; A.S = eos ? (double *)st.scratch(bH) : nullptr; A.c1 = eos ? (double *)st.scratch(bH) : nullptr;
   double *uhD = (double *)st.scratch(bU), *vhD = (double *)st.scratch(bV);
   double *Work_u = A.find_work ? (double *)st.scratch(bU2) : nullptr, *Work_v = A.find_work ? (double *)st.scratch(bV2) : nullptr;
-  A.use_FGNV = cs->use_FGNV_streamfn; A.FGNV_scale = cs->FGNV_scale; A.N2_floor = cs->N2_floor;
+  A.use_FGNV = cs->use_FGNV_streamfn; A.FGNV_scale = cs->FGNV_scale;
+  A.N2_floor = cs->use_FGNV_streamfn ? cs->N2_floor : 0.0;      // (:2336-2337: zero without the FGNV streamfunction; MEKE_GM_SRC_ALT reads it too)
   A.cg1 = nullptr; A.g_prime = nullptr; A.W_sfn = A.W_s2r = A.W_n2 = A.W_dkde = A.W_dik = nullptr;
   if (A.use_FGNV) {
     M6_REQUIRE(eos || cs->g_prime, "thickness_diffuse: the FGNV streamfunction without an equation of state needs GV%%g_prime");
@@ -626,16 +749,21 @@ extern "C" int mom6hip_thickness_diffuse(mom6hip_ctx_t *ctx, const mom6hip_thick
   }
   const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1;
   hipLaunchKernelGGL(td_column_kernel, dim3((ni + 2 + 63) / 64, nj + 2), dim3(64), 0, s, A);
-  A.L2 = L2u; A.SN = SNu; A.Res_fn = Ru; A.Depth_fn = Du; A.slope = sx; A.hD = uhD; A.Work = Work_u;
-  if (A.use_FGNV) hipLaunchKernelGGL(td_face_fgnv_kernel<0>, dim3((ni + 1 + 63) / 64, nj), dim3(64), 0, s, A);
-  else hipLaunchKernelGGL(td_face_kernel<0>, dim3((ni + 1 + 63) / 64, nj), dim3(64), 0, s, A);
-  A.L2 = L2v; A.SN = SNv; A.Res_fn = Rv; A.Depth_fn = Dv; A.slope = sy; A.hD = vhD; A.Work = Work_v;
-  if (A.use_FGNV) hipLaunchKernelGGL(td_face_fgnv_kernel<1>, dim3((ni + 63) / 64, nj + 1), dim3(64), 0, s, A);
-  else hipLaunchKernelGGL(td_face_kernel<1>, dim3((ni + 63) / 64, nj + 1), dim3(64), 0, s, A);
+  A.L2 = L2u; A.SN = SNu; A.Res_fn = Ru; A.Depth_fn = Du; A.slope = sx; A.hD = uhD; A.Work = Work_u; A.PE = PE_u;
+  launch_face<0>(mode, A, dim3((ni + 1 + 63) / 64, nj), s);
+  A.L2 = L2v; A.SN = SNv; A.Res_fn = Rv; A.Depth_fn = Dv; A.slope = sy; A.hD = vhD; A.Work = Work_v; A.PE = PE_v;
+  launch_face<1>(mode, A, dim3((ni + 63) / 64, nj + 1), s);
   UpdArgs Up;
   Up.g = g; Up.uhD = uhD; Up.vhD = vhD; Up.Work_u = Work_u; Up.Work_v = Work_v; Up.h = d_h; Up.uhtr = d_uhtr; Up.vhtr = d_vhtr;
-  Up.uhGM = d_uhGM; Up.vhGM = d_vhGM; Up.GM_src = d_src; Up.dt = dt;
+  Up.uhGM = d_uhGM; Up.vhGM = d_vhGM; Up.GM_src = src_alt ? nullptr : d_src; Up.dt = dt;      // (Work_h is not added with GM_src_alt, :1613)
   hipLaunchKernelGGL(td_update_kernel, dim3((ni + 1 + 63) / 64, (nj + 1 + 3) / 4, nz), dim3(64, 4), 0, s, Up);
+  if (src_alt || use_geom) {
+    SrcArgs Sa;
+    Sa.g = g; Sa.PE_u = PE_u; Sa.PE_v = PE_v; Sa.SN_u = SNu; Sa.SN_v = SNv; Sa.MEKE = A.MEKE; Sa.GM_src = src_alt ? d_src : nullptr;
+    Sa.MEKE_Kh = d_Kh; Sa.alpha = cs->MEKE_GEOMETRIC_alpha; Sa.eps = cs->MEKE_GEOMETRIC_epsilon;
+    Sa.date_2024 = cs->MEKE_src_answer_date >= 20240601;
+    hipLaunchKernelGGL(td_meke_kernel, dim3((ni + 63) / 64, (nj + 3) / 4), dim3(64, 4), 0, s, Sa);
+  }
   M6_HIP(hipGetLastError());
   return st.finish();
 }

@@ -3,10 +3,11 @@
 !! with the reference's dummy-argument lists, so step_MOM_thermo / step_MOM (src/core/MOM.F90:1149-1165) compile unchanged.
 !! Provided: isopycnal height diffusion with KHTH, KHTH_MIN / KHTH_MAX / KHTH_MAX_CFL, the MEKE%Kh and Visbeck contributions,
 !! VarMix%Res_fn_u/v, stored slopes or slopes from the density gradients (with or without an equation of state), the work into
-!! MEKE%GM_src, CDp%uhGM / vhGM -- on the GPU through libmom6hip (mom6hip_thickness_diffuse, HOST memspace).  The FGNV
-!! streamfunction, DETANGLE_INTERFACES, KH_ETA_*, USE_STANLEY_GM, MEKE_GEOMETRIC, MEKE_GM_SRC_ALT, READ_KHTH, the EBT structure,
-!! QG Leith GM, depth scaling, USE_KH_IN_MEKE, USE_GME, SKEB and non-Boussinesq mode stop with a FATAL error; the diagnostics
-!! other than uhGM / vhGM are not registered.
+!! MEKE%GM_src, CDp%uhGM / vhGM, the FGNV streamfunction, depth scaling, KHTH_USE_EBT_STRUCT with FULL_DEPTH_KHTH_MIN, MEKE_GEOMETRIC
+!! (MEKE%Kh becomes an output) and MEKE_GM_SRC_ALT -- on the GPU through libmom6hip (mom6hip_thickness_diffuse).
+!! DETANGLE_INTERFACES, KH_ETA_*, USE_STANLEY_GM, READ_KHTH, QG Leith GM, USE_KH_IN_MEKE, USE_GME, SKEB,
+!! MEKE_GEOMETRIC_ANSWER_DATE < 20190101 and non-Boussinesq mode stop with a FATAL error; the diagnostics other than uhGM / vhGM
+!! are not registered.
 !!
 !! Compiled INSIDE a MOM6 source tree in place of src/parameterizations/lateral/MOM_thickness_diffuse.F90; here against
 !! tests/fortran/stubs.
@@ -51,6 +52,15 @@ type, public :: thickness_diffuse_CS ; private
   type(diag_ctrl), pointer :: diag => NULL()
   logical :: use_FGNV_streamfn = .false. !< KHTH_USE_FGNV_STREAMFUNCTION: the streamfunction of Ferrari et al. (2010)
   real :: FGNV_scale = 1.0, N2_floor = 0.0 !< FGNV_FILTER_SCALE and (FGNV_STRAT_FLOOR * OMEGA)**2
+  logical :: full_depth_khth_min = .false. !< If true, KHTH_MIN is enforced throughout the whole water column.
+  logical :: MEKE_GEOMETRIC = .false.    !< If true, uses the GM coefficient formulation from the GEOMETRIC framework
+  real    :: MEKE_GEOMETRIC_alpha = 0.05 !< The nondimensional coefficient governing the efficiency of the GEOMETRIC isopycnal
+                                         !! height diffusion [nondim]
+  real    :: MEKE_GEOMETRIC_epsilon = 1.0e-7 !< Minimum Eady growth rate for the GEOMETRIC thickness diffusivity [T-1 ~> s-1].
+  integer :: MEKE_GEOM_answer_date = 99991231 !< The vintage of the expressions in the MEKE_GEOMETRIC calculation.
+  logical :: GM_src_alt = .false.        !< If true, use the GM energy conversion form S^2*N^2*kappa
+  integer :: MEKE_src_answer_date = 20240101 !< The vintage of the expressions in the GM energy conversion calculation
+  logical :: MEKE_src_slope_bug = .true. !< If true, only the positive slopes are limited in the alternative source
 end type thickness_diffuse_CS
 
 contains
@@ -89,8 +99,14 @@ subroutine thickness_diffuse(h, uhtr, vhtr, tv, dt, G, GV, US, MEKE, VarMix, CDp
   ccs%thickness_diffuse = 1 ; ccs%use_GM_work_bug = merge(1, 0, CS%use_GM_work_bug) ; ccs%nkml = GV%nkml ; ccs%initialized = 1
   if (VarMix%use_variable_mixing) then
     ccs%use_variable_mixing = 1
-    if (VarMix%khth_use_ebt_struct .or. VarMix%use_QG_Leith_GM) call MOM_error(FATAL, &
-        "thickness_diffuse (HIP): KHTH_USE_EBT_STRUCT and USE_QG_LEITH_GM are not provided by the GPU path.")
+    if (VarMix%use_QG_Leith_GM) call MOM_error(FATAL, &
+        "thickness_diffuse (HIP): USE_QG_LEITH_GM is not provided by the GPU path.")
+    if (VarMix%khth_use_ebt_struct) then      ! :306-324 (unsupported(8): the slot of VarMix%khth_use_ebt_struct)
+      if (.not.allocated(VarMix%ebt_struct)) call MOM_error(FATAL, &
+          "thickness_diffuse (HIP): KHTH_USE_EBT_STRUCT needs VarMix%ebt_struct.")
+      ccs%unsupported(8) = 1 ; ccs%ebt_struct = c_loc(VarMix%ebt_struct)
+      ccs%full_depth_khth_min = merge(1, 0, CS%full_depth_khth_min)
+    endif
     if (VarMix%Depth_scaled_KhTh) then      ! DEPTH_SCALED_KHTH :284-289
       ccs%Depth_fn_u = c_loc(VarMix%Depth_fn_u) ; ccs%Depth_fn_v = c_loc(VarMix%Depth_fn_v)
     endif
@@ -104,7 +120,23 @@ subroutine thickness_diffuse(h, uhtr, vhtr, tv, dt, G, GV, US, MEKE, VarMix, CDp
       ccs%slope_x = c_loc(VarMix%slope_x) ; ccs%slope_y = c_loc(VarMix%slope_y)
     endif
   endif
-  if (allocated(MEKE%Kh)) then ; ccs%MEKE_Kh = c_loc(MEKE%Kh) ; ccs%KhTh_fac = MEKE%KhTh_fac ; endif
+  if (CS%MEKE_GEOMETRIC) then      ! :261-268, :446-468 (unsupported(5): the slot of MEKE_GEOMETRIC); MEKE%Kh is written, not read
+    ccs%unsupported(5) = 1 ; ccs%MEKE_GEOMETRIC_alpha = CS%MEKE_GEOMETRIC_alpha ; ccs%MEKE_GEOMETRIC_epsilon = CS%MEKE_GEOMETRIC_epsilon
+    ccs%MEKE_GEOM_answer_date = CS%MEKE_GEOM_answer_date
+    if (allocated(MEKE%Kh)) then
+      if (.not.allocated(MEKE%MEKE)) call MOM_error(FATAL, "thickness_diffuse (HIP): MEKE_GEOMETRIC needs MEKE%MEKE.")
+      if (.not.(allocated(VarMix%SN_u) .and. allocated(VarMix%SN_v))) call MOM_error(FATAL, &
+          "thickness_diffuse (HIP): MEKE_GEOMETRIC needs VarMix%SN_u and VarMix%SN_v.")
+      ccs%MEKE_Kh_out = c_loc(MEKE%Kh) ; ccs%MEKE_MEKE = c_loc(MEKE%MEKE)
+      ccs%SN_u = c_loc(VarMix%SN_u) ; ccs%SN_v = c_loc(VarMix%SN_v)      ! (read regardless of use_variable_mixing)
+    endif
+  elseif (allocated(MEKE%Kh)) then
+    ccs%MEKE_Kh = c_loc(MEKE%Kh) ; ccs%KhTh_fac = MEKE%KhTh_fac
+  endif
+  if (CS%GM_src_alt) then          ! :1633-1652 (unsupported(6): the slot of MEKE_GM_SRC_ALT)
+    ccs%unsupported(6) = 1 ; ccs%MEKE_src_answer_date = CS%MEKE_src_answer_date
+  endif
+  ccs%MEKE_src_slope_bug = merge(1, 0, CS%MEKE_src_slope_bug)
   if (allocated(MEKE%GM_src)) ccs%MEKE_GM_src = c_loc(MEKE%GM_src)
   if (allocated(GV%Rlay)) then ; allocate(Rlay(GV%ke)) ; Rlay(:) = GV%Rlay(1:GV%ke) ; ccs%Rlay = c_loc(Rlay) ; endif
   if (CS%use_FGNV_streamfn) then      ! :217, :860, :1095: VarMix%cg1, and GV%g_prime for the stratification without an equation of state
@@ -129,6 +161,7 @@ subroutine thickness_diffuse(h, uhtr, vhtr, tv, dt, G, GV, US, MEKE, VarMix, CDp
     call to_dev(p_T, size(h), .false.) ; call to_dev(p_S, size(h), .false.)
     call to_dev(p_uhGM, size(uhtr), .true.) ; call to_dev(p_vhGM, size(vhtr), .true.)
     call to_dev(ccs%MEKE_Kh, n2, .false.) ; call to_dev(ccs%MEKE_GM_src, n2, .true.) ; call to_dev(ccs%cg1, n2, .false.)
+    call to_dev(ccs%MEKE_Kh_out, n2, .true.) ; call to_dev(ccs%MEKE_MEKE, n2, .false.) ; call to_dev(ccs%ebt_struct, size(h), .false.)
     call to_dev(ccs%Res_fn_u, size(uhtr(:,:,1)), .false.) ; call to_dev(ccs%Res_fn_v, size(vhtr(:,:,1)), .false.)
     call to_dev(ccs%Depth_fn_u, size(uhtr(:,:,1)), .false.) ; call to_dev(ccs%Depth_fn_v, size(vhtr(:,:,1)), .false.)
     call to_dev(ccs%L2u, size(uhtr(:,:,1)), .false.) ; call to_dev(ccs%SN_u, size(uhtr(:,:,1)), .false.)
@@ -173,8 +206,9 @@ subroutine thickness_diffuse_init(Time, G, GV, US, param_file, diag, CDp, CS)
   type(thickness_diffuse_CS), intent(inout) :: CS
 # include "version_variable.h"
   character(len=40)  :: mdl = "MOM_thickness_diffuse"
-  logical :: flag
+  logical :: flag, khth_use_ebt_struct
   real :: val, val2, strat_floor, omega
+  integer :: default_answer_date
 
   CS%initialized = .true.
   CS%diag => diag
@@ -189,8 +223,14 @@ subroutine thickness_diffuse_init(Time, G, GV, US, param_file, diag, CDp, CS)
                  units="nondim", default=0.0)
   call get_param(param_file, mdl, "KHTH_MIN", CS%KHTH_Min, "The minimum horizontal thickness diffusivity.", &
                  default=0.0, units="m2 s-1", scale=US%m_to_L**2*US%T_to_s)
-  call get_param(param_file, mdl, "KHTH_USE_EBT_STRUCT", flag, default=.false., do_not_log=.true.)
-  call refuse(flag, "KHTH_USE_EBT_STRUCT")
+  call get_param(param_file, mdl, "KHTH_USE_EBT_STRUCT", khth_use_ebt_struct, &
+                 "If true, uses the equivalent barotropic structure as the vertical structure of thickness diffusivity.", &
+                 default=.false., do_not_log=.true.)
+  if (khth_use_ebt_struct .and. CS%KHTH_Min>0.0) then      ! :2245
+    call get_param(param_file, mdl, "FULL_DEPTH_KHTH_MIN", CS%full_depth_khth_min, &
+                   "If true, KHTH_MIN is enforced throughout the whole water column. Otherwise, KHTH_MIN is only enforced at the "// &
+                   "surface. This parameter is only available when KHTH_USE_EBT_STRUCT=True and KHTH_MIN>0.", default=.false.)
+  endif
   call get_param(param_file, mdl, "KHTH_MAX", CS%KHTH_Max, "The maximum horizontal thickness diffusivity.", &
                  default=0.0, units="m2 s-1", scale=US%m_to_L**2*US%T_to_s)
   call get_param(param_file, mdl, "KHTH_MAX_CFL", CS%max_Khth_CFL, &
@@ -221,8 +261,33 @@ subroutine thickness_diffuse_init(Time, G, GV, US, param_file, diag, CDp, CS)
                  do_not_log=.not.CS%use_FGNV_streamfn)
   if (CS%use_FGNV_streamfn) CS%N2_floor = (strat_floor*omega)**2      ! :2337
   call get_param(param_file, mdl, "USE_STANLEY_GM", flag, default=.false.) ; call refuse(flag, "USE_STANLEY_GM")
-  call get_param(param_file, mdl, "MEKE_GM_SRC_ALT", flag, default=.false.) ; call refuse(flag, "MEKE_GM_SRC_ALT")
-  call get_param(param_file, mdl, "MEKE_GEOMETRIC", flag, default=.false.) ; call refuse(flag, "MEKE_GEOMETRIC")
+  call get_param(param_file, mdl, "DEFAULT_ANSWER_DATE", default_answer_date, &
+                 "This sets the default value for the various _ANSWER_DATE parameters.", default=99991231, do_not_log=.true.)
+  call get_param(param_file, mdl, "MEKE_GM_SRC_ALT", CS%GM_src_alt, &
+                 "If true, use the GM energy conversion form S^2*N^2*kappa rather than the streamfunction for the GM source term.", &
+                 default=.false.)
+  call get_param(param_file, mdl, "MEKE_GM_SRC_ANSWER_DATE", CS%MEKE_src_answer_date, &
+                 "The vintage of the expressions in the GM energy conversion calculation when MEKE_GM_SRC_ALT is true.  Values below "// &
+                 "20240601 recover the answers from the original implementation, while higher values use expressions that satisfy "// &
+                 "rotational symmetry.", default=20240101, do_not_log=.not.CS%GM_src_alt)
+  call get_param(param_file, mdl, "MEKE_GM_SRC_ALT_SLOPE_BUG", CS%MEKE_src_slope_bug, &
+                 "If true, use a bug that limits the positive values, but not the negative values, of the slopes used when "// &
+                 "MEKE_GM_SRC_ALT is true.", default=.true., do_not_log=.not.CS%GM_src_alt)
+  call get_param(param_file, mdl, "MEKE_GEOMETRIC", CS%MEKE_GEOMETRIC, &
+                 "If true, uses the GM coefficient formulation from the GEOMETRIC framework (Marshall et al., 2012).", default=.false.)
+  if (CS%MEKE_GEOMETRIC) then      ! :2364-2378
+    call get_param(param_file, mdl, "MEKE_GEOMETRIC_EPSILON", CS%MEKE_GEOMETRIC_epsilon, &
+                 "Minimum Eady growth rate used in the calculation of GEOMETRIC thickness diffusivity.", &
+                 units="s-1", default=1.0e-7, scale=US%T_to_s)
+    call get_param(param_file, mdl, "MEKE_GEOMETRIC_ALPHA", CS%MEKE_GEOMETRIC_alpha, &
+                 "The nondimensional coefficient governing the efficiency of the GEOMETRIC thickness diffusion.", &
+                 units="nondim", default=0.05)
+    call get_param(param_file, mdl, "MEKE_GEOMETRIC_ANSWER_DATE", CS%MEKE_GEOM_answer_date, &
+                 "The vintage of the expressions in the MEKE_GEOMETRIC calculation.  Values below 20190101 recover the answers from "// &
+                 "the original implementation, while higher values use expressions that satisfy rotational symmetry.", &
+                 default=default_answer_date, do_not_log=.not.GV%Boussinesq)
+    call refuse(CS%MEKE_GEOM_answer_date < 20190101, "MEKE_GEOMETRIC_ANSWER_DATE < 20190101")
+  endif
   call get_param(param_file, mdl, "USE_KH_IN_MEKE", flag, default=.false.) ; call refuse(flag, "USE_KH_IN_MEKE")
   call get_param(param_file, mdl, "USE_GME", CS%use_GME_thickness_diffuse, default=.false.)
   call refuse(CS%use_GME_thickness_diffuse, "USE_GME")

@@ -1,0 +1,427 @@
+"""A plain numpy restatement of thickness_diffuse (src/parameterizations/lateral/MOM_thickness_diffuse.F90:133) and
+thickness_diffuse_full (:634) in the reference's order of operations (IEEE fp64, one numpy operation per Fortran operation, no
+contraction), Boussinesq, with the three switches the oracle does not restate:
+  KHTH_USE_EBT_STRUCT / FULL_DEPTH_KHTH_MIN   the diffusivity of interface K >= 2 (:306-324, :410-428),
+  MEKE_GEOMETRIC                              the face term (:262-268, :363-369) and MEKE%Kh (:446-468, the form with the parentheses),
+  MEKE_GM_SRC_ALT                             hN2_PE, Slope_PE (:1022-1023, :1055-1061) and the source of MEKE (:1633-1652).
+With all three off it is orc.thickness_diffuse bit for bit (tests/test_td_geometric.py), which ties this text to what is already pinned;
+with them on it is the reference's own module bit for bit (tests/test_td_geometric_reference.py).
+
+What the oracle exports is called, not restated: the density derivatives of the equation of state.
+
+The faces of a direction are handled as arrays: L and R are the cells on either side of a face (i, i+1 or j, j+1)."""
+import numpy as np
+
+from mom6_amd import _abi
+from oracle import orc
+
+H, U, V = _abi.POS_H, _abi.POS_U, _abi.POS_V
+
+
+def max2(a, b):
+    return np.where(a > b, a, b)
+
+
+def min2(a, b):
+    return np.where(a < b, a, b)
+
+
+def _derivs(E, T, S, p):
+    """calculate_density_derivs, point by point"""
+    T, S, p = np.ascontiguousarray(T), np.ascontiguousarray(S), np.ascontiguousarray(p)
+    dT, dS = np.empty(T.shape), np.empty(T.shape)
+    a, b, Tf, Sf, pf = dT.reshape(-1), dS.reshape(-1), T.reshape(-1), S.reshape(-1), p.reshape(-1)
+    for n in range(Tf.size):
+        a[n], b[n] = orc.eos_density_derivs(E, float(Tf[n]), float(Sf[n]), float(pf[n]))
+    return dT, dS
+
+
+def _vert_fill_TS(g, h, T_in, S_in, kappa_dt):
+    """vert_fill_TS (src/core/MOM_isopycnal_slopes.F90:541-629) with larger_h_denom"""
+    nz = g.nk
+    h_neglect = g.H_subroundoff
+    kap_dt_x2 = (2.0 * kappa_dt) * (1.0 * g.Z_to_H)
+    if kap_dt_x2 <= 0.0 or nz < 2:
+        return T_in.copy(), S_in.copy()
+    T, S, c1 = np.empty_like(T_in), np.empty_like(S_in), np.empty_like(T_in)
+    h0 = 1.0e-16 * np.sqrt(0.5 * kap_dt_x2)
+    h_here, h_next = h[0], h[1]
+    ent_K = kap_dt_x2 / ((h_here + h_next) + h0)
+    h_tr = h_here + h_neglect
+    b1 = 1.0 / (h_tr + ent_K)
+    d1 = b1 * h_tr
+    Tf, Sf = (b1 * h_tr) * T_in[0], (b1 * h_tr) * S_in[0]
+    T[0], S[0] = Tf, Sf
+    for k in range(1, nz - 1):
+        h_here, h_next = h_next, h[k + 1]
+        ent_Kp1 = kap_dt_x2 / ((h_here + h_next) + h0)
+        h_tr = h_here + h_neglect
+        c1[k] = ent_K * b1
+        b1 = 1.0 / ((h_tr + d1 * ent_K) + ent_Kp1)
+        d1 = b1 * (h_tr + d1 * ent_K)
+        Tf = b1 * (h_tr * T_in[k] + ent_K * Tf)
+        Sf = b1 * (h_tr * S_in[k] + ent_K * Sf)
+        T[k], S[k] = Tf, Sf
+        ent_K = ent_Kp1
+    c1[nz - 1] = ent_K * b1
+    h_tr = h_next + h_neglect
+    b1 = 1.0 / (h_tr + d1 * ent_K)
+    Tf = b1 * (h_tr * T_in[nz - 1] + ent_K * Tf)
+    Sf = b1 * (h_tr * S_in[nz - 1] + ent_K * Sf)
+    T[nz - 1], S[nz - 1] = Tf, Sf
+    for k in range(nz - 2, -1, -1):
+        Tf = T[k] + c1[k + 1] * Tf
+        Sf = S[k] + c1[k + 1] * Sf
+        T[k], S[k] = Tf, Sf
+    return T, S
+
+
+def thickness_diffuse(g, h, uhtr, vhtr, T, S, eos, dt, Khth=0.0, Khth_Min=0.0, Khth_Max=0.0, max_Khth_CFL=0.8, slope_max=0.01,
+                      kappa_smooth=1.0e-6, KHTH_Slope_Cff=0.0, KhTh_fac=1.0, use_GM_work_bug=False, nkml=0, use_variable_mixing=False,
+                      use_FGNV_streamfn=False, FGNV_scale=1.0, FGNV_strat_floor=1.0e-15, omega=7.2921e-5,
+                      MEKE_Kh=None, L2u=None, L2v=None, SN_u=None, SN_v=None, Res_fn_u=None, Res_fn_v=None, slope_x=None, slope_y=None,
+                      MEKE_GM_src=None, Rlay=None, cg1=None, g_prime=None, Depth_fn_u=None, Depth_fn_v=None,
+                      ebt_struct=None, full_depth_khth_min=False, MEKE_GEOMETRIC=False, MEKE_MEKE=None, MEKE_GEOMETRIC_alpha=0.05,
+                      MEKE_GEOMETRIC_epsilon=1.0e-7, GM_src_alt=False, MEKE_src_answer_date=20240101, MEKE_src_slope_bug=True):
+    """thickness_diffuse on numpy arrays of the data domain.  h, uhtr, vhtr are left alone; the result is a dict with h, uhtr, vhtr, uhGM,
+    vhGM, GM_src (None without MEKE_GM_src), MEKE_Kh (MEKE%Kh after the call, None without it) and stats (counts over the wet faces of
+    both directions, for the tests that assert that the inputs are not trivial).  The fields have the names of
+    mom6hip_thickness_diffuse_cs_t; ebt_struct not None is VarMix%khth_use_ebt_struct; MEKE_Kh not None is allocated(MEKE%Kh)."""
+    nz, hl, ni, nj = g.nk, g.halo, g.ni, g.nj
+    use_EOS, find_work = eos is not None, MEKE_GM_src is not None
+    present_slope = slope_x is not None
+    use_Visbeck = use_variable_mixing and KHTH_Slope_Cff > 0. and all(a is not None for a in (L2u, L2v, SN_u, SN_v))
+    use_ebt = use_variable_mixing and ebt_struct is not None
+    full_depth = bool(full_depth_khth_min) and use_ebt and Khth_Min > 0.0      # :2245
+    src_alt = bool(GM_src_alt) and find_work
+    N2_floor = (FGNV_strat_floor * omega) ** 2 if use_FGNV_streamfn else 0.      # :2336-2337
+    nk_linear = max(nkml, 1)
+    stats = dict(wet_ifaces=0, kh_differs=0, floor_binds=0, floor_free=0, slope_ifaces=0, slope_above=0, slope_below=0, wet_faces=0, cfl_binds=0)
+    err = np.errstate(all="ignore")      # (land and halo points hold what they hold; nothing of them reaches a result)
+    err.__enter__()
+
+    # ---- find_eta :235, pres and h_avail_rsum :866-884, vert_fill_TS :854
+    e = np.empty((nz + 1,) + h.shape[1:]); pres = np.empty_like(e); rsum = np.empty_like(e)
+    e[nz] = -(g.bathyT + 0.0)
+    for k in range(nz - 1, -1, -1):
+        e[k] = e[k + 1] + h[k] * g.H_to_Z
+    I4dt = 0.25 / dt
+    gH = g.g_Earth * (g.Rho0 * g.H_to_Z)
+    avail = max2(I4dt * g.areaT[None] * (h - g.Angstrom_H), 0.0)
+    pres[0] = 0.0; rsum[0] = 0.0
+    for k in range(nz):
+        rsum[k + 1] = avail[0] if k == 0 else rsum[k] + avail[k]
+        pres[k + 1] = pres[k] + gH * h[k]
+    if use_EOS:
+        Tf, Sf = _vert_fill_TS(g, h, T, S, kappa_smooth * dt)
+
+    I_slope_max2 = 1.0 / (slope_max * slope_max)
+    h_neglect = g.H_subroundoff; h_neglect2 = h_neglect * h_neglect
+    dz_neglect = g.dZ_subroundoff; dz_neglect2 = dz_neglect * dz_neglect
+    G_scale = g.g_Earth * g.H_to_Z
+    G_rho0 = g.g_Earth / g.Rho0
+    Z_to_H = g.Z_to_H
+
+    def face(DIR):
+        """one direction of thickness_diffuse_full: hD (nz planes), Work, PE (nz planes) at the faces of the compute range"""
+        if DIR == 0:
+            rows = slice(hl, hl + nj); L = (rows, slice(hl - 1, hl + ni)); R = (rows, slice(hl, hl + ni + 1)); F = (rows, slice(hl, hl + ni + 1))
+            IdxC, IdyC, dLf, OBCmask = g.IdxCu[F], g.IdyCu[F], g.dy_Cu[F], g.mask2dCu[F]
+            IdL = IdxC
+            L2, SN, Res_fn, Depth_fn, slope = L2u, SN_u, Res_fn_u, Depth_fn_u, slope_x
+        else:
+            cols = slice(hl, hl + ni); L = (slice(hl - 1, hl + nj), cols); R = (slice(hl, hl + nj + 1), cols); F = (slice(hl, hl + nj + 1), cols)
+            IdxC, IdyC, dLf, OBCmask = g.IdxCv[F], g.IdyCv[F], g.dx_Cv[F], g.mask2dCv[F]
+            IdL = IdyC
+            L2, SN, Res_fn, Depth_fn, slope = L2v, SN_v, Res_fn_v, Depth_fn_v, slope_y
+        c = lambda a, side: a[(Ellipsis,) + side]
+        # ---- the diffusivity of the face :225-304 / :342-408
+        KH_CFL = (0.25 * max_Khth_CFL) / (dt * (IdxC * IdxC + IdyC * IdyC))
+        Kh = np.full(IdxC.shape, float(Khth))
+        if use_Visbeck:
+            Kh = Kh + KHTH_Slope_Cff * L2[F] * SN[F]
+        if MEKE_Kh is not None:
+            if MEKE_GEOMETRIC:
+                Kh = Kh + OBCmask * MEKE_GEOMETRIC_alpha * 0.5 * (MEKE_MEKE[L] + MEKE_MEKE[R]) / (SN[F] + MEKE_GEOMETRIC_epsilon)
+            else:
+                Kh = Kh + KhTh_fac * np.sqrt(MEKE_Kh[L] * MEKE_Kh[R])
+        if Res_fn is not None:
+            Kh = Kh * Res_fn[F]
+        if Depth_fn is not None:
+            Kh = Kh * Depth_fn[F]
+        if Khth_Max > 0:
+            Kh = max2(Khth_Min, min2(Kh, Khth_Max))
+        else:
+            Kh = max2(Khth_Min, Kh)
+        KH = min2(KH_CFL, Kh)
+        wet = OBCmask > 0.
+        stats["wet_faces"] += int(wet.sum()); stats["cfl_binds"] += int((wet & (KH_CFL < Kh)).sum())
+
+        hL, hR, eL, eR = c(h, L), c(h, R), c(e, L), c(e, R)
+        pL, pR, rsL, rsR, avL, avR = c(pres, L), c(pres, R), c(rsum, L), c(rsum, R), c(avail, L), c(avail, R)
+        if use_EOS:
+            TL, TR, SL, SR = c(Tf, L), c(Tf, R), c(Sf, L), c(Sf, R)
+        e_botL, e_botR = eL[nz], eR[nz]
+        shp = IdxC.shape
+        Z = np.zeros(shp)
+        Sfn_unlim = np.zeros((nz + 1,) + shp); s2r = np.zeros((nz + 1,) + shp); dzN2 = np.zeros((nz + 1,) + shp)
+        drdkDe_K = np.zeros((nz + 1,) + shp); drdi = np.zeros((nz,) + shp); PE = np.zeros((nz,) + shp)
+        drdiA = drdiB = drdkL = drdkR = Z
+        # ---- the first sweep :920-1103 (interface K one-based; arrays zero-based)
+        for K in range(nz, 1, -1):
+            k = K
+            KH_K = KH
+            if use_ebt:      # :306-324
+                KH_K = KH * 0.5 * (ebt_struct[k - 2][L] + ebt_struct[k - 2][R])
+                stats["wet_ifaces"] += int(wet.sum()); stats["kh_differs"] += int((wet & (KH_K != KH)).sum())
+                if full_depth:
+                    stats["floor_binds"] += int((wet & (KH_K < Khth_Min)).sum()); stats["floor_free"] += int((wet & (KH_K > Khth_Min)).sum())
+                    KH_K = max2(KH_K, Khth_Min)
+            hL_k, hR_k, hL_km1, hR_km1 = hL[k - 1], hR[k - 1], hL[k - 2], hR[k - 2]
+            eL_K, eR_K, eL_Kp1, eR_Kp1 = eL[K - 1], eR[K - 1], eL[K], eR[K]
+            if find_work and not use_EOS:      # :921-924
+                drdiA = Z; drdiB = Z
+                drdkL = np.full(shp, Rlay[k - 1] - Rlay[k - 2]); drdkR = drdkL
+            calc_derivatives = use_EOS and (k >= nk_linear) and (find_work or not present_slope or use_FGNV_streamfn)
+            if calc_derivatives:      # :930-966
+                pres_u = 0.5 * (pL[K - 1] + pR[K - 1])
+                T_u = 0.25 * ((TL[k - 1] + TR[k - 1]) + (TL[k - 2] + TR[k - 2]))
+                S_u = 0.25 * ((SL[k - 1] + SR[k - 1]) + (SL[k - 2] + SR[k - 2]))
+                drho_dT, drho_dS = _derivs(eos, T_u, S_u, pres_u)
+                drdiA = drho_dT * (TR[k - 2] - TL[k - 2]) + drho_dS * (SR[k - 2] - SL[k - 2])
+                drdiB = drho_dT * (TR[k - 1] - TL[k - 1]) + drho_dS * (SR[k - 1] - SL[k - 1])
+                drdkL = (drho_dT * (TL[k - 1] - TL[k - 2]) + drho_dS * (SL[k - 1] - SL[k - 2]))
+                drdkR = (drho_dT * (TR[k - 1] - TR[k - 2]) + drho_dS * (SR[k - 1] - SR[k - 2]))
+                drdkDe_K[K - 1] = drdkR * eR_K - drdkL * eL_K
+            elif find_work:
+                drdkDe_K[K - 1] = drdkR * eR_K - drdkL * eL_K
+            if find_work:
+                drdi[k - 1] = drdiB
+            if k > nk_linear:
+                if use_EOS:
+                    hg2A = hg2B = haA = haB = drdz = Z
+                    if use_FGNV_streamfn or find_work or not present_slope:      # :982-1024
+                        hg2L = hL_km1 * hL_k + h_neglect2
+                        hg2R = hR_km1 * hR_k + h_neglect2
+                        haL = 0.5 * (hL_km1 + hL_k) + h_neglect
+                        haR = 0.5 * (hR_km1 + hR_k) + h_neglect
+                        dzaL = haL * g.H_to_Z; dzaR = haR * g.H_to_Z
+                        wtL = hg2L * (haR * dzaR); wtR = hg2R * (haL * dzaL)
+                        drdz = (wtL * drdkL + wtR * drdkR) / (dzaL * wtL + dzaR * wtR)
+                        hg2A = hL_km1 * hR_km1 + h_neglect2
+                        hg2B = hL_k * hR_k + h_neglect2
+                        haA = 0.5 * (hL_km1 + hR_km1) + h_neglect
+                        haB = 0.5 * (hL_k + hR_k) + h_neglect
+                        N2_unlim = drdz * G_rho0
+                        dzLm, dzRm, dzLk, dzRk = g.H_to_Z * hL_km1, g.H_to_Z * hR_km1, g.H_to_Z * hL_k, g.H_to_Z * hR_k
+                        dzg2A = dzLm * dzRm + dz_neglect2
+                        dzg2B = dzLk * dzRk + dz_neglect2
+                        dzaA = 0.5 * (dzLm + dzRm) + dz_neglect
+                        dzaB = 0.5 * (dzLk + dzRk) + dz_neglect
+                        dzN2[K - 1] = (0.5 * (dzg2A / dzaA + dzg2B / dzaB)) * max2(N2_unlim, N2_floor)
+                        if src_alt:      # :1022-1023
+                            hN2_PE = (0.5 * (hg2A / haA + hg2B / haB)) * max2(N2_unlim, N2_floor)
+                    if present_slope:
+                        Slope = slope[K - 1][F]
+                        slope2_Ratio = (Slope * Slope) * I_slope_max2
+                    else:      # :1030-1046
+                        wtA = hg2A * haB; wtB = hg2B * haA
+                        drdx = ((wtA * drdiA + wtB * drdiB) / (wtA + wtB) - drdz * (eL_K - eR_K)) * IdL
+                        mag_grad2 = (1.0 * drdx) * (1.0 * drdx) + drdz * drdz
+                        pos = mag_grad2 > 0.0
+                        Slope = np.where(pos, drdx / np.sqrt(mag_grad2), 0.0)
+                        slope2_Ratio = np.where(pos, (Slope * Slope) * I_slope_max2, 1.0e20)
+                    Slope = (1.0 - 0.0) * Slope + 0.0 * ((eR_K - eL_K) * IdL)      # int_slope = 0 :1051
+                    slope2_Ratio = (1.0 - 0.0) * slope2_Ratio
+                    if src_alt:      # :1055-1061, and the product of :1637
+                        if MEKE_src_slope_bug:
+                            Slope_PE = min2(Slope, slope_max)
+                        else:
+                            Slope_PE = np.where(Slope > slope_max, slope_max, Slope)
+                            Slope_PE = np.where(Slope < -slope_max, -slope_max, Slope_PE)
+                        PE[k - 1] = KH_K * (Slope_PE * Slope_PE) * hN2_PE
+                        stats["slope_ifaces"] += int(wet.sum())
+                        stats["slope_above"] += int((wet & (Slope > slope_max)).sum()); stats["slope_below"] += int((wet & (Slope < -slope_max)).sum())
+                    Su = -(KH_K * dLf) * Slope      # :1065
+                    up = np.where(eL_K < e_botR, 0.0, np.where(e_botR > eL_Kp1, Su * ((eL_K - e_botR) / ((eL_K - eL_Kp1) + dz_neglect)), Su))
+                    dn = np.where(eR_K < e_botL, 0.0, np.where(e_botL > eR_Kp1, Su * ((eR_K - e_botL) / ((eR_K - eR_Kp1) + dz_neglect)), Su))
+                    Sfn_unlim[K - 1] = np.where(Su > 0.0, up, dn)
+                    s2r[K - 1] = slope2_Ratio
+                else:      # :1087-1096
+                    Slope = slope[K - 1][F] if present_slope else ((eL_K - eR_K) * IdL) * OBCmask
+                    Sfn_unlim[K - 1] = ((KH_K * dLf) * Slope)
+                    if use_FGNV_streamfn:
+                        dzN2[K - 1] = g_prime[K - 1]
+            else:
+                dzN2[K - 1] = N2_floor * dz_neglect
+                Sfn_unlim[K - 1] = 0.
+        # ---- the streamfunction of Ferrari et al. (2010) :1105-1124, streamfn_solver :1673-1707
+        if use_FGNV_streamfn:
+            cg = 0.5 * (cg1[L] + cg1[R])
+
+            def c2_dz(k):
+                dzL, dzR = g.H_to_Z * hL[k - 1], g.H_to_Z * hR[k - 1]
+                dz_harm = max2(dz_neglect, 2. * dzL * dzR / ((dzL + dzR) + dz_neglect))
+                return FGNV_scale * (cg * cg) / dz_harm
+            scale = (1. + FGNV_scale)
+            sfn = np.zeros_like(Sfn_unlim); c1 = np.zeros_like(Sfn_unlim)
+            c2_km1, c2_k = c2_dz(1), c2_dz(2)
+            hN2 = dzN2[1]
+            b_denom = hN2 + c2_km1
+            beta = 1.0 / (b_denom + c2_k)
+            d1 = beta * b_denom
+            sfn[1] = (beta * hN2) * (scale * Sfn_unlim[1])
+            for K in range(3, nz + 1):
+                c2_km1, c2_k = c2_k, c2_dz(K)
+                hN2 = dzN2[K - 1]
+                c1[K - 2] = beta * c2_km1
+                b_denom = hN2 + d1 * c2_km1
+                beta = 1.0 / (b_denom + c2_k)
+                d1 = beta * b_denom
+                sfn[K - 1] = beta * (hN2 * (scale * Sfn_unlim[K - 1]) + c2_km1 * sfn[K - 2])
+            c1[nz - 1] = beta * c2_k
+            below = Z
+            for K in range(nz, 1, -1):
+                below = sfn[K - 1] + c1[K - 1] * below
+                sfn[K - 1] = below
+            Sfn_unlim = np.where(wet[None], sfn, 0.)
+        # ---- the second sweep :1127-1214
+        hD = np.zeros((nz,) + shp)
+        htot = Z; Work = Z
+        for K in range(nz, 1, -1):
+            k = K
+            availL, availR = avL[k - 1], avR[k - 1]
+            fracL = np.where(availL > 0.0, availL / rsL[K], 0.0)
+            fracR = np.where(availR > 0.0, availR / rsR[K], 0.0)
+            if k > nk_linear:
+                if use_EOS:
+                    Sfn_safe = np.where(htot <= 0.0, htot * (1.0 - fracL), htot * (1.0 - fracR))
+                    Sfn_est = (Z_to_H * Sfn_unlim[K - 1] + s2r[K - 1] * Sfn_safe) / (1.0 + s2r[K - 1])
+                else:
+                    Sfn_est = Z_to_H * Sfn_unlim[K - 1]
+                Sfn_in_H = min2(max2(Sfn_est, -rsL[K - 1]), rsR[K - 1])
+                hDk = max2(min2((Sfn_in_H - htot), availL), -availR)
+            else:
+                hDk = np.where(htot <= 0.0, -htot * fracL, -htot * fracR)
+            hD[k - 1] = hDk
+            htot = htot + hDk
+            if find_work:      # :1207-1210
+                Work = Work + G_scale * (htot * drdkDe_K[K - 1] - (hDk * drdi[k - 1]) * 0.25 * ((eL[K - 1] + eL[K]) + (eR[K - 1] + eR[K])))
+        # ---- the top layer :1534-1606
+        hD1 = -htot
+        hD[0] = hD1
+        if find_work and use_EOS:
+            pres_u = 0.5 * (pL[0] + pR[0])
+            T_u, S_u = 0.5 * (TL[0] + TR[0]), 0.5 * (SL[0] + SR[0])
+            drho_dT, drho_dS = _derivs(eos, T_u, S_u, pres_u)
+            drdiB1 = drho_dT * (TR[0] - TL[0]) + drho_dS * (SR[0] - SL[0])
+            w = G_scale * ((hD1 * drdiB1) * 0.25 * ((eL[0] + eL[1]) + (eR[0] + eR[1])))
+            Work = Work + w if (DIR == 0 and use_GM_work_bug) else Work - w
+        return F, hD, Work, PE
+
+    Fu, uhD_f, Work_u, PE_u = face(0)
+    Fv, vhD_f, Work_v, PE_v = face(1)
+    uhD = np.zeros_like(uhtr); vhD = np.zeros_like(vhtr)
+    uhD[(slice(None),) + Fu] = uhD_f; vhD[(slice(None),) + Fv] = vhD_f
+    out = dict(uhtr=uhtr.copy(), vhtr=vhtr.copy(), uhGM=np.zeros_like(uhtr), vhGM=np.zeros_like(vhtr), h=h.copy(), GM_src=None, MEKE_Kh=None)
+    # ---- :599-614
+    su, sv, sh = (slice(None),) + Fu, (slice(None),) + Fv, (slice(None),) + g.csl(H)
+    out["uhtr"][su] = uhtr[su] + uhD[su] * dt; out["uhGM"][su] = uhD[su]
+    out["vhtr"][sv] = vhtr[sv] + vhD[sv] * dt; out["vhGM"][sv] = vhD[sv]
+    IareaT = g.IareaT[g.csl(H)]
+    hn = h[sh] - dt * IareaT * ((uhD_f[:, :, 1:] - uhD_f[:, :, :-1]) + (vhD_f[:, 1:, :] - vhD_f[:, :-1, :]))
+    out["h"][sh] = np.where(hn < g.Angstrom_H, g.Angstrom_H, hn)
+    if find_work:
+        src = MEKE_GM_src.copy()
+        if not src_alt:      # :1608-1615
+            Work_h = 0.5 * IareaT * ((Work_u[:, :-1] + Work_u[:, 1:]) + (Work_v[:-1, :] + Work_v[1:, :]))
+            src[g.csl(H)] = 0. + Work_h
+        else:                # :1633-1652
+            acc = np.zeros(IareaT.shape)
+            fac = -0.25 * (g.Rho0 * g.H_to_Z)      # -0.25 * GV%H_to_RZ
+            for k in range(nz - 1, -1, -1):
+                uE, uW, vN, vS = PE_u[k][:, 1:], PE_u[k][:, :-1], PE_v[k][1:, :], PE_v[k][:-1, :]
+                if MEKE_src_answer_date >= 20240601:
+                    PE_release_h = fac * ((uE + uW) + (vN + vS))
+                else:
+                    PE_release_h = fac * (uE + uW + vN + vS)
+                acc = acc + PE_release_h
+            src[g.csl(H)] = acc
+        out["GM_src"] = src
+    if MEKE_Kh is not None:
+        Kh_out = MEKE_Kh.copy()
+        if MEKE_GEOMETRIC:      # :457-465
+            SNu, SNv = SN_u[Fu], SN_v[Fv]
+            Kh_out[g.csl(H)] = MEKE_GEOMETRIC_alpha * MEKE_MEKE[g.csl(H)] / \
+                (0.25 * ((SNu[:, 1:] + SNu[:, :-1]) + (SNv[1:, :] + SNv[:-1, :])) + MEKE_GEOMETRIC_epsilon)
+        out["MEKE_Kh"] = Kh_out
+    err.__exit__(None, None, None)
+    out["stats"] = stats
+    return out
+
+
+# ---- the inputs and the option table shared by tests/test_td_geometric.py and tests/test_td_geometric_reference.py ----------------------
+SLOPE_MAX = 2.0e-5      # KHTH_SLOPE_MAX of the table: inside the spread of the slopes of the synthetic state, so both signs exceed it
+
+
+def geom_fields(g, seed=11):
+    """MEKE%MEKE, MEKE%Kh, VarMix%ebt_struct, SN_u/v, L2u/v, Res_fn, Depth_fn, stored slopes and cg1 with the halos the operator reads"""
+    rng = np.random.default_rng(seed)
+    su, sv, s2 = g.shape2(U), g.shape2(V), g.shape2(H)
+    f = dict(MEKE_MEKE=np.ascontiguousarray(0.02 + 8.0 * rng.random(s2)), MEKE_Kh=np.ascontiguousarray(-3.0 + 0.0 * rng.random(s2)),
+             cg1=np.ascontiguousarray(0.5 + 2.5 * rng.random(s2)))
+    ebt = np.ascontiguousarray(0.05 + 0.95 * rng.random((g.nk,) + s2))      # no level is 1: every interface differs from the surface
+    for a in (f["MEKE_MEKE"], f["MEKE_Kh"], f["cg1"], ebt):
+        orc.halo_update(g, a, H)
+    f.update(ebt_struct=ebt, SN_u=1.0e-6 * rng.random(su), SN_v=1.0e-6 * rng.random(sv), L2u=1.0e8 * rng.random(su), L2v=1.0e8 * rng.random(sv),
+             Res_fn_u=rng.random(su), Res_fn_v=rng.random(sv), Depth_fn_u=rng.random(su), Depth_fn_v=rng.random(sv))
+    sx = 8.0e-5 * (rng.random((g.nk + 1,) + su) - 0.5) * g.mask2dCu[None]
+    sy = 8.0e-5 * (rng.random((g.nk + 1,) + sv) - 0.5) * g.mask2dCv[None]
+    f.update(slope_x=np.ascontiguousarray(sx), slope_y=np.ascontiguousarray(sy))
+    return f
+
+
+_EBT = dict(use_variable_mixing=True, use=("ebt_struct",))
+_GEO = dict(MEKE_GEOMETRIC=True, use_variable_mixing=True, use=("MEKE_Kh", "MEKE_MEKE", "SN_u", "SN_v"))
+_ALT = dict(GM_src_alt=True, work=True, slope_max=SLOPE_MAX)
+# the keywords of thickness_diffuse above; use: the fields of geom_fields that are passed; work: MEKE%GM_src is allocated; eos: None without one
+TABLE = {
+    "ebt": dict(Khth=600.0, **_EBT),
+    "ebt_full_depth_min": dict(Khth=600.0, Khth_Min=200.0, full_depth_khth_min=True, **_EBT),
+    "ebt_fgnv": dict(Khth=600.0, use_variable_mixing=True, use_FGNV_streamfn=True, FGNV_scale=0.5, use=("ebt_struct", "cg1"), work=True),
+    "ebt_stored_slopes": dict(Khth=300.0, use_variable_mixing=True, use=("ebt_struct", "slope_x", "slope_y"), work=True),
+    "ebt_no_eos": dict(Khth=600.0, eos=None, work=True, **_EBT),
+    "geometric": dict(Khth=10.0, **_GEO),
+    "geometric_resfn_depthfn_max": dict(Khth=10.0, Khth_Max=9000.0, MEKE_GEOMETRIC=True, use_variable_mixing=True, work=True,
+                                        use=("MEKE_Kh", "MEKE_MEKE", "SN_u", "SN_v", "Res_fn_u", "Res_fn_v", "Depth_fn_u", "Depth_fn_v")),
+    "src_alt": dict(Khth=600.0, **_ALT),
+    "src_alt_2024": dict(Khth=600.0, MEKE_src_answer_date=20240601, **_ALT),
+    "src_alt_no_slope_bug": dict(Khth=600.0, MEKE_src_slope_bug=False, **_ALT),
+    "src_alt_2024_no_slope_bug": dict(Khth=600.0, MEKE_src_answer_date=20240601, MEKE_src_slope_bug=False, **_ALT),
+    "src_alt_nkml2": dict(Khth=600.0, nkml=2, **_ALT),
+    "src_alt_fgnv": dict(Khth=600.0, use_variable_mixing=True, use_FGNV_streamfn=True, FGNV_scale=0.5, FGNV_strat_floor=2.0e-2, use=("cg1",), **_ALT),
+    "all_three": dict(Khth=10.0, Khth_Min=9000.0, full_depth_khth_min=True, MEKE_GEOMETRIC=True, use_variable_mixing=True,
+                      use=("ebt_struct", "MEKE_Kh", "MEKE_MEKE", "SN_u", "SN_v"), MEKE_src_answer_date=20240601, MEKE_src_slope_bug=False, **_ALT),
+}
+# the names of the reference's parameters (thickness_diffuse_init :2203-2400) for the keywords above
+PARAMS = dict(Khth="KHTH", Khth_Min="KHTH_MIN", Khth_Max="KHTH_MAX", max_Khth_CFL="KHTH_MAX_CFL", slope_max="KHTH_SLOPE_MAX", kappa_smooth="KD_SMOOTH",
+              KHTH_Slope_Cff="KHTH_SLOPE_CFF", nkml="NKML", use_GM_work_bug="USE_GM_WORK_BUG", use_FGNV_streamfn="KHTH_USE_FGNV_STREAMFUNCTION",
+              FGNV_scale="FGNV_FILTER_SCALE", FGNV_strat_floor="FGNV_STRAT_FLOOR", full_depth_khth_min="FULL_DEPTH_KHTH_MIN",
+              MEKE_GEOMETRIC="MEKE_GEOMETRIC", MEKE_GEOMETRIC_alpha="MEKE_GEOMETRIC_ALPHA", MEKE_GEOMETRIC_epsilon="MEKE_GEOMETRIC_EPSILON",
+              GM_src_alt="MEKE_GM_SRC_ALT", MEKE_src_answer_date="MEKE_GM_SRC_ANSWER_DATE", MEKE_src_slope_bug="MEKE_GM_SRC_ALT_SLOPE_BUG")
+
+
+def run_table(g, d, name, dt=3600.0, fields=None, **override):
+    """the checker on one entry of TABLE (override: keywords that replace the entry's) -> (result, kw, args, eos): kw the keywords, args the
+    fields passed, eos its name or None"""
+    kw = dict(TABLE[name], **override)
+    eos = kw.pop("eos", "WRIGHT"); use = kw.pop("use", ()); work = kw.pop("work", False)
+    f = geom_fields(g) if fields is None else fields
+    args = {n: f[n] for n in use}
+    if work:
+        args["MEKE_GM_src"] = np.full(g.shape2(H), 7.0)
+    if eos is None:
+        args["Rlay"] = 1025.0 + 0.5 * np.arange(g.nk)
+    out = thickness_diffuse(g, d["h"], np.zeros_like(d["u"]), np.zeros_like(d["v"]), d["T"], d["S"], None if eos is None else orc.eos(eos), dt,
+                            **kw, **args)
+    return out, kw, args, eos
