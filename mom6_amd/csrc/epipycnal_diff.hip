@@ -21,7 +21,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "common.hpp"
+#include "hordiff_call.hpp"
 #include "eos.hpp"
 
 namespace {
@@ -451,9 +451,15 @@ namespace m6 {
 
 // tracer_epipycnal_ML_diff on device arrays (the tail of tracer_hordiff with CS%Diffuse_ML_interior, :613-620); khdt_x, khdt_y and
 // the iteration count are those tracer_hordiff has formed
-int epipycnal_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_epipycnal_cs_t *epi, const mom6hip_eos_t *eos, const double *h,
-                     const double *khdt_x, const double *khdt_y, int num_itts, const std::vector<double *> &d_tr,
-                     const std::vector<double> &cu, int idx_T, int idx_S, int *halo_updates) {
+int epipycnal_branch(const HordiffCall &c, const mom6hip_epipycnal_cs_t *epi) {
+  mom6hip_ctx_t *ctx = c.ctx;
+  Stager &st = c.st;
+  const mom6hip_eos_t *eos = c.eos;
+  const double *h = c.h, *khdt_x = c.khdt_x, *khdt_y = c.khdt_y;
+  const std::vector<double *> &d_tr = c.d_tr;
+  const std::vector<double> &cu = c.cu;
+  const int num_itts = c.num_itts, idx_T = c.idx_T, idx_S = c.idx_S;
+  int *halo_updates = c.halo_updates;
   const int ntr = (int)d_tr.size();
   const m6::GridDev g = ctx->g;
   M6_REQUIRE(epi != nullptr && eos != nullptr && epi->Rlay != nullptr, "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR needs its control structure with GV%%Rlay, and tv%%eqn_of_state");

@@ -24,7 +24,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "common.hpp"
+#include "neutral_common.hpp"      // boundary_k_range_surface, the layer search neutral diffusion's NDIFF_INTERIOR_ONLY shares
 #define REMAP_PIECES_SELECT 1      // m6::min2 / max2, as the oracle (remap_pieces.hpp says why there are two flavours)
 #include "remap_pieces.hpp"
 #include "remap_column.hpp"
@@ -240,20 +240,6 @@ __device__ __forceinline__ double flux_limiter(double F_layer, double area_L, do
   return 0.0;
 }
 
-// boundary_k_range(SURFACE, ...) :609-647: k_bot (1-based); h is a plane-strided column of nk values
-__device__ int boundary_k_bot(int nk, const double *h, long stride, double hbl) {
-  if (hbl == 0.) return 1;
-  double hsum = 0.;
-  for (int k = 0; k < nk; k++) hsum = hsum + h[stride * k];
-  if (hbl >= hsum) return nk;
-  double htot = 0.;
-  for (int k = 0; k < nk; k++) {
-    htot = htot + h[stride * k];
-    if (htot >= hbl) return k + 1;
-  }
-  return 1;
-}
-
 struct HBDArgs {
   m6::GridDev g;
   const double *h, *hbl, *khdt[2];
@@ -417,7 +403,10 @@ __global__ __launch_bounds__(64) void hbd_flux_kernel(HBDArgs A) {
   remapping_core_h<NKM>(W, A.scheme, A.extrap != 0, nk, hL, pL, km, dz, pLz, A.h_neglect);
   remapping_core_h<NKM>(W, A.scheme, A.extrap != 0, nk, hR, pR, km, dz, pRz, A.h_neglect);
   const double *khz = A.khz[DIR] + f;
-  const int k_bot_L = boundary_k_bot(km, dz, 1, hbl_L), k_bot_R = boundary_k_bot(km, dz, 1, hbl_R);
+  int k_bot_L, k_bot_R;      // boundary_k_range(SURFACE, ...) :609-647 on the HBD grid
+  double zeta_bot;
+  m6::boundary_k_range_surface(dz, 1, km, hbl_L, k_bot_L, zeta_bot);
+  m6::boundary_k_range_surface(dz, 1, km, hbl_R, k_bot_R, zeta_bot);
   const int k_bot_min = min(k_bot_L, k_bot_R), k_bot_max = max(k_bot_L, k_bot_R);
   for (int k = k_bot_min; k >= 1; k--) {      // 1-based as in the reference
     Fz[k - 1] = -(dz[k - 1] * khz[fpl * (k - 1)]) * (pRz[k - 1] - pLz[k - 1]);
@@ -488,17 +477,17 @@ bool hbd_scheme_provided(int scheme) {
 }
 
 // USE_HORIZONTAL_BOUNDARY_DIFFUSION, MOM_tracer_hor_diff.F90:408-472: num_itts calls of hor_bnd_diffusion with Coef_x = I_numitts *
-// khdt_x at every interface, each after a group pass of the tracers.  h, h_ML, khdt_x / khdt_y and the tracers are device arrays.
-// ebt_struct is VarMix%ebt_struct with KHTR_USE_EBT_STRUCT and null without.
-int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_cs_t *hbd, const double *h, const double *h_ML,
-               const double *ebt_struct, double KhTr_min, bool full_depth_khtr_min, const double *khdt_x, const double *khdt_y, int num_itts,
-               double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int *halo_updates) {
+// khdt_x at every interface, each after a group pass of the tracers.
+int hbd_branch(const HordiffCall &c, const mom6hip_hor_bnd_diffusion_cs_t *hbd, double KhTr_min, bool full_depth_khtr_min) {
+  mom6hip_ctx_t *ctx = c.ctx;
+  Stager &st = c.st;
+  const std::vector<double *> &d_tr = c.d_tr;
   M6_REQUIRE(hbd->initialized, "hor_bnd_diffusion: the control structure is not initialised");
   M6_REQUIRE(!hbd->debug, "hor_bnd_diffusion: HBD_DEBUG is not provided by libmom6hip");
   M6_REQUIRE(!hbd->diagnostics, "hor_bnd_diffusion: the hbd_* diagnostics are not provided by libmom6hip");
   M6_REQUIRE(hbd_scheme_provided(hbd->remap_scheme), "hor_bnd_diffusion: HBD_REMAPPING_SCHEME %d is not provided by libmom6hip "
              "(PCM, PLM, PPM_H4, PPM_IH4 and PPM_CW are)", hbd->remap_scheme);
-  M6_REQUIRE(h_ML != nullptr, "hor_bnd_diffusion requires that visc%%h_ML is associated.");
+  M6_REQUIRE(c.h_ML != nullptr, "hor_bnd_diffusion requires that visc%%h_ML is associated.");
   const m6::GridDev g = ctx->g;
   M6_REQUIRE(g.mask2dT && g.mask2dCu && g.mask2dCv && g.areaT && g.IareaT, "hor_bnd_diffusion: mask2dT, mask2dCu, mask2dCv, areaT and IareaT are needed");
   M6_REQUIRE(g.nk >= 1 && g.nk <= 128, "hor_bnd_diffusion: 1 to 128 layers are supported");
@@ -506,10 +495,10 @@ int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_c
   const int ntr = (int)d_tr.size(), nk = g.nk;
   const size_t hpl = (size_t)g.nih * g.njh, upl = (size_t)(g.nih + 1) * g.njh, vpl = (size_t)g.nih * (g.njh + 1);
   HBDArgs A;
-  A.g = g; A.h = h; A.khdt[0] = khdt_x; A.khdt[1] = khdt_y; A.I_numitts = I_numitts; A.h_neglect = g.H_subroundoff;
+  A.g = g; A.h = c.h; A.khdt[0] = c.khdt_x; A.khdt[1] = c.khdt_y; A.I_numitts = c.I_numitts; A.h_neglect = g.H_subroundoff;
   A.linear = hbd->linear; A.limiter = hbd->limiter; A.limiter_remap = hbd->limiter_remap; A.extrap = hbd->boundary_extrap;
   A.scheme = hbd->remap_scheme; A.t = nullptr; A.cu = 0.0;
-  A.ebt = ebt_struct; A.KhTr_min = KhTr_min; A.full_depth_khtr_min = full_depth_khtr_min ? 1 : 0;
+  A.ebt = c.ebt_struct; A.KhTr_min = KhTr_min; A.full_depth_khtr_min = full_depth_khtr_min ? 1 : 0;
   double *hbl = (double *)st.scratch(sizeof(double) * hpl);
   A.kmax[0] = (int *)st.scratch(sizeof(int) * upl); A.nflx[0] = (int *)st.scratch(sizeof(int) * upl);
   A.kmax[1] = (int *)st.scratch(sizeof(int) * vpl); A.nflx[1] = (int *)st.scratch(sizeof(int) * vpl);
@@ -517,7 +506,7 @@ int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_c
   M6_REQUIRE(!st.failed() && hbl && A.kmax[0] && A.nflx[0] && A.kmax[1] && A.nflx[1] && A.maxes, "hor_bnd_diffusion: out of device memory");
   A.hbl = hbl;
   // hbl = visc%h_ML; pass_var(hbl, halo=1) (:217-222).  h and hbl do not change between the calls: the HBD grid is built once.
-  M6_HIP(hipMemcpyAsync(hbl, h_ML, sizeof(double) * hpl, hipMemcpyDeviceToDevice, s));
+  M6_HIP(hipMemcpyAsync(hbl, c.h_ML, sizeof(double) * hpl, hipMemcpyDeviceToDevice, s));
   {
     double *f1[1] = {hbl}; int32_t p1[1] = {MOM6HIP_POS_H}, n1[1] = {1};
     if (int rc = m6::group_pass(ctx, f1, p1, n1, 1)) return rc;
@@ -548,11 +537,11 @@ int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_c
   M6_HIP(hipGetLastError());
   std::vector<double *> pf(d_tr);
   std::vector<int32_t> ppos(ntr, MOM6HIP_POS_H), pnk(ntr, nk);
-  for (int itt = 1; itt <= num_itts; itt++) {
+  for (int itt = 1; itt <= c.num_itts; itt++) {
     if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;      // :412, and :466 for itt > 1
-    (*halo_updates)++;
+    (*c.halo_updates)++;
     for (int m = 0; m < ntr; m++) {
-      A.t = d_tr[m]; A.cu = cu[m];
+      A.t = d_tr[m]; A.cu = c.cu[m];
       if (A.nflx_max[0] + A.nflx_max[1] > 0) {
         if (nkm == 16) launch_flux<16>(A, nbu, nj, nbv, nj + 1, s);
         else if (nkm == 80) launch_flux<80>(A, nbu, nj, nbv, nj + 1, s);

@@ -24,18 +24,19 @@
 // A lane owns a column or a face and walks it: the walks are serial in the surface index and differ from lane to lane.  What a walk
 // reads at a depth of its own (the interfaces of a column) is stored as records, so that a gather is one or two sectors and not one a
 // number, and kept in registers while the walk stays in the cell: a step down a column loads one record.  What all lanes read at the
-// same step (the surfaces of a face) is stored as planes.  The blocks are dealt to the XCDs by their range of i (xcd_block).
+// same step (the surfaces of a face) is stored as planes.  A row of the grid is nbx blocks of 64 lanes along i (nd_face, nd_column).
+// What the branch shares with the discontinuous one is neutral_common.hpp; neutral_drive, the host driver of both, is below beside the
+// update kernels, which finish the step of either.
 #include <cfloat>
 #include <cmath>
 #include <type_traits>
 
-#include "common.hpp"
+#include "neutral_common.hpp"
 #include "eos.hpp"
 
 namespace {
 
-using m6::max2;
-using m6::min2;
+using namespace m6;
 using namespace m6::eos;
 
 __device__ __forceinline__ double fsign(double a, double b) { return copysign(fabs(a), b); }
@@ -137,9 +138,6 @@ __device__ __forceinline__ double ppm_ave(double xL, double xR, double aL, doubl
   return (aL + xave * ((aR - aL) + a6)) - a6o3 * (xR * xR + xR * xL + xL * xL);
 }
 
-#define ND_BATCH 4
-typedef unsigned char ko_t;      // a layer number 1 .. nk <= 128
-
 // ppm_left_right_edge_values :2541 for one cell: the interface values above and below it and its mean
 __device__ __forceinline__ void ppm_edges(double Ti0, double Ti1, double Tl, double &aL, double &aR) {
   aL = Ti0; aR = Ti1;
@@ -149,83 +147,36 @@ __device__ __forceinline__ void ppm_edges(double Ti0, double Ti1, double Tl, dou
 }
 
 constexpr int IREC = 5;      // an interface of a column: P, T, S, drho/dT, drho/dS
-#ifndef ND_IREC_AOS
-#define ND_IREC_AOS 0
-#endif
 // where field q of interface K (0-based) of the column c is: planes [field][K][h points] (the columns of a wave stand at nearly the same
-// depth of their walks: a load of the wave is a few lines) or records [K][h points][field]
-__device__ __forceinline__ long irec_at(long K, long c, int q, long hpl, int nk) {
-  return ND_IREC_AOS ? (K * hpl + c) * IREC + q : ((long)q * (nk + 1) + K) * hpl + c;
-}
+// depth of their walks: a load of the wave is a few lines; records [K][h points][field] were slower, profiles/r04_experiments.txt)
+__device__ __forceinline__ long irec_at(long K, long c, int q, long hpl, int nk) { return ((long)q * (nk + 1) + K) * hpl + c; }
 constexpr int TREC = 2 * ND_BATCH;      // an interface of a column for a batch of tracers: their interface values, the means of the cell below
 
-struct NDArgs {
-  m6::GridDev g;
+struct NDArgs : NDFaces {
   EosDev E;
   double ref_pres, gH;              // NDIFF_REF_PRES ; GV%g_Earth*GV%H_to_RZ
-  double pa_to_H, h_neglect, scale; // scale: I_numitts
-  int ns, symmetric;                // 2nk+2 ; ndiff_answer_date > 20240330
-  const double *h, *T, *S, *p_surf;
+  double pa_to_H, h_neglect;
+  const double *T, *S, *p_surf;
   int interior;                     // NDIFF_INTERIOR_ONLY
   const double *hbl;                // the boundary-layer depth visc%h_ML with its halo (interior)
   int *kbot; double *zbot;          // boundary_k_range of every column: the layer and the fraction of it the boundary layer ends in
-  double *irec;                     // [(nk+1)][h points][IREC]: the interfaces of the columns as records (a walk's gather reads one record)
-  double *PoL[2], *PoR[2], *hEff[2]; // [surface][faces of the direction]
-  double *Flx[2];                   // (the order of 2024 and before) [surface][faces], + flx_stride per tracer of the batch
-  double *tend[2][2];               // (the symmetric order) [direction][side of the face: the cell it is the E | N face of, the W | S face of]
-                                    // [layer][faces]: the tendency of the cell's layer from this face, + flx_stride per tracer
-  ko_t *KoL[2], *KoR[2];
-  const double *khdt[2];
-  int nb;                           // tracers in this batch (<= ND_BATCH): the surfaces are read once for all of them
-  double *t[ND_BATCH];              // the tracers being diffused
+  double *irec;                     // [IREC][(nk+1)][h points]: the interfaces of the columns (irec_at)
   double *trec;                     // [(nk+1)][h points][TREC]: interface values and cell means of the batch's tracers
-  long flx_stride;
-  double cu[ND_BATCH];              // conc_underflow of the tracers
-  int *bad;
   const double *ebt;                // KHTR_USE_EBT_STRUCT: VarMix%ebt_struct [layer][h points] (null: off)
   double *coef_h;                   // Coef_h [(nk+1)][h points]
   ko_t *kt[2];                      // NDIFF_TAPERING: [k_min_l, k_max_l, k_min_r, k_max_r][faces of the direction] (null: off)
 };
 
-// boundary_k_range(SURFACE, ...), src/tracer/MOM_hor_bnd_diffusion.F90:609-647, for the column n2: k_bot (1-based) and zeta_bot
-__device__ __forceinline__ void boundary_k_range_surface(const double *__restrict__ h, long n2, long hpl, int nk, double hbl, int &k_bot,
-                                                         double &zeta_bot) {
-  k_bot = 1; zeta_bot = 0.;
-  if (hbl == 0.) return;
-  double hsum = 0., htot = 0.;
-  for (int k = 0; k < nk; k++) hsum = hsum + h[n2 + hpl * k];
-  if (hbl >= hsum) { k_bot = nk; zeta_bot = 1.; return; }
-  for (int k = 0; k < nk; k++) {
-    const double hk = h[n2 + hpl * k];
-    htot = htot + hk;
-    if (htot >= hbl) { k_bot = k + 1; zeta_bot = 1 - (htot - hbl) / hk; return; }
-  }
-}
-
-// Workgroups go round the eight XCDs by their index; a face reads the columns on its two sides, so the blocks of one range of i are given
-// to one XCD, row after row: the column a row's faces read on their far side is in that XCD's L2 when the next row asks for it.
-#ifndef ND_XCD
-#define ND_XCD 0      // (measured: no gain on the benchmark grid, profiles/r04_experiments.txt section 9)
-#endif
-__device__ __forceinline__ bool xcd_block(int nbx, int nby, int &bx, int &by) {
-  const int L = blockIdx.x, xcd = L & 7, q = L >> 3, per = (nbx + 7) >> 3;
-  if (ND_XCD) { bx = xcd + 8 * (q % per); by = q / per; }
-  else { const int nb8 = 8 * per; bx = L % nb8; by = L / nb8; }
-  return bx < nbx && by < nby;
-}
-inline int xcd_grid(int nbx, int nby) { return 8 * ((nbx + 7) >> 3) * nby; }
-
-__global__ __launch_bounds__(64) void nd_column_kernel(NDArgs A, int nbx, int nby) {
+__global__ __launch_bounds__(64) void nd_column_kernel(NDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  if (!xcd_block(nbx, nby, bx, by)) return;
-  const int i = g.isc - 1 + bx * 64 + threadIdx.x, j = g.jsc - 1 + by, nk = g.nk;
-  if (i > g.iec + 1) return;
-  const long n2 = g.h2(i, j), hpl = (long)g.nih * g.njh;
+  const NDCol C = nd_column(g, nbx);
+  if (!C.has) return;
+  const long n2 = C.n2, hpl = C.hpl;
+  const int nk = g.nk;
   if (A.interior) {      // boundary_k_range(SURFACE, ...), src/tracer/MOM_hor_bnd_diffusion.F90:609-647, for wet columns (:381-386)
     int k_bot = 1;
     double zeta_bot = 0.;
-    if (g.mask2dT[n2] > 0.0) boundary_k_range_surface(A.h, n2, hpl, nk, A.hbl[n2], k_bot, zeta_bot);
+    if (g.mask2dT[n2] > 0.0) boundary_k_range_surface(A.h + n2, hpl, nk, A.hbl[n2], k_bot, zeta_bot);
     A.kbot[n2] = k_bot; A.zbot[n2] = zeta_bot;
   }
   double P = A.p_surf ? A.p_surf[n2] : 0.;
@@ -245,24 +196,15 @@ __global__ __launch_bounds__(64) void nd_column_kernel(NDArgs A, int nbx, int nb
 
 // find_neutral_surface_positions_continuous :1353 (KoL / KoR keep the reference's 1-based layer numbers)
 template <int DIR>
-__global__ __launch_bounds__(64) void nd_surfaces_kernel(NDArgs A, int nbx, int nby) {
+__global__ __launch_bounds__(64) void nd_surfaces_kernel(NDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  if (!xcd_block(nbx, nby, bx, by)) return;
-  const int i = (DIR ? g.isc : g.isc - 1) + bx * 64 + threadIdx.x, j = (DIR ? g.jsc - 1 : g.jsc) + by, nk = g.nk;
-  if (i > g.iec) return;
-  const long f = DIR ? g.v2(i, j) : g.u2(i, j), pl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
-  const long hpl = (long)g.nih * g.njh, cl = g.h2(i, j), cr = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const NDFace F = nd_face<DIR>(g, nbx);
+  if (!F.has) return;
+  const long f = F.f, pl = F.pl, hpl = F.hpl, cl = F.cl, cr = F.cr;
+  if (!F.wet) { nd_dry_surfaces<DIR>(A, f, pl); return; }
   double *__restrict__ PoL = A.PoL[DIR], *__restrict__ PoR = A.PoR[DIR], *__restrict__ hEff = A.hEff[DIR];
   ko_t *__restrict__ KoL = A.KoL[DIR], *__restrict__ KoR = A.KoR[DIR];
-  const int ns = A.ns;
-  if (!((DIR ? g.mask2dCv[f] : g.mask2dCu[f]) > 0.0)) {      // :472-481: what the arrays hold where no surfaces are searched for
-    for (int ks = 0; ks < ns; ks++) {
-      PoL[f + pl * ks] = 0.; PoR[f + pl * ks] = 0.; KoL[f + pl * ks] = 1; KoR[f + pl * ks] = 1;
-      if (ks < ns - 1) hEff[f + pl * ks] = 0.;
-    }
-    return;
-  }
+  const int ns = A.ns, nk = g.nk;
   const double *__restrict__ irec = A.irec;
   // The walk reads interface klm1 = max(kl-1, 1), klm1+1 and kl of the left column (and the same of the right): two interfaces a side
   // are kept in registers -- A at klm1, B at klm1+1; interface kl is A while kl = 1 and B afterwards -- and a step that moves kl or kr
@@ -345,23 +287,20 @@ __global__ __launch_bounds__(64) void nd_surfaces_kernel(NDArgs A, int nbx, int 
 
 // compute_tapering_coeffs :1044-1058 for one wet face: k_min and k_max of the left and of the right column
 template <int DIR>
-__global__ __launch_bounds__(64) void nd_taper_kernel(NDArgs A, int nbx, int nby) {
+__global__ __launch_bounds__(64) void nd_taper_kernel(NDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  if (!xcd_block(nbx, nby, bx, by)) return;
-  const int i = (DIR ? g.isc : g.isc - 1) + bx * 64 + threadIdx.x, j = (DIR ? g.jsc - 1 : g.jsc) + by, nk = g.nk;
-  if (i > g.iec) return;
-  const long f = DIR ? g.v2(i, j) : g.u2(i, j), pl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
-  if (!((DIR ? g.mask2dCv[f] : g.mask2dCu[f]) > 0.0)) return;      // (read by the wet faces only)
-  const long hpl = (long)g.nih * g.njh, cl = g.h2(i, j), cr = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const NDFace F = nd_face<DIR>(g, nbx);
+  if (!F.wet) return;      // (read by the wet faces only)
+  const long f = F.f, pl = F.pl, hpl = F.hpl, cl = F.cl, cr = F.cr;
+  const int nk = g.nk;
   const double bld_l = A.hbl[cl], bld_r = A.hbl[cr];
   const double max_bld = max2(bld_l, bld_r), min_bld = min2(bld_l, bld_r);
   int k[4];
   double zeta;
-  boundary_k_range_surface(A.h, cl, hpl, nk, min_bld, k[0], zeta);
-  boundary_k_range_surface(A.h, cl, hpl, nk, max_bld, k[1], zeta);
-  boundary_k_range_surface(A.h, cr, hpl, nk, min_bld, k[2], zeta);
-  boundary_k_range_surface(A.h, cr, hpl, nk, max_bld, k[3], zeta);
+  boundary_k_range_surface(A.h + cl, hpl, nk, min_bld, k[0], zeta);
+  boundary_k_range_surface(A.h + cl, hpl, nk, max_bld, k[1], zeta);
+  boundary_k_range_surface(A.h + cr, hpl, nk, min_bld, k[2], zeta);
+  boundary_k_range_surface(A.h + cr, hpl, nk, max_bld, k[3], zeta);
 #pragma unroll
   for (int q = 0; q < 4; q++) A.kt[DIR][f + pl * q] = (ko_t)k[q];
 }
@@ -399,13 +338,12 @@ __global__ __launch_bounds__(64) void nd_coef_h_kernel(NDArgs A) {
 }
 
 // the interface values of the batch's tracers (neutral_surface_flux :2373-2374) and the means of their cells, as records
-__global__ __launch_bounds__(64) void nd_tracer_cols_kernel(NDArgs A, int nbx, int nby) {
+__global__ __launch_bounds__(64) void nd_tracer_cols_kernel(NDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  if (!xcd_block(nbx, nby, bx, by)) return;
-  const int i = g.isc - 1 + bx * 64 + threadIdx.x, j = g.jsc - 1 + by, nk = g.nk;
-  if (i > g.iec + 1) return;
-  const long n2 = g.h2(i, j), hpl = (long)g.nih * g.njh;
+  const NDCol C = nd_column(g, nbx);
+  if (!C.has) return;
+  const long n2 = C.n2, hpl = C.hpl;
+  const int nk = g.nk;
   const double *ts[ND_BATCH];
 #pragma unroll
   for (int z = 0; z < ND_BATCH; z++) ts[z] = A.t[z < A.nb ? z : 0];
@@ -421,22 +359,16 @@ __global__ __launch_bounds__(64) void nd_tracer_cols_kernel(NDArgs A, int nbx, i
 // are -- absent (khtr_ave = 1), the taper, Coef_h, or their product (:703-764); with Coef_h the fluxes carry the diffusivity (:834-878)
 enum { ND_COEF_NONE = 0, ND_COEF_TAPER = 1, ND_COEF_EBT = 2, ND_COEF_BOTH = 3 };
 template <int DIR, bool SYM, int COEF = ND_COEF_NONE>
-__global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby) {
+__global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  if (!xcd_block(nbx, nby, bx, by)) return;
-  const int i = (DIR ? g.isc : g.isc - 1) + bx * 64 + threadIdx.x, j = (DIR ? g.jsc - 1 : g.jsc) + by;
-  if (i > g.iec) return;
-  const long f = DIR ? g.v2(i, j) : g.u2(i, j), pl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
-  const long hpl = (long)g.nih * g.njh, cl = g.h2(i, j), cr = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const NDFace F = nd_face<DIR>(g, nbx);
+  if (!F.has) return;
+  const long f = F.f, pl = F.pl, hpl = F.hpl, cl = F.cl, cr = F.cr;
   double *__restrict__ Flx = A.Flx[DIR];
   double *__restrict__ tdL = A.tend[DIR][0], *__restrict__ tdR = A.tend[DIR][1];
   const int ns = A.ns, nb = A.nb, nk = g.nk;
-  if (!((DIR ? g.mask2dCv[f] : g.mask2dCu[f]) > 0.0)) {
-    for (int z = 0; z < nb; z++) {
-      if (SYM) for (int k = 0; k < nk; k++) { tdL[A.flx_stride * z + f + pl * k] = 0.; tdR[A.flx_stride * z + f + pl * k] = 0.; }
-      else for (int ks = 0; ks < ns - 1; ks++) Flx[A.flx_stride * z + f + pl * ks] = 0.;
-    }
+  if (!F.wet) {
+    for (int z = 0; z < nb; z++) nd_dry_fluxes<SYM>(ns, nk, Flx, tdL, tdR, A.flx_stride * z + f, pl);
     return;
   }
   const double *__restrict__ PiL = A.PoL[DIR], *__restrict__ PiR = A.PoR[DIR], *__restrict__ hEff = A.hEff[DIR];
@@ -498,8 +430,8 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby)
   if constexpr (COEF != ND_COEF_NONE) { cLt = coefL(klt); cRt = coefR(krt); }
   if (SYM) {
     for (int z = 0; z < nb; z++) {
-      for (int k = 0; k < klt; k++) tdL[A.flx_stride * z + f + pl * k] = 0.;
-      for (int k = 0; k < krt; k++) tdR[A.flx_stride * z + f + pl * k] = 0.;
+      nd_tend_store(tdL, A.flx_stride * z + f, pl, -1, klt, 0.);
+      nd_tend_store(tdR, A.flx_stride * z + f, pl, -1, krt, 0.);
     }
   }
   for (int ks = 0; ks < ns - 1; ks++) {
@@ -550,10 +482,7 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby)
       for (int z = 0; z < ND_BATCH; z++) {
         ppm_edges(sl.i0[z], sl.i1[z], sl.m0[z], sl.eL[z], sl.eR[z]);
         if (SYM) {
-          if (z < nb) {
-            tdL[A.flx_stride * z + f + pl * klt] = accL[z];
-            for (int k = klt + 1; k < klb; k++) tdL[A.flx_stride * z + f + pl * k] = 0.;
-          }
+          if (z < nb) nd_tend_store(tdL, A.flx_stride * z + f, pl, klt, klb, accL[z]);
           accL[z] = 0.;
         }
       }
@@ -563,10 +492,7 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby)
       for (int z = 0; z < ND_BATCH; z++) {
         ppm_edges(sr.i0[z], sr.i1[z], sr.m0[z], sr.eL[z], sr.eR[z]);
         if (SYM) {
-          if (z < nb) {
-            tdR[A.flx_stride * z + f + pl * krt] = accR[z];
-            for (int k = krt + 1; k < krb; k++) tdR[A.flx_stride * z + f + pl * k] = 0.;
-          }
+          if (z < nb) nd_tend_store(tdR, A.flx_stride * z + f, pl, krt, krb, accR[z]);
           accR[z] = 0.;
         }
       }
@@ -575,17 +501,15 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, int nby)
   }
   if (SYM) {
     for (int z = 0; z < nb; z++) {
-      tdL[A.flx_stride * z + f + pl * klt] = accL[z];
-      for (int k = klt + 1; k < nk; k++) tdL[A.flx_stride * z + f + pl * k] = 0.;
-      tdR[A.flx_stride * z + f + pl * krt] = accR[z];
-      for (int k = krt + 1; k < nk; k++) tdR[A.flx_stride * z + f + pl * k] = 0.;
+      nd_tend_store(tdL, A.flx_stride * z + f, pl, klt, nk, accL[z]);
+      nd_tend_store(tdR, A.flx_stride * z + f, pl, krt, nk, accR[z]);
     }
   }
   if (bad) atomicOr(A.bad, bad);
 }
 
 // :955-959 after the sums of :939-954 (the symmetric order): the four faces' tendencies of the layer, then the tracer
-__global__ __launch_bounds__(256) void nd_update_sym_kernel(NDArgs A) {
+__global__ __launch_bounds__(256) void nd_update_sym_kernel(NDFaces A) {
   const m6::GridDev &g = A.g;
   const int i = g.isc + blockIdx.x * 256 + threadIdx.x, j = g.jsc + blockIdx.y, k = blockIdx.z % g.nk, z = blockIdx.z / g.nk;
   if (i > g.iec) return;
@@ -606,7 +530,7 @@ __global__ __launch_bounds__(256) void nd_update_sym_kernel(NDArgs A) {
 // the runs of its four faces -- no LDS, full occupancy -- reads the fluxes as gathers and is slower: profiles/r04_experiments.txt.)
 // EBT: the fluxes carry the diffusivity (:834-848); otherwise they are multiplied by Coef_x(I,j,1), Coef_y(i,J,1) (:880-893)
 template <bool EBT>
-__global__ __launch_bounds__(64) void nd_update_kernel(NDArgs A) {
+__global__ __launch_bounds__(64) void nd_update_kernel(NDFaces A) {
   extern __shared__ double acc[];      // [nk][64]
   const m6::GridDev &g = A.g;
   const int lane = threadIdx.x, i = g.isc + blockIdx.x * 64 + lane, j = g.jsc + blockIdx.y, nk = g.nk, z = blockIdx.z;
@@ -667,130 +591,152 @@ __global__ __launch_bounds__(64) void nd_update_kernel(NDArgs A) {
 
 namespace m6 {
 
-int neutral_disc_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_ndiff_discontinuous_cs_t *ndd,
-                        const mom6hip_eos_t *eos, const double *h, const double *p_surf, const double *h_ML, const double *khdt_x,
-                        const double *khdt_y, int num_itts, double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu,
-                        int idx_T, int idx_S, int *halo_updates);
-
-// the update of a batch's tracers from the tendencies (symmetric) or the fluxes its flux kernels left, for the discontinuous branch
-// (neutral_diffusion_disc.hip), whose surfaces, fluxes and tendencies are laid out as nd_flux_kernel's: ns = 4 nk there
-int nd_launch_update(mom6hip_ctx_t *ctx, const double *h, double scale, int ns, bool symmetric, unsigned char *const *KoL,
-                     unsigned char *const *KoR, double *const *Flx, double *const *tend, long flx_stride, const double *const *khdt,
-                     double *const *t, const double *cu, int nb) {
-  NDArgs A = {};
-  const m6::GridDev g = ctx->g;
-  A.g = g; A.h = h; A.scale = scale; A.ns = ns; A.symmetric = symmetric; A.flx_stride = flx_stride; A.nb = nb;
-  for (int d = 0; d < 2; d++) {
-    A.KoL[d] = KoL[d]; A.KoR[d] = KoR[d]; A.Flx[d] = Flx[d]; A.khdt[d] = khdt[d];
-    A.tend[d][0] = tend[2 * d]; A.tend[d][1] = tend[2 * d + 1];
-  }
-  for (int z = 0; z < ND_BATCH; z++) { A.t[z] = z < nb ? t[z] : nullptr; A.cu[z] = z < nb ? cu[z] : 0.; }
-  const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1, nk = g.nk;
-  if (symmetric) hipLaunchKernelGGL(nd_update_sym_kernel, dim3((ni + 255) / 256, nj, nk * nb), dim3(256), 0, ctx->stream, A);
-  else hipLaunchKernelGGL(nd_update_kernel<false>, dim3((ni + 63) / 64, nj, nb), dim3(64), sizeof(double) * 64 * nk, ctx->stream, A);
-  M6_HIP(hipGetLastError());
-  return 0;
-}
-
-// the neutral branch of tracer_hordiff (MOM_tracer_hor_diff.F90:474-534) on device arrays; khdt_x, khdt_y and the iteration count
-// are those tracer_hordiff has formed; ebt_struct is VarMix%ebt_struct with KHTR_USE_EBT_STRUCT (tracer_hordiff has checked that
-// nd->unsupported[3] says the same) and null without
-int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_eos_t *eos, const double *h,
-                   const double *p_surf, const double *h_ML, const double *ebt_struct, const double *khdt_x, const double *khdt_y, int num_itts,
-                   double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S,
-                   int *halo_updates, const mom6hip_ndiff_discontinuous_cs_t *ndd) {
-  static const char *names[8] = {"NDIFF_CONTINUOUS = False", "(free)", "NDIFF_TAPERING", "KHTR_USE_EBT_STRUCT",
-                                 "NDIFF_USE_UNMASKED_TRANSPORT_BUG", "the neutral-diffusion diagnostics", "(free)", "(free)"};
+int neutral_drive(const HordiffCall &c, const mom6hip_neutral_diffusion_cs_t *nd, NDFaces &S, const NDBranch &b) {
+  mom6hip_ctx_t *ctx = c.ctx;
+  const std::vector<double *> &d_tr = c.d_tr;
   const int ntr = (int)d_tr.size();
-  M6_REQUIRE(nd != nullptr && eos != nullptr, "tracer_hordiff: USE_NEUTRAL_DIFFUSION needs the neutral_diffusion control structure and tv%%eqn_of_state");
-  M6_REQUIRE(nd->initialized, "neutral_diffusion: the control structure is not initialised");
-  if (nd->unsupported[0] && ndd) {      // NDIFF_CONTINUOUS = False with its parameters: neutral_diffusion_disc.hip
-    for (int q = 4; q < 8; q++) M6_REQUIRE(!nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
-    return neutral_disc_branch(ctx, st, nd, ndd, eos, h, p_surf, h_ML, khdt_x, khdt_y, num_itts, I_numitts, d_tr, cu, idx_T, idx_S, halo_updates);
-  }
-  // unsupported[2] (tapering) and [3] (KhTh_use_ebt_struct) are the switches of the two modes of the fluxes
-  for (int q = 0; q < 8; q++) M6_REQUIRE(q == 2 || q == 3 || !nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
-  const bool taper = nd->unsupported[2] != 0, ebt = ebt_struct != nullptr;
-  M6_REQUIRE(!taper || nd->interior_only, "neutral_diffusion: NDIFF_TAPERING is read with NDIFF_INTERIOR_ONLY only (the reference never reads it "
-             "otherwise): it is refused without");
-  M6_REQUIRE(idx_T >= 0 && idx_T < ntr && idx_S >= 0 && idx_S < ntr, "tracer_hordiff: tv%%T and tv%%S must be among the tracers (idx_T, idx_S)");
+  M6_REQUIRE(c.idx_T >= 0 && c.idx_T < ntr && c.idx_S >= 0 && c.idx_S < ntr, "tracer_hordiff: tv%%T and tv%%S must be among the tracers (idx_T, idx_S)");
   const m6::GridDev g = ctx->g;
   M6_REQUIRE(g.mask2dT && g.mask2dCu && g.mask2dCv && g.IareaT, "neutral_diffusion: mask2dT, mask2dCu, mask2dCv and IareaT are needed");
   M6_REQUIRE(g.nk >= 2 && g.nk <= 128, "neutral_diffusion: 2 to 128 layers are supported");
   hipStream_t s = ctx->stream;
-  const int nk = g.nk, ns = 2 * nk + 2;
+  const int nk = g.nk, ns = b.ns;
   const size_t hpl = (size_t)g.nih * g.njh, upl = (size_t)(g.nih + 1) * g.njh, vpl = (size_t)g.nih * (g.njh + 1);
   const size_t fpl = upl > vpl ? upl : vpl;
-  NDArgs A;
-  A.g = g; A.E = EosDev{eos->form, eos->Rho_T0_S0, eos->dRho_dT, eos->dRho_dS};
-  A.ref_pres = nd->ref_pres; A.gH = g.g_Earth * nd->H_to_RZ; A.pa_to_H = 1. / (nd->H_to_RZ * g.g_Earth);
-  A.h_neglect = g.H_subroundoff; A.scale = I_numitts; A.ns = ns; A.symmetric = nd->ndiff_answer_date > 20240330;
-  A.h = h; A.p_surf = p_surf; A.khdt[0] = khdt_x; A.khdt[1] = khdt_y;
-  double *irec = (double *)st.scratch(sizeof(double) * hpl * (nk + 1) * IREC);
+  const bool symmetric = nd->ndiff_answer_date > 20240330, interior = nd->interior_only != 0;
+  S.g = g; S.h = c.h; S.scale = c.I_numitts; S.ns = ns; S.khdt[0] = c.khdt_x; S.khdt[1] = c.khdt_y;
   const int nbmax = ntr < ND_BATCH ? ntr : ND_BATCH;
   // per direction PoL, PoR, hEff [surface][faces]; then per tracer of a batch either the fluxes [surface][faces] of the two directions or
   // the tendencies [layer][faces] of the two sides of the faces of the two directions
-  const size_t per_tracer = A.symmetric ? fpl * nk * 4 : fpl * ns * 2;
-  double *faces = (double *)st.scratch(sizeof(double) * (fpl * ns * 6 + per_tracer * (size_t)nbmax));
-  ko_t *kos = (ko_t *)st.scratch(sizeof(ko_t) * fpl * ns * 4);
-  double *trec = (double *)st.scratch(sizeof(double) * hpl * ((size_t)nk + 1) * TREC);
-  int *bad = (int *)st.scratch(64);
-  A.interior = nd->interior_only != 0; A.hbl = nullptr; A.kbot = nullptr; A.zbot = nullptr;
+  const size_t per_tracer = symmetric ? fpl * nk * 4 : fpl * ns * 2;
+  double *faces = (double *)c.st.scratch(sizeof(double) * (fpl * ns * 6 + per_tracer * (size_t)nbmax));
+  ko_t *kos = (ko_t *)c.st.scratch(sizeof(ko_t) * fpl * ns * 4);
+  int *bad = (int *)c.st.scratch(64);
   double *hbl = nullptr;
-  if (A.interior) {      // :370-390: CS%hbl = visc%h_ML, pass_var(CS%hbl, halo=1)
-    M6_REQUIRE(h_ML != nullptr, "hor_bnd_diffusion requires that visc%%h_ML is associated.");
-    hbl = (double *)st.scratch(sizeof(double) * hpl);
-    A.zbot = (double *)st.scratch(sizeof(double) * hpl); A.kbot = (int *)st.scratch(sizeof(int) * hpl);
-    M6_REQUIRE(!st.failed() && hbl && A.zbot && A.kbot, "neutral_diffusion: out of device memory");
-    A.hbl = hbl;
+  if (interior) {      // :370-390: CS%hbl = visc%h_ML, pass_var(CS%hbl, halo=1)
+    M6_REQUIRE(c.h_ML != nullptr, "hor_bnd_diffusion requires that visc%%h_ML is associated.");
+    hbl = (double *)c.st.scratch(sizeof(double) * hpl);
+    M6_REQUIRE(!c.st.failed() && hbl, "neutral_diffusion: out of device memory");
   }
-  M6_REQUIRE(!st.failed() && irec && faces && kos && trec && bad, "neutral_diffusion: out of device memory");
-  A.irec = irec; A.trec = trec; A.bad = bad;
-  A.ebt = ebt_struct; A.coef_h = nullptr; A.kt[0] = A.kt[1] = nullptr;
-  if (ebt) {
-    A.coef_h = (double *)st.scratch(sizeof(double) * hpl * ((size_t)nk + 1));
-    M6_REQUIRE(!st.failed() && A.coef_h, "neutral_diffusion: out of device memory");
-  }
-  if (taper) {
-    ko_t *kt = (ko_t *)st.scratch(sizeof(ko_t) * fpl * 8);
-    M6_REQUIRE(!st.failed() && kt, "neutral_diffusion: out of device memory");
-    A.kt[0] = kt; A.kt[1] = kt + fpl * 4;
-  }
-  const int coef = (taper ? ND_COEF_TAPER : 0) | (ebt ? ND_COEF_EBT : 0);
+  if (int rc = b.scratch(hbl)) return rc;
+  M6_REQUIRE(!c.st.failed() && faces && kos && bad, "neutral_diffusion: out of device memory");
+  S.bad = bad;
   double *per = faces + fpl * ns * 6;
   for (int d = 0; d < 2; d++) {
-    A.PoL[d] = faces + fpl * ns * (3 * d); A.PoR[d] = A.PoL[d] + fpl * ns; A.hEff[d] = A.PoR[d] + fpl * ns;
-    A.KoL[d] = kos + fpl * ns * (2 * d); A.KoR[d] = A.KoL[d] + fpl * ns;
-    A.Flx[d] = A.symmetric ? nullptr : per + fpl * ns * d;
-    A.tend[d][0] = A.symmetric ? per + fpl * nk * (2 * d) : nullptr; A.tend[d][1] = A.symmetric ? per + fpl * nk * (2 * d + 1) : nullptr;
+    S.PoL[d] = faces + fpl * ns * (3 * d); S.PoR[d] = S.PoL[d] + fpl * ns; S.hEff[d] = S.PoR[d] + fpl * ns;
+    S.KoL[d] = kos + fpl * ns * (2 * d); S.KoR[d] = S.KoL[d] + fpl * ns;
+    S.Flx[d] = symmetric ? nullptr : per + fpl * ns * d;
+    S.tend[d][0] = symmetric ? per + fpl * nk * (2 * d) : nullptr; S.tend[d][1] = symmetric ? per + fpl * nk * (2 * d + 1) : nullptr;
   }
-  A.flx_stride = (long)per_tracer;
+  S.flx_stride = (long)per_tracer;
   M6_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
 
   const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1;
-  const int nbc = (ni + 2 + 63) / 64, nbu = (ni + 1 + 63) / 64, nbv = (ni + 63) / 64;      // blocks along i: columns with the halo, u faces, v faces
   std::vector<double *> pf(d_tr);
   std::vector<int32_t> ppos(ntr, MOM6HIP_POS_H), pnk(ntr, nk);
   auto calc_coeffs = [&]() -> int {      // neutral_diffusion_calc_coeffs :337
-    A.T = d_tr[idx_T]; A.S = d_tr[idx_S];
-    if (A.interior) {
-      M6_HIP(hipMemcpyAsync(hbl, h_ML, sizeof(double) * hpl, hipMemcpyDeviceToDevice, s));
+    if (interior) {
+      M6_HIP(hipMemcpyAsync(hbl, c.h_ML, sizeof(double) * hpl, hipMemcpyDeviceToDevice, s));
       double *f1[1] = {hbl}; int32_t p1[1] = {MOM6HIP_POS_H}, n1[1] = {1};
       if (int rc = m6::group_pass(ctx, f1, p1, n1, 1)) return rc;
     }
-    hipLaunchKernelGGL(nd_column_kernel, dim3(xcd_grid(nbc, nj + 2)), dim3(64), 0, s, A, nbc, nj + 2);
-    hipLaunchKernelGGL(nd_surfaces_kernel<0>, dim3(xcd_grid(nbu, nj)), dim3(64), 0, s, A, nbu, nj);
-    hipLaunchKernelGGL(nd_surfaces_kernel<1>, dim3(xcd_grid(nbv, nj + 1)), dim3(64), 0, s, A, nbv, nj + 1);
+    return b.surfaces();
+  };
+  if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;      // do_group_pass(CS%pass_t) :478
+  (*c.halo_updates)++;
+  if (int rc = calc_coeffs()) return rc;
+  if (b.once) { if (int rc = b.once()) return rc; }
+  for (int itt = 1; itt <= c.num_itts; itt++) {
+    if (itt > 1) {
+      if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;
+      (*c.halo_updates)++;
+      if (nd->recalc_neutral_surf) { if (int rc = calc_coeffs()) return rc; }
+    }
+    for (int m0 = 0; m0 < ntr; m0 += nbmax) {      // neutral_diffusion :605: the tracers are independent of each other, a batch at a time
+      S.nb = (ntr - m0 < nbmax) ? ntr - m0 : nbmax;
+      for (int z = 0; z < ND_BATCH; z++) { S.t[z] = z < S.nb ? d_tr[m0 + z] : nullptr; S.cu[z] = z < S.nb ? c.cu[m0 + z] : 0.; }
+      b.tracer_cols();
+      b.fluxes(symmetric);
+      if (symmetric) hipLaunchKernelGGL(nd_update_sym_kernel, dim3((ni + 255) / 256, nj, nk * S.nb), dim3(256), 0, s, S);
+      else if (b.flux_has_coef) hipLaunchKernelGGL(nd_update_kernel<true>, dim3((ni + 63) / 64, nj, S.nb), dim3(64), sizeof(double) * 64 * nk, s, S);
+      else hipLaunchKernelGGL(nd_update_kernel<false>, dim3((ni + 63) / 64, nj, S.nb), dim3(64), sizeof(double) * 64 * nk, s, S);
+    }
+  }
+  M6_HIP(hipGetLastError());
+  int hbad = 0;
+  M6_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+  M6_HIP(hipStreamSynchronize(s));
+  for (const NDBranch::Bad &e : b.bad) M6_REQUIRE(!(hbad & e.bit), "%s", e.message);
+  return 0;
+}
+
+// the neutral branch of tracer_hordiff (MOM_tracer_hor_diff.F90:474-534) with the continuous reconstruction; c.ebt_struct is
+// VarMix%ebt_struct with KHTR_USE_EBT_STRUCT (tracer_hordiff has checked that nd->unsupported[3] says the same) and null without
+int neutral_branch(const HordiffCall &c, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_ndiff_discontinuous_cs_t *ndd) {
+  static const char *names[8] = {"NDIFF_CONTINUOUS = False", "(free)", "NDIFF_TAPERING", "KHTR_USE_EBT_STRUCT",
+                                 "NDIFF_USE_UNMASKED_TRANSPORT_BUG", "the neutral-diffusion diagnostics", "(free)", "(free)"};
+  const mom6hip_eos_t *eos = c.eos;
+  M6_REQUIRE(nd != nullptr && eos != nullptr, "tracer_hordiff: USE_NEUTRAL_DIFFUSION needs the neutral_diffusion control structure and tv%%eqn_of_state");
+  M6_REQUIRE(nd->initialized, "neutral_diffusion: the control structure is not initialised");
+  if (nd->unsupported[0] && ndd) {      // NDIFF_CONTINUOUS = False with its parameters: neutral_diffusion_disc.hip
+    for (int q = 4; q < 8; q++) M6_REQUIRE(!nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
+    return neutral_disc_branch(c, nd, ndd);
+  }
+  // unsupported[2] (tapering) and [3] (KhTh_use_ebt_struct) are the switches of the two modes of the fluxes
+  for (int q = 0; q < 8; q++) M6_REQUIRE(q == 2 || q == 3 || !nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
+  const bool taper = nd->unsupported[2] != 0, ebt = c.ebt_struct != nullptr;
+  M6_REQUIRE(!taper || nd->interior_only, "neutral_diffusion: NDIFF_TAPERING is read with NDIFF_INTERIOR_ONLY only (the reference never reads it "
+             "otherwise): it is refused without");
+  const m6::GridDev g = c.ctx->g;
+  hipStream_t s = c.ctx->stream;
+  const int nk = g.nk;
+  const size_t hpl = (size_t)g.nih * g.njh, upl = (size_t)(g.nih + 1) * g.njh, vpl = (size_t)g.nih * (g.njh + 1);
+  const size_t fpl = upl > vpl ? upl : vpl;
+  NDArgs A = {};
+  A.E = EosDev{eos->form, eos->Rho_T0_S0, eos->dRho_dT, eos->dRho_dS};
+  A.ref_pres = nd->ref_pres; A.gH = g.g_Earth * nd->H_to_RZ; A.pa_to_H = 1. / (nd->H_to_RZ * g.g_Earth);
+  A.h_neglect = g.H_subroundoff; A.p_surf = c.p_surf; A.interior = nd->interior_only != 0; A.ebt = c.ebt_struct;
+  const int coef = (taper ? ND_COEF_TAPER : 0) | (ebt ? ND_COEF_EBT : 0);
+  const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1;
+  const int nbc = (ni + 2 + 63) / 64, nbu = (ni + 1 + 63) / 64, nbv = (ni + 63) / 64;      // blocks along i: columns with the halo, u faces, v faces
+  const dim3 gc(nbc * (nj + 2)), gu(nbu * nj), gv(nbv * (nj + 1)), b64(64);
+  NDBranch b;
+  b.ns = 2 * nk + 2; b.flux_has_coef = ebt;
+  b.bad = {{1, "ppm_ave: dx<0 or dx>1 should not happened! (a neutral layer spans more than one cell)"},
+           {2, "neutral_diffusion: a neutral surface lies above the one before it in a column"}};
+  b.scratch = [&](const double *hbl) -> int {
+    A.hbl = hbl;
+    A.irec = (double *)c.st.scratch(sizeof(double) * hpl * (nk + 1) * IREC);
+    A.trec = (double *)c.st.scratch(sizeof(double) * hpl * ((size_t)nk + 1) * TREC);
+    if (A.interior) { A.zbot = (double *)c.st.scratch(sizeof(double) * hpl); A.kbot = (int *)c.st.scratch(sizeof(int) * hpl); }
+    if (ebt) A.coef_h = (double *)c.st.scratch(sizeof(double) * hpl * ((size_t)nk + 1));
+    if (taper) { A.kt[0] = (ko_t *)c.st.scratch(sizeof(ko_t) * fpl * 8); A.kt[1] = A.kt[0] + fpl * 4; }
+    M6_REQUIRE(!c.st.failed() && A.irec && A.trec && (!A.interior || (A.zbot && A.kbot)) && (!ebt || A.coef_h) && (!taper || A.kt[0]),
+               "neutral_diffusion: out of device memory");
+    return 0;
+  };
+  b.surfaces = [&]() -> int {
+    A.T = c.d_tr[c.idx_T]; A.S = c.d_tr[c.idx_S];
+    hipLaunchKernelGGL(nd_column_kernel, gc, b64, 0, s, A, nbc);
+    hipLaunchKernelGGL(nd_surfaces_kernel<0>, gu, b64, 0, s, A, nbu);
+    hipLaunchKernelGGL(nd_surfaces_kernel<1>, gv, b64, 0, s, A, nbv);
     if (taper) {      // the layer numbers of the taper depend on h and CS%hbl only: once where the surfaces are formed
-      hipLaunchKernelGGL(nd_taper_kernel<0>, dim3(xcd_grid(nbu, nj)), dim3(64), 0, s, A, nbu, nj);
-      hipLaunchKernelGGL(nd_taper_kernel<1>, dim3(xcd_grid(nbv, nj + 1)), dim3(64), 0, s, A, nbv, nj + 1);
+      hipLaunchKernelGGL(nd_taper_kernel<0>, gu, b64, 0, s, A, nbu);
+      hipLaunchKernelGGL(nd_taper_kernel<1>, gv, b64, 0, s, A, nbv);
     }
     return 0;
   };
+  if (ebt) b.once = [&]() -> int {      // Coef_h :670-684 depends on khdt, I_numitts and ebt_struct only: once a call, not once an iteration
+    M6_HIP(hipMemsetAsync(A.coef_h, 0, sizeof(double) * hpl * ((size_t)nk + 1), s));
+    hipLaunchKernelGGL(nd_coef_h_kernel, dim3((ni + 63) / 64, nj), b64, 0, s, A);
+    double *f1[1] = {A.coef_h}; int32_t p1[1] = {MOM6HIP_POS_H}, n1[1] = {nk + 1};
+    return m6::group_pass(c.ctx, f1, p1, n1, 1);      // pass_var(CS%Coef_h, G%Domain)
+  };
+  b.tracer_cols = [&]() { hipLaunchKernelGGL(nd_tracer_cols_kernel, gc, b64, 0, s, A, nbc); };
   // the two flux kernels of a batch in the coefficient mode of the call
   auto launch_flux = [&](auto sym, auto mode) {
-    hipLaunchKernelGGL((nd_flux_kernel<0, decltype(sym)::value, decltype(mode)::value>), dim3(xcd_grid(nbu, nj)), dim3(64), 0, s, A, nbu, nj);
-    hipLaunchKernelGGL((nd_flux_kernel<1, decltype(sym)::value, decltype(mode)::value>), dim3(xcd_grid(nbv, nj + 1)), dim3(64), 0, s, A, nbv, nj + 1);
+    hipLaunchKernelGGL((nd_flux_kernel<0, decltype(sym)::value, decltype(mode)::value>), gu, b64, 0, s, A, nbu);
+    hipLaunchKernelGGL((nd_flux_kernel<1, decltype(sym)::value, decltype(mode)::value>), gv, b64, 0, s, A, nbv);
   };
   auto launch_fluxes = [&](auto sym) {
     if (coef == ND_COEF_NONE) launch_flux(sym, std::integral_constant<int, ND_COEF_NONE>());
@@ -798,43 +744,7 @@ int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusi
     else if (coef == ND_COEF_EBT) launch_flux(sym, std::integral_constant<int, ND_COEF_EBT>());
     else launch_flux(sym, std::integral_constant<int, ND_COEF_BOTH>());
   };
-  if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;      // do_group_pass(CS%pass_t) :478
-  (*halo_updates)++;
-  if (int rc = calc_coeffs()) return rc;
-  if (ebt) {      // Coef_h :670-684 depends on khdt, I_numitts and ebt_struct only: once a call, not once an iteration
-    M6_HIP(hipMemsetAsync(A.coef_h, 0, sizeof(double) * hpl * ((size_t)nk + 1), s));
-    hipLaunchKernelGGL(nd_coef_h_kernel, dim3((ni + 63) / 64, nj), dim3(64), 0, s, A);
-    double *f1[1] = {A.coef_h}; int32_t p1[1] = {MOM6HIP_POS_H}, n1[1] = {nk + 1};
-    if (int rc = m6::group_pass(ctx, f1, p1, n1, 1)) return rc;      // pass_var(CS%Coef_h, G%Domain)
-  }
-  for (int itt = 1; itt <= num_itts; itt++) {
-    if (itt > 1) {
-      if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;
-      (*halo_updates)++;
-      if (nd->recalc_neutral_surf) { if (int rc = calc_coeffs()) return rc; }
-    }
-    for (int m0 = 0; m0 < ntr; m0 += nbmax) {      // neutral_diffusion :605: the tracers are independent of each other, a batch at a time
-      A.nb = (ntr - m0 < nbmax) ? ntr - m0 : nbmax;
-      for (int z = 0; z < A.nb; z++) { A.t[z] = d_tr[m0 + z]; A.cu[z] = cu[m0 + z]; }
-      for (int z = A.nb; z < ND_BATCH; z++) { A.t[z] = nullptr; A.cu[z] = 0.; }
-      hipLaunchKernelGGL(nd_tracer_cols_kernel, dim3(xcd_grid(nbc, nj + 2)), dim3(64), 0, s, A, nbc, nj + 2);
-      if (A.symmetric) {
-        launch_fluxes(std::true_type());
-        hipLaunchKernelGGL(nd_update_sym_kernel, dim3((ni + 255) / 256, nj, nk * A.nb), dim3(256), 0, s, A);
-      } else {
-        launch_fluxes(std::false_type());
-        if (ebt) hipLaunchKernelGGL(nd_update_kernel<true>, dim3((ni + 63) / 64, nj, A.nb), dim3(64), sizeof(double) * 64 * nk, s, A);
-        else hipLaunchKernelGGL(nd_update_kernel<false>, dim3((ni + 63) / 64, nj, A.nb), dim3(64), sizeof(double) * 64 * nk, s, A);
-      }
-    }
-  }
-  M6_HIP(hipGetLastError());
-  int hbad = 0;
-  M6_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-  M6_HIP(hipStreamSynchronize(s));
-  M6_REQUIRE(!(hbad & 1), "ppm_ave: dx<0 or dx>1 should not happened! (a neutral layer spans more than one cell)");
-  M6_REQUIRE(!(hbad & 2), "neutral_diffusion: a neutral surface lies above the one before it in a column");
-  return 0;
+  b.fluxes = [&](bool symmetric) { if (symmetric) launch_fluxes(std::true_type()); else launch_fluxes(std::false_type()); };
+  return neutral_drive(c, nd, A, b);
 }
-
 }  // namespace m6

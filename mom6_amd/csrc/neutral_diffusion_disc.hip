@@ -1,6 +1,7 @@
 // neutral_diffusion_disc.hip -- the discontinuous-reconstruction branch (NDIFF_CONTINUOUS = False) of MOM_neutral_diffusion
 // (src/tracer/MOM_neutral_diffusion.F90) as gfx950 kernels, called from neutral_branch (neutral_diffusion.hip) when
-// nd->unsupported[0] is set and the parameters of the branch (mom6hip_ndiff_discontinuous_cs_t) came with the call.
+// nd->unsupported[0] is set and the parameters of the branch (mom6hip_ndiff_discontinuous_cs_t) came with the call.  The branch supplies
+// its kernels to neutral_drive (neutral_common.hpp), the host driver it shares with the continuous reconstruction.
 //
 //   ndd_column_kernel      neutral_diffusion_calc_coeffs :394-508 for one h column (halo 1): P_i(k,1:2) as :436-451 sums them,
 //                          build_reconstructions_1d of T and S (remap_column.hpp), the edge values re-evaluated from the polynomial at 0
@@ -24,42 +25,26 @@
 #include <cfloat>
 #include <cmath>
 
-#include "common.hpp"
+#include "neutral_common.hpp"
 #include "eos.hpp"
 #define REMAP_PIECES_SELECT 1
 #include "remap_pieces.hpp"
 #include "remap_column.hpp"
 
-namespace m6 {
-// the update of the tracers of a batch from the tendencies or the fluxes (neutral_diffusion.hip: nd_update_sym_kernel / nd_update_kernel)
-int nd_launch_update(mom6hip_ctx_t *ctx, const double *h, double scale, int ns, bool symmetric, unsigned char *const *KoL,
-                     unsigned char *const *KoR, double *const *Flx, double *const *tend, long flx_stride, const double *const *khdt,
-                     double *const *t, const double *cu, int nb);
-}
-
 namespace {
 
+using namespace m6;
 using namespace m6::eos;
 
-typedef unsigned char ko_t;
-constexpr int NDD_BATCH = 4;
 constexpr int CREC = 13;      // a layer of a column: P_i(k,1:2), the coefficients of T and of S (three each), T_i(k,1:2), S_i(k,1:2), stable_cell
 constexpr int QREC = 5;       // a layer of a column for one tracer: its coefficients (three) and Tid(k,1:2)
 
-struct NDDArgs {
-  m6::GridDev g;
+struct NDDArgs : NDFaces {
   EosDev E;
-  double ref_pres, gH, h_neglect, scale, drho_tol, x_tol;
-  int ns, scheme, nterm, method, imethod, form, max_iter, hard_fail, interior;      // method: NEUTRAL_POS_METHOD; imethod: the integration method
-  const double *h, *T, *S, *p_surf, *hbl;
+  double ref_pres, gH, h_neglect, drho_tol, x_tol;
+  int scheme, nterm, method, imethod, form, max_iter, hard_fail, interior;      // method: NEUTRAL_POS_METHOD; imethod: the integration method
+  const double *T, *S, *p_surf, *hbl;
   double *crec, *qrec;
-  double *PoL[2], *PoR[2], *hEff[2], *Flx[2], *tend[2][2];
-  ko_t *KoL[2], *KoR[2];
-  const double *khdt[2];
-  int nb;
-  double *t[NDD_BATCH];
-  long flx_stride;
-  int *bad;
 };
 
 __device__ __forceinline__ long crec_at(int q, int k, long c, long hpl, int nk) { return ((long)q * nk + k) * hpl + c; }
@@ -253,16 +238,13 @@ __device__ double search_other_column(const NDDArgs &A, int ksurf, double pos_la
   return find_neutral_pos_full(A, pos_last, T_from, S_from, P_from, L.P1, L.P2, L.cT, L.cS);
 }
 
-__device__ __forceinline__ bool block_ij(int nbx, int &bx, int &by) { bx = blockIdx.x % nbx; by = blockIdx.x / nbx; return true; }
-
 template <int NKM>
 __global__ __launch_bounds__(64) void ndd_column_kernel(NDDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  block_ij(nbx, bx, by);
-  const int i = g.isc - 1 + bx * 64 + threadIdx.x, j = g.jsc - 1 + by, nk = g.nk;
-  if (i > g.iec + 1) return;
-  const long n2 = g.h2(i, j), hpl = (long)g.nih * g.njh;
+  const NDCol C = nd_column(g, nbx);
+  if (!C.has) return;
+  const long n2 = C.n2, hpl = C.hpl;
+  const int nk = g.nk;
   double h[NKM], u[NKM], EL[NKM], ER[NKM], C1[NKM], w[5 * (NKM + 1)];
   double *__restrict__ r = A.crec;
   for (int k = 0; k < nk; k++) h[k] = A.h[n2 + hpl * k];
@@ -289,16 +271,9 @@ __global__ __launch_bounds__(64) void ndd_column_kernel(NDDArgs A, int nbx) {
   }
   int k_bot = 0;
   if (A.interior) {      // :383-388, :500-506
+    double zeta_bot;
     k_bot = 1;
-    if (g.mask2dT[n2] > 0.0) {
-      const double hbl = A.hbl[n2];
-      if (hbl != 0.) {      // boundary_k_range(SURFACE, ...), src/tracer/MOM_hor_bnd_diffusion.F90:609-647
-        double hsum = 0., htot = 0.;
-        for (int k = 0; k < nk; k++) hsum = hsum + h[k];
-        if (hbl >= hsum) k_bot = nk;
-        else for (int k = 0; k < nk; k++) { htot = htot + h[k]; if (htot >= hbl) { k_bot = k + 1; break; } }
-      }
-    }
+    if (g.mask2dT[n2] > 0.0) boundary_k_range_surface(h, 1, nk, A.hbl[n2], k_bot, zeta_bot);
   }
   for (int k = 0; k < nk; k++) {      // mark_unstable_cells :1841
     const double P1 = r[crec_at(0, k, n2, hpl, nk)], Pb = r[crec_at(1, k, n2, hpl, nk)];
@@ -311,22 +286,13 @@ __global__ __launch_bounds__(64) void ndd_column_kernel(NDDArgs A, int nbx) {
 template <int DIR>
 __global__ __launch_bounds__(64) void ndd_surfaces_kernel(NDDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  block_ij(nbx, bx, by);
-  const int i = (DIR ? g.isc : g.isc - 1) + bx * 64 + threadIdx.x, j = (DIR ? g.jsc - 1 : g.jsc) + by, nk = g.nk;
-  if (i > g.iec) return;
-  const long f = DIR ? g.v2(i, j) : g.u2(i, j), pl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
-  const long hpl = (long)g.nih * g.njh, cl = g.h2(i, j), cr = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const NDFace F = nd_face<DIR>(g, nbx);
+  if (!F.has) return;
+  const long f = F.f, pl = F.pl, hpl = F.hpl, cl = F.cl, cr = F.cr;
+  if (!F.wet) { nd_dry_surfaces<DIR>(A, f, pl); return; }
   double *__restrict__ PoL = A.PoL[DIR], *__restrict__ PoR = A.PoR[DIR], *__restrict__ hEff = A.hEff[DIR];
   ko_t *__restrict__ KoL = A.KoL[DIR], *__restrict__ KoR = A.KoR[DIR];
-  const int ns = A.ns;
-  if (!((DIR ? g.mask2dCv[f] : g.mask2dCu[f]) > 0.0)) {      // :510-519: what the arrays hold where no surfaces are searched for
-    for (int ks = 0; ks < ns; ks++) {
-      PoL[f + pl * ks] = 0.; PoR[f + pl * ks] = 0.; KoL[f + pl * ks] = 1; KoR[f + pl * ks] = 1;
-      if (ks < ns - 1) hEff[f + pl * ks] = 0.;
-    }
-    return;
-  }
+  const int ns = A.ns, nk = g.nk;
   const double *__restrict__ r = A.crec;
   auto load = [&](long c, int kl) {      // the layer kl (1-based) of the column c
     const int k = kl - 1;
@@ -425,11 +391,10 @@ __global__ __launch_bounds__(64) void ndd_surfaces_kernel(NDDArgs A, int nbx) {
 template <int NKM>
 __global__ __launch_bounds__(64) void ndd_tracer_cols_kernel(NDDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  block_ij(nbx, bx, by);
-  const int i = g.isc - 1 + bx * 64 + threadIdx.x, j = g.jsc - 1 + by, nk = g.nk;
-  if (i > g.iec + 1) return;
-  const long n2 = g.h2(i, j), hpl = (long)g.nih * g.njh;
+  const NDCol C = nd_column(g, nbx);
+  if (!C.has) return;
+  const long n2 = C.n2, hpl = C.hpl;
+  const int nk = g.nk;
   double h[NKM], u[NKM], EL[NKM], ER[NKM], C1[NKM], w[5 * (NKM + 1)];
   for (int k = 0; k < nk; k++) h[k] = A.h[n2 + hpl * k];
   for (int z = 0; z < A.nb; z++) {
@@ -467,14 +432,15 @@ __device__ __forceinline__ TEval t_eval(const NDDArgs &A, int z, long c, int k, 
 template <int DIR, bool SYM>
 __global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx) {
   const m6::GridDev &g = A.g;
-  int bx, by;
-  block_ij(nbx, bx, by);
-  const int i = (DIR ? g.isc : g.isc - 1) + bx * 64 + threadIdx.x, j = (DIR ? g.jsc - 1 : g.jsc) + by;
-  if (i > g.iec) return;
-  const long f = DIR ? g.v2(i, j) : g.u2(i, j), pl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
-  const long hpl = (long)g.nih * g.njh, cl = g.h2(i, j), cr = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const NDFace F = nd_face<DIR>(g, nbx);
+  if (!F.has) return;
+  const long f = F.f, pl = F.pl, hpl = F.hpl, cl = F.cl, cr = F.cr;
   const int ns = A.ns, nb = A.nb, nk = g.nk;
-  const bool wet = (DIR ? g.mask2dCv[f] : g.mask2dCu[f]) > 0.0;
+  if (!F.wet) {
+    for (int z = 0; z < nb; z++)
+      nd_dry_fluxes<SYM>(ns, nk, A.Flx[DIR] + A.flx_stride * z, A.tend[DIR][0] + A.flx_stride * z, A.tend[DIR][1] + A.flx_stride * z, f, pl);
+    return;
+  }
   const double *__restrict__ PiL = A.PoL[DIR], *__restrict__ PiR = A.PoR[DIR], *__restrict__ hEff = A.hEff[DIR];
   const ko_t *__restrict__ KoL = A.KoL[DIR], *__restrict__ KoR = A.KoR[DIR];
   const double cf = A.scale * A.khdt[DIR][f];
@@ -482,18 +448,10 @@ __global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx) {
   for (int z = 0; z < nb; z++) {
     double *__restrict__ Flx = SYM ? nullptr : A.Flx[DIR] + A.flx_stride * z;
     double *__restrict__ tdL = SYM ? A.tend[DIR][0] + A.flx_stride * z : nullptr, *__restrict__ tdR = SYM ? A.tend[DIR][1] + A.flx_stride * z : nullptr;
-    if (!wet) {
-      if (SYM) for (int k = 0; k < nk; k++) { tdL[f + pl * k] = 0.; tdR[f + pl * k] = 0.; }
-      else for (int ks = 0; ks < ns - 1; ks++) Flx[f + pl * ks] = 0.;
-      continue;
-    }
     double pLt = PiL[f], pRt = PiR[f];
     int klt = KoL[f] - 1, krt = KoR[f] - 1;
     double accL = 0., accR = 0.;
-    if (SYM) {
-      for (int k = 0; k < klt; k++) tdL[f + pl * k] = 0.;
-      for (int k = 0; k < krt; k++) tdR[f + pl * k] = 0.;
-    }
+    if (SYM) { nd_tend_store(tdL, f, pl, -1, klt, 0.); nd_tend_store(tdR, f, pl, -1, krt, 0.); }
     for (int ks = 0; ks < ns - 1; ks++) {
       const double pLb = PiL[f + pl * (ks + 1)], pRb = PiR[f + pl * (ks + 1)];
       const int klb = KoL[f + pl * (ks + 1)] - 1, krb = KoR[f + pl * (ks + 1)] - 1;
@@ -513,24 +471,13 @@ __global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx) {
       }
       if (SYM) { accL = accL + cf * flx; accR = accR - cf * flx; }
       else Flx[f + pl * ks] = flx;
-      if (SYM && klb > klt) {
-        tdL[f + pl * klt] = accL; accL = 0.;
-        for (int k = klt + 1; k < klb; k++) tdL[f + pl * k] = 0.;
-      }
-      if (SYM && krb > krt) {
-        tdR[f + pl * krt] = accR; accR = 0.;
-        for (int k = krt + 1; k < krb; k++) tdR[f + pl * k] = 0.;
-      }
+      if (SYM && klb > klt) { nd_tend_store(tdL, f, pl, klt, klb, accL); accL = 0.; }
+      if (SYM && krb > krt) { nd_tend_store(tdR, f, pl, krt, krb, accR); accR = 0.; }
       pLt = pLb; pRt = pRb;
       if (klb > klt) klt = klb;
       if (krb > krt) krt = krb;
     }
-    if (SYM) {
-      tdL[f + pl * klt] = accL;
-      for (int k = klt + 1; k < nk; k++) tdL[f + pl * k] = 0.;
-      tdR[f + pl * krt] = accR;
-      for (int k = krt + 1; k < nk; k++) tdR[f + pl * k] = 0.;
-    }
+    if (SYM) { nd_tend_store(tdL, f, pl, klt, nk, accL); nd_tend_store(tdR, f, pl, krt, nk, accR); }
   }
   if (bad) atomicOr(A.bad, bad);
 }
@@ -545,12 +492,8 @@ void launch_columns(const NDDArgs &A, int nbc, int rows, hipStream_t s, bool tra
 
 namespace m6 {
 
-// neutral_branch (neutral_diffusion.hip) with NDIFF_CONTINUOUS = False; the arguments are its own, ndd the parameters of the branch
-int neutral_disc_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_ndiff_discontinuous_cs_t *ndd,
-                        const mom6hip_eos_t *eos, const double *h, const double *p_surf, const double *h_ML, const double *khdt_x,
-                        const double *khdt_y, int num_itts, double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu,
-                        int idx_T, int idx_S, int *halo_updates) {
-  const int ntr = (int)d_tr.size();
+// neutral_branch (neutral_diffusion.hip) with NDIFF_CONTINUOUS = False; ndd holds the parameters of the branch
+int neutral_disc_branch(const HordiffCall &c, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_ndiff_discontinuous_cs_t *ndd) {
   M6_REQUIRE(ndd->initialized, "neutral_diffusion: the control structure of NDIFF_CONTINUOUS = False is not initialised");
   M6_REQUIRE(ndd->remap_scheme == MOM6HIP_REMAP_PLM || ndd->remap_scheme == MOM6HIP_REMAP_PPM_H4 || ndd->remap_scheme == MOM6HIP_REMAP_PPM_IH4,
              "neutral_diffusion: NDIFF_REMAPPING_SCHEME other than PLM, PPM_H4 or PPM_IH4 is not provided by libmom6hip");
@@ -567,106 +510,57 @@ int neutral_disc_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_di
   M6_REQUIRE(!nd->unsupported[2], "neutral_diffusion: NDIFF_TAPERING with NDIFF_CONTINUOUS = False is not provided by libmom6hip");
   M6_REQUIRE(!nd->unsupported[3], "neutral_diffusion: KHTR_USE_EBT_STRUCT with NDIFF_CONTINUOUS = False is not provided by libmom6hip");
   M6_REQUIRE(ndd->neutral_pos_method == 1 || ndd->max_iter >= 0, "neutral_diffusion: NDIFF_MAX_ITER must not be negative");
-  M6_REQUIRE(idx_T >= 0 && idx_T < ntr && idx_S >= 0 && idx_S < ntr, "tracer_hordiff: tv%%T and tv%%S must be among the tracers (idx_T, idx_S)");
-  const m6::GridDev g = ctx->g;
-  M6_REQUIRE(g.mask2dT && g.mask2dCu && g.mask2dCv && g.IareaT, "neutral_diffusion: mask2dT, mask2dCu, mask2dCv and IareaT are needed");
-  M6_REQUIRE(g.nk >= 2 && g.nk <= 128, "neutral_diffusion: 2 to 128 layers are supported");
-  hipStream_t s = ctx->stream;
-  const int nk = g.nk, ns = 4 * nk;
-  const size_t hpl = (size_t)g.nih * g.njh, upl = (size_t)(g.nih + 1) * g.njh, vpl = (size_t)g.nih * (g.njh + 1);
-  const size_t fpl = upl > vpl ? upl : vpl;
-  const bool symmetric = nd->ndiff_answer_date > 20240330;
+  const m6::GridDev g = c.ctx->g;
+  hipStream_t s = c.ctx->stream;
+  const int nk = g.nk, ntr = (int)c.d_tr.size();
+  const size_t hpl = (size_t)g.nih * g.njh;
   NDDArgs A = {};
-  A.g = g; A.E = EosDev{eos->form, eos->Rho_T0_S0, eos->dRho_dT, eos->dRho_dS};
-  A.ref_pres = nd->ref_pres; A.gH = g.g_Earth * nd->H_to_RZ; A.h_neglect = g.H_subroundoff; A.scale = I_numitts;
-  A.drho_tol = ndd->drho_tol; A.x_tol = ndd->x_tol; A.ns = ns; A.scheme = ndd->remap_scheme;
+  A.E = EosDev{c.eos->form, c.eos->Rho_T0_S0, c.eos->dRho_dT, c.eos->dRho_dS};
+  A.ref_pres = nd->ref_pres; A.gH = g.g_Earth * nd->H_to_RZ; A.h_neglect = g.H_subroundoff;
+  A.drho_tol = ndd->drho_tol; A.x_tol = ndd->x_tol; A.scheme = ndd->remap_scheme;
   A.nterm = ndd->remap_scheme == MOM6HIP_REMAP_PLM ? 2 : 3;      // CS%deg + 1
-  {      // the integration method build_reconstructions_1d returns on nk cells
-    const int local = remap_local_scheme(ndd->remap_scheme, nk);
-    A.imethod = local == MOM6HIP_REMAP_PCM ? INT_PCM : local == MOM6HIP_REMAP_PLM ? INT_PLM : INT_PPM;
-  }
   A.form = ndd->delta_rho_form; A.max_iter = ndd->max_iter; A.hard_fail = ndd->hard_fail_heff != 0;
-  A.method = ndd->neutral_pos_method; A.interior = nd->interior_only != 0;
-  A.h = h; A.p_surf = p_surf; A.khdt[0] = khdt_x; A.khdt[1] = khdt_y; A.hbl = nullptr;
-  const int nbmax = ntr < NDD_BATCH ? ntr : NDD_BATCH;
-  const size_t per_tracer = symmetric ? fpl * nk * 4 : fpl * ns * 2;
-  double *crec = (double *)st.scratch(sizeof(double) * hpl * nk * CREC);
-  double *qrec = (double *)st.scratch(sizeof(double) * hpl * nk * QREC * (size_t)nbmax);
-  double *faces = (double *)st.scratch(sizeof(double) * (fpl * ns * 6 + per_tracer * (size_t)nbmax));
-  ko_t *kos = (ko_t *)st.scratch(sizeof(ko_t) * fpl * ns * 4);
-  int *bad = (int *)st.scratch(64);
-  double *hbl = nullptr;
-  if (A.interior) {      // :374-380: CS%hbl = visc%h_ML, pass_var(CS%hbl, halo=1)
-    M6_REQUIRE(h_ML != nullptr, "hor_bnd_diffusion requires that visc%%h_ML is associated.");
-    hbl = (double *)st.scratch(sizeof(double) * hpl);
-    M6_REQUIRE(!st.failed() && hbl, "neutral_diffusion: out of device memory");
-    A.hbl = hbl;
-  }
-  M6_REQUIRE(!st.failed() && crec && qrec && faces && kos && bad, "neutral_diffusion: out of device memory");
-  A.crec = crec; A.qrec = qrec; A.bad = bad;
-  double *per = faces + fpl * ns * 6;
-  for (int d = 0; d < 2; d++) {
-    A.PoL[d] = faces + fpl * ns * (3 * d); A.PoR[d] = A.PoL[d] + fpl * ns; A.hEff[d] = A.PoR[d] + fpl * ns;
-    A.KoL[d] = kos + fpl * ns * (2 * d); A.KoR[d] = A.KoL[d] + fpl * ns;
-    A.Flx[d] = symmetric ? nullptr : per + fpl * ns * d;
-    A.tend[d][0] = symmetric ? per + fpl * nk * (2 * d) : nullptr; A.tend[d][1] = symmetric ? per + fpl * nk * (2 * d + 1) : nullptr;
-  }
-  A.flx_stride = (long)per_tracer;
-  M6_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
-
+  A.method = ndd->neutral_pos_method; A.interior = nd->interior_only != 0; A.p_surf = c.p_surf;
   const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1;
   const int nbc = (ni + 2 + 63) / 64, nbu = (ni + 1 + 63) / 64, nbv = (ni + 63) / 64;
+  const dim3 gu(nbu * nj), gv(nbv * (nj + 1)), b64(64);
   auto columns = [&](bool tracers) {
     if (nk <= 32) launch_columns<32>(A, nbc, nj + 2, s, tracers);
     else if (nk <= 80) launch_columns<80>(A, nbc, nj + 2, s, tracers);
     else launch_columns<128>(A, nbc, nj + 2, s, tracers);
   };
-  std::vector<double *> pf(d_tr);
-  std::vector<int32_t> ppos(ntr, MOM6HIP_POS_H), pnk(ntr, nk);
-  auto calc_coeffs = [&]() -> int {      // neutral_diffusion_calc_coeffs :337
-    A.T = d_tr[idx_T]; A.S = d_tr[idx_S];
-    if (A.interior) {
-      M6_HIP(hipMemcpyAsync(hbl, h_ML, sizeof(double) * hpl, hipMemcpyDeviceToDevice, s));
-      double *f1[1] = {hbl}; int32_t p1[1] = {MOM6HIP_POS_H}, n1[1] = {1};
-      if (int rc = m6::group_pass(ctx, f1, p1, n1, 1)) return rc;
-    }
-    columns(false);
-    hipLaunchKernelGGL(ndd_surfaces_kernel<0>, dim3(nbu * nj), dim3(64), 0, s, A, nbu);
-    hipLaunchKernelGGL(ndd_surfaces_kernel<1>, dim3(nbv * (nj + 1)), dim3(64), 0, s, A, nbv);
+  NDBranch b;
+  b.ns = 4 * nk; b.flux_has_coef = false;
+  b.bad = {{4, "Negative thicknesses in neutral diffusion"},      // :1812 (HARD_FAIL_HEFF)
+           {8, "drho_min is the same sign as dhro_max"},          // :2032
+           {2, "neutral_diffusion: a neutral surface lies above the one before it in a column"}};
+  b.scratch = [&](const double *hbl) -> int {      // (the driver has checked nk by now)
+    A.hbl = hbl;
+    const int local = remap_local_scheme(ndd->remap_scheme, nk);      // the integration method build_reconstructions_1d returns on nk cells
+    A.imethod = local == MOM6HIP_REMAP_PCM ? INT_PCM : local == MOM6HIP_REMAP_PLM ? INT_PLM : INT_PPM;
+    A.crec = (double *)c.st.scratch(sizeof(double) * hpl * nk * CREC);
+    A.qrec = (double *)c.st.scratch(sizeof(double) * hpl * nk * QREC * (size_t)(ntr < ND_BATCH ? ntr : ND_BATCH));
+    M6_REQUIRE(!c.st.failed() && A.crec && A.qrec, "neutral_diffusion: out of device memory");
     return 0;
   };
-  if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;      // do_group_pass(CS%pass_t) :478
-  (*halo_updates)++;
-  if (int rc = calc_coeffs()) return rc;
-  for (int itt = 1; itt <= num_itts; itt++) {
-    if (itt > 1) {
-      if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;
-      (*halo_updates)++;
-      if (nd->recalc_neutral_surf) { if (int rc = calc_coeffs()) return rc; }
+  b.surfaces = [&]() -> int {
+    A.T = c.d_tr[c.idx_T]; A.S = c.d_tr[c.idx_S];
+    columns(false);
+    hipLaunchKernelGGL(ndd_surfaces_kernel<0>, gu, b64, 0, s, A, nbu);
+    hipLaunchKernelGGL(ndd_surfaces_kernel<1>, gv, b64, 0, s, A, nbv);
+    return 0;
+  };
+  b.tracer_cols = [&]() { columns(true); };
+  b.fluxes = [&](bool symmetric) {
+    if (symmetric) {
+      hipLaunchKernelGGL((ndd_flux_kernel<0, true>), gu, b64, 0, s, A, nbu);
+      hipLaunchKernelGGL((ndd_flux_kernel<1, true>), gv, b64, 0, s, A, nbv);
+    } else {
+      hipLaunchKernelGGL((ndd_flux_kernel<0, false>), gu, b64, 0, s, A, nbu);
+      hipLaunchKernelGGL((ndd_flux_kernel<1, false>), gv, b64, 0, s, A, nbv);
     }
-    for (int m0 = 0; m0 < ntr; m0 += nbmax) {
-      A.nb = (ntr - m0 < nbmax) ? ntr - m0 : nbmax;
-      double cub[NDD_BATCH];
-      for (int z = 0; z < NDD_BATCH; z++) { A.t[z] = z < A.nb ? d_tr[m0 + z] : nullptr; cub[z] = z < A.nb ? cu[m0 + z] : 0.; }
-      columns(true);
-      if (symmetric) {
-        hipLaunchKernelGGL((ndd_flux_kernel<0, true>), dim3(nbu * nj), dim3(64), 0, s, A, nbu);
-        hipLaunchKernelGGL((ndd_flux_kernel<1, true>), dim3(nbv * (nj + 1)), dim3(64), 0, s, A, nbv);
-      } else {
-        hipLaunchKernelGGL((ndd_flux_kernel<0, false>), dim3(nbu * nj), dim3(64), 0, s, A, nbu);
-        hipLaunchKernelGGL((ndd_flux_kernel<1, false>), dim3(nbv * (nj + 1)), dim3(64), 0, s, A, nbv);
-      }
-      if (int rc = m6::nd_launch_update(ctx, h, I_numitts, ns, symmetric, A.KoL, A.KoR, A.Flx, &A.tend[0][0], A.flx_stride, A.khdt, A.t, cub, A.nb)) return rc;
-    }
-  }
-  M6_HIP(hipGetLastError());
-  int hbad = 0;
-  M6_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-  M6_HIP(hipStreamSynchronize(s));
-  M6_REQUIRE(!(hbad & 4), "Negative thicknesses in neutral diffusion");      // :1812 (HARD_FAIL_HEFF)
-  M6_REQUIRE(!(hbad & 8), "drho_min is the same sign as dhro_max");          // :2032
-  M6_REQUIRE(!(hbad & 2), "neutral_diffusion: a neutral surface lies above the one before it in a column");
-  return 0;
+  };
+  return neutral_drive(c, nd, A, b);
 }
 
 }  // namespace m6

@@ -15,7 +15,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "common.hpp"
+#include "hordiff_call.hpp"
 
 namespace {
 
@@ -148,106 +148,45 @@ __global__ __launch_bounds__(256) void hd_commit_kernel(HDArgs A) {
 
 }  // namespace
 
-extern "C" int mom6hip_tracer_hordiff(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const double *h, double dt,
-                                      double *const *tr, const double *conc_underflow, int32_t ntr, int32_t memspace,
-                                      mom6hip_hordiff_stats_t *stats) {
-  return mom6hip_tracer_hordiff_varmix(ctx, cs, nullptr, h, dt, tr, conc_underflow, ntr, memspace, stats);
-}
+// what an entry point hands on beside the arguments all of them have: the control structures it takes, and whether it is the one
+// that takes DIFFUSE_ML_TO_INTERIOR (epi) or USE_HORIZONTAL_BOUNDARY_DIFFUSION (hbd)
+struct HordiffOpts {
+  const mom6hip_neutral_diffusion_cs_t *nd;
+  const mom6hip_epipycnal_cs_t *epi;
+  const mom6hip_hor_bnd_diffusion_cs_t *hbd;
+  const mom6hip_ndiff_discontinuous_cs_t *ndd;
+  const mom6hip_eos_t *eos;
+  const double *p_surf;
+  int32_t idx_T, idx_S;
+  bool takes_epi, takes_hbd;
+};
 
-extern "C" int mom6hip_tracer_hordiff_varmix(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hordiff_fields_t *F,
-                                             const double *h, double dt, double *const *tr, const double *conc_underflow, int32_t ntr,
-                                             int32_t memspace, mom6hip_hordiff_stats_t *stats) {
+static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hordiff_fields_t *F, const double *h, double dt,
+                        double *const *tr, const double *conc_underflow, int32_t ntr, int32_t memspace, mom6hip_hordiff_stats_t *stats,
+                        const HordiffOpts &o) {
   M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
-  M6_REQUIRE(!cs->unsupported[0], "tracer_hordiff: USE_NEUTRAL_DIFFUSION is not provided by this entry point (mom6hip_tracer_hordiff_neutral takes it)");
-  return mom6hip_tracer_hordiff_neutral(ctx, cs, nullptr, F, h, nullptr, nullptr, dt, tr, conc_underflow, ntr, 0, 0, memspace, stats);
-}
-
-namespace m6 {
-int epipycnal_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_epipycnal_cs_t *epi, const mom6hip_eos_t *eos, const double *h,
-                     const double *khdt_x, const double *khdt_y, int num_itts, const std::vector<double *> &d_tr,
-                     const std::vector<double> &cu, int idx_T, int idx_S, int *halo_updates);
-int neutral_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_eos_t *eos, const double *h,
-                   const double *p_surf, const double *h_ML, const double *ebt_struct, const double *khdt_x, const double *khdt_y, int num_itts,
-                   double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int idx_T, int idx_S,
-                   int *halo_updates, const mom6hip_ndiff_discontinuous_cs_t *ndd);
-int hbd_branch(mom6hip_ctx_t *ctx, Stager &st, const mom6hip_hor_bnd_diffusion_cs_t *hbd, const double *h, const double *h_ML,
-               const double *ebt_struct, double KhTr_min, bool full_depth_khtr_min, const double *khdt_x, const double *khdt_y, int num_itts,
-               double I_numitts, const std::vector<double *> &d_tr, const std::vector<double> &cu, int *halo_updates);
-}
-
-static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
-                        const mom6hip_epipycnal_cs_t *epi, const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos,
-                        const double *p_surf, double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
-                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_hor_bnd_diffusion_cs_t *hbd = nullptr,
-                        const mom6hip_ndiff_discontinuous_cs_t *ndd = nullptr);
-
-extern "C" int mom6hip_tracer_hordiff_neutral(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
-                                              const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, const double *p_surf,
-                                              double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
-                                              int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats) {
-  M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
-  M6_REQUIRE(!cs->unsupported[2], "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR is not provided by this entry point (mom6hip_tracer_hordiff_epipycnal takes it)");
-  return hordiff_impl(ctx, cs, nd, nullptr, F, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, stats);
-}
-
-extern "C" int mom6hip_tracer_hordiff_epipycnal(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_epipycnal_cs_t *epi,
-                                                const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, double dt,
-                                                double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S,
-                                                int32_t memspace, mom6hip_hordiff_stats_t *stats) {
-  M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
-  M6_REQUIRE(!cs->unsupported[0], "MOM_tracer_hor_diff: USE_NEUTRAL_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!");      // :1732
-  M6_REQUIRE(!cs->unsupported[2] || epi != nullptr, "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR needs its control structure (mom6hip_epipycnal_cs_t)");
-  return hordiff_impl(ctx, cs, nullptr, cs->unsupported[2] ? epi : nullptr, F, h, eos, nullptr, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, stats);
-}
-
-extern "C" int mom6hip_tracer_hordiff_hbd(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hor_bnd_diffusion_cs_t *hbd,
-                                          const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_hordiff_fields_t *F, const double *h,
-                                          const mom6hip_eos_t *eos, const double *p_surf, double dt, double *const *tr,
-                                          const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S, int32_t memspace,
-                                          mom6hip_hordiff_stats_t *stats) {
-  M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
-  M6_REQUIRE(!(cs->unsupported[1] && cs->unsupported[2]),
-             "MOM_tracer_hor_diff: USE_HORIZONTAL_BOUNDARY_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!");      // :1735
-  M6_REQUIRE(!cs->unsupported[2], "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR is not provided by this entry point (mom6hip_tracer_hordiff_epipycnal takes it)");
-  M6_REQUIRE(!cs->unsupported[1] || hbd != nullptr, "tracer_hordiff: USE_HORIZONTAL_BOUNDARY_DIFFUSION needs its control structure (mom6hip_hor_bnd_diffusion_cs_t)");
-  return hordiff_impl(ctx, cs, nd, nullptr, F, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, stats, hbd);
-}
-
-// the same with the parameters of NDIFF_CONTINUOUS = False; hbd is read with USE_HORIZONTAL_BOUNDARY_DIFFUSION only
-extern "C" int mom6hip_tracer_hordiff_neutral_discontinuous(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs,
-                                                            const mom6hip_hor_bnd_diffusion_cs_t *hbd, const mom6hip_neutral_diffusion_cs_t *nd,
-                                                            const mom6hip_ndiff_discontinuous_cs_t *ndd, const mom6hip_hordiff_fields_t *F,
-                                                            const double *h, const mom6hip_eos_t *eos, const double *p_surf, double dt,
-                                                            double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
-                                                            int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats) {
-  M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
-  M6_REQUIRE(!(cs->unsupported[1] && cs->unsupported[2]),
-             "MOM_tracer_hor_diff: USE_HORIZONTAL_BOUNDARY_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!");      // :1735
-  M6_REQUIRE(!cs->unsupported[2], "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR is not provided by this entry point (mom6hip_tracer_hordiff_epipycnal takes it)");
-  M6_REQUIRE(!cs->unsupported[1] || hbd != nullptr, "tracer_hordiff: USE_HORIZONTAL_BOUNDARY_DIFFUSION needs its control structure (mom6hip_hor_bnd_diffusion_cs_t)");
-  return hordiff_impl(ctx, cs, nd, nullptr, F, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, stats,
-                      cs->unsupported[1] ? hbd : nullptr, ndd);
-}
-
-static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
-                        const mom6hip_epipycnal_cs_t *epi, const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos,
-                        const double *p_surf, double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
-                        int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_hor_bnd_diffusion_cs_t *hbd,
-                        const mom6hip_ndiff_discontinuous_cs_t *ndd) {
+  // the branches an entry point does not take, and those that exclude each other (MOM_tracer_hor_diff.F90:1732, :1735)
+  M6_REQUIRE(!(o.takes_epi && cs->unsupported[0]), "MOM_tracer_hor_diff: USE_NEUTRAL_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!");
+  M6_REQUIRE(!(o.takes_hbd && cs->unsupported[1] && cs->unsupported[2]),
+             "MOM_tracer_hor_diff: USE_HORIZONTAL_BOUNDARY_DIFFUSION and DIFFUSE_ML_TO_INTERIOR are mutually exclusive!");
+  M6_REQUIRE(o.takes_epi || !cs->unsupported[2], "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR is not provided by this entry point (mom6hip_tracer_hordiff_epipycnal takes it)");
+  M6_REQUIRE(!cs->unsupported[2] || o.epi != nullptr, "tracer_hordiff: DIFFUSE_ML_TO_INTERIOR needs its control structure (mom6hip_epipycnal_cs_t)");
+  M6_REQUIRE(!(o.takes_hbd && cs->unsupported[1]) || o.hbd != nullptr, "tracer_hordiff: USE_HORIZONTAL_BOUNDARY_DIFFUSION needs its control structure (mom6hip_hor_bnd_diffusion_cs_t)");
+  const mom6hip_neutral_diffusion_cs_t *nd = o.nd;
+  const mom6hip_epipycnal_cs_t *epi = cs->unsupported[2] ? o.epi : nullptr;
+  const mom6hip_hor_bnd_diffusion_cs_t *hbd = cs->unsupported[1] ? o.hbd : nullptr;
   static const char *names[8] = {"USE_NEUTRAL_DIFFUSION", "USE_HORIZONTAL_BOUNDARY_DIFFUSION", "DIFFUSE_ML_TO_INTERIOR",
                                  "(free)", "(free)", "KHTR_USE_EBT_STRUCT", "offline khdt (do_online = false)",
                                  "the df_x / df_y flux diagnostics"};
   M6_REQUIRE(ctx != nullptr, "MOM_tracer_hor_diff: register_tracer must be called before tracer_hordiff.");
-  M6_REQUIRE(cs != nullptr && h != nullptr, "tracer_hordiff: null argument");
+  M6_REQUIRE(h != nullptr, "tracer_hordiff: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "tracer_hordiff: bad memspace");
-  // hbd: the call came through mom6hip_tracer_hordiff_hbd, which takes USE_HORIZONTAL_BOUNDARY_DIFFUSION
   // unsupported[5] (CS%KhTr_use_ebt_struct) is a switch every entry point takes: the neutral and the boundary-diffusion branch read
   // fields->ebt_struct, the along-layer and the epipycnal branch read level 1 of the coefficients only and ignore the field
   for (int q = 1; q < 8; q++)
     M6_REQUIRE(q == 2 || q == 5 || (q == 1 && hbd) || !cs->unsupported[q], "tracer_hordiff: %s is not provided by libmom6hip", names[q]);
-  M6_REQUIRE(!cs->unsupported[2] || epi != nullptr, "tracer_hordiff: %s is not provided by this entry point", names[2]);
   const bool use_neutral = cs->unsupported[0] != 0;      // CS%use_neutral_diffusion
-  const bool use_hbd = hbd && cs->unsupported[1];
+  const bool use_hbd = hbd != nullptr;      // (the entry point takes it, and CS%use_hor_bnd_diffusion)
   const bool use_ebt = cs->unsupported[5] != 0 && (use_neutral || use_hbd);      // CS%KhTr_use_ebt_struct where ebt_struct is read
   M6_REQUIRE(!use_ebt || (F && F->ebt_struct), "tracer_hordiff: KHTR_USE_EBT_STRUCT needs VarMix%%ebt_struct (fields->ebt_struct)");
   M6_REQUIRE(!use_neutral || nd == nullptr || (nd->unsupported[3] != 0) == (cs->unsupported[5] != 0),
@@ -334,20 +273,17 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   std::vector<int32_t> ppos(ntr, MOM6HIP_POS_H), pnk(ntr, g.nk);
   int halo_updates = 0;
   const double *d_ebt = use_ebt ? st.in(F->ebt_struct, bH) : nullptr;
+  // visc%h_ML where a branch reads it: the boundary diffusion, and the neutral branch with NDIFF_INTERIOR_ONLY
+  const bool reads_h_ML = F && F->h_ML && (use_hbd || (use_neutral && nd && nd->interior_only));
+  const double *d_hml = reads_h_ML ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
+  const double *d_ps = (use_neutral && o.p_surf) ? st.in(o.p_surf, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
+  M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
+  const m6::HordiffCall call = {ctx, st, A.h, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, o.idx_T, o.idx_S, o.eos, d_ps, d_hml, d_ebt, &halo_updates};
   if (use_hbd) {      // :408-472, before the neutral or the along-layer branch
-    const double *d_hbl = (F && F->h_ML) ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
-    M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
-    if (int rc = m6::hbd_branch(ctx, st, hbd, A.h, d_hbl, d_ebt, cs->KhTr_min, cs->full_depth_khtr_min != 0, A.khdt_x, A.khdt_y, num_itts,
-                                A.scale, d_tr, cu, &halo_updates))
-      return rc;
+    if (int rc = m6::hbd_branch(call, hbd, cs->KhTr_min, cs->full_depth_khtr_min != 0)) return rc;
   }
   if (use_neutral) {      // :474-534
-    const double *d_ps = p_surf ? st.in(p_surf, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
-    const double *d_hml = (nd && nd->interior_only && F && F->h_ML) ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
-    M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
-    if (int rc = m6::neutral_branch(ctx, st, nd, eos, A.h, d_ps, d_hml, d_ebt, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, idx_T, idx_S,
-                                    &halo_updates, ndd))
-      return rc;
+    if (int rc = m6::neutral_branch(call, nd, o.ndd)) return rc;
   } else
   for (int itt = 1; itt <= num_itts; itt++) {      // :540-614
     if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;
@@ -357,10 +293,61 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   }
   M6_HIP(hipGetLastError());
   if (epi) {      // :613-620
-    if (int rc = m6::epipycnal_branch(ctx, st, epi, eos, A.h, A.khdt_x, A.khdt_y, num_itts, d_tr, cu, idx_T, idx_S, &halo_updates)) return rc;
+    if (int rc = m6::epipycnal_branch(call, epi)) return rc;
   }
   if (stats) { stats->num_itts = num_itts; stats->halo_updates = halo_updates; stats->max_CFL = max_CFL; }
   return st.finish();
+}
+
+
+extern "C" int mom6hip_tracer_hordiff(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const double *h, double dt,
+                                      double *const *tr, const double *conc_underflow, int32_t ntr, int32_t memspace,
+                                      mom6hip_hordiff_stats_t *stats) {
+  return mom6hip_tracer_hordiff_varmix(ctx, cs, nullptr, h, dt, tr, conc_underflow, ntr, memspace, stats);
+}
+
+extern "C" int mom6hip_tracer_hordiff_varmix(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hordiff_fields_t *F,
+                                             const double *h, double dt, double *const *tr, const double *conc_underflow, int32_t ntr,
+                                             int32_t memspace, mom6hip_hordiff_stats_t *stats) {
+  M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
+  M6_REQUIRE(!cs->unsupported[0], "tracer_hordiff: USE_NEUTRAL_DIFFUSION is not provided by this entry point (mom6hip_tracer_hordiff_neutral takes it)");
+  return mom6hip_tracer_hordiff_neutral(ctx, cs, nullptr, F, h, nullptr, nullptr, dt, tr, conc_underflow, ntr, 0, 0, memspace, stats);
+}
+
+extern "C" int mom6hip_tracer_hordiff_neutral(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
+                                              const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, const double *p_surf,
+                                              double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
+                                              int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats) {
+  const HordiffOpts o = {nd, nullptr, nullptr, nullptr, eos, p_surf, idx_T, idx_S, false, false};
+  return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
+}
+
+extern "C" int mom6hip_tracer_hordiff_epipycnal(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_epipycnal_cs_t *epi,
+                                                const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, double dt,
+                                                double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S,
+                                                int32_t memspace, mom6hip_hordiff_stats_t *stats) {
+  const HordiffOpts o = {nullptr, epi, nullptr, nullptr, eos, nullptr, idx_T, idx_S, true, false};
+  return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
+}
+
+extern "C" int mom6hip_tracer_hordiff_hbd(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hor_bnd_diffusion_cs_t *hbd,
+                                          const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_hordiff_fields_t *F, const double *h,
+                                          const mom6hip_eos_t *eos, const double *p_surf, double dt, double *const *tr,
+                                          const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S, int32_t memspace,
+                                          mom6hip_hordiff_stats_t *stats) {
+  const HordiffOpts o = {nd, nullptr, hbd, nullptr, eos, p_surf, idx_T, idx_S, false, true};
+  return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
+}
+
+// the same with the parameters of NDIFF_CONTINUOUS = False; hbd is read with USE_HORIZONTAL_BOUNDARY_DIFFUSION only
+extern "C" int mom6hip_tracer_hordiff_neutral_discontinuous(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs,
+                                                            const mom6hip_hor_bnd_diffusion_cs_t *hbd, const mom6hip_neutral_diffusion_cs_t *nd,
+                                                            const mom6hip_ndiff_discontinuous_cs_t *ndd, const mom6hip_hordiff_fields_t *F,
+                                                            const double *h, const mom6hip_eos_t *eos, const double *p_surf, double dt,
+                                                            double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
+                                                            int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats) {
+  const HordiffOpts o = {nd, nullptr, hbd, ndd, eos, p_surf, idx_T, idx_S, false, true};
+  return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
 }
 
 extern "C" uint64_t mom6hip_abi_sizeof_tracer_hor_diff_cs(void) { return sizeof(mom6hip_tracer_hor_diff_cs_t); }

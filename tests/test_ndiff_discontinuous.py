@@ -92,6 +92,8 @@ DISC_CASES = {
     "p_surf_70x9x3": dict(p_surf=True, reentrant=(False, False), ni=70, nj=9, nk=3, NDIFF_REMAPPING_SCHEME="PPM_H4"),
     "nk75": dict(ni=12, nj=8, nk=75, NDIFF_REMAPPING_SCHEME="PPM_IH4", NDIFF_ANSWER_DATE=20240401),
     "five_tracers": dict(ntr=5, conc_underflow=[0.0, 0.0, 0.5, 0.0, 0.0], NDIFF_ANSWER_DATE=20240401),
+    # the order of 2024 and before with a partial second batch: the update from the fluxes [surface][face] (nd_update_kernel) with ns = 4 nk
+    "five_tracers_2024": dict(ntr=5, conc_underflow=[0.0, 0.0, 0.5, 0.0, 0.0], NDIFF_ANSWER_DATE=20240330),
 }
 _DISC_KEYS = ("NDIFF_REMAPPING_SCHEME", "NEUTRAL_POS_METHOD", "DELTA_RHO_FORM", "NDIFF_DRHO_TOL", "NDIFF_X_TOL", "NDIFF_MAX_ITER", "HARD_FAIL_HEFF",
               "NDIFF_REF_PRES")
