@@ -9,6 +9,7 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -92,7 +93,49 @@ struct HostTable {
   std::vector<double> last;
   const double *get(const double *host, size_t n);      // nullptr on failure (error set)
 };
-enum { TABLE_PGF_RLAY = 0, TABLE_PGF_GPRIME, TABLE_SVML_RLAY, TABLE_TD_RLAY, TABLE_TD_GPRIME, TABLE_COUNT = 8 };
+enum { TABLE_PGF_RLAY = 0, TABLE_PGF_GPRIME, TABLE_SVML_RLAY, TABLE_TD_RLAY, TABLE_TD_GPRIME, TABLE_SVBBL_RLAY, TABLE_COUNT = 8 };
+
+// ---- a lane's face column, its launch grid, the two directions, the arrays' sizes (vert_friction.hip, set_viscosity.hip) -------
+// The lane's face of direction DIR (u faces I = isc-1 .. iec, j = jsc .. jec; v faces i = isc .. iec, J = jsc-1 .. jec) in a launch over
+// face_grid(g, DIR, W) with blocks of W lanes; past: the lane lies past iec and has no face.  A kernel leaves on `past` before it forms
+// the column: formed ahead of that return, the offsets cost the column kernels of vert_friction.hip registers.
+struct FaceLane { int i, j; bool past; };
+template <int DIR>
+__device__ __forceinline__ FaceLane face_lane(const GridDev &g, int W) {
+  const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * W + threadIdx.x;
+  return FaceLane{i, (DIR ? g.jsc - 1 : g.jsc) + (int)blockIdx.y, i > g.iec};
+}
+// The face column (i, j): its offset f2 in a plane of faces, the cells c0 and c1 on its two sides, the plane sizes of face and h arrays.
+// The mask and the face's length are read by those who need them.
+// (thickness_diffuse.hip, mixedlayer_restrat.hip, epipycnal_diff.hip and barotropic.hip open with the same lines: tuned separately.)
+template <int DIR>
+struct FaceCol {
+  int i, j;
+  long f2, c0, c1, fpl, hpl;
+  __device__ __forceinline__ FaceCol(const GridDev &g, int i_, int j_) : i(i_), j(j_) {
+    f2 = DIR ? g.v2(i, j) : g.u2(i, j);
+    c0 = g.h2(i, j); c1 = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+    fpl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh; hpl = (long)g.nih * g.njh;
+  }
+  __device__ __forceinline__ double mask(const GridDev &g) const { return DIR ? g.mask2dCv[f2] : g.mask2dCu[f2]; }
+  __device__ __forceinline__ double dL(const GridDev &g) const { return DIR ? g.dx_Cv[f2] : g.dy_Cu[f2]; }      // dy_Cu | dx_Cv
+};
+inline dim3 face_grid(const GridDev &g, int d, int W, int nk = 1) {
+  return dim3((g.iec - g.isc + 1 + (d ? 0 : 1) + W - 1) / W, g.jec - g.jsc + 1 + (d ? 1 : 0), nk);
+}
+// f(D) for the direction 0 and then for 1, D a std::integral_constant: `constexpr int d = decltype(D)::value` picks the instantiation
+template <typename F>
+inline void both_dirs(F &&f) { f(std::integral_constant<int, 0>()); f(std::integral_constant<int, 1>()); }
+
+// bytes of the h-, u-, v- and q-shaped arrays of doubles: a plane (2), the layers (3), the interfaces (i)
+struct FieldBytes {
+  size_t h2, u2, v2, q2, h3, u3, v3, q3, hi, ui, vi, qi;
+  explicit FieldBytes(const GridDev &g)
+      : h2(sizeof(double) * (size_t)g.nih * g.njh), u2(sizeof(double) * (size_t)(g.nih + 1) * g.njh),
+        v2(sizeof(double) * (size_t)g.nih * (g.njh + 1)), q2(sizeof(double) * (size_t)(g.nih + 1) * (g.njh + 1)),
+        h3(h2 * g.nk), u3(u2 * g.nk), v3(v2 * g.nk), q3(q2 * g.nk),
+        hi(h2 * (g.nk + 1)), ui(u2 * (g.nk + 1)), vi(v2 * (g.nk + 1)), qi(q2 * (g.nk + 1)) {}
+};
 
 }  // namespace m6
 
@@ -126,7 +169,6 @@ struct mom6hip_ctx {
   bool cont_fluxes_only = false;   // the caller reads the transports and BT_cont of this continuity call but not its thicknesses (the RK2 step's
                                    // first call, MOM_dynamics_split_RK2.F90:634: hp is rewritten by :757 before anything reads it): the second
                                    // direction's convergence is not launched
-  m6::DevBuf sv_rlay;           // device copy of GV%Rlay for set_viscous_BBL (set_viscosity.hip)
   m6::DevBuf adv_gen;           // the general path of advect_tracer: the transports and fluxes of a pass, the segments' tables (tracer_advect.hip)
   m6::DevBuf adv_obc[64];       // device copies of the segments' tracer reservoirs handed over as host arrays
   int adv_obc_n = 0;

@@ -9,6 +9,11 @@ namespace m6 {
 namespace eos {
 
 struct EosDev { int form; double Rho_T0_S0, dRho_dT, dRho_dS; };
+// the caller's equation of state; none: the linear form with zeros
+inline EosDev eos_dev(const mom6hip_eos_t *eos) {
+  if (!eos) return EosDev{MOM6HIP_EOS_LINEAR, 0.0, 0.0, 0.0};
+  return EosDev{eos->form, eos->Rho_T0_S0, eos->dRho_dT, eos->dRho_dS};
+}
 
 // Wright 1997 coefficients, MOM_EOS_Wright.F90:23-38
 constexpr double a0 = 7.057924e-4, a1 = 3.480336e-7, a2 = -1.112733e-7;

@@ -305,7 +305,7 @@ extern "C" int mom6hip_mixedlayer_restrat(mom6hip_ctx_t *ctx, const mom6hip_mixe
   m6::Stager st(ctx, memspace);
   MLEArgs A;
   A.g = g;
-  A.E.form = eos->form; A.E.Rho_T0_S0 = eos->Rho_T0_S0; A.E.dRho_dT = eos->dRho_dT; A.E.dRho_dS = eos->dRho_dS;
+  A.E = m6::eos::eos_dev(eos);
   A.nkml = cs->nkml; A.use_PBL_MLD = cs->MLE_use_PBL_MLD; A.res_upscale = (!bml && cs->front_length > 0.) ? 1 : 0;
   A.ml_restrat_coef = cs->ml_restrat_coef; A.ml_restrat_coef2 = cs->ml_restrat_coef2;
   A.I_LFront = A.res_upscale ? 1. / cs->front_length : 0.0;

@@ -339,15 +339,13 @@ struct ChanGeom {
 template <int DIR, bool OBC>
 __global__ __launch_bounds__(64) void set_viscous_bbl_kernel(BBLArgs A) {
   const m6::GridDev &g = A.g;
-  const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 64 + threadIdx.x;
-  const int j = (DIR ? g.jsc - 1 : g.jsc) + blockIdx.y;
-  if (i > g.iec) return;
-  const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
-  if (!((DIR ? g.mask2dCv[f2] : g.mask2dCu[f2]) > 0.0)) return;      // do_i
-  const int nz = g.nk;
-  const long hpl = (long)g.nih * g.njh, upl = (long)(g.nih + 1) * g.njh, vpl = (long)g.nih * (g.njh + 1);
-  const long fpl = DIR ? vpl : upl;
-  long c0 = g.h2(i, j), c1 = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const auto L = m6::face_lane<DIR>(g, 64);
+  if (L.past) return;
+  const m6::FaceCol<DIR> F(g, L.i, L.j);
+  if (!(F.mask(g) > 0.0)) return;      // do_i
+  const int i = F.i, j = F.j, nz = g.nk;
+  const long f2 = F.f2, fpl = F.fpl, hpl = F.hpl, upl = (long)(g.nih + 1) * g.njh, vpl = (long)g.nih * (g.njh + 1);
+  long c0 = F.c0, c1 = F.c1;
   const double *vel = DIR ? A.v : A.u;
   const double h_neglect = g.H_subroundoff, dz_neglect = g.dZ_subroundoff;
   // a face of an open-boundary segment: the thicknesses, T and S are those of the cell inside (:502-580); every two-cell mean below
@@ -609,15 +607,13 @@ struct MLArgs {
 template <int DIR>
 __global__ __launch_bounds__(64) void set_viscous_ml_kernel(MLArgs A) {
   const m6::GridDev &g = A.g;
-  const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 64 + threadIdx.x;
-  const int j = (DIR ? g.jsc - 1 : g.jsc) + blockIdx.y;
-  if (i > g.iec) return;
-  const int nz = g.nk, nkml = A.nkml;
-  const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
-  const double mask = DIR ? g.mask2dCv[f2] : g.mask2dCu[f2];
-  if (mask < 0.5) { A.nkml_visc[f2] = (double)nkml; return; }
-  const long hpl = (long)g.nih * g.njh, upl = (long)(g.nih + 1) * g.njh, vpl = (long)g.nih * (g.njh + 1);
-  const long c0 = g.h2(i, j), c1 = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const auto L = m6::face_lane<DIR>(g, 64);
+  if (L.past) return;
+  const m6::FaceCol<DIR> F(g, L.i, L.j);
+  const int i = F.i, j = F.j, nz = g.nk, nkml = A.nkml;
+  const long f2 = F.f2, c0 = F.c0, c1 = F.c1;
+  if (F.mask(g) < 0.5) { A.nkml_visc[f2] = (double)nkml; return; }
+  const long hpl = F.hpl, upl = (long)(g.nih + 1) * g.njh, vpl = (long)g.nih * (g.njh + 1);
   const double dt_Rho0 = A.dt / A.H_to_RZ;
   const double h_neglect = g.H_subroundoff;
   const double h_tiny = 2.0 * g.Angstrom_H + h_neglect;
@@ -732,8 +728,7 @@ int set_viscous_BBL_dev(mom6hip_ctx_t *ctx, const mom6hip_set_visc_cs_t *cs, con
   const bool use_EOS = (eos != nullptr) && cs->BBL_use_EOS;
   BBLArgs A;
   A.g = g;
-  A.E.form = eos ? eos->form : MOM6HIP_EOS_LINEAR; A.E.Rho_T0_S0 = eos ? eos->Rho_T0_S0 : 0.0;
-  A.E.dRho_dT = eos ? eos->dRho_dT : 0.0; A.E.dRho_dS = eos ? eos->dRho_dS : 0.0;
+  A.E = eos_dev(eos);
   A.cdrag = cs->cdrag; A.drag_bg_vel = cs->drag_bg_vel; A.Hbbl = cs->Hbbl; A.dz_bbl = cs->dz_bbl; A.BBL_thick_min = cs->BBL_thick_min;
   A.Kv_BBL_min = cs->Kv_BBL_min; A.BBL_thick_max = cs->BBL_thick_max; A.H_to_RZ = cs->H_to_RZ;
   A.linear_drag = cs->linear_drag; A.use_BBL_EOS = use_EOS; A.correct_BBL_bounds = cs->correct_BBL_bounds;
@@ -743,24 +738,22 @@ int set_viscous_BBL_dev(mom6hip_ctx_t *ctx, const mom6hip_set_visc_cs_t *cs, con
   M6_REQUIRE(!(cs->Channel_drag || cs->body_force_drag) || (Ray_u && Ray_v),
              "set_viscous_BBL: CHANNEL_DRAG and DRAG_AS_BODY_FORCE need visc%%Ray_u and visc%%Ray_v");
   A.u = u; A.v = v; A.h = h; A.T = T; A.S = S; A.Rlay = nullptr;
-  if (!use_EOS) {
-    M6_REQUIRE(ctx->sv_rlay.reserve(sizeof(double) * (size_t)g.nk) == 0, "set_viscous_BBL: out of device memory");
-    M6_HIP(hipMemcpyAsync(ctx->sv_rlay.p, cs->Rlay, sizeof(double) * (size_t)g.nk, hipMemcpyHostToDevice, s));
-    A.Rlay = (const double *)ctx->sv_rlay.p;
+  if (!use_EOS) {      // (the host's Rlay may change after the call: the table is uploaded again when it has)
+    A.Rlay = ctx->tables[m6::TABLE_SVBBL_RLAY].get(cs->Rlay, (size_t)g.nk);
+    if (!A.Rlay) return 1;
   }
-  if (Ray_u) M6_HIP(hipMemsetAsync(Ray_u, 0, sizeof(double) * (size_t)g.nu3(), s));      // :416-417
-  if (Ray_v) M6_HIP(hipMemsetAsync(Ray_v, 0, sizeof(double) * (size_t)g.nv3(), s));
-  const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1;
+  const m6::FieldBytes sz(g);
+  if (Ray_u) M6_HIP(hipMemsetAsync(Ray_u, 0, sz.u3, s));      // :416-417
+  if (Ray_v) M6_HIP(hipMemsetAsync(Ray_v, 0, sz.v3, s));
   A.side_u = A.side_v = nullptr; A.D_u = A.D_v = A.mask_u = A.mask_v = nullptr;
   if (ob) { A.side_u = ob->side_u; A.side_v = ob->side_v; A.D_u = ob->D_u; A.D_v = ob->D_v; A.mask_u = ob->mask_u; A.mask_v = ob->mask_v; }
-  A.bbl_thick = bbl_thick_u; A.Kv_bbl = Kv_bbl_u; A.Ray = Ray_u;
-  if (ob) hipLaunchKernelGGL((set_viscous_bbl_kernel<0, true>), dim3((ni + 1 + 63) / 64, nj), dim3(64), 0, s, A);
-  else hipLaunchKernelGGL((set_viscous_bbl_kernel<0, false>), dim3((ni + 1 + 63) / 64, nj), dim3(64), 0, s, A);
-  A.bbl_thick = bbl_thick_v; A.Kv_bbl = Kv_bbl_v; A.Ray = Ray_v;
-  if (ob) hipLaunchKernelGGL((set_viscous_bbl_kernel<1, true>), dim3((ni + 63) / 64, nj + 1), dim3(64), 0, s, A);
-  else hipLaunchKernelGGL((set_viscous_bbl_kernel<1, false>), dim3((ni + 63) / 64, nj + 1), dim3(64), 0, s, A);
+  m6::both_dirs([&](auto D) {
+    constexpr int d = decltype(D)::value;
+    A.bbl_thick = d ? bbl_thick_v : bbl_thick_u; A.Kv_bbl = d ? Kv_bbl_v : Kv_bbl_u; A.Ray = d ? Ray_v : Ray_u;
+    if (ob) hipLaunchKernelGGL((set_viscous_bbl_kernel<d, true>), m6::face_grid(g, d, 64), dim3(64), 0, s, A);
+    else hipLaunchKernelGGL((set_viscous_bbl_kernel<d, false>), m6::face_grid(g, d, 64), dim3(64), 0, s, A);
+  });
   M6_HIP(hipGetLastError());
-  if (!use_EOS) M6_HIP(hipStreamSynchronize(s));      // (the host's Rlay may change after the call)
   return 0;
 }
 }  // namespace m6
@@ -776,8 +769,7 @@ int set_viscous_ML_dev(mom6hip_ctx_t *ctx, const mom6hip_set_visc_cs_t *cs, cons
   MLArgs A;
   A.g = g;
   A.use_EOS = eos != nullptr;
-  A.E.form = eos ? eos->form : MOM6HIP_EOS_LINEAR; A.E.Rho_T0_S0 = eos ? eos->Rho_T0_S0 : 0.0;
-  A.E.dRho_dT = eos ? eos->dRho_dT : 0.0; A.E.dRho_dS = eos ? eos->dRho_dS : 0.0;
+  A.E = eos_dev(eos);
   A.u = u; A.v = v; A.h = h; A.T = T; A.S = S; A.taux = taux; A.tauy = tauy; A.ustar = ustar; A.Rlay = nullptr;
   if (!A.use_EOS) {
     M6_REQUIRE(cs->Rlay, "set_viscous_ML: GV%%Rlay is needed without an equation of state");
@@ -786,11 +778,11 @@ int set_viscous_ML_dev(mom6hip_ctx_t *ctx, const mom6hip_set_visc_cs_t *cs, cons
   }
   A.dt = dt; A.H_to_RZ = cs->H_to_RZ; A.omega = cs->omega; A.omega_frac = cs->omega_frac; A.ustar_min = cs->ustar_min;
   A.TKE_decay = cs->TKE_decay; A.bulk_Ri_ML = cs->bulk_Ri_ML; A.nkml = cs->nkml;
-  const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1;
-  A.nkml_visc = nkml_visc_u;
-  hipLaunchKernelGGL(set_viscous_ml_kernel<0>, dim3((ni + 1 + 63) / 64, nj), dim3(64), 0, ctx->stream, A);
-  A.nkml_visc = nkml_visc_v;
-  hipLaunchKernelGGL(set_viscous_ml_kernel<1>, dim3((ni + 63) / 64, nj + 1), dim3(64), 0, ctx->stream, A);
+  m6::both_dirs([&](auto D) {
+    constexpr int d = decltype(D)::value;
+    A.nkml_visc = d ? nkml_visc_v : nkml_visc_u;
+    hipLaunchKernelGGL(set_viscous_ml_kernel<d>, m6::face_grid(g, d, 64), dim3(64), 0, ctx->stream, A);
+  });
   M6_HIP(hipGetLastError());
   return 0;
 }
@@ -808,14 +800,11 @@ extern "C" int mom6hip_set_viscous_ml(mom6hip_ctx_t *ctx, const mom6hip_set_visc
              "set_viscous_ML: forces%%ustar (visc->ustar) and visc%%nkml_visc_u / nkml_visc_v must be allocated with DYNAMIC_VISCOUS_ML");
   M6_REQUIRE(cs->nkml >= 0 && cs->nkml < ctx->g.nk, "set_viscous_ML: GV%%nkml must be in 0 .. nk-1");
   M6_REQUIRE(!eos || (T && S), "set_viscous_ML: an equation of state needs tv%%T and tv%%S");
-  const m6::GridDev g = ctx->g;
-  const size_t bH = sizeof(double) * (size_t)g.nh3(), bU = sizeof(double) * (size_t)g.nu3(), bV = sizeof(double) * (size_t)g.nv3();
-  const size_t bH2 = sizeof(double) * (size_t)g.nih * g.njh, bU2 = sizeof(double) * (size_t)(g.nih + 1) * g.njh,
-               bV2 = sizeof(double) * (size_t)g.nih * (g.njh + 1);
+  const m6::FieldBytes sz(ctx->g);
   m6::Stager st(ctx, memspace);
-  const double *du = st.in(u, bU), *dv = st.in(v, bV), *dh = st.in(h, bH), *dT = eos ? st.in(T, bH) : nullptr, *dS = eos ? st.in(S, bH) : nullptr;
-  const double *dtx = st.in(taux, bU2), *dty = st.in(tauy, bV2), *dus = st.in(visc->ustar, bH2);
-  double *nu = st.inout((double *)visc->nkml_visc_u, bU2), *nv = st.inout((double *)visc->nkml_visc_v, bV2);
+  const double *du = st.in(u, sz.u3), *dv = st.in(v, sz.v3), *dh = st.in(h, sz.h3), *dT = eos ? st.in(T, sz.h3) : nullptr, *dS = eos ? st.in(S, sz.h3) : nullptr;
+  const double *dtx = st.in(taux, sz.u2), *dty = st.in(tauy, sz.v2), *dus = st.in(visc->ustar, sz.h2);
+  double *nu = st.inout((double *)visc->nkml_visc_u, sz.u2), *nv = st.inout((double *)visc->nkml_visc_v, sz.v2);
   M6_REQUIRE(!st.failed(), "set_viscous_ML: staging failed");
   if (int rc = m6::set_viscous_ML_dev(ctx, cs, du, dv, dh, dT, dS, eos, dtx, dty, dus, nu, nv, dt)) return rc;
   return st.finish();
@@ -881,13 +870,12 @@ extern "C" int mom6hip_set_viscous_bbl_obc(mom6hip_ctx_t *ctx, const mom6hip_set
   const m6::GridDev g = ctx->g;
   M6_REQUIRE(g.mask2dCu && g.mask2dCv && g.CoriolisBu, "set_viscous_BBL: mask2dCu, mask2dCv and CoriolisBu are required");
   M6_REQUIRE(g.isc - g.isd >= 1 && g.jsc - g.jsd >= 1, "set_viscous_BBL: the halo must be at least 1 point wide");
-  const size_t bH = sizeof(double) * (size_t)g.nh3(), bU = sizeof(double) * (size_t)g.nu3(), bV = sizeof(double) * (size_t)g.nv3();
-  const size_t bU2 = sizeof(double) * (size_t)(g.nih + 1) * g.njh, bV2 = sizeof(double) * (size_t)g.nih * (g.njh + 1);
+  const m6::FieldBytes sz(g);
   m6::Stager st(ctx, memspace);
-  const double *du = st.in(u, bU), *dv = st.in(v, bV), *dh = st.in(h, bH), *dT = st.in(T, bH), *dS = st.in(S, bH);
-  double *btu = st.inout((double *)visc->bbl_thick_u, bU2), *btv = st.inout((double *)visc->bbl_thick_v, bV2);
-  double *kvu = st.inout((double *)visc->Kv_bbl_u, bU2), *kvv = st.inout((double *)visc->Kv_bbl_v, bV2);
-  double *ru = st.inout((double *)visc->Ray_u, bU), *rv = st.inout((double *)visc->Ray_v, bV);
+  const double *du = st.in(u, sz.u3), *dv = st.in(v, sz.v3), *dh = st.in(h, sz.h3), *dT = st.in(T, sz.h3), *dS = st.in(S, sz.h3);
+  double *btu = st.inout((double *)visc->bbl_thick_u, sz.u2), *btv = st.inout((double *)visc->bbl_thick_v, sz.v2);
+  double *kvu = st.inout((double *)visc->Kv_bbl_u, sz.u2), *kvv = st.inout((double *)visc->Kv_bbl_v, sz.v2);
+  double *ru = st.inout((double *)visc->Ray_u, sz.u3), *rv = st.inout((double *)visc->Ray_v, sz.v3);
   M6_REQUIRE(!st.failed(), "set_viscous_BBL: staging failed");
   m6::BBLObcDev ob;
   const bool with_obc = obc != nullptr;      // (associated(OBC): the branches are taken whatever the number of segments)

@@ -705,8 +705,7 @@ extern "C" int mom6hip_thickness_diffuse(mom6hip_ctx_t *ctx, const mom6hip_thick
   m6::Stager st(ctx, memspace);
   TDArgs A;
   A.g = g;
-  A.E.form = eos ? eos->form : MOM6HIP_EOS_LINEAR; A.E.Rho_T0_S0 = eos ? eos->Rho_T0_S0 : 0.0;
-  A.E.dRho_dT = eos ? eos->dRho_dT : 0.0; A.E.dRho_dS = eos ? eos->dRho_dS : 0.0;
+  A.E = m6::eos::eos_dev(eos);
   A.use_EOS = eos != nullptr; A.find_work = cs->MEKE_GM_src != nullptr; A.nkml = cs->nkml; A.use_GM_work_bug = cs->use_GM_work_bug;
   A.use_Visbeck = use_Visbeck;
   A.Khth = cs->Khth; A.Khth_Min = cs->Khth_Min; A.Khth_Max = cs->Khth_Max; A.max_Khth_CFL = cs->max_Khth_CFL; A.slope_max = cs->slope_max;

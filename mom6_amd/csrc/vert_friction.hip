@@ -10,7 +10,13 @@
 //                          viscosities in a_u.)
 //   vv_solve_kernel<DIR>   the implicit solve: forward elimination writing the modified right-hand side in place and
 //                          c1 to a work array, back substitution; the same kernel gives visc_rem (vertvisc_remnant).
-//   vv_limit_kernel<DIR>   vertvisc_limit_vel, one thread per point; truncations are counted with an atomic.
+//   vv_coef_solve_kernel   the two column functions above one after the other in one lane (the RK2 step's form).
+//   vv_limit_kernel<DIR>   vertvisc_limit_vel as a pass of its own (with Rayleigh drag), one thread per point: load, limit_vel, store.
+//                          limit_vel is the one text of the limiter, also fused into the solve's final store; truncations are
+//                          counted with an atomic.
+//   vv_increment_kernel    the RK2 step's increment as a sweep of its own; vel_increment is its one text, also read by the sweep.
+// A lane's (i, j) comes from m6::face_lane, the column's offsets from m6::FaceCol (common.hpp); the column functions rebuild the
+// frame from (i, j), which keeps the registers they had when they computed the offsets themselves.
 // Algorithmic traffic per cell: coef 8 (h) + 4 (vel) + 16 (a, h_vel) [B, both directions: x2 on vel/a/h_vel];
 // solve: read a, h_vel, x, write x, c1, read both again, write x.
 #include <cmath>
@@ -37,34 +43,38 @@ constexpr int VB = VB_LAYERS;      // layers loaded at once by the column sweeps
 struct CoefArgs {
   m6::GridDev g;
   VVPar p;
-  const double *vel, *h, *dz, *kv_bbl, *bbl_thick, *Kv_shear;
-  double *a, *hv;
+  const double *vel = nullptr, *h = nullptr, *dz = nullptr, *kv_bbl = nullptr, *bbl_thick = nullptr, *Kv_shear = nullptr;
+  double *a = nullptr, *hv = nullptr;
   // the surface boundary layer of DYNAMIC_VISCOUS_ML / a bulk mixed layer (find_coupling_coef :2047-2252)
-  const double *ustar, *nkml_visc;      // forces%ustar (h points), visc%nkml_visc_u or _v
-  double *dzv;                          // scratch: dz_vel of every layer of the column (written bottom-up, read top-down)
+  const double *ustar = nullptr, *nkml_visc = nullptr;      // forces%ustar (h points), visc%nkml_visc_u or _v
+  double *dzv = nullptr;                // scratch: dz_vel of every layer of the column (written bottom-up, read top-down)
   // the velocity as the increment the RK2 step applies just before the call (MOM_dynamics_split_RK2.F90:582-589, :667-676, :930-939):
   // vel = mask * (f_u0 + f_dt * (f_a1 [+ f_a2])) formed here instead of by a sweep of its own; f_u0 = null: vel is read as it is.
   // f_store (the solve's x): where the sweep leaves the velocity for the solve (null: the velocities are not updated)
-  const double *f_u0, *f_a1, *f_a2;
-  double f_dt;
-  double *f_store;
+  const double *f_u0 = nullptr, *f_a1 = nullptr, *f_a2 = nullptr;
+  double f_dt = 0.0;
+  double *f_store = nullptr;
   // open boundaries (the OBC instantiation only): per face, the cell the thicknesses, the depth, Kv_shear and ustar are projected
   // outward from, -1 the first (OBC_DIRECTION_E | N), +1 the second (W | S), 0 not on a segment (m6::obc_side_maps)
-  const int32_t *side;
+  const int32_t *side = nullptr;
   // the KV_ML_INVZ2 profile of :1873-1886 kept apart from a(K), for a caller that knows h (or dz) stays as it is between calls
   // (m6::KvmlProfile).  Both null: the top-down sweep parks the profile in a(K), as the reference does.  kvml_dst: the sweep stores it
   // there instead and the bottom-up sweep reads it from there.  kvml_src: no top-down sweep, the bottom-up sweep reads what an earlier
   // call stored.  Which of the three is a template parameter of coef_column (KV), so that each form keeps the registers of the one sweep it
   // runs: as a run-time choice the two extra pointers pushed the fused kernel over its scalar registers and into scratch.
-  const double *kvml_src;
-  double *kvml_dst;
+  const double *kvml_src = nullptr;
+  double *kvml_dst = nullptr;
 };
 
-// the velocity of layer k of the face column at f2: read, or formed from the step's increment (the reference's expression)
+// the increment the RK2 step applies just before vertvisc_coef, at the point n of a face array (the reference's expression)
+__device__ __forceinline__ double vel_increment(double mask, const double *u0, const double *a1, const double *a2, double dtv, long n) {
+  const double acc = a2 ? (a1[n] + a2[n]) : a1[n];
+  return mask * (u0[n] + dtv * acc);
+}
+// the velocity of layer k of the face column at f2: read, or formed from the step's increment
 __device__ __forceinline__ double coef_vel(const CoefArgs &A, long n, double mask) {
   if (!A.f_u0) return A.vel[n];
-  const double acc = A.f_a2 ? (A.f_a1[n] + A.f_a2[n]) : A.f_a1[n];
-  return mask * (A.f_u0[n] + A.f_dt * acc);
+  return vel_increment(mask, A.f_u0, A.f_a1, A.f_a2, A.f_dt, n);
 }
 
 // vertvisc_coef + find_coupling_coef for the face column (i, j); the caller has checked do_i
@@ -73,9 +83,8 @@ template <int DIR, bool OBC = false, int KV = KV_PARK>
 __device__ __forceinline__ void coef_column(const CoefArgs &A, int i, int j) {
   const m6::GridDev &g = A.g;
   const VVPar &P = A.p;
-  const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
-  const long c0 = g.h2(i, j), c1 = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
-  const long hpl = (long)g.nih * g.njh, fpl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
+  const m6::FaceCol<DIR> F(g, i, j);
+  const long f2 = F.f2, c0 = F.c0, c1 = F.c1, hpl = F.hpl, fpl = F.fpl;
   const int nz = g.nk;
   const double h_neglect = g.H_subroundoff, dz_neglect = g.dZ_subroundoff;
   const double a_cpl_max = 1.0e37 * g.Z_to_H * 1.0;                 // :1283
@@ -88,7 +97,7 @@ __device__ __forceinline__ void coef_column(const CoefArgs &A, int i, int j) {
     I_Hbbl = 1.0 / bbl_thick;
   }
   const double hn = dz_neglect, I_amax = 0.0;                        // find_coupling_coef :1846, :1858
-  const double fmask = A.f_u0 ? (DIR ? g.mask2dCv[f2] : g.mask2dCu[f2]) : 0.0;
+  const double fmask = A.f_u0 ? F.mask(g) : 0.0;
   auto DZ = [&](long c, int k) { return A.dz ? A.dz[c + hpl * k] : g.H_to_Z * A.h[c + hpl * k]; };
   const int side = OBC ? A.side[f2] : 0;      // :1335-1355 / :1546-1566 (zi_dir)
 
@@ -279,22 +288,19 @@ __device__ __forceinline__ void coef_column(const CoefArgs &A, int i, int j) {
 
 template <int DIR, bool OBC>
 __global__ __launch_bounds__(64) void vv_coef_kernel(CoefArgs A) {
-  const m6::GridDev &g = A.g;
-  const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 64 + threadIdx.x;
-  const int j = (DIR ? g.jsc - 1 : g.jsc) + blockIdx.y;
-  if (i > g.iec) return;
-  const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
-  if (!((DIR ? g.mask2dCv[f2] : g.mask2dCu[f2]) > 0.0)) return;      // do_i
-  coef_column<DIR, OBC>(A, i, j);
+  const auto L = m6::face_lane<DIR>(A.g, 64);
+  if (L.past) return;
+  if (!(m6::FaceCol<DIR>(A.g, L.i, L.j).mask(A.g) > 0.0)) return;      // do_i
+  coef_column<DIR, OBC>(A, L.i, L.j);
 }
 
 struct SolveArgs {
   m6::GridDev g;
   VVPar p;
-  const double *a, *hv, *Ray, *h, *tau;
-  double *x, *xr, *c1, *tbot;      // x: velocity (or null), xr: visc_rem (or null)
-  unsigned long long *ntrunc;      // non-null: vertvisc_limit_vel is applied as the final velocities are stored
-  double dt;
+  const double *a = nullptr, *hv = nullptr, *Ray = nullptr, *h = nullptr, *tau = nullptr;
+  double *x = nullptr, *xr = nullptr, *c1 = nullptr, *tbot = nullptr;      // x: velocity (or null), xr: visc_rem (or null)
+  unsigned long long *ntrunc = nullptr;      // non-null: vertvisc_limit_vel is applied as the final velocities are stored
+  double dt = 0.0;
 };
 
 // vertvisc_limit_vel :2346-2370 / :2431-2455 for one point (no truncation files); returns the value to store
@@ -333,16 +339,15 @@ template <int DIR>
 __device__ __forceinline__ void solve_column(const SolveArgs &A, int i, int j) {
   const m6::GridDev &g = A.g;
   const VVPar &P = A.p;
-  const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
-  const long fpl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh, hpl = (long)g.nih * g.njh;
-  const long c0 = g.h2(i, j), cc1 = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
+  const m6::FaceCol<DIR> F(g, i, j);
+  const long f2 = F.f2, fpl = F.fpl, hpl = F.hpl, c0 = F.c0, c1 = F.c1;
   const int nz = g.nk;
   const double dt = A.dt;
-  const double mask = DIR ? g.mask2dCv[f2] : g.mask2dCu[f2];
+  const double mask = F.mask(g);
   const bool do_i = mask > 0.0;
   double *x = A.x, *xr = A.xr;
   const bool lim = A.ntrunc != nullptr;
-  const double dL = lim ? (DIR ? g.dx_Cv[f2] : g.dy_Cu[f2]) : 0.0;
+  const double dL = lim ? F.dL(g) : 0.0;
   double x_bot = 0.0;      // the untruncated bottom velocity (for taux_bot)
   if (do_i) {
     double surface_stress = 0.0;
@@ -353,7 +358,7 @@ __device__ __forceinline__ void solve_column(const SolveArgs &A, int i, int j) {
         double zDS = 0.0;
         const double stress = dt_Rho0 * A.tau[f2];
         for (int k = 0; k < nz; k++) {
-          const double h_a = 0.5 * (A.h[c0 + hpl * k] + A.h[cc1 + hpl * k]) + g.H_subroundoff;
+          const double h_a = 0.5 * (A.h[c0 + hpl * k] + A.h[c1 + hpl * k]) + g.H_subroundoff;
           double hfr = 1.0;
           if ((zDS + h_a) > Hmix) hfr = (Hmix - zDS) / h_a;
           x[f2 + fpl * k] = x[f2 + fpl * k] + I_Hmix * hfr * stress;
@@ -400,7 +405,7 @@ __device__ __forceinline__ void solve_column(const SolveArgs &A, int i, int j) {
       }
     }
     x_bot = xk;
-    if (x && lim) x[f2 + fpl * (nz - 1)] = limit_vel<DIR>(g, P, xk, dt, dL, c0, cc1, A.h, hpl * (nz - 1), A.ntrunc);
+    if (x && lim) x[f2 + fpl * (nz - 1)] = limit_vel<DIR>(g, P, xk, dt, dL, c0, c1, A.h, hpl * (nz - 1), A.ntrunc);
     for (int kb = nz - 2; kb >= 0; kb -= VB) {
       double b_c[VB], b_x[VB], b_r[VB];
 #pragma unroll
@@ -422,7 +427,7 @@ __device__ __forceinline__ void solve_column(const SolveArgs &A, int i, int j) {
         const double c = b_c[q];
         if (x) {
           xk = b_x[q] + c * xk;
-          x[n] = lim ? limit_vel<DIR>(g, P, xk, dt, dL, c0, cc1, A.h, hpl * k, A.ntrunc) : xk;
+          x[n] = lim ? limit_vel<DIR>(g, P, xk, dt, dL, c0, c1, A.h, hpl * k, A.ntrunc) : xk;
         }
         if (xr) { rk = b_r[q] + c * rk; xr[n] = rk; }
       }
@@ -430,7 +435,7 @@ __device__ __forceinline__ void solve_column(const SolveArgs &A, int i, int j) {
   } else if (x) {
     x_bot = x[f2 + fpl * (nz - 1)];
     if (lim)      // vertvisc_limit_vel runs over every face of the compute rows, masked or not
-      for (int k = 0; k < nz; k++) x[f2 + fpl * k] = limit_vel<DIR>(g, P, x[f2 + fpl * k], dt, dL, c0, cc1, A.h, hpl * k, A.ntrunc);
+      for (int k = 0; k < nz; k++) x[f2 + fpl * k] = limit_vel<DIR>(g, P, x[f2 + fpl * k], dt, dL, c0, c1, A.h, hpl * k, A.ntrunc);
   }
   if (A.tbot) {                                                      // :798-805 (before the truncation)
     double tb = P.H_to_RZ * (x_bot * A.a[f2 + fpl * nz]);
@@ -441,11 +446,9 @@ __device__ __forceinline__ void solve_column(const SolveArgs &A, int i, int j) {
 
 template <int DIR>
 __global__ __launch_bounds__(64) void vv_solve_kernel(SolveArgs A) {
-  const m6::GridDev &g = A.g;
-  const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 64 + threadIdx.x;
-  const int j = (DIR ? g.jsc - 1 : g.jsc) + blockIdx.y;
-  if (i > g.iec) return;
-  solve_column<DIR>(A, i, j);
+  const auto L = m6::face_lane<DIR>(A.g, 64);
+  if (L.past) return;
+  solve_column<DIR>(A, L.i, L.j);
 }
 
 // vertvisc_coef followed by the solve(s) of the same column: the coupling coefficients and thicknesses the bottom-up sweep
@@ -456,30 +459,25 @@ __global__ __launch_bounds__(64) void vv_solve_kernel(SolveArgs A) {
 template <int DIR, int KV>
 __global__ __launch_bounds__(64, VV_OCC) void vv_coef_solve_kernel(CoefArgs C, SolveArgs A) {
   const m6::GridDev &g = A.g;
-  const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 64 + threadIdx.x;
-  const int j = (DIR ? g.jsc - 1 : g.jsc) + blockIdx.y;
-  if (i > g.iec) return;
-  const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
-  const double mask = DIR ? g.mask2dCv[f2] : g.mask2dCu[f2];
-  if (mask > 0.0) coef_column<DIR, false, KV>(C, i, j);
-  else if (C.f_u0 && C.f_store) {      // a masked column: the increment alone (0 * (...)), as the step's sweep would have left it
-    const long fpl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh;
-    for (int k = 0; k < g.nk; k++) C.f_store[f2 + fpl * k] = coef_vel(C, f2 + fpl * k, mask);
-  }
-  solve_column<DIR>(A, i, j);
+  const auto L = m6::face_lane<DIR>(g, 64);
+  if (L.past) return;
+  const m6::FaceCol<DIR> F(g, L.i, L.j);
+  const double mask = F.mask(g);
+  if (mask > 0.0) coef_column<DIR, false, KV>(C, F.i, F.j);
+  else if (C.f_u0 && C.f_store)      // a masked column: the increment alone (0 * (...)), as the step's sweep would have left it
+    for (int k = 0; k < g.nk; k++) C.f_store[F.f2 + F.fpl * k] = coef_vel(C, F.f2 + F.fpl * k, mask);
+  solve_column<DIR>(A, F.i, F.j);
 }
 
 // the increment as a sweep of its own, for the forms of the step that go through the separate entries
 template <int DIR>
 __global__ __launch_bounds__(256) void vv_increment_kernel(m6::GridDev g, const double *u0, const double *a1, const double *a2, double dtv,
                                                            double *out) {
-  const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 256 + threadIdx.x;
-  const int j = (DIR ? g.jsc - 1 : g.jsc) + blockIdx.y;
-  if (i > g.iec) return;
-  const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
-  const long n = f2 + (DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh) * blockIdx.z;
-  const double acc = a2 ? (a1[n] + a2[n]) : a1[n];
-  out[n] = (DIR ? g.mask2dCv[f2] : g.mask2dCu[f2]) * (u0[n] + dtv * acc);
+  const auto L = m6::face_lane<DIR>(g, 256);
+  if (L.past) return;
+  const m6::FaceCol<DIR> F(g, L.i, L.j);
+  const long n = F.f2 + F.fpl * blockIdx.z;
+  out[n] = vel_increment(F.mask(g), u0, a1, a2, dtv, n);
 }
 
 struct LimitArgs {
@@ -490,43 +488,15 @@ struct LimitArgs {
   unsigned long long *ntrunc;
   double dt;
 };
-
-// vertvisc_limit_vel :2346-2370 / :2431-2455 (no truncation files)
+// vertvisc_limit_vel as a pass of its own, one thread per point
 template <int DIR>
 __global__ __launch_bounds__(256) void vv_limit_kernel(LimitArgs A) {
   const m6::GridDev &g = A.g;
-  const VVPar &P = A.p;
-  const int i = (DIR ? g.isc : g.isc - 1) + blockIdx.x * 256 + threadIdx.x;
-  const int j = (DIR ? g.jsc - 1 : g.jsc) + blockIdx.y;
-  const int k = blockIdx.z;
-  if (i > g.iec) return;
-  const long f2 = DIR ? g.v2(i, j) : g.u2(i, j);
-  const long fpl = DIR ? (long)g.nih * (g.njh + 1) : (long)(g.nih + 1) * g.njh, hpl = (long)g.nih * g.njh;
-  const long n = f2 + fpl * k;
-  const long c0 = g.h2(i, j), c1 = DIR ? g.h2(i, j + 1) : g.h2(i + 1, j);
-  const double dL = DIR ? g.dx_Cv[f2] : g.dy_Cu[f2];
-  const double H_report = 6.0 * g.Angstrom_H;
-  const double xv = A.x[n];
-  const double dt = A.dt;
-  bool trunc = false;
-  if (P.CFL_based_trunc) {
-    if (fabs(xv) < P.vel_underflow) { A.x[n] = 0.0; }
-    else if ((xv * (dt * dL)) * g.IareaT[c1] < -P.CFL_trunc) {
-      A.x[n] = (-0.9 * P.CFL_trunc) * (g.areaT[c1] / (dt * dL));
-      trunc = true;
-    } else if ((xv * (dt * dL)) * g.IareaT[c0] > P.CFL_trunc) {
-      A.x[n] = (0.9 * P.CFL_trunc) * (g.areaT[c0] / (dt * dL));
-      trunc = true;
-    }
-  } else {
-    const double maxvel = P.maxvel, truncvel = 0.9 * maxvel;
-    if (fabs(xv) < P.vel_underflow) { A.x[n] = 0.0; }
-    else if (fabs(xv) > maxvel) {
-      A.x[n] = copysign(truncvel, xv);
-      trunc = true;
-    }
-  }
-  if (trunc && (A.h[c0 + hpl * k] + A.h[c1 + hpl * k] > H_report)) atomicAdd(A.ntrunc, 1ull);
+  const auto L = m6::face_lane<DIR>(g, 256);
+  if (L.past) return;
+  const m6::FaceCol<DIR> F(g, L.i, L.j);
+  const long n = F.f2 + F.fpl * blockIdx.z;
+  A.x[n] = limit_vel<DIR>(g, A.p, A.x[n], A.dt, F.dL(g), F.c0, F.c1, A.h, F.hpl * blockIdx.z, A.ntrunc);
 }
 
 int check_cs(const mom6hip_vertvisc_cs_t *cs, const char *who) {
@@ -549,14 +519,56 @@ VVPar par_of(const mom6hip_vertvisc_cs_t *cs) {
   return p;
 }
 
-struct Sz { size_t h2, u2, v2, h3, u3, v3, ui, vi, hi; };
-Sz sizes(const m6::GridDev &g) {
-  Sz s;
-  s.h2 = sizeof(double) * (size_t)g.nih * g.njh; s.u2 = sizeof(double) * (size_t)(g.nih + 1) * g.njh;
-  s.v2 = sizeof(double) * (size_t)g.nih * (g.njh + 1);
-  s.h3 = s.h2 * g.nk; s.u3 = s.u2 * g.nk; s.v3 = s.v2 * g.nk;
-  s.ui = s.u2 * (g.nk + 1); s.vi = s.v2 * (g.nk + 1); s.hi = s.h2 * (g.nk + 1);
-  return s;
+// What the coefficient stage requires of cs, visc and the grid, in the order it is reported.  g null: the one-kernel step, which has no
+// surface boundary layer and reports the grid's metrics with the solve's (require_solve)
+int require_coef(const mom6hip_vertvisc_cs_t *cs, const mom6hip_vertvisc_type_t *visc, const m6::GridDev *g) {
+  M6_REQUIRE(visc->Kv_shear_Bu == nullptr, "vertvisc_coef: visc%%Kv_shear_Bu is not provided by libmom6hip");
+  M6_REQUIRE(!cs->bottomdraglaw || (visc->Kv_bbl_u && visc->Kv_bbl_v && visc->bbl_thick_u && visc->bbl_thick_v),
+             "vertvisc_coef: BOTTOMDRAGLAW needs visc%%Kv_bbl_u/v and visc%%bbl_thick_u/v");
+  M6_REQUIRE(!(cs->Kvml_invZ2 > 0.0) || cs->Hmix > 0.0, "vertvisc_coef: KV_ML_INVZ2 needs HMIX_FIXED");
+  if (!g) return 0;
+  M6_REQUIRE(g->mask2dCu && g->mask2dCv && g->bathyT, "vertvisc_coef: mask2dCu, mask2dCv and bathyT are required");
+  if (cs->dynamic_viscous_ML || cs->nkml > 0) {      // find_coupling_coef :2047
+    M6_REQUIRE(visc->ustar, "vertvisc_coef: DYNAMIC_VISCOUS_ML / a bulk mixed layer needs forces%%ustar (visc->ustar)");
+    M6_REQUIRE(!cs->dynamic_viscous_ML || (visc->nkml_visc_u && visc->nkml_visc_v),
+               "vertvisc_coef: DYNAMIC_VISCOUS_ML needs visc%%nkml_visc_u / nkml_visc_v (set_viscous_ML)");
+    M6_REQUIRE(cs->nkml >= 0 && cs->nkml <= g->nk && g->CoriolisBu, "vertvisc_coef: GV%%nkml out of range, or CoriolisBu missing");
+  }
+  return 0;
+}
+
+// What the solve stage requires.  coef_of: the visc of the one-kernel step, whose coefficient stage is checked here too, at the place its
+// checks have in that entry's order of refusals (between dt and HMIX_STRESS), and whose sweep reads bathyT
+int require_solve(const mom6hip_vertvisc_cs_t *cs, double dt, const m6::GridDev &g, const mom6hip_vertvisc_type_t *coef_of = nullptr) {
+  M6_REQUIRE(dt > 0.0 && cs->H_to_RZ > 0.0, "vertvisc: dt and GV%%H_to_RZ must be positive");
+  if (coef_of) if (int rc = require_coef(cs, coef_of, nullptr)) return rc;
+  M6_REQUIRE(!cs->direct_stress || cs->Hmix_stress > 0.0, "vertvisc_init: HMIX_STRESS must be set to a positive value if DIRECT_STRESS is true.");
+  M6_REQUIRE(g.mask2dCu && g.mask2dCv && (!coef_of || g.bathyT) && g.areaT && g.IareaT && g.dy_Cu && g.dx_Cv, "vertvisc: a required grid metric is missing");
+  return 0;
+}
+
+// The coefficient sweep's arguments of direction d, from the arrays both entries stage alike.  The caller adds what only it has: the
+// surface boundary layer and the side maps, or the increment and the kept KV_ML_INVZ2 profile
+CoefArgs coef_args(m6::Stager &st, const m6::GridDev &g, const VVPar &p, const m6::FieldBytes &sz, int d, mom6hip_vertvisc_cs_t *cs,
+                   const mom6hip_vertvisc_type_t *visc, const double *vel, const double *dh, const double *ddz, const double *dks) {
+  CoefArgs A;
+  A.g = g; A.p = p; A.vel = vel; A.h = dh; A.dz = ddz; A.Kv_shear = dks;
+  A.kv_bbl = st.in(d ? visc->Kv_bbl_v : visc->Kv_bbl_u, d ? sz.v2 : sz.u2);
+  A.bbl_thick = st.in(d ? visc->bbl_thick_v : visc->bbl_thick_u, d ? sz.v2 : sz.u2);
+  A.a = st.inout(d ? cs->a_v : cs->a_u, d ? sz.vi : sz.ui);
+  A.hv = st.inout(d ? cs->h_v : cs->h_u, d ? sz.v3 : sz.u3);
+  return A;
+}
+
+// The device counter of vertvisc_limit_vel's truncations, zeroed when it is first reserved (mom6hip_vertvisc_ntrunc reads and zeroes it)
+int trunc_counter(mom6hip_ctx_t *ctx, unsigned long long **cnt) {
+  if (ctx->vv_ntrunc.reserve(sizeof(unsigned long long)) || !ctx->vv_ntrunc.p) return 1;
+  if (!ctx->vv_ntrunc_ready) {
+    M6_HIP(hipMemsetAsync(ctx->vv_ntrunc.p, 0, sizeof(unsigned long long), ctx->stream));
+    ctx->vv_ntrunc_ready = true;
+  }
+  *cnt = (unsigned long long *)ctx->vv_ntrunc.p;
+  return 0;
 }
 
 }  // namespace
@@ -577,53 +589,27 @@ extern "C" int mom6hip_vertvisc_coef_obc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs
   M6_REQUIRE(cs && u && v && h && visc, "vertvisc_coef: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "vertvisc_coef: bad memspace");
   if (check_cs(cs, "vertvisc_coef")) return 1;
-  M6_REQUIRE(visc->Kv_shear_Bu == nullptr, "vertvisc_coef: visc%%Kv_shear_Bu is not provided by libmom6hip");
-  M6_REQUIRE(!cs->bottomdraglaw || (visc->Kv_bbl_u && visc->Kv_bbl_v && visc->bbl_thick_u && visc->bbl_thick_v),
-             "vertvisc_coef: BOTTOMDRAGLAW needs visc%%Kv_bbl_u/v and visc%%bbl_thick_u/v");
-  M6_REQUIRE(!(cs->Kvml_invZ2 > 0.0) || cs->Hmix > 0.0, "vertvisc_coef: KV_ML_INVZ2 needs HMIX_FIXED");
   const m6::GridDev g = ctx->g;
-  M6_REQUIRE(g.mask2dCu && g.mask2dCv && g.bathyT, "vertvisc_coef: mask2dCu, mask2dCv and bathyT are required");
-  const bool surface_bl = cs->dynamic_viscous_ML || cs->nkml > 0;      // find_coupling_coef :2047
-  if (surface_bl) {
-    M6_REQUIRE(visc->ustar, "vertvisc_coef: DYNAMIC_VISCOUS_ML / a bulk mixed layer needs forces%%ustar (visc->ustar)");
-    M6_REQUIRE(!cs->dynamic_viscous_ML || (visc->nkml_visc_u && visc->nkml_visc_v),
-               "vertvisc_coef: DYNAMIC_VISCOUS_ML needs visc%%nkml_visc_u / nkml_visc_v (set_viscous_ML)");
-    M6_REQUIRE(cs->nkml >= 0 && cs->nkml <= g.nk && g.CoriolisBu, "vertvisc_coef: GV%%nkml out of range, or CoriolisBu missing");
-  }
-  const Sz sz = sizes(g);
+  if (int rc = require_coef(cs, visc, &g)) return rc;
+  const m6::FieldBytes sz(g);
+  const VVPar p = par_of(cs);
   m6::Stager st(ctx, memspace);
+  const double *vel[2] = {st.in(u, sz.u3), st.in(v, sz.v3)};
+  const double *dh = st.in(h, sz.h3), *ddz = st.in(dz, sz.h3), *dks = st.in(visc->Kv_shear, sz.hi);
   CoefArgs A[2];
-  for (int d = 0; d < 2; d++) {
-    A[d].ustar = A[d].nkml_visc = nullptr; A[d].dzv = nullptr;
-    A[d].f_u0 = A[d].f_a1 = A[d].f_a2 = nullptr; A[d].f_dt = 0.0; A[d].f_store = nullptr;
-    A[d].kvml_src = nullptr; A[d].kvml_dst = nullptr;
-  }
-  if (surface_bl) {
-    const double *dus = st.in(visc->ustar, sz.h2);
-    A[0].ustar = A[1].ustar = dus;
+  for (int d = 0; d < 2; d++) A[d] = coef_args(st, g, p, sz, d, cs, visc, vel[d], dh, ddz, dks);
+  if (cs->dynamic_viscous_ML || cs->nkml > 0) {      // the surface boundary layer
+    A[0].ustar = A[1].ustar = st.in(visc->ustar, sz.h2);
     if (cs->dynamic_viscous_ML) { A[0].nkml_visc = st.in(visc->nkml_visc_u, sz.u2); A[1].nkml_visc = st.in(visc->nkml_visc_v, sz.v2); }
     A[0].dzv = (double *)st.scratch(sz.u3); A[1].dzv = (double *)st.scratch(sz.v3);
   }
-  A[0].vel = st.in(u, sz.u3); A[1].vel = st.in(v, sz.v3);
-  const double *dh = st.in(h, sz.h3), *ddz = st.in(dz, sz.h3), *dks = st.in(visc->Kv_shear, sz.hi);
-  A[0].kv_bbl = st.in(visc->Kv_bbl_u, sz.u2); A[1].kv_bbl = st.in(visc->Kv_bbl_v, sz.v2);
-  A[0].bbl_thick = st.in(visc->bbl_thick_u, sz.u2); A[1].bbl_thick = st.in(visc->bbl_thick_v, sz.v2);
-  A[0].a = st.inout(cs->a_u, sz.ui); A[1].a = st.inout(cs->a_v, sz.vi);
-  A[0].hv = st.inout(cs->h_u, sz.u3); A[1].hv = st.inout(cs->h_v, sz.v3);
   M6_REQUIRE(!st.failed(), "vertvisc_coef: staging failed");
-  A[0].side = A[1].side = nullptr;
   if (m6::obc_side_maps(ctx, st, obc, &A[0].side, &A[1].side, "vertvisc_coef")) return 1;
-  for (int d = 0; d < 2; d++) {
-    A[d].g = g; A[d].p = par_of(cs); A[d].h = dh; A[d].dz = ddz; A[d].Kv_shear = dks;
-    const dim3 grid((g.iec - g.isc + 1 + (d ? 0 : 1) + 63) / 64, g.jec - g.jsc + 1 + (d ? 1 : 0));
-    if (A[d].side) {
-      if (d == 0) hipLaunchKernelGGL((vv_coef_kernel<0, true>), grid, dim3(64), 0, ctx->stream, A[d]);
-      else hipLaunchKernelGGL((vv_coef_kernel<1, true>), grid, dim3(64), 0, ctx->stream, A[d]);
-    } else {
-      if (d == 0) hipLaunchKernelGGL((vv_coef_kernel<0, false>), grid, dim3(64), 0, ctx->stream, A[d]);
-      else hipLaunchKernelGGL((vv_coef_kernel<1, false>), grid, dim3(64), 0, ctx->stream, A[d]);
-    }
-  }
+  m6::both_dirs([&](auto D) {
+    constexpr int d = decltype(D)::value;
+    if (A[d].side) hipLaunchKernelGGL((vv_coef_kernel<d, true>), m6::face_grid(g, d, 64), dim3(64), 0, ctx->stream, A[d]);
+    else hipLaunchKernelGGL((vv_coef_kernel<d, false>), m6::face_grid(g, d, 64), dim3(64), 0, ctx->stream, A[d]);
+  });
   M6_HIP(hipGetLastError());
   return st.finish();
 }
@@ -631,41 +617,28 @@ extern "C" int mom6hip_vertvisc_coef_obc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs
 namespace {
 // the solve of both directions: velocities x (with vertvisc_limit_vel fused when the Rayleigh drag is off), visc_rem xr,
 // or both at once
-int run_solve(mom6hip_ctx_t *ctx, m6::Stager &st, const mom6hip_vertvisc_cs_t *cs, const double *const a[2], const double *const hv[2],
+int run_solve(mom6hip_ctx_t *ctx, m6::Stager &st, const VVPar &p, const double *const a[2], const double *const hv[2],
               const double *const Ray[2], const double *dh, const double *const tau[2], double *const x[2], double *const xr[2],
               double *const tbot[2], double dt, bool want_limit) {
   const m6::GridDev g = ctx->g;
-  const Sz sz = sizes(g);
+  const m6::FieldBytes sz(g);
   double *c1 = (double *)st.scratch(sz.u3 > sz.v3 ? sz.u3 : sz.v3);
   M6_REQUIRE(!st.failed() && c1, "vertvisc: out of device memory");
   unsigned long long *cnt = nullptr;
-  if (want_limit) {
-    if (ctx->vv_ntrunc.reserve(sizeof(unsigned long long)) || !ctx->vv_ntrunc.p) return 1;
-    if (!ctx->vv_ntrunc_ready) {
-      M6_HIP(hipMemsetAsync(ctx->vv_ntrunc.p, 0, sizeof(unsigned long long), ctx->stream));
-      ctx->vv_ntrunc_ready = true;
-    }
-    cnt = (unsigned long long *)ctx->vv_ntrunc.p;
-  }
+  if (want_limit && trunc_counter(ctx, &cnt)) return 1;
   // with Rayleigh drag taux_bot sums Ray*u over the untruncated velocities in k order: the truncation stays a separate pass
   const bool fuse_limit = want_limit && !(Ray[0] || Ray[1]);
-  for (int d = 0; d < 2; d++) {
+  m6::both_dirs([&](auto D) {
+    constexpr int d = decltype(D)::value;
     SolveArgs A;
-    A.g = g; A.p = par_of(cs); A.a = a[d]; A.hv = hv[d]; A.Ray = Ray[d]; A.h = dh; A.tau = tau[d]; A.x = x[d]; A.xr = xr[d]; A.c1 = c1;
+    A.g = g; A.p = p; A.a = a[d]; A.hv = hv[d]; A.Ray = Ray[d]; A.h = dh; A.tau = tau[d]; A.x = x[d]; A.xr = xr[d]; A.c1 = c1;
     A.tbot = tbot[d]; A.dt = dt; A.ntrunc = fuse_limit ? cnt : nullptr;
-    const dim3 grid((g.iec - g.isc + 1 + (d ? 0 : 1) + 63) / 64, g.jec - g.jsc + 1 + (d ? 1 : 0));
-    if (d == 0) hipLaunchKernelGGL(vv_solve_kernel<0>, grid, dim3(64), 0, ctx->stream, A);
-    else hipLaunchKernelGGL(vv_solve_kernel<1>, grid, dim3(64), 0, ctx->stream, A);
-  }
-  if (want_limit && !fuse_limit) {
-    for (int d = 0; d < 2; d++) {
-      LimitArgs L;
-      L.g = g; L.p = par_of(cs); L.h = dh; L.x = x[d]; L.ntrunc = cnt; L.dt = dt;
-      const dim3 grid((g.iec - g.isc + 1 + (d ? 0 : 1) + 255) / 256, g.jec - g.jsc + 1 + (d ? 1 : 0), g.nk);
-      if (d == 0) hipLaunchKernelGGL(vv_limit_kernel<0>, grid, dim3(256), 0, ctx->stream, L);
-      else hipLaunchKernelGGL(vv_limit_kernel<1>, grid, dim3(256), 0, ctx->stream, L);
-    }
-  }
+    hipLaunchKernelGGL(vv_solve_kernel<d>, m6::face_grid(g, d, 64), dim3(64), 0, ctx->stream, A);
+  });
+  if (want_limit && !fuse_limit) m6::both_dirs([&](auto D) {
+    constexpr int d = decltype(D)::value;
+    hipLaunchKernelGGL(vv_limit_kernel<d>, m6::face_grid(g, d, 256, g.nk), dim3(256), 0, ctx->stream, LimitArgs{g, p, dh, x[d], cnt, dt});
+  });
   M6_HIP(hipGetLastError());
   return 0;
 }
@@ -677,12 +650,9 @@ int vertvisc_impl(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double *u, doub
   M6_REQUIRE(cs && u && v && h && taux && tauy && visc, "vertvisc: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "vertvisc: bad memspace");
   if (check_cs(cs, "vertvisc")) return 1;
-  M6_REQUIRE(dt > 0.0 && cs->H_to_RZ > 0.0, "vertvisc: dt and GV%%H_to_RZ must be positive");
-  M6_REQUIRE(!cs->direct_stress || cs->Hmix_stress > 0.0, "vertvisc_init: HMIX_STRESS must be set to a positive value if DIRECT_STRESS is true.");
-  M6_REQUIRE((visc_rem_u != nullptr) == (visc_rem_v != nullptr), "vertvisc: visc_rem_u and visc_rem_v come as a pair");
-  const m6::GridDev g = ctx->g;
-  M6_REQUIRE(g.mask2dCu && g.mask2dCv && g.areaT && g.IareaT && g.dy_Cu && g.dx_Cv, "vertvisc: a required grid metric is missing");
-  const Sz sz = sizes(g);
+  M6_REQUIRE((visc_rem_u != nullptr) == (visc_rem_v != nullptr), "vertvisc: visc_rem_u and visc_rem_v come as a pair");      // (the entries see to it)
+  if (int rc = require_solve(cs, dt, ctx->g)) return rc;
+  const m6::FieldBytes sz(ctx->g);
   m6::Stager st(ctx, memspace);
   double *x[2] = {st.inout(u, sz.u3), st.inout(v, sz.v3)};
   double *xr[2] = {st.inout(visc_rem_u, sz.u3), st.inout(visc_rem_v, sz.v3)};
@@ -693,7 +663,7 @@ int vertvisc_impl(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double *u, doub
   const double *Ray[2] = {st.in(visc->Ray_u, sz.u3), st.in(visc->Ray_v, sz.v3)};
   double *tbot[2] = {st.inout(taux_bot, sz.u2), st.inout(tauy_bot, sz.v2)};      // (only the compute rows are written)
   M6_REQUIRE(!st.failed(), "vertvisc: staging failed");
-  if (run_solve(ctx, st, cs, a, hv, Ray, dh, tau, x, xr, tbot, dt, true)) return 1;      // incl. vertvisc_limit_vel :986
+  if (run_solve(ctx, st, par_of(cs), a, hv, Ray, dh, tau, x, xr, tbot, dt, true)) return 1;      // incl. vertvisc_limit_vel :986
   if (m6::obc_store_specified(ctx, st, obc, x[0], x[1], "vertvisc")) return 1;           // :988-1006
   const int rc = st.finish();
   if (rc == 0 && memspace == MOM6HIP_MEM_HOST) return mom6hip_vertvisc_ntrunc(ctx, cs);
@@ -753,10 +723,12 @@ int m6::vertvisc_step_inc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double 
   // bulk mixed layer its own scratch: the plain sequence
   if (visc->Ray_u || visc->Ray_v || cs->dynamic_viscous_ML || cs->nkml > 0) {
     if (inc) {      // the increment as its own sweep (into u and v: they are the step's work arrays when the velocities stay untouched)
-      const m6::GridDev gg = ctx->g;
-      const dim3 gu((gg.iec - gg.isc + 2 + 255) / 256, gg.jec - gg.jsc + 1, gg.nk), gv((gg.iec - gg.isc + 1 + 255) / 256, gg.jec - gg.jsc + 2, gg.nk);
-      hipLaunchKernelGGL(vv_increment_kernel<0>, gu, dim3(256), 0, ctx->stream, gg, inc->u0, inc->a1u, inc->a2u, inc->dtv, u);
-      hipLaunchKernelGGL(vv_increment_kernel<1>, gv, dim3(256), 0, ctx->stream, gg, inc->v0, inc->a1v, inc->a2v, inc->dtv, v);
+      const m6::GridDev g = ctx->g;
+      m6::both_dirs([&](auto D) {
+        constexpr int d = decltype(D)::value;
+        hipLaunchKernelGGL(vv_increment_kernel<d>, m6::face_grid(g, d, 256, g.nk), dim3(256), 0, ctx->stream, g, d ? inc->v0 : inc->u0,
+                           d ? inc->a1v : inc->a1u, d ? inc->a2v : inc->a2u, inc->dtv, d ? v : u);
+      });
       M6_HIP(hipGetLastError());
     }
     if (int rc = mom6hip_vertvisc_coef(ctx, cs, u, v, h, dz, visc, dt, memspace)) return rc;
@@ -766,37 +738,23 @@ int m6::vertvisc_step_inc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double 
   }
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "vertvisc_step: bad memspace");
   if (check_cs(cs, "vertvisc_step")) return 1;
-  M6_REQUIRE(dt > 0.0 && cs->H_to_RZ > 0.0, "vertvisc: dt and GV%%H_to_RZ must be positive");
-  M6_REQUIRE(visc->Kv_shear_Bu == nullptr, "vertvisc_coef: visc%%Kv_shear_Bu is not provided by libmom6hip");
-  M6_REQUIRE(!cs->bottomdraglaw || (visc->Kv_bbl_u && visc->Kv_bbl_v && visc->bbl_thick_u && visc->bbl_thick_v),
-             "vertvisc_coef: BOTTOMDRAGLAW needs visc%%Kv_bbl_u/v and visc%%bbl_thick_u/v");
-  M6_REQUIRE(!(cs->Kvml_invZ2 > 0.0) || cs->Hmix > 0.0, "vertvisc_coef: KV_ML_INVZ2 needs HMIX_FIXED");
-  M6_REQUIRE(!cs->direct_stress || cs->Hmix_stress > 0.0, "vertvisc_init: HMIX_STRESS must be set to a positive value if DIRECT_STRESS is true.");
   const m6::GridDev g = ctx->g;
-  M6_REQUIRE(g.mask2dCu && g.mask2dCv && g.bathyT && g.areaT && g.IareaT && g.dy_Cu && g.dx_Cv, "vertvisc: a required grid metric is missing");
-  const Sz sz = sizes(g);
+  if (int rc = require_solve(cs, dt, g, visc)) return rc;
+  const m6::FieldBytes sz(g);
+  const VVPar p = par_of(cs);
   m6::Stager st(ctx, memspace);
   double *x[2] = {update_velocities ? st.inout(u, sz.u3) : (double *)st.in((const double *)u, sz.u3),
                   update_velocities ? st.inout(v, sz.v3) : (double *)st.in((const double *)v, sz.v3)};
   double *xr[2] = {st.inout(visc_rem_u, sz.u3), st.inout(visc_rem_v, sz.v3)};
   const double *dh = st.in(h, sz.h3), *ddz = st.in(dz, sz.h3), *dks = st.in(visc->Kv_shear, sz.hi);
   const double *tau[2] = {st.in(taux, sz.u2), st.in(tauy, sz.v2)};
-  const double *kvb[2] = {st.in(visc->Kv_bbl_u, sz.u2), st.in(visc->Kv_bbl_v, sz.v2)};
-  const double *bth[2] = {st.in(visc->bbl_thick_u, sz.u2), st.in(visc->bbl_thick_v, sz.v2)};
-  double *a[2] = {st.inout(cs->a_u, sz.ui), st.inout(cs->a_v, sz.vi)};
-  double *hv[2] = {st.inout(cs->h_u, sz.u3), st.inout(cs->h_v, sz.v3)};
+  CoefArgs C[2];
+  for (int d = 0; d < 2; d++) C[d] = coef_args(st, g, p, sz, d, cs, visc, x[d], dh, ddz, dks);
   double *tbot[2] = {update_velocities ? st.inout(taux_bot, sz.u2) : nullptr, update_velocities ? st.inout(tauy_bot, sz.v2) : nullptr};
   double *c1 = (double *)st.scratch(sz.u3 > sz.v3 ? sz.u3 : sz.v3);
   M6_REQUIRE(!st.failed() && c1, "vertvisc_step: staging failed");
   unsigned long long *cnt = nullptr;
-  if (update_velocities) {
-    if (ctx->vv_ntrunc.reserve(sizeof(unsigned long long)) || !ctx->vv_ntrunc.p) return 1;
-    if (!ctx->vv_ntrunc_ready) {
-      M6_HIP(hipMemsetAsync(ctx->vv_ntrunc.p, 0, sizeof(unsigned long long), ctx->stream));
-      ctx->vv_ntrunc_ready = true;
-    }
-    cnt = (unsigned long long *)ctx->vv_ntrunc.p;
-  }
+  if (update_velocities && trunc_counter(ctx, &cnt)) return 1;
   // the KV_ML_INVZ2 profile kept from one call of a step to the next: two interface-sized arrays of the context, reserved the first time
   // a caller produces (never without KV_ML_INVZ2).  Not a cache: nothing is looked up, the caller states what it knows; that the
   // thicknesses are the array the profile was formed from is checked all the same.
@@ -812,29 +770,25 @@ int m6::vertvisc_step_inc(mom6hip_ctx_t *ctx, mom6hip_vertvisc_cs_t *cs, double 
     M6_REQUIRE(ctx->vv_kvml[0].p && ctx->vv_kvml[1].p && ctx->vv_kvml[0].bytes >= sz.ui && ctx->vv_kvml[1].bytes >= sz.vi &&
                ctx->vv_kvml_h == (ddz ? ddz : dh), "vertvisc_step: no KV_ML_INVZ2 profile of these thicknesses has been produced");
   }
-  for (int d = 0; d < 2; d++) {
-    CoefArgs C;
-    C.g = g; C.p = par_of(cs); C.vel = x[d]; C.h = dh; C.dz = ddz; C.kv_bbl = kvb[d]; C.bbl_thick = bth[d]; C.Kv_shear = dks;
-    C.a = a[d]; C.hv = hv[d]; C.ustar = C.nkml_visc = nullptr; C.dzv = nullptr;
-    C.f_u0 = C.f_a1 = C.f_a2 = nullptr; C.f_dt = 0.0; C.f_store = nullptr; C.side = nullptr;
-    C.kvml_src = (kvml == m6::KVML_CONSUME) ? (const double *)ctx->vv_kvml[d].p : nullptr;
-    C.kvml_dst = (kvml == m6::KVML_PRODUCE) ? (double *)ctx->vv_kvml[d].p : nullptr;
+  // MOM6HIP_VV_LDS_BYTES: unused dynamic LDS per block, an occupancy throttle for experiments (a column's intermediates stay in
+  // the memory-side cache only while few enough waves are in flight); 0 = none
+  static const int lds_throttle = [] { const char *e = getenv("MOM6HIP_VV_LDS_BYTES"); return e ? atoi(e) : 0; }();
+  m6::both_dirs([&](auto D) {
+    constexpr int d = decltype(D)::value;
+    if (kvml == m6::KVML_CONSUME) C[d].kvml_src = (const double *)ctx->vv_kvml[d].p;
+    if (kvml == m6::KVML_PRODUCE) C[d].kvml_dst = (double *)ctx->vv_kvml[d].p;
     if (inc) {
-      C.f_u0 = d ? inc->v0 : inc->u0; C.f_a1 = d ? inc->a1v : inc->a1u; C.f_a2 = d ? inc->a2v : inc->a2u; C.f_dt = inc->dtv;
-      C.f_store = update_velocities ? x[d] : nullptr;
+      C[d].f_u0 = d ? inc->v0 : inc->u0; C[d].f_a1 = d ? inc->a1v : inc->a1u; C[d].f_a2 = d ? inc->a2v : inc->a2u; C[d].f_dt = inc->dtv;
+      C[d].f_store = update_velocities ? x[d] : nullptr;
     }
     SolveArgs A;
-    A.g = g; A.p = C.p; A.a = a[d]; A.hv = hv[d]; A.Ray = nullptr; A.h = dh; A.tau = tau[d]; A.x = update_velocities ? x[d] : nullptr;
+    A.g = g; A.p = p; A.a = C[d].a; A.hv = C[d].hv; A.h = dh; A.tau = tau[d]; A.x = update_velocities ? x[d] : nullptr;
     A.xr = xr[d]; A.c1 = c1; A.tbot = tbot[d]; A.dt = dt; A.ntrunc = cnt;
-    const dim3 grid((g.iec - g.isc + 1 + (d ? 0 : 1) + 63) / 64, g.jec - g.jsc + 1 + (d ? 1 : 0));
-    // MOM6HIP_VV_LDS_BYTES: unused dynamic LDS per block, an occupancy throttle for experiments (a column's intermediates stay in
-    // the memory-side cache only while few enough waves are in flight); 0 = none
-    static const int lds_throttle = [] { const char *e = getenv("MOM6HIP_VV_LDS_BYTES"); return e ? atoi(e) : 0; }();
-    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64), lds_throttle, ctx->stream, C, A); };
-    if (kvml == m6::KVML_PRODUCE) { if (d == 0) launch(vv_coef_solve_kernel<0, KV_PRODUCE>); else launch(vv_coef_solve_kernel<1, KV_PRODUCE>); }
-    else if (kvml == m6::KVML_CONSUME) { if (d == 0) launch(vv_coef_solve_kernel<0, KV_CONSUME>); else launch(vv_coef_solve_kernel<1, KV_CONSUME>); }
-    else { if (d == 0) launch(vv_coef_solve_kernel<0, KV_PARK>); else launch(vv_coef_solve_kernel<1, KV_PARK>); }
-  }
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, m6::face_grid(g, d, 64), dim3(64), lds_throttle, ctx->stream, C[d], A); };
+    if (kvml == m6::KVML_PRODUCE) launch(vv_coef_solve_kernel<d, KV_PRODUCE>);
+    else if (kvml == m6::KVML_CONSUME) launch(vv_coef_solve_kernel<d, KV_CONSUME>);
+    else launch(vv_coef_solve_kernel<d, KV_PARK>);
+  });
   M6_HIP(hipGetLastError());
   const int rc = st.finish();
   if (rc == 0 && update_velocities && memspace == MOM6HIP_MEM_HOST) return mom6hip_vertvisc_ntrunc(ctx, cs);
@@ -859,8 +813,7 @@ extern "C" int mom6hip_vertvisc_remnant(mom6hip_ctx_t *ctx, const mom6hip_vertvi
   M6_REQUIRE(cs && visc && visc_rem_u && visc_rem_v, "vertvisc_remnant: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "vertvisc_remnant: bad memspace");
   if (check_cs(cs, "vertvisc_remnant")) return 1;
-  const m6::GridDev g = ctx->g;
-  const Sz sz = sizes(g);
+  const m6::FieldBytes sz(ctx->g);
   m6::Stager st(ctx, memspace);
   double *x[2] = {st.inout(visc_rem_u, sz.u3), st.inout(visc_rem_v, sz.v3)};
   const double *a[2] = {st.in((const double *)cs->a_u, sz.ui), st.in((const double *)cs->a_v, sz.vi)};
@@ -869,6 +822,6 @@ extern "C" int mom6hip_vertvisc_remnant(mom6hip_ctx_t *ctx, const mom6hip_vertvi
   const double *tau[2] = {nullptr, nullptr};
   double *tbot[2] = {nullptr, nullptr}, *none[2] = {nullptr, nullptr};
   M6_REQUIRE(!st.failed(), "vertvisc_remnant: staging failed");
-  if (run_solve(ctx, st, cs, a, hv, Ray, nullptr, tau, none, x, tbot, dt, false)) return 1;
+  if (run_solve(ctx, st, par_of(cs), a, hv, Ray, nullptr, tau, none, x, tbot, dt, false)) return 1;
   return st.finish();
 }

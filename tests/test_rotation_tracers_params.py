@@ -560,7 +560,7 @@ class VertVisc:
     ARRS = ("Kv_bbl_u", "Kv_bbl_v", "bbl_thick_u", "bbl_thick_v", "Ray_u", "Ray_v", "nkml_visc_u", "nkml_visc_v", "Kv_shear", "ustar")
     NAMES = dict(harmonic_visc="HARMONIC_VISC", harm_BL_val="HARMONIC_BL_SCALE", Kvml_invZ2="KV_ML_INVZ2", Hmix="HMIX_FIXED", bottomdraglaw="BOTTOMDRAGLAW",
                  Kv_extra_bbl="KV_EXTRA_BBL", direct_stress="DIRECT_STRESS", CFL_based_trunc="CFL_BASED_TRUNCATIONS", maxvel="MAXVEL",
-                 vel_underflow="VEL_UNDERFLOW", dynamic_viscous_ML="DYNAMIC_VISCOUS_ML", nkml="NKML")
+                 vel_underflow="VEL_UNDERFLOW", dynamic_viscous_ML="DYNAMIC_VISCOUS_ML", nkml="NKML", CFL_trunc="CFL_TRUNCATE")
     DT = 900.0
 
     @staticmethod

@@ -310,6 +310,38 @@ def test_gpu_parity(name):
 
 
 @pytest.mark.gpu
+def test_gpu_rlay_is_uploaded_again_when_it_changes():
+    """Without BBL_USE_EOS the context keeps a device copy of GV%Rlay and uploads it again only when the host's values differ: calls with
+    one table, another, and the first again each give the oracle's result for their own table, on host and on device arrays."""
+    import torch
+    from mom6_amd.pressure_force import EOS_init
+    from mom6_amd.set_viscosity import set_visc_init, set_viscous_BBL
+    from mom6_amd.tracer_advect import DeviceGrid
+    from mom6_amd.vert_friction import vertvisc_type
+    g = xs.make_grid(10, 8, 30)
+    d = xs.make_state(g, umax=0.3)
+    tables = [rlay(g.nk), 1027.0 + 2.0 * np.arange(g.nk)]
+    refs = []
+    for R in tables:
+        visc = orc.vertvisc_type(**visc_arrays(g, d))
+        orc.set_viscous_BBL(g, orc.set_visc_cs(g, 10.0, 1.0e-4, BBL_use_EOS=False, Rlay=R), d["u"], d["v"], d["h"], d["T"], d["S"], orc.eos("WRIGHT"), visc)
+        refs.append(visc._keep)
+    assert not bits_equal(refs[0]["bbl_thick_u"], refs[1]["bbl_thick_u"])
+    dg = DeviceGrid(g)
+    for resident in (True, False):
+        X = (lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()) if resident else (lambda a: a.copy())
+        N = (lambda a: a.cpu().numpy()) if resident else (lambda a: a)
+        for n in (0, 1, 0):
+            CS = set_visc_init(dg, HBBL=10.0, KV=1.0e-4, BBL_USE_EOS=False, Rlay=tables[n].copy())
+            arrs = {k: X(a) for k, a in visc_arrays(g, d).items()}
+            set_viscous_BBL(X(d["u"]), X(d["v"]), X(d["h"]), (X(d["T"]), X(d["S"]), EOS_init("WRIGHT")), vertvisc_type(**arrs), dg, CS)
+            dg.sync()
+            for k in ("bbl_thick_u", "bbl_thick_v", "Kv_bbl_u", "Kv_bbl_v", "Ray_u", "Ray_v"):
+                assert bits_equal(N(arrs[k]), refs[n][k]), (resident, n, k)
+    dg.close()
+
+
+@pytest.mark.gpu
 def test_gpu_parity_unesco_eos():
     """BBL_USE_EOS with EQN_OF_STATE = UNESCO: the density derivatives at the bottom pressure come from MOM_EOS_UNESCO."""
     import torch

@@ -20,6 +20,9 @@ VARIANTS = [
     dict(dynamic_viscous_ML=True),                                 # DYNAMIC_VISCOUS_ML (.testing/tc1, tc2): visc%nkml_visc_u/v, forces%ustar
     dict(nkml=2),                                                  # the viscous mixed layer of a bulk mixed layer (tc1)
     dict(dynamic_viscous_ML=True, nkml=2, Kvml_invZ2=1.0e-2, Hmix=20.0),
+    # CFL_BASED_TRUNCATIONS that truncate: with dx ~ 250 km the default CFL_TRUNCATE = 0.5 needs ~139 m/s.  At 5e-5 the oracle truncates
+    # 481 / 432 / 327 points of the three grids below, to the positive and to the negative value, at u and at v faces (asserted there)
+    dict(CFL_trunc=5.0e-5),
 ]
 
 
@@ -52,6 +55,22 @@ def face_cols(g, a3, pos):
         sl = (slice(g.jsc - g.jsd, g.jec - g.jsd + 2), slice(g.isc - g.isd, g.iec - g.isd + 1))
         m = np.asarray(g.mask2dCv)[sl]
     return a3[(slice(None),) + sl].reshape(a3.shape[0], -1), m.reshape(-1) > 0
+
+
+def cfl_truncated(g, x, pos, CFL_trunc, dt):
+    """how many compute-range faces of x hold the two values vertvisc_limit_vel truncates to with CFL_BASED_TRUNCATIONS,
+    +0.9 CFL_trunc areaT(c0) / (dt dL) and -0.9 CFL_trunc areaT(c1) / (dt dL), c0 and c1 the cells on the two sides of the face"""
+    js, je, i0, ie = g.jsc - g.jsd, g.jec - g.jsd, g.isc - g.isd, g.iec - g.isd
+    aT = np.asarray(g.areaT)
+    if pos == _abi.POS_U:
+        sl = (slice(js, je + 1), slice(i0, ie + 2)); a0, a1 = aT[js:je + 1, i0 - 1:ie + 1], aT[js:je + 1, i0:ie + 2]
+    else:
+        sl = (slice(js, je + 2), slice(i0, ie + 1)); a0, a1 = aT[js - 1:je + 1, i0:ie + 1], aT[js:je + 2, i0:ie + 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dtdL = dt * np.asarray(g.dy_Cu if pos == _abi.POS_U else g.dx_Cv)[sl]
+        up, down = (0.9 * CFL_trunc) * (a0 / dtdL), (-0.9 * CFL_trunc) * (a1 / dtdL)
+    xs = x[(slice(None),) + sl]
+    return int(((xs == up[None]) & (xs > 0)).sum()), int(((xs == down[None]) & (xs < 0)).sum())
 
 
 def test_momentum_budget_of_the_implicit_solve(oracle):
@@ -126,7 +145,7 @@ def test_gpu_parity(oracle, variant):
     names = dict(harmonic_visc="HARMONIC_VISC", harm_BL_val="HARMONIC_BL_SCALE", Kvml_invZ2="KV_ML_INVZ2", Hmix="HMIX_FIXED",
                  bottomdraglaw="BOTTOMDRAGLAW", Kv_extra_bbl="KV_EXTRA_BBL", direct_stress="DIRECT_STRESS",
                  CFL_based_trunc="CFL_BASED_TRUNCATIONS", maxvel="MAXVEL", vel_underflow="VEL_UNDERFLOW",
-                 dynamic_viscous_ML="DYNAMIC_VISCOUS_ML", nkml="NKML")
+                 dynamic_viscous_ML="DYNAMIC_VISCOUS_ML", nkml="NKML", CFL_trunc="CFL_TRUNCATE")
     pk.update({names[k]: v for k, v in kw.items()})
     ml = bool(kw.get("dynamic_viscous_ML") or kw.get("nkml"))
     for (ni, nj, nk, topo, extra) in [(24, 18, 7, dict(reentrant_x=True), dict()), (70, 9, 3, dict(reentrant_x=False), dict(with_shear=True, with_ray=True)),
@@ -142,6 +161,11 @@ def test_gpu_parity(oracle, variant):
         ru, rv = st["u"].copy(), st["v"].copy()
         rtbx, rtby = g.zeros2(_abi.POS_U), g.zeros2(_abi.POS_V)
         orc.vertvisc(g, rcs, ru, rv, st["h"], taux, tauy, rvisc, dt, rtbx, rtby)
+        if "CFL_trunc" in kw:      # the variant is there for the two CFL branches of the limiter: the oracle has to take both, at u and at v
+            assert rcs.ntrunc > 0, ((ni, nj, nk), rcs.ntrunc)
+            for pos, x in ((_abi.POS_U, ru), (_abi.POS_V, rv)):
+                up, down = cfl_truncated(g, x, pos, kw["CFL_trunc"], dt)
+                assert up > 0 and down > 0, ((ni, nj, nk), pos, up, down)
         dg = DeviceGrid(g)
         for resident in (False, True):
             X = (lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a).copy()).cuda()) if resident else \

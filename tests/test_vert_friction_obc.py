@@ -183,7 +183,7 @@ def test_gpu_vertvisc_with_open_boundaries_matches_oracle_bitwise(variant, space
     names = dict(harmonic_visc="HARMONIC_VISC", harm_BL_val="HARMONIC_BL_SCALE", Kvml_invZ2="KV_ML_INVZ2", Hmix="HMIX_FIXED",
                  bottomdraglaw="BOTTOMDRAGLAW", Kv_extra_bbl="KV_EXTRA_BBL", direct_stress="DIRECT_STRESS",
                  CFL_based_trunc="CFL_BASED_TRUNCATIONS", maxvel="MAXVEL", vel_underflow="VEL_UNDERFLOW",
-                 dynamic_viscous_ML="DYNAMIC_VISCOUS_ML", nkml="NKML")
+                 dynamic_viscous_ML="DYNAMIC_VISCOUS_ML", nkml="NKML", CFL_trunc="CFL_TRUNCATE")
     pk.update({names[k]: v for k, v in kw.items()})
     dt = 900.0
     for (ni, nj, nk) in [(22, 16, 6), (70, 20, 3)]:
