@@ -20,16 +20,50 @@ using m6::min2;
 __device__ __forceinline__ double max4(double a, double b, double c, double d) { return max2(max2(max2(a, b), c), d); }
 __device__ __forceinline__ double min4(double a, double b, double c, double d) { return min2(min2(min2(a, b), c), d); }
 
-struct HVOpt {
+// The thirteen on / off options of the control structure (hv_flags_of) as bits of one scalar register.  HVFlags reads them at
+// run time; HVConstFlags<BITS> is the same record at compile time, for the production set.
+enum { F_LAPLACIAN, F_BIHARMONIC, F_SMAG_KH, F_SMAG_AH, F_BOUND_KH, F_BETTER_BOUND_KH, F_BOUND_AH, F_BETTER_BOUND_AH, F_BOUND_CORIOLIS,
+       F_ADD_LES, F_NO_SLIP, F_LAND_MASK, F_CONT_THICK };
+struct HVFlags {
+  unsigned bits;
+  __host__ __device__ bool operator[](int n) const { return (bits >> n) & 1u; }
+};
+template <unsigned BITS>
+struct HVConstFlags {
+  __host__ __device__ constexpr bool operator[](int n) const { return (BITS >> n) & 1u; }
+};
+// the production set: biharmonic Smagorinsky with the better bounds (hv_chunk_kernel)
+constexpr unsigned HV_BIH_SMAG = (1u << F_BIHARMONIC) | (1u << F_SMAG_AH) | (1u << F_BOUND_KH) | (1u << F_BETTER_BOUND_KH) | (1u << F_BOUND_AH) |
+                                 (1u << F_BETTER_BOUND_AH) | (1u << F_LAND_MASK);
+
+struct HVCoef {      // the coefficients hor_visc_init reads
   double Kh, Kh_bg_min, Kh_vel_scale, Smag_Lap_const, Ah, Ah_vel_scale, Ah_time_scale, Smag_bi_const, bound_Cor_vel, bound_coef;
-  int Laplacian, biharmonic, Smagorinsky_Kh, Smagorinsky_Ah, bound_Kh, better_bound_Kh, bound_Ah, better_bound_Ah, bound_Coriolis,
-      add_LES_viscosity, no_slip, use_land_mask, use_cont_thick;
 };
 
 struct HVStatic {      // device pointers to the arrays of the control structure
   double *Kh_bg_xx, *Kh_Max_xx, *Ah_bg_xx, *Ah_Max_xx, *Laplac2_const_xx, *Biharm_const_xx, *Biharm_const2_xx, *reduction_xx;
   double *Kh_bg_xy, *Kh_Max_xy, *Ah_bg_xy, *Ah_Max_xy, *Laplac2_const_xy, *Biharm_const_xy, *Biharm_const2_xy, *reduction_xy;
 };
+// The sixteen arrays are walked by number, in the control structure and in HVStatic: eight h-shaped, then eight q-shaped.
+constexpr int HV_NARRAYS = 16;
+#define HV_ARRAY_OFFSETS(T)                                                                                                         \
+  {offsetof(T, Kh_bg_xx), offsetof(T, Kh_Max_xx), offsetof(T, Ah_bg_xx), offsetof(T, Ah_Max_xx), offsetof(T, Laplac2_const_xx),      \
+   offsetof(T, Biharm_const_xx), offsetof(T, Biharm_const2_xx), offsetof(T, reduction_xx), offsetof(T, Kh_bg_xy),                    \
+   offsetof(T, Kh_Max_xy), offsetof(T, Ah_bg_xy), offsetof(T, Ah_Max_xy), offsetof(T, Laplac2_const_xy), offsetof(T, Biharm_const_xy), \
+   offsetof(T, Biharm_const2_xy), offsetof(T, reduction_xy)}
+constexpr bool hv_arrays_in_a_row(const size_t (&off)[HV_NARRAYS]) {
+  for (int n = 0; n < HV_NARRAYS; n++)
+    if (off[n] != off[0] + n * sizeof(double *)) return false;
+  return true;
+}
+constexpr size_t hv_cs_offsets[HV_NARRAYS] = HV_ARRAY_OFFSETS(mom6hip_hor_visc_cs_t), hv_dev_offsets[HV_NARRAYS] = HV_ARRAY_OFFSETS(HVStatic);
+static_assert(hv_arrays_in_a_row(hv_cs_offsets) && hv_arrays_in_a_row(hv_dev_offsets), "hor_visc: the sixteen static arrays are walked by number");
+#undef HV_ARRAY_OFFSETS
+template <class T>
+auto &hv_array(T &t, int n) { return (&t.Kh_bg_xx)[n]; }      // array n of a control structure or of HVStatic
+size_t hv_array_bytes(const m6::GridDev &g, int n) {
+  return sizeof(double) * (n < HV_NARRAYS / 2 ? (size_t)g.nih * g.njh : (size_t)(g.nih + 1) * (g.njh + 1));
+}
 
 #define H2(i, j) g.h2(i, j)
 #define U2(i, j) g.u2(i, j)
@@ -51,16 +85,54 @@ struct HVStatic {      // device pointers to the arrays of the control structure
 // ---- hor_visc_init ---------------------------------------------------------------------------------------------------
 struct InitArgs {
   m6::GridDev g;
-  HVOpt o;
+  HVFlags F;
+  HVCoef o;
   HVStatic s;
   double *u0u, *u0v, *v0u, *v0v;      // work arrays of the better_bound_Ah bound (:2695-2717)
   double dt;
 };
 
+// one face of reduction_xx / reduction_xy (:2476-2489, :2495-2508): its open width d against its full width D
+__device__ __forceinline__ double hv_reduction(double r, double d, double D) {
+  if ((d > 0.0) && (d < D) && (d < D * r)) r = d / (D);
+  return r;
+}
+
+// Laplac2_const, Kh_Max (the legacy bound) and Kh_bg of a point from its dx2, dy2 :2516-2567
+__device__ __forceinline__ void hv_init_laplacian(HVFlags F, const HVCoef &o, double Kh_Limit, double dx2, double dy2, double &Laplac2_const,
+                                                  double &Kh_Max, double &Kh_bg) {
+  const double grid_sp2 = (2.0 * dx2 * dy2) / (dx2 + dy2);
+  if (F[F_SMAG_KH]) Laplac2_const = o.Smag_Lap_const * grid_sp2;
+  double kb = max2(o.Kh, o.Kh_vel_scale * sqrt(grid_sp2));
+  if (F[F_BOUND_KH] && !F[F_BETTER_BOUND_KH]) {
+    Kh_Max = Kh_Limit * grid_sp2;
+    kb = min2(kb, Kh_Limit * grid_sp2);
+  }
+  Kh_bg = kb;
+}
+
+// Biharm_const, Biharm_const2, Ah_Max (the legacy bound) and Ah_bg of a point from its dx2, dy2 and fmax, its largest |f| :2578-2659
+__device__ __forceinline__ void hv_init_biharmonic(HVFlags F, const HVCoef &o, double Ah_Limit, double BoundCorConst, double dx2, double dy2,
+                                                   double fmax, double &Biharm_const, double &Biharm_const2, double &Ah_Max, double &Ah_bg) {
+  const double grid_sp2 = (2.0 * dx2 * dy2) / (dx2 + dy2);
+  if (F[F_SMAG_AH]) {
+    Biharm_const = o.Smag_bi_const * (grid_sp2 * grid_sp2);
+    if (F[F_BOUND_CORIOLIS]) Biharm_const2 = (grid_sp2 * grid_sp2 * grid_sp2) * (fmax * BoundCorConst);
+  }
+  double ab = max2(o.Ah, o.Ah_vel_scale * grid_sp2 * sqrt(grid_sp2));
+  if (o.Ah_time_scale > 0.) ab = max2(ab, (grid_sp2 * grid_sp2) / o.Ah_time_scale);
+  if (F[F_BOUND_AH] && !F[F_BETTER_BOUND_AH]) {
+    Ah_Max = Ah_Limit * (grid_sp2 * grid_sp2);
+    ab = min2(ab, Ah_Limit * (grid_sp2 * grid_sp2));
+  }
+  Ah_bg = ab;
+}
+
 // thread (i, j) over the data domain; each block of the reference's loops is guarded by its own index range
 __global__ __launch_bounds__(256) void hv_init1_kernel(InitArgs A) {
   const m6::GridDev &g = A.g;
-  const HVOpt &o = A.o;
+  const HVFlags F = A.F;
+  const HVCoef &o = A.o;
   const int i = g.isd + blockIdx.x * blockDim.x + threadIdx.x, j = g.jsd + blockIdx.y;
   if (i > g.ied || j > g.jed) return;
   const int is = g.isc, ie = g.iec, js = g.jsc, je = g.jec;
@@ -70,95 +142,48 @@ __global__ __launch_bounds__(256) void hv_init1_kernel(InitArgs A) {
   // reduction_xx :2473-2490
   if (j >= Jsq && j <= Jeq + 1 && i >= Isq && i <= Ieq + 1) {
     double r = 1.0;
-    if ((g.dy_Cu[U2(I, j)] > 0.0) && (g.dy_Cu[U2(I, j)] < g.dyCu[U2(I, j)]) && (g.dy_Cu[U2(I, j)] < g.dyCu[U2(I, j)] * r))
-      r = g.dy_Cu[U2(I, j)] / (g.dyCu[U2(I, j)]);
-    if ((g.dy_Cu[U2(I - 1, j)] > 0.0) && (g.dy_Cu[U2(I - 1, j)] < g.dyCu[U2(I - 1, j)]) && (g.dy_Cu[U2(I - 1, j)] < g.dyCu[U2(I - 1, j)] * r))
-      r = g.dy_Cu[U2(I - 1, j)] / (g.dyCu[U2(I - 1, j)]);
-    if ((g.dx_Cv[V2(i, J)] > 0.0) && (g.dx_Cv[V2(i, J)] < g.dxCv[V2(i, J)]) && (g.dx_Cv[V2(i, J)] < g.dxCv[V2(i, J)] * r))
-      r = g.dx_Cv[V2(i, J)] / (g.dxCv[V2(i, J)]);
-    if ((g.dx_Cv[V2(i, J - 1)] > 0.0) && (g.dx_Cv[V2(i, J - 1)] < g.dxCv[V2(i, J - 1)]) && (g.dx_Cv[V2(i, J - 1)] < g.dxCv[V2(i, J - 1)] * r))
-      r = g.dx_Cv[V2(i, J - 1)] / (g.dxCv[V2(i, J - 1)]);
+    r = hv_reduction(r, g.dy_Cu[U2(I, j)], g.dyCu[U2(I, j)]);
+    r = hv_reduction(r, g.dy_Cu[U2(I - 1, j)], g.dyCu[U2(I - 1, j)]);
+    r = hv_reduction(r, g.dx_Cv[V2(i, J)], g.dxCv[V2(i, J)]);
+    r = hv_reduction(r, g.dx_Cv[V2(i, J - 1)], g.dxCv[V2(i, J - 1)]);
     A.s.reduction_xx[H2(i, j)] = r;
   }
   // reduction_xy :2492-2509
   if (J >= js - 1 && J <= Jeq && I >= is - 1 && I <= Ieq) {
     double r = 1.0;
-    if ((g.dy_Cu[U2(I, j)] > 0.0) && (g.dy_Cu[U2(I, j)] < g.dyCu[U2(I, j)]) && (g.dy_Cu[U2(I, j)] < g.dyCu[U2(I, j)] * r))
-      r = g.dy_Cu[U2(I, j)] / (g.dyCu[U2(I, j)]);
-    if ((g.dy_Cu[U2(I, j + 1)] > 0.0) && (g.dy_Cu[U2(I, j + 1)] < g.dyCu[U2(I, j + 1)]) && (g.dy_Cu[U2(I, j + 1)] < g.dyCu[U2(I, j + 1)] * r))
-      r = g.dy_Cu[U2(I, j + 1)] / (g.dyCu[U2(I, j + 1)]);
-    if ((g.dx_Cv[V2(i, J)] > 0.0) && (g.dx_Cv[V2(i, J)] < g.dxCv[V2(i, J)]) && (g.dx_Cv[V2(i, J)] < g.dxCv[V2(i, J)] * r))
-      r = g.dx_Cv[V2(i, J)] / (g.dxCv[V2(i, J)]);
-    if ((g.dx_Cv[V2(i + 1, J)] > 0.0) && (g.dx_Cv[V2(i + 1, J)] < g.dxCv[V2(i + 1, J)]) && (g.dx_Cv[V2(i + 1, J)] < g.dxCv[V2(i + 1, J)] * r))
-      r = g.dx_Cv[V2(i + 1, J)] / (g.dxCv[V2(i + 1, J)]);
+    r = hv_reduction(r, g.dy_Cu[U2(I, j)], g.dyCu[U2(I, j)]);
+    r = hv_reduction(r, g.dy_Cu[U2(I, j + 1)], g.dyCu[U2(I, j + 1)]);
+    r = hv_reduction(r, g.dx_Cv[V2(i, J)], g.dxCv[V2(i, J)]);
+    r = hv_reduction(r, g.dx_Cv[V2(i + 1, J)], g.dxCv[V2(i + 1, J)]);
     A.s.reduction_xy[Q2(I, J)] = r;
   }
   const bool in_h = (j >= js - 1 && j <= Jeq + 1 && i >= is - 1 && i <= Ieq + 1);
   const bool in_q = (J >= js - 1 && J <= Jeq && I >= is - 1 && I <= Ieq);
-  if (o.Laplacian) {      // :2511-2568
+  if (F[F_LAPLACIAN]) {      // :2511-2568
     double Kh_Limit = 0.0;
-    if (o.bound_Kh || o.bound_Ah) Kh_Limit = 0.3 / (dt * 4.0);
-    if (in_h) {
-      const double grid_sp_h2 = (2.0 * dx2h(i, j) * dy2h(i, j)) / (dx2h(i, j) + dy2h(i, j));
-      if (o.Smagorinsky_Kh) A.s.Laplac2_const_xx[H2(i, j)] = o.Smag_Lap_const * grid_sp_h2;
-      double kb = max2(o.Kh, o.Kh_vel_scale * sqrt(grid_sp_h2));
-      if (o.bound_Kh && !o.better_bound_Kh) {
-        A.s.Kh_Max_xx[H2(i, j)] = Kh_Limit * grid_sp_h2;
-        kb = min2(kb, Kh_Limit * grid_sp_h2);
-      }
-      A.s.Kh_bg_xx[H2(i, j)] = kb;
-    }
-    if (in_q) {
-      const double grid_sp_q2 = (2.0 * dx2q(I, J) * dy2q(I, J)) / (dx2q(I, J) + dy2q(I, J));
-      if (o.Smagorinsky_Kh) A.s.Laplac2_const_xy[Q2(I, J)] = o.Smag_Lap_const * grid_sp_q2;
-      double kb = max2(o.Kh, o.Kh_vel_scale * sqrt(grid_sp_q2));
-      if (o.bound_Kh && !o.better_bound_Kh) {
-        A.s.Kh_Max_xy[Q2(I, J)] = Kh_Limit * grid_sp_q2;
-        kb = min2(kb, Kh_Limit * grid_sp_q2);
-      }
-      A.s.Kh_bg_xy[Q2(I, J)] = kb;
-    }
+    if (F[F_BOUND_KH] || F[F_BOUND_AH]) Kh_Limit = 0.3 / (dt * 4.0);
+    if (in_h)
+      hv_init_laplacian(F, o, Kh_Limit, dx2h(i, j), dy2h(i, j), A.s.Laplac2_const_xx[H2(i, j)], A.s.Kh_Max_xx[H2(i, j)], A.s.Kh_bg_xx[H2(i, j)]);
+    if (in_q)
+      hv_init_laplacian(F, o, Kh_Limit, dx2q(I, J), dy2q(I, J), A.s.Laplac2_const_xy[Q2(I, J)], A.s.Kh_Max_xy[Q2(I, J)], A.s.Kh_bg_xy[Q2(I, J)]);
   }
-  if (o.biharmonic) {      // :2570-2660
+  if (F[F_BIHARMONIC]) {      // :2570-2660
     double Ah_Limit = 0.0, BoundCorConst = 0.0;
-    if (o.better_bound_Ah || o.bound_Ah) Ah_Limit = 0.3 / (dt * 64.0);
-    if (o.Smagorinsky_Ah && o.bound_Coriolis) BoundCorConst = 1.0 / (5.0 * (o.bound_Cor_vel * o.bound_Cor_vel));
+    if (F[F_BETTER_BOUND_AH] || F[F_BOUND_AH]) Ah_Limit = 0.3 / (dt * 64.0);
+    const bool cor = F[F_SMAG_AH] && F[F_BOUND_CORIOLIS];
+    if (cor) BoundCorConst = 1.0 / (5.0 * (o.bound_Cor_vel * o.bound_Cor_vel));
     if (in_h) {
-      const double grid_sp_h2 = (2.0 * dx2h(i, j) * dy2h(i, j)) / (dx2h(i, j) + dy2h(i, j));
-      if (o.Smagorinsky_Ah) {
-        A.s.Biharm_const_xx[H2(i, j)] = o.Smag_bi_const * (grid_sp_h2 * grid_sp_h2);
-        if (o.bound_Coriolis) {
-          const double fmax = max4(fabs(g.CoriolisBu[Q2(I - 1, J - 1)]), fabs(g.CoriolisBu[Q2(I, J - 1)]),
-                                   fabs(g.CoriolisBu[Q2(I - 1, J)]), fabs(g.CoriolisBu[Q2(I, J)]));
-          A.s.Biharm_const2_xx[H2(i, j)] = (grid_sp_h2 * grid_sp_h2 * grid_sp_h2) * (fmax * BoundCorConst);
-        }
-      }
-      double ab = max2(o.Ah, o.Ah_vel_scale * grid_sp_h2 * sqrt(grid_sp_h2));
-      if (o.Ah_time_scale > 0.) ab = max2(ab, (grid_sp_h2 * grid_sp_h2) / o.Ah_time_scale);
-      if (o.bound_Ah && !o.better_bound_Ah) {
-        A.s.Ah_Max_xx[H2(i, j)] = Ah_Limit * (grid_sp_h2 * grid_sp_h2);
-        ab = min2(ab, Ah_Limit * (grid_sp_h2 * grid_sp_h2));
-      }
-      A.s.Ah_bg_xx[H2(i, j)] = ab;
+      const double fmax = cor ? max4(fabs(g.CoriolisBu[Q2(I - 1, J - 1)]), fabs(g.CoriolisBu[Q2(I, J - 1)]),
+                                     fabs(g.CoriolisBu[Q2(I - 1, J)]), fabs(g.CoriolisBu[Q2(I, J)])) : 0.0;
+      hv_init_biharmonic(F, o, Ah_Limit, BoundCorConst, dx2h(i, j), dy2h(i, j), fmax, A.s.Biharm_const_xx[H2(i, j)],
+                         A.s.Biharm_const2_xx[H2(i, j)], A.s.Ah_Max_xx[H2(i, j)], A.s.Ah_bg_xx[H2(i, j)]);
     }
-    if (in_q) {
-      const double grid_sp_q2 = (2.0 * dx2q(I, J) * dy2q(I, J)) / (dx2q(I, J) + dy2q(I, J));
-      if (o.Smagorinsky_Ah) {
-        A.s.Biharm_const_xy[Q2(I, J)] = o.Smag_bi_const * (grid_sp_q2 * grid_sp_q2);
-        if (o.bound_Coriolis)
-          A.s.Biharm_const2_xy[Q2(I, J)] = (grid_sp_q2 * grid_sp_q2 * grid_sp_q2) * (fabs(g.CoriolisBu[Q2(I, J)]) * BoundCorConst);
-      }
-      double ab = max2(o.Ah, o.Ah_vel_scale * grid_sp_q2 * sqrt(grid_sp_q2));
-      if (o.Ah_time_scale > 0.) ab = max2(ab, (grid_sp_q2 * grid_sp_q2) / o.Ah_time_scale);
-      if (o.bound_Ah && !o.better_bound_Ah) {
-        A.s.Ah_Max_xy[Q2(I, J)] = Ah_Limit * (grid_sp_q2 * grid_sp_q2);
-        ab = min2(ab, Ah_Limit * (grid_sp_q2 * grid_sp_q2));
-      }
-      A.s.Ah_bg_xy[Q2(I, J)] = ab;
-    }
+    if (in_q)
+      hv_init_biharmonic(F, o, Ah_Limit, BoundCorConst, dx2q(I, J), dy2q(I, J), cor ? fabs(g.CoriolisBu[Q2(I, J)]) : 0.0,
+                         A.s.Biharm_const_xy[Q2(I, J)], A.s.Biharm_const2_xy[Q2(I, J)], A.s.Ah_Max_xy[Q2(I, J)], A.s.Ah_bg_xy[Q2(I, J)]);
   }
   const double Idt = 1.0 / dt;
-  if (o.Laplacian && o.better_bound_Kh) {      // :2664-2693
+  if (F[F_LAPLACIAN] && F[F_BETTER_BOUND_KH]) {      // :2664-2693
     if (in_h) {
       const double denom = max2(
           (dy2h(i, j) * DY_dxT(i, j) * (g.IdyCu[U2(I, j)] + g.IdyCu[U2(I - 1, j)]) *
@@ -180,7 +205,7 @@ __global__ __launch_bounds__(256) void hv_init1_kernel(InitArgs A) {
       A.s.Kh_Max_xy[Q2(I, J)] = km;
     }
   }
-  if (o.biharmonic && o.better_bound_Ah) {      // the responses u0u, u0v, v0u, v0v :2695-2717
+  if (F[F_BIHARMONIC] && F[F_BETTER_BOUND_AH]) {      // the responses u0u, u0v, v0u, v0v :2695-2717
     if (j >= js - 1 && j <= Jeq + 1 && I >= is - 2 && I <= Ieq + 1) {
       A.u0u[U2(I, j)] = (Idxdy2u(I, j) * (dy2h(i + 1, j) * DY_dxT(i + 1, j) * (g.IdyCu[U2(I + 1, j)] + g.IdyCu[U2(I, j)]) +
                                          dy2h(i, j) * DY_dxT(i, j) * (g.IdyCu[U2(I, j)] + g.IdyCu[U2(I - 1, j)])) +
@@ -207,7 +232,7 @@ __global__ __launch_bounds__(256) void hv_init1_kernel(InitArgs A) {
 // Ah_Max_xx / Ah_Max_xy from the responses :2719-2755
 __global__ __launch_bounds__(256) void hv_init2_kernel(InitArgs A) {
   const m6::GridDev &g = A.g;
-  const HVOpt &o = A.o;
+  const HVCoef &o = A.o;
   const int i = g.isd + blockIdx.x * blockDim.x + threadIdx.x, j = g.jsd + blockIdx.y;
   if (i > g.ied || j > g.jed) return;
   const int is = g.isc, ie = g.iec, js = g.jsc, je = g.jec;
@@ -289,19 +314,6 @@ __global__ __launch_bounds__(256) void hv_pack_kernel(m6::GridDev g, double *pk)
   put(P_IDXDY2V, inv ? Idxdy2v(i, J) : 0.0); put(P_MASKCV, inv ? g.mask2dCv[V2(i, J)] : 0.0);
 }
 
-// the options the stress stage reads, as bits of one scalar register (the struct of ints and doubles cost 40)
-struct HVFlags {
-  unsigned bits;
-  __host__ __device__ bool operator[](int n) const { return (bits >> n) & 1u; }
-};
-enum { F_LAPLACIAN, F_BIHARMONIC, F_SMAG_KH, F_SMAG_AH, F_BOUND_KH, F_BETTER_BOUND_KH, F_BOUND_AH, F_BETTER_BOUND_AH, F_BOUND_CORIOLIS,
-       F_ADD_LES, F_NO_SLIP, F_LAND_MASK, F_CONT_THICK };
-struct HVFOpt {      // HVOpt as the fused kernel sees it
-  bool Laplacian, biharmonic, Smagorinsky_Kh, Smagorinsky_Ah, bound_Kh, better_bound_Kh, bound_Ah, better_bound_Ah, bound_Coriolis,
-      add_LES_viscosity, no_slip, use_land_mask, use_cont_thick;
-  double Kh_bg_min;
-};
-
 struct HVFArgs {
   HVFlags flags;
   double Kh_bg_min;
@@ -327,22 +339,83 @@ struct HVFArgs {
   const double *obc_tang_u, *obc_tang_v;      // segment%tangential_vel at the q points, all layers
 };
 
+// ---- the viscosity at a point :1056-1380 (h), :1414-1693 (q) --------------------------------------------------------------
+// One text for both kernels and both kinds of point.  FL is HVFlags or HVConstFlags<..>: with the latter the branches a set does
+// not take are gone at compile time.  The callers own their operands: where the strains, thicknesses, coefficients and MEKE
+// averages of the point come from is their business.
+struct HVCoefAt {      // the point's coefficients of hor_visc_init, each read only under the options that use it (null: not provided)
+  const double *Kh_bg, *Kh_Max, *Laplac2_const, *Ah_bg, *Ah_Max, *Biharm_const, *Biharm_const2;
+};
 
-// CFG = HV_GENERIC: the options are read from the argument; otherwise they are the bits of CFG at compile time (the branches
-// and the static arrays a set does not use are gone, which is what lets the remaining base pointers stay in scalar registers).
-// Only HV_GENERIC is launched: the production set -- biharmonic Smagorinsky with the better bounds, HV_BIH_SMAG -- runs in
-// hv_chunk_kernel below.
-constexpr unsigned HV_GENERIC = ~0u;
-constexpr unsigned HV_BIH_SMAG = (1u << F_BIHARMONIC) | (1u << F_SMAG_AH) | (1u << F_BOUND_KH) | (1u << F_BETTER_BOUND_KH) | (1u << F_BOUND_AH) |
-                                 (1u << F_BETTER_BOUND_AH) | (1u << F_LAND_MASK);
+// Shear_mag :1056-1063, :1414-1421 from the square of the point's own strain and the squares of the other strain at its four neighbours
+__device__ __forceinline__ double hv_shear_mag(double own_sq, double a_sq, double b_sq, double c_sq, double d_sq) {
+  return sqrt(own_sq + 0.25 * ((a_sq + b_sq) + (c_sq + d_sq)));
+}
 
-template <unsigned CFG, int HV_TI, int HV_TJ, int HV_NT, int WPE>
-__global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx, int ntiles) {
+// hrat_min :1065-1076, :1430-1441 from the thicknesses of the point's four faces and its own
+__device__ __forceinline__ double hv_hrat_min(double h0, double h1, double h2, double h3, double h_point, double h_neglect) {
+  return min2(1.0, min4(h0, h1, h2, h3) / (h_point + h_neglect));
+}
+
+// hq :1423-1428: the harmonic mean of the four face thicknesses around a q point
+__device__ __forceinline__ double hv_hq(double hu0, double hu1, double hv0, double hv1, double h_neglect3) {
+  const double h2uq = 4.0 * (hu0 * hu1);
+  const double h2vq = 4.0 * (hv0 * hv1);
+  return (2.0 * (h2uq * h2vq)) / (h_neglect3 + (h2uq + h2vq) * ((hu0 + hu1) + (hv0 + hv1)));
+}
+
+// Kh :1078-1214, :1473-1585.  meke, Ku: MEKE%Ku at the point (:1141-1151, :1537-1541).  at_q: the q point leaves visc_bound_rem alone
+// where the bound hrat_min * Kh_Max is not positive (:1552), the h point does not ask (:1167).
+template <class FL>
+__device__ __forceinline__ double hv_Kh(const FL F, const HVCoefAt &c, double Kh_bg_min, double Shear_mag, double hrat_min, bool meke, double Ku,
+                                        bool at_q, double &visc_bound_rem) {
+  double K_ = *c.Kh_bg;
+  if (F[F_SMAG_KH]) {
+    if (F[F_ADD_LES]) K_ = K_ + *c.Laplac2_const * Shear_mag;
+    else K_ = max2(K_, *c.Laplac2_const * Shear_mag);
+    if (F[F_BOUND_KH] && !F[F_BETTER_BOUND_KH]) K_ = min2(K_, *c.Kh_Max);
+  }
+  K_ = max2(K_, Kh_bg_min);
+  if (meke) K_ = K_ + Ku;
+  if (F[F_BETTER_BOUND_KH]) {
+    const double KhM = *c.Kh_Max;
+    if (K_ >= hrat_min * KhM) {
+      visc_bound_rem = 0.0;
+      K_ = hrat_min * KhM;
+    } else if (!at_q || hrat_min * KhM > 0.) {
+      visc_bound_rem = 1.0 - K_ / (hrat_min * KhM);
+    }
+  }
+  return K_;
+}
+
+// Ah :1227-1380, :1598-1693.  meke, Au: MEKE%Au at the point (:1318-1323, :1634-1639).
+template <class FL>
+__device__ __forceinline__ double hv_Ah(const FL F, const HVCoefAt &c, double Shear_mag, double hrat_min, double visc_bound_rem, bool meke, double Au) {
+  double A_ = *c.Ah_bg;
+  if (F[F_SMAG_AH]) {
+    double AhSm;
+    if (F[F_BOUND_CORIOLIS]) AhSm = Shear_mag * (*c.Biharm_const + *c.Biharm_const2 * Shear_mag);
+    else AhSm = *c.Biharm_const * Shear_mag;
+    A_ = max2(A_, AhSm);
+    if (F[F_BOUND_AH] && !F[F_BETTER_BOUND_AH]) A_ = min2(A_, *c.Ah_Max);
+  }
+  if (meke) A_ = A_ + Au;
+  if (F[F_BETTER_BOUND_AH]) {
+    if (F[F_BETTER_BOUND_KH]) A_ = min2(A_, visc_bound_rem * hrat_min * *c.Ah_Max);
+    else A_ = min2(A_, hrat_min * *c.Ah_Max);
+  }
+  return A_;
+}
+
+// hv_fused_kernel serves every set of options, read from the argument at run time, with the OBC maps and the MEKE members.  (The
+// production set, HV_BIH_SMAG without either, runs in hv_chunk_kernel below.)
+constexpr int HV_TI = 64, HV_TJ = 16, HV_NT = 512;      // the tile and the threads of a block
+
+__global__ __launch_bounds__(HV_NT, 4) void hv_fused_kernel(HVFArgs A, int ntx, int ntiles) {
   constexpr int HV_W = HV_TI + 4, HV_H = HV_TJ + 4, HV_NP = HV_W * HV_H, HV_NIT = (HV_NP + HV_NT - 1) / HV_NT;
   __shared__ double s_xx[HV_NP], s_xy[HV_NP], s_d2u[HV_NP], s_d2v[HV_NP], s_hu[HV_NP], s_hv[HV_NP];
-  const HVFlags F = {CFG == HV_GENERIC ? A.flags.bits : CFG};
-  const HVFOpt o = {F[F_LAPLACIAN], F[F_BIHARMONIC], F[F_SMAG_KH], F[F_SMAG_AH], F[F_BOUND_KH], F[F_BETTER_BOUND_KH], F[F_BOUND_AH],
-                    F[F_BETTER_BOUND_AH], F[F_BOUND_CORIOLIS], F[F_ADD_LES], F[F_NO_SLIP], F[F_LAND_MASK], F[F_CONT_THICK], A.Kh_bg_min};
+  const HVFlags F = A.flags;
   const int L = blockIdx.x, m = L >> 3;
   const int k = m % A.nk, tile = (m / A.nk) * 8 + (L & 7);
   if (tile >= ntiles) return;
@@ -357,12 +430,12 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
   // the layer's planes of the 3-D arrays (wave-uniform)
   const size_t kH = (size_t)A.nih * A.njh * k, kU = (size_t)(A.nih + 1) * A.njh * k, kV = (size_t)A.nih * (A.njh + 1) * k;
   const char *u_k = (const char *)(A.u + kU), *v_k = (const char *)(A.v + kV), *h_k = (const char *)(A.h + kH);
-  const bool cont = o.use_cont_thick && A.hu_cont && A.hv_cont;
+  const bool cont = F[F_CONT_THICK] && A.hu_cont && A.hv_cont;
   const char *huc_k = cont ? (const char *)(A.hu_cont + kU) : nullptr, *hvc_k = cont ? (const char *)(A.hv_cont + kV) : nullptr;
   char *du_k = (char *)(A.diffu + kU), *dv_k = (char *)(A.diffv + kV);
   const char *pk = A.pk;
   const unsigned PB = A.plane_bytes;
-  const bool obc = (CFG == HV_GENERIC) && A.obc_q != nullptr;
+  const bool obc = A.obc_q != nullptr;
   // the thickness of the face fs of direction d (0: u, 1: v) with open boundaries: that of the face the projections across the segments'
   // corner points take it from, there the cell inside a segment or the plain interpolation (:740-849)
   auto h_face_obc = [&](int d, int fs) -> double {
@@ -377,7 +450,7 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
     if (side == 2) return hk[h1];
     if (d == 0 && huc_k && (c - 1 + A.isd) >= A.isc - 2) return ((const double *)huc_k)[f];
     if (d == 1 && hvc_k && (r - 1 + A.jsd) >= A.jsc - 2) return ((const double *)hvc_k)[f];
-    if (o.use_land_mask) {
+    if (F[F_LAND_MASK]) {
       const double *mT = (const double *)(pk + (size_t)P_MASKT * PB);
       const int q0 = d ? r * (A.nih + 1) + c + 1 : (r + 1) * (A.nih + 1) + c, q1 = d ? (r + 1) * (A.nih + 1) + c + 1 : (r + 1) * (A.nih + 1) + c + 1;
       return 0.5 * (mT[q0] * hk[h0] + mT[q1] * hk[h1]);
@@ -409,7 +482,7 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
 // thicknesses at velocity points :740-765 (land mask or not; hu_cont / hv_cont inside their ranges with USE_CONT_THICKNESS)
 #define HU_AT(di)                                                                                                        \
   ((huc_k && I + (di) >= A.isc - 2) ? AU(huc_k, di, 0)                                                                    \
-   : o.use_land_mask ? 0.5 * (G(P_MASKT, di, 0) * AH(h_k, di, 0) + G(P_MASKT, (di) + 1, 0) * AH(h_k, (di) + 1, 0))          \
+   : F[F_LAND_MASK] ? 0.5 * (G(P_MASKT, di, 0) * AH(h_k, di, 0) + G(P_MASKT, (di) + 1, 0) * AH(h_k, (di) + 1, 0))          \
                      : 0.5 * (AH(h_k, di, 0) + AH(h_k, (di) + 1, 0)))
 
   // ---- strains and the thicknesses at velocity points ----
@@ -434,7 +507,7 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
           if (qc & 128) dvdx = 2.0 * G(P_DYDXBU, 0, 0) * (AV(v_k, 1, 0) - A.obc_tang_v[q3]) * G(P_IDYCV, 1, 0);
         }
       }
-      if (o.no_slip) LX(s_xy, 0, 0) = (2.0 - G(P_MASKBU, 0, 0)) * (dvdx + dudy);
+      if (F[F_NO_SLIP]) LX(s_xy, 0, 0) = (2.0 - G(P_MASKBU, 0, 0)) * (dvdx + dudy);
       else LX(s_xy, 0, 0) = G(P_MASKBU, 0, 0) * (dvdx + dudy);
     }
     if (j >= js - 1 && j <= je + 1 && I >= is - 2 && I <= ie + 1) {      // :740-765
@@ -446,14 +519,14 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
       const int fs = obc ? (int)(bv >> 3) : 0;
       if (obc && (A.obc_hv[fs] >= 0 || (A.obc_fv[fs] & 12))) LX(s_hv, 0, 0) = h_face_obc(1, fs);
       else if (hvc_k && J >= A.jsc - 2) LX(s_hv, 0, 0) = AV(hvc_k, 0, 0);
-      else if (o.use_land_mask) LX(s_hv, 0, 0) = 0.5 * (G(P_MASKT, 0, 0) * AH(h_k, 0, 0) + G(P_MASKT, 0, 1) * AH(h_k, 0, 1));
+      else if (F[F_LAND_MASK]) LX(s_hv, 0, 0) = 0.5 * (G(P_MASKT, 0, 0) * AH(h_k, 0, 0) + G(P_MASKT, 0, 1) * AH(h_k, 0, 1));
       else LX(s_hv, 0, 0) = 0.5 * (AH(h_k, 0, 0) + AH(h_k, 0, 1));
     }
   } END_POINTS
   __syncthreads();
 
   // ---- the Laplacian of the velocity :882-891 ----
-  if (o.biharmonic) {
+  if (F[F_BIHARMONIC]) {
     FOR_POINTS {
       if (j >= js - 1 && j <= Jeq + 1 && I >= Isq - 1 && I <= Ieq + 1) {
         LX(s_d2u, 0, 0) = G(P_IDXDY2U, 0, 0) * (G(P_DY2H, 1, 0) * LX(s_xx, 1, 0) - G(P_DY2H, 0, 0) * LX(s_xx, 0, 0)) +
@@ -471,62 +544,25 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
 
   // ---- viscosities and layer-integrated stresses :1056-1741 (into registers: they replace the strains in LDS) ----
   const double h_neglect3 = h_neglect * h_neglect * h_neglect;
-  const bool legacy_bound = o.Smagorinsky_Kh && (o.bound_Kh && !o.better_bound_Kh);
-  const bool smag = o.Smagorinsky_Kh || o.Smagorinsky_Ah, bb = o.better_bound_Ah || o.better_bound_Kh;
+  const bool smag = F[F_SMAG_KH] || F[F_SMAG_AH], bb = F[F_BETTER_BOUND_AH] || F[F_BETTER_BOUND_KH];
+  const bool has_Ku = A.Ku != nullptr, has_Au = A.Au != nullptr;
+#define LX2(a, di, dj) (LX(a, di, dj) * LX(a, di, dj))
   double r_xx[HV_NIT], r_xy[HV_NIT];
   FOR_POINTS {
     r_xx[it] = 0.0; r_xy[it] = 0.0;
     if (j >= Jsq && j <= Jeq + 1 && i >= Isq && i <= Ieq + 1) {      // ---- h point (is_Kh : ie_Kh, js_Kh : je_Kh) ----
+      const HVCoefAt c = {&AH(A.s.Kh_bg_xx, 0, 0), &AH(A.s.Kh_Max_xx, 0, 0), &AH(A.s.Laplac2_const_xx, 0, 0), &AH(A.s.Ah_bg_xx, 0, 0),
+                          &AH(A.s.Ah_Max_xx, 0, 0), &AH(A.s.Biharm_const_xx, 0, 0), &AH(A.s.Biharm_const2_xx, 0, 0)};
       const double sxx = LX(s_xx, 0, 0);
-      double Shear_mag = 0.0, hrat_min = 0.0, visc_bound_rem = 0.0;
-      if (smag) {      // :1056-1063
-        const double sh_xx_sq = sxx * sxx;
-        const double sh_xy_sq = 0.25 * ((LX(s_xy, -1, -1) * LX(s_xy, -1, -1) + LX(s_xy, 0, 0) * LX(s_xy, 0, 0)) +
-                                        (LX(s_xy, -1, 0) * LX(s_xy, -1, 0) + LX(s_xy, 0, -1) * LX(s_xy, 0, -1)));
-        Shear_mag = sqrt(sh_xx_sq + sh_xy_sq);
-      }
+      const double Shear_mag = smag ? hv_shear_mag(sxx * sxx, LX2(s_xy, -1, -1), LX2(s_xy, 0, 0), LX2(s_xy, -1, 0), LX2(s_xy, 0, -1)) : 0.0;
       const double h_here = AH(h_k, 0, 0);
-      if (bb) {      // :1065-1076
-        const double h_min = min4(LX(s_hu, 0, 0), LX(s_hu, -1, 0), LX(s_hv, 0, 0), LX(s_hv, 0, -1));
-        hrat_min = min2(1.0, h_min / (h_here + h_neglect));
-        if (o.better_bound_Kh) visc_bound_rem = 1.0;
-      }
+      const double hrat_min = bb ? hv_hrat_min(LX(s_hu, 0, 0), LX(s_hu, -1, 0), LX(s_hv, 0, 0), LX(s_hv, 0, -1), h_here, h_neglect) : 0.0;
+      double visc_bound_rem = F[F_BETTER_BOUND_KH] ? 1.0 : 0.0;
       double str = 0.0;
-      if (o.Laplacian) {      // :1078-1214
-        double K_ = AH(A.s.Kh_bg_xx, 0, 0);
-        if (o.add_LES_viscosity) {
-          if (o.Smagorinsky_Kh) K_ = K_ + AH(A.s.Laplac2_const_xx, 0, 0) * Shear_mag;
-        } else {
-          if (o.Smagorinsky_Kh) K_ = max2(K_, AH(A.s.Laplac2_const_xx, 0, 0) * Shear_mag);
-        }
-        if (legacy_bound) K_ = min2(K_, AH(A.s.Kh_Max_xx, 0, 0));
-        K_ = max2(K_, o.Kh_bg_min);
-        if (CFG == HV_GENERIC && A.Ku) K_ = K_ + AH(A.Ku, 0, 0);      // :1141-1151
-        if (o.better_bound_Kh) {
-          const double KhM = AH(A.s.Kh_Max_xx, 0, 0);
-          if (K_ >= hrat_min * KhM) {
-            visc_bound_rem = 0.0;
-            K_ = hrat_min * KhM;
-          } else {
-            visc_bound_rem = 1.0 - K_ / (hrat_min * KhM);
-          }
-        }
-        str = -K_ * sxx;
-      }
-      if (o.biharmonic) {      // :1227-1380
-        double A_ = AH(A.s.Ah_bg_xx, 0, 0);
-        if (o.Smagorinsky_Ah) {
-          double AhSm;
-          if (o.bound_Coriolis) AhSm = Shear_mag * (AH(A.s.Biharm_const_xx, 0, 0) + AH(A.s.Biharm_const2_xx, 0, 0) * Shear_mag);
-          else AhSm = AH(A.s.Biharm_const_xx, 0, 0) * Shear_mag;
-          A_ = max2(A_, AhSm);
-          if (o.bound_Ah && !o.better_bound_Ah) A_ = min2(A_, AH(A.s.Ah_Max_xx, 0, 0));
-        }
-        if (CFG == HV_GENERIC && A.Au) A_ = A_ + AH(A.Au, 0, 0);      // :1318-1323
-        if (o.better_bound_Ah) {
-          if (o.better_bound_Kh) A_ = min2(A_, visc_bound_rem * hrat_min * AH(A.s.Ah_Max_xx, 0, 0));
-          else A_ = min2(A_, hrat_min * AH(A.s.Ah_Max_xx, 0, 0));
-        }
+      if (F[F_LAPLACIAN])
+        str = -hv_Kh(F, c, A.Kh_bg_min, Shear_mag, hrat_min, has_Ku, has_Ku ? AH(A.Ku, 0, 0) : 0.0, false, visc_bound_rem) * sxx;
+      if (F[F_BIHARMONIC]) {
+        const double A_ = hv_Ah(F, c, Shear_mag, hrat_min, visc_bound_rem, has_Au, has_Au ? AH(A.Au, 0, 0) : 0.0);
         const double d_del2u = G(P_IDYCU, 0, 0) * LX(s_d2u, 0, 0) - G(P_IDYCU, -1, 0) * LX(s_d2u, -1, 0);
         const double d_del2v = G(P_IDXCV, 0, 0) * LX(s_d2v, 0, 0) - G(P_IDXCV, 0, -1) * LX(s_d2v, 0, -1);
         const double d_str = A_ * (G(P_DYDXT, 0, 0) * d_del2u - G(P_DXDYT, 0, 0) * d_del2v);
@@ -536,26 +572,16 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
     }
 
     if (J >= js - 1 && J <= Jeq && I >= is - 1 && I <= Ieq) {      // ---- q point ----
+      const HVCoefAt c = {&AQ(A.s.Kh_bg_xy, 0, 0), &AQ(A.s.Kh_Max_xy, 0, 0), &AQ(A.s.Laplac2_const_xy, 0, 0), &AQ(A.s.Ah_bg_xy, 0, 0),
+                          &AQ(A.s.Ah_Max_xy, 0, 0), &AQ(A.s.Biharm_const_xy, 0, 0), &AQ(A.s.Biharm_const2_xy, 0, 0)};
       const double sxy = LX(s_xy, 0, 0);
-      double Shear_mag = 0.0;
-      if (smag) {      // :1414-1421
-        const double sh_xy_sq = sxy * sxy;
-        const double sh_xx_sq = 0.25 * ((LX(s_xx, 0, 0) * LX(s_xx, 0, 0) + LX(s_xx, 1, 1) * LX(s_xx, 1, 1)) +
-                                        (LX(s_xx, 0, 1) * LX(s_xx, 0, 1) + LX(s_xx, 1, 0) * LX(s_xx, 1, 0)));
-        Shear_mag = sqrt(sh_xy_sq + sh_xx_sq);
-      }
+      const double Shear_mag = smag ? hv_shear_mag(sxy * sxy, LX2(s_xx, 0, 0), LX2(s_xx, 1, 1), LX2(s_xx, 0, 1), LX2(s_xx, 1, 0)) : 0.0;
       const double hu0 = LX(s_hu, 0, 0), hu1 = LX(s_hu, 0, 1);
       const double hv0 = LX(s_hv, 0, 0), hv1 = LX(s_hv, 1, 0);
-      const double h2uq = 4.0 * (hu0 * hu1);      // :1423-1428
-      const double h2vq = 4.0 * (hv0 * hv1);
-      double hq = (2.0 * (h2uq * h2vq)) / (h_neglect3 + (h2uq + h2vq) * ((hu0 + hu1) + (hv0 + hv1)));
-      double hrat_min = 0.0, visc_bound_rem = 0.0;
-      if (bb) {      // :1430-1441
-        const double h_min = min4(hu0, hu1, hv0, hv1);
-        hrat_min = min2(1.0, h_min / (hq + h_neglect));
-        if (o.better_bound_Kh) visc_bound_rem = 1.0;
-      }
-      if (o.no_slip && (G(P_MASKBU, 0, 0) < 0.5)) {      // coastal vorticity points :1443-1466
+      double hq = hv_hq(hu0, hu1, hv0, hv1, h_neglect3);
+      double hrat_min = bb ? hv_hrat_min(hu0, hu1, hv0, hv1, hq, h_neglect) : 0.0;
+      double visc_bound_rem = F[F_BETTER_BOUND_KH] ? 1.0 : 0.0;
+      if (F[F_NO_SLIP] && (G(P_MASKBU, 0, 0) < 0.5)) {      // coastal vorticity points :1443-1466
         const double mu0 = G(P_MASKCU, 0, 0), mu1 = G(P_MASKCU, 0, 1), mv0 = G(P_MASKCV, 0, 0), mv1 = G(P_MASKCV, 1, 0);
         if ((mu0 + mu1) + (mv0 + mv1) > 0.0) {
           const double hu = mu0 * hu0 + mu1 * hu1;
@@ -570,42 +596,13 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
         }
       }
       double str = 0.0;
-      if (o.Laplacian) {      // :1473-1585
-        double K_ = AQ(A.s.Kh_bg_xy, 0, 0);
-        if (o.Smagorinsky_Kh) {
-          if (o.add_LES_viscosity) K_ = K_ + AQ(A.s.Laplac2_const_xy, 0, 0) * Shear_mag;
-          else K_ = max2(K_, AQ(A.s.Laplac2_const_xy, 0, 0) * Shear_mag);
-        }
-        if (legacy_bound) K_ = min2(K_, AQ(A.s.Kh_Max_xy, 0, 0));
-        K_ = max2(K_, o.Kh_bg_min);
-        if (CFG == HV_GENERIC && A.Ku)      // :1537-1541 (meke_res_fn = 1)
-          K_ = K_ + 0.25 * ((AH(A.Ku, 0, 0) + AH(A.Ku, 1, 1)) + (AH(A.Ku, 1, 0) + AH(A.Ku, 0, 1))) * 1.0;
-        if (o.better_bound_Kh) {
-          const double KhM = AQ(A.s.Kh_Max_xy, 0, 0);
-          if (K_ >= hrat_min * KhM) {
-            visc_bound_rem = 0.0;
-            K_ = hrat_min * KhM;
-          } else if (hrat_min * KhM > 0.) {
-            visc_bound_rem = 1.0 - K_ / (hrat_min * KhM);
-          }
-        }
-        str = -K_ * sxy;
+      if (F[F_LAPLACIAN]) {      // MEKE%Ku :1537-1541 (meke_res_fn = 1)
+        const double Ku = has_Ku ? 0.25 * ((AH(A.Ku, 0, 0) + AH(A.Ku, 1, 1)) + (AH(A.Ku, 1, 0) + AH(A.Ku, 0, 1))) * 1.0 : 0.0;
+        str = -hv_Kh(F, c, A.Kh_bg_min, Shear_mag, hrat_min, has_Ku, Ku, true, visc_bound_rem) * sxy;
       }
-      if (o.biharmonic) {      // :1598-1693, with the gradient of the Laplacian :1382-1387
-        double A_ = AQ(A.s.Ah_bg_xy, 0, 0);
-        if (o.Smagorinsky_Ah) {
-          double AhSm;
-          if (o.bound_Coriolis) AhSm = Shear_mag * (AQ(A.s.Biharm_const_xy, 0, 0) + AQ(A.s.Biharm_const2_xy, 0, 0) * Shear_mag);
-          else AhSm = AQ(A.s.Biharm_const_xy, 0, 0) * Shear_mag;
-          A_ = max2(A_, AhSm);
-          if (o.bound_Ah && !o.better_bound_Ah) A_ = min2(A_, AQ(A.s.Ah_Max_xy, 0, 0));
-        }
-        if (CFG == HV_GENERIC && A.Au)      // :1634-1639
-          A_ = A_ + 0.25 * ((AH(A.Au, 0, 0) + AH(A.Au, 1, 1)) + (AH(A.Au, 1, 0) + AH(A.Au, 0, 1)));
-        if (o.better_bound_Ah) {
-          if (o.better_bound_Kh) A_ = min2(A_, visc_bound_rem * hrat_min * AQ(A.s.Ah_Max_xy, 0, 0));
-          else A_ = min2(A_, hrat_min * AQ(A.s.Ah_Max_xy, 0, 0));
-        }
+      if (F[F_BIHARMONIC]) {      // with the gradient of the Laplacian :1382-1387
+        const double Au = has_Au ? 0.25 * ((AH(A.Au, 0, 0) + AH(A.Au, 1, 1)) + (AH(A.Au, 1, 0) + AH(A.Au, 0, 1))) : 0.0;
+        const double A_ = hv_Ah(F, c, Shear_mag, hrat_min, visc_bound_rem, has_Au, Au);
         double dDel2vdx = G(P_DYDXBU, 0, 0) * (LX(s_d2v, 1, 0) * G(P_IDYCV, 1, 0) - LX(s_d2v, 0, 0) * G(P_IDYCV, 0, 0));
         double dDel2udy = G(P_DXDYBU, 0, 0) * (LX(s_d2u, 0, 1) * G(P_IDXCU, 0, 1) - LX(s_d2u, 0, 0) * G(P_IDXCU, 0, 0));
         if (obc) {
@@ -616,7 +613,7 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
         const double d_str = A_ * (dDel2vdx + dDel2udy);
         str = str + d_str;
       }
-      if (o.no_slip) r_xy[it] = str * (hq * AQ(A.s.reduction_xy, 0, 0));      // :1733-1740
+      if (F[F_NO_SLIP]) r_xy[it] = str * (hq * AQ(A.s.reduction_xy, 0, 0));      // :1733-1740
       else r_xy[it] = str * (hq * G(P_MASKBU, 0, 0) * AQ(A.s.reduction_xy, 0, 0));
     }
   } END_POINTS
@@ -629,7 +626,7 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
 
   // ---- diffu, diffv :1744-1770: the tile's own points (the western / southern edge points belong to the first tiles) ----
   const int Iw = (i0 == A.isc) ? is - 1 : is, Js = (j0 == A.jsc) ? js - 1 : js;
-  if (CFG == HV_GENERIC && A.str_xx_out) {      // the stresses of this layer, for MEKE%mom_src
+  if (A.str_xx_out) {      // the stresses of this layer, for MEKE%mom_src
     char *sxx_k = (char *)(A.str_xx_out + kH), *sxy_k = (char *)(A.str_xy_out + (size_t)(A.nih + 1) * (A.njh + 1) * k);
     FOR_POINTS {
       if (j >= js && j <= je && i >= is && i <= ie) *(double *)(sxx_k + bh) = LX(s_xx, 0, 0);
@@ -647,6 +644,7 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
                                 G(P_IAREACV, 0, 0)) / (LX(s_hv, 0, 0) + h_neglect);
   } END_POINTS
 #undef LX
+#undef LX2
 #undef LDB
 #undef G
 #undef AH
@@ -659,7 +657,7 @@ __global__ __launch_bounds__(HV_NT, WPE) void hv_fused_kernel(HVFArgs A, int ntx
 }
 
 // ---- the production set, layer-chunked --------------------------------------------------------------------------------
-// hv_fused_kernel<HV_BIH_SMAG> reads, for every layer, the ~30 k-independent planes of its 68 x 20 frame from L2: ~400 KB per
+// hv_fused_kernel reads, for every layer, the ~30 k-independent planes of its 68 x 20 frame from L2: ~400 KB per
 // block, 47 GB per call at 1440x1080x75, which is what bounded it.  hv_chunk_kernel does the same chain for the same options
 // with ONE frame point per thread (a W x H frame = a (W-4) x (H-4) tile, W*H threads) and works through HV_KCH consecutive layers
 // of its tile: the 28 metrics and coefficients a point uses AT ITSELF are loaded into registers once per block.
@@ -693,6 +691,10 @@ constexpr int HV_CW = HV_CW_DEF, HV_CH = HV_CH_DEF;      // the frame of hv_chun
 template <int W, int H>
 __global__ __launch_bounds__(W * H) void hv_chunk_kernel(HVFArgs A, int ntx, int ntiles, int nch) {
   constexpr int NP = W * H, TI = W - 4, TJ = H - 4;
+  constexpr HVConstFlags<HV_BIH_SMAG> F;
+  // what the operands below are laid out for: no Laplacian stress, no NOSLIP, the land mask in the face thicknesses, no Biharm_const2
+  static_assert(!F[F_LAPLACIAN] && F[F_BIHARMONIC] && !F[F_NO_SLIP] && F[F_LAND_MASK] && !F[F_CONT_THICK] && !F[F_BOUND_CORIOLIS],
+                "hv_chunk_kernel: its planes and registers are those of the production set");
   static_assert(13 * NP * 8 <= 160 * 1024, "hv_chunk_kernel: the frame's planes do not fit in LDS");
   enum { P_MH, P_YU, P_XU, P_XV, P_YV, NPP };      // (P_MH first: no plane read at (-1, 0) or (0, -1) is the first)
   enum { S_D2H_XX, S_D2H_XX2, S_D2Q_XY, S_D2Q_XY2, S_XX2, S_XY2, S_HU, S_HV, NSP };
@@ -789,39 +791,26 @@ __global__ __launch_bounds__(W * H) void hv_chunk_kernel(HVFArgs A, int ntx, int
 
     // ---- viscosities and layer-integrated stresses :1056-1741 (biharmonic Smagorinsky, better bounds, land mask) ----
     double r_xx = 0.0, r_xy = 0.0;
+    const double visc_bound_rem = 1.0;      // (no Laplacian viscosity has used any of the bound)
     if (j >= Jsq && j <= Jeq + 1 && i >= Isq && i <= Ieq + 1) {      // h point
-      const double sh_xx_sq = sxx2;
-      const double sh_xy_sq = 0.25 * ((SX(S_XY2, -1, -1) + sxy2) + (SX(S_XY2, -1, 0) + SX(S_XY2, 0, -1)));
-      const double Shear_mag = sqrt(sh_xx_sq + sh_xy_sq);
-      const double h_min = min4(hu, SX(S_HU, -1, 0), hv, SX(S_HV, 0, -1));
-      const double hrat_min = min2(1.0, h_min / (h + h_neglect));
-      const double visc_bound_rem = 1.0;
-      double A_ = Ah_bg_xx;
-      const double AhSm = Biharm_xx * Shear_mag;
-      A_ = max2(A_, AhSm);
-      A_ = min2(A_, visc_bound_rem * hrat_min * Ah_Max_xx);
+      const HVCoefAt c = {nullptr, nullptr, nullptr, &Ah_bg_xx, &Ah_Max_xx, &Biharm_xx, nullptr};
+      const double Shear_mag = hv_shear_mag(sxx2, SX(S_XY2, -1, -1), sxy2, SX(S_XY2, -1, 0), SX(S_XY2, 0, -1));
+      const double hrat_min = hv_hrat_min(hu, SX(S_HU, -1, 0), hv, SX(S_HV, 0, -1), h, h_neglect);
+      const double A_ = hv_Ah(F, c, Shear_mag, hrat_min, visc_bound_rem, false, 0.0);
       const double d_del2u = yd2u - PX(P_YU, -1, 0);
       const double d_del2v = xd2v - PX(P_XV, 0, -1);
       const double d_str = A_ * (DY_dxT * d_del2u - DX_dyT * d_del2v);
-      const double str = 0.0 + d_str;
+      const double str = 0.0 + d_str;      // (str is 0 without the Laplacian; the sum turns a -0 into +0 as it does there)
       r_xx = str * (h * red_xx);
     }
     if (J >= js - 1 && J <= Jeq && I >= is - 1 && I <= Ieq) {      // q point
-      const double sh_xy_sq = sxy2;
-      const double sh_xx_sq = 0.25 * ((sxx2 + SX(S_XX2, 1, 1)) + (SX(S_XX2, 0, 1) + SX(S_XX2, 1, 0)));
-      const double Shear_mag = sqrt(sh_xy_sq + sh_xx_sq);
+      const HVCoefAt c = {nullptr, nullptr, nullptr, &Ah_bg_xy, &Ah_Max_xy, &Biharm_xy, nullptr};
+      const double Shear_mag = hv_shear_mag(sxy2, sxx2, SX(S_XX2, 1, 1), SX(S_XX2, 0, 1), SX(S_XX2, 1, 0));
       const double hu0 = hu, hu1 = SX(S_HU, 0, 1);
       const double hv0 = hv, hv1 = SX(S_HV, 1, 0);
-      const double h2uq = 4.0 * (hu0 * hu1);
-      const double h2vq = 4.0 * (hv0 * hv1);
-      const double hq = (2.0 * (h2uq * h2vq)) / (h_neglect3 + (h2uq + h2vq) * ((hu0 + hu1) + (hv0 + hv1)));
-      const double h_min = min4(hu0, hu1, hv0, hv1);
-      const double hrat_min = min2(1.0, h_min / (hq + h_neglect));
-      const double visc_bound_rem = 1.0;
-      double A_ = Ah_bg_xy;
-      const double AhSm = Biharm_xy * Shear_mag;
-      A_ = max2(A_, AhSm);
-      A_ = min2(A_, visc_bound_rem * hrat_min * Ah_Max_xy);
+      const double hq = hv_hq(hu0, hu1, hv0, hv1, h_neglect3);
+      const double hrat_min = hv_hrat_min(hu0, hu1, hv0, hv1, hq, h_neglect);
+      const double A_ = hv_Ah(F, c, Shear_mag, hrat_min, visc_bound_rem, false, 0.0);
       const double dDel2vdx = DY_dxBu * (PX(P_YV, 1, 0) - yd2v);
       const double dDel2udy = DX_dyBu * (PX(P_XU, 0, 1) - xd2u);
       const double d_str = A_ * (dDel2vdx + dDel2udy);
@@ -883,26 +872,23 @@ __global__ __launch_bounds__(256) void hv_frictwork_kernel(m6::GridDev g, const 
   mom_src[g.h2(i, j)] = src;
 }
 
-int check_cs(const mom6hip_hor_visc_cs_t *cs, const char *who) {
+// the checks hor_visc_init and horizontal_viscosity share
+int hv_check(const mom6hip_ctx_t *ctx, const mom6hip_hor_visc_cs_t *cs, const char *who) {
   static const char *names[10] = {"LEITH_KH", "LEITH_AH", "USE_LEITHY", "MEKE backscatter (MEKE_BACKSCAT_RO_C) / RES_SCALE_MEKE_VISC", "USE_GME", "ANISOTROPIC_VISCOSITY", "RE_AH", "KH_SIN_LAT",
                                   "USE_KH_BG_2D", "USE_ZB2020"};
   for (int n = 0; n < 10; n++) M6_REQUIRE(!cs->unsupported[n], "%s: %s is not provided by libmom6hip", who, names[n]);
   M6_REQUIRE(!(cs->no_slip && cs->biharmonic), "ERROR: NOSLIP and BIHARMONIC cannot be defined at the same time in MOM.");
-  double *const *a = &cs->Kh_bg_xx;
-  for (int n = 0; n < 16; n++) M6_REQUIRE(a[n] != nullptr, "%s: array %d of the control structure is missing", who, n);
+  for (int n = 0; n < HV_NARRAYS; n++) M6_REQUIRE(hv_array(*cs, n) != nullptr, "%s: array %d of the control structure is missing", who, n);
+  M6_REQUIRE(ctx->g.isc - ctx->g.isd >= 2 && ctx->g.jsc - ctx->g.jsd >= 2, "%s: the halo must be at least 2 points wide", who);
   return 0;
 }
 
-HVOpt opt_of(const mom6hip_hor_visc_cs_t *cs) {
-  HVOpt o;
-  o.Kh = cs->Kh; o.Kh_bg_min = cs->Kh_bg_min; o.Kh_vel_scale = cs->Kh_vel_scale; o.Smag_Lap_const = cs->Smag_Lap_const;
-  o.Ah = cs->Ah; o.Ah_vel_scale = cs->Ah_vel_scale; o.Ah_time_scale = cs->Ah_time_scale; o.Smag_bi_const = cs->Smag_bi_const;
-  o.bound_Cor_vel = cs->bound_Cor_vel; o.bound_coef = cs->bound_coef;
-  o.Laplacian = cs->Laplacian; o.biharmonic = cs->biharmonic; o.Smagorinsky_Kh = cs->Smagorinsky_Kh; o.Smagorinsky_Ah = cs->Smagorinsky_Ah;
-  o.bound_Kh = cs->bound_Kh; o.better_bound_Kh = cs->better_bound_Kh; o.bound_Ah = cs->bound_Ah; o.better_bound_Ah = cs->better_bound_Ah;
-  o.bound_Coriolis = cs->bound_Coriolis; o.add_LES_viscosity = cs->add_LES_viscosity; o.no_slip = cs->no_slip;
-  o.use_land_mask = cs->use_land_mask; o.use_cont_thick = cs->use_cont_thick;
-  return o;
+HVFlags hv_flags_of(const mom6hip_hor_visc_cs_t *cs) {
+  auto bit = [](int n, int32_t on) { return (on ? 1u : 0u) << n; };
+  return {bit(F_LAPLACIAN, cs->Laplacian) | bit(F_BIHARMONIC, cs->biharmonic) | bit(F_SMAG_KH, cs->Smagorinsky_Kh) | bit(F_SMAG_AH, cs->Smagorinsky_Ah) |
+          bit(F_BOUND_KH, cs->bound_Kh) | bit(F_BETTER_BOUND_KH, cs->better_bound_Kh) | bit(F_BOUND_AH, cs->bound_Ah) |
+          bit(F_BETTER_BOUND_AH, cs->better_bound_Ah) | bit(F_BOUND_CORIOLIS, cs->bound_Coriolis) | bit(F_ADD_LES, cs->add_LES_viscosity) |
+          bit(F_NO_SLIP, cs->no_slip) | bit(F_LAND_MASK, cs->use_land_mask) | bit(F_CONT_THICK, cs->use_cont_thick)};
 }
 
 }  // namespace
@@ -910,25 +896,23 @@ HVOpt opt_of(const mom6hip_hor_visc_cs_t *cs) {
 extern "C" int mom6hip_hor_visc_init(mom6hip_ctx_t *ctx, mom6hip_hor_visc_cs_t *cs, double dt, int32_t memspace) {
   M6_REQUIRE(ctx != nullptr && cs != nullptr, "hor_visc_init: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "hor_visc_init: bad memspace");
-  if (check_cs(cs, "hor_visc_init")) return 1;
+  if (hv_check(ctx, cs, "hor_visc_init")) return 1;
   M6_REQUIRE(dt > 0.0, "hor_visc_init: DT must be positive");
   const m6::GridDev g = ctx->g;
   M6_REQUIRE(g.dxT && g.dyT && g.IdxT && g.IdyT && g.dxCu && g.dyCu && g.dy_Cu && g.IdxCu && g.IdyCu && g.IareaCu && g.dxCv && g.dyCv &&
              g.dx_Cv && g.IdxCv && g.IdyCv && g.IareaCv && g.dxBu && g.dyBu && g.IdxBu && g.IdyBu && g.CoriolisBu && g.mask2dBu &&
              g.mask2dT && g.mask2dCu && g.mask2dCv, "hor_visc_init: a required grid metric is missing");
-  M6_REQUIRE(g.isc - g.isd >= 2 && g.jsc - g.jsd >= 2, "hor_visc_init: the halo must be at least 2 points wide");
-  const size_t bH = sizeof(double) * (size_t)g.nih * g.njh, bQ = sizeof(double) * (size_t)(g.nih + 1) * (g.njh + 1);
   const size_t bU = sizeof(double) * (size_t)(g.nih + 1) * g.njh, bV = sizeof(double) * (size_t)g.nih * (g.njh + 1);
   hipStream_t s = ctx->stream;
   m6::Stager st(ctx, memspace);
   InitArgs A;
-  A.g = g; A.o = opt_of(cs); A.dt = dt;
-  double *const *src = &cs->Kh_bg_xx;
-  double **dst = &A.s.Kh_bg_xx;
-  for (int n = 0; n < 16; n++) dst[n] = st.out(src[n], n < 8 ? bH : bQ);
+  A.g = g; A.F = hv_flags_of(cs); A.dt = dt;
+  A.o = {cs->Kh, cs->Kh_bg_min, cs->Kh_vel_scale, cs->Smag_Lap_const, cs->Ah, cs->Ah_vel_scale, cs->Ah_time_scale, cs->Smag_bi_const,
+         cs->bound_Cor_vel, cs->bound_coef};
+  for (int n = 0; n < HV_NARRAYS; n++) hv_array(A.s, n) = st.out(hv_array(*cs, n), hv_array_bytes(g, n));
   A.u0u = (double *)st.scratch(bU); A.u0v = (double *)st.scratch(bU); A.v0u = (double *)st.scratch(bV); A.v0v = (double *)st.scratch(bV);
   M6_REQUIRE(!st.failed(), "hor_visc_init: staging failed");
-  for (int n = 0; n < 16; n++) M6_HIP(hipMemsetAsync(dst[n], 0, n < 8 ? bH : bQ, s));
+  for (int n = 0; n < HV_NARRAYS; n++) M6_HIP(hipMemsetAsync(hv_array(A.s, n), 0, hv_array_bytes(g, n), s));
   M6_HIP(hipMemsetAsync(A.u0u, 0, bU, s)); M6_HIP(hipMemsetAsync(A.u0v, 0, bU, s));
   M6_HIP(hipMemsetAsync(A.v0u, 0, bV, s)); M6_HIP(hipMemsetAsync(A.v0v, 0, bV, s));
   if (cs->Laplacian || cs->biharmonic) {
@@ -941,6 +925,42 @@ extern "C" int mom6hip_hor_visc_init(mom6hip_ctx_t *ctx, mom6hip_hor_visc_cs_t *
   return st.finish();
 }
 
+namespace {
+// the metric planes of this grid, once per context
+int hv_pack_once(mom6hip_ctx_t *ctx, size_t plane) {
+  if (ctx->hv_pack_ready) return 0;
+  const m6::GridDev g = ctx->g;
+  M6_REQUIRE(ctx->hv_pack.reserve(plane * HV_NPLANES) == 0, "horizontal_viscosity: out of device memory");
+  hipLaunchKernelGGL(hv_pack_kernel, dim3((g.nih + 1 + 255) / 256, g.njh + 1), dim3(256), 0, ctx->stream, g, (double *)ctx->hv_pack.p);
+  M6_HIP(hipGetLastError());
+  ctx->hv_pack_ready = true;
+  return 0;
+}
+
+int hv_fill(mom6hip_ctx_t *ctx, const mom6hip_hor_visc_cs_t *cs, const double *u, const double *v, const double *h, double *diffu, double *diffv,
+            const double *hu_cont, const double *hv_cont, const m6::HVObcDev *ob, size_t plane, HVFArgs &A) {
+  const m6::GridDev g = ctx->g;
+  A.flags = hv_flags_of(cs);
+  A.Kh_bg_min = cs->Kh_bg_min;
+  for (int n = 0; n < HV_NARRAYS; n++) hv_array(A.s, n) = hv_array(*cs, n);
+  A.pk = (const char *)ctx->hv_pack.p; A.plane_bytes = (unsigned)plane;
+  A.isc = g.isc; A.iec = g.iec; A.jsc = g.jsc; A.jec = g.jec; A.isd = g.isd; A.jsd = g.jsd; A.nih = g.nih; A.njh = g.njh; A.nk = g.nk;
+  A.h_neglect = g.H_subroundoff;
+  A.u = u; A.v = v; A.h = h; A.hu_cont = hu_cont; A.hv_cont = hv_cont; A.diffu = diffu; A.diffv = diffv;
+  A.Ku = cs->Laplacian ? cs->MEKE_Ku : nullptr; A.Au = cs->biharmonic ? cs->MEKE_Au : nullptr;
+  A.str_xx_out = nullptr; A.str_xy_out = nullptr;
+  const m6::HVObcDev none;
+  if (!ob) ob = &none;
+  A.obc_q = ob->q; A.obc_fu = ob->fu; A.obc_fv = ob->fv; A.obc_hu = ob->hu; A.obc_hv = ob->hv; A.obc_tang_u = ob->tang_u; A.obc_tang_v = ob->tang_v;
+  if (cs->MEKE_mom_src) {
+    const size_t nH3 = (size_t)g.nih * g.njh * g.nk, nQ3 = (size_t)(g.nih + 1) * (g.njh + 1) * g.nk;
+    M6_REQUIRE(ctx->hv_str.reserve(sizeof(double) * (nH3 + nQ3)) == 0, "horizontal_viscosity: out of device memory for MEKE%%mom_src");
+    A.str_xx_out = (double *)ctx->hv_str.p; A.str_xy_out = A.str_xx_out + nH3;
+  }
+  return 0;
+}
+}  // namespace
+
 // the launches of horizontal_viscosity on device arrays (also called by the split RK2 step at :860 and :1543)
 namespace m6 {
 int horizontal_viscosity_dev(mom6hip_ctx_t *ctx, const mom6hip_hor_visc_cs_t *cs, const double *u, const double *v, const double *h,
@@ -948,62 +968,22 @@ int horizontal_viscosity_dev(mom6hip_ctx_t *ctx, const mom6hip_hor_visc_cs_t *cs
   const m6::GridDev g = ctx->g;
   if (!(cs->Laplacian || cs->biharmonic)) return 0;      // :451
   const size_t plane = sizeof(double) * (size_t)(g.nih + 1) * (g.njh + 1);
-  M6_REQUIRE(plane < (1ull << 31) && sizeof(double) * (size_t)(g.nih + 1) * (g.njh + 1) < (1ull << 31),
-             "horizontal_viscosity: a layer is too large for 32-bit byte offsets");
-  if (!ctx->hv_pack_ready) {      // the metric planes of this grid, once per context
-    M6_REQUIRE(ctx->hv_pack.reserve(plane * HV_NPLANES) == 0, "horizontal_viscosity: out of device memory");
-    hipLaunchKernelGGL(hv_pack_kernel, dim3((g.nih + 1 + 255) / 256, g.njh + 1), dim3(256), 0, ctx->stream, g, (double *)ctx->hv_pack.p);
-    M6_HIP(hipGetLastError());
-    ctx->hv_pack_ready = true;
-  }
+  M6_REQUIRE(plane < (1ull << 31), "horizontal_viscosity: a layer is too large for 32-bit byte offsets");
+  if (const int rc = hv_pack_once(ctx, plane)) return rc;
   HVFArgs A;
-  const HVOpt o = opt_of(cs);
-  const int fl[13] = {o.Laplacian, o.biharmonic, o.Smagorinsky_Kh, o.Smagorinsky_Ah, o.bound_Kh, o.better_bound_Kh, o.bound_Ah, o.better_bound_Ah,
-                      o.bound_Coriolis, o.add_LES_viscosity, o.no_slip, o.use_land_mask, o.use_cont_thick};
-  A.flags.bits = 0;
-  for (int n = 0; n < 13; n++) A.flags.bits |= (fl[n] ? 1u : 0u) << n;
-  A.Kh_bg_min = o.Kh_bg_min;
-  double *const *src = &cs->Kh_bg_xx;
-  double **dst = &A.s.Kh_bg_xx;
-  for (int n = 0; n < 16; n++) dst[n] = src[n];
-  A.pk = (const char *)ctx->hv_pack.p; A.plane_bytes = (unsigned)plane;
-  A.isc = g.isc; A.iec = g.iec; A.jsc = g.jsc; A.jec = g.jec; A.isd = g.isd; A.jsd = g.jsd; A.nih = g.nih; A.njh = g.njh; A.nk = g.nk;
-  A.h_neglect = g.H_subroundoff;
-  A.u = u; A.v = v; A.h = h; A.hu_cont = hu_cont; A.hv_cont = hv_cont; A.diffu = diffu; A.diffv = diffv;
-  A.Ku = cs->Laplacian ? cs->MEKE_Ku : nullptr; A.Au = cs->biharmonic ? cs->MEKE_Au : nullptr;
-  A.str_xx_out = nullptr; A.str_xy_out = nullptr;
-  A.obc_q = A.obc_fu = A.obc_fv = A.obc_hu = A.obc_hv = nullptr;
-  A.obc_tang_u = A.obc_tang_v = nullptr;
-  if (ob) { A.obc_q = ob->q; A.obc_fu = ob->fu; A.obc_fv = ob->fv; A.obc_hu = ob->hu; A.obc_hv = ob->hv; A.obc_tang_u = ob->tang_u; A.obc_tang_v = ob->tang_v; }
-  const bool meke = A.Ku || A.Au || cs->MEKE_mom_src;
-  if (cs->MEKE_mom_src) {
-    const size_t nH3 = (size_t)g.nih * g.njh * g.nk, nQ3 = (size_t)(g.nih + 1) * (g.njh + 1) * g.nk;
-    M6_REQUIRE(ctx->hv_str.reserve(sizeof(double) * (nH3 + nQ3)) == 0, "horizontal_viscosity: out of device memory for MEKE%%mom_src");
-    A.str_xx_out = (double *)ctx->hv_str.p; A.str_xy_out = A.str_xx_out + nH3;
-  }
+  if (const int rc = hv_fill(ctx, cs, u, v, h, diffu, diffv, hu_cont, hv_cont, ob, plane, A)) return rc;
   const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1;
-  auto launch = [&](auto kern, int TI, int TJ, int NT) {
-    const int ntx = (ni + TI - 1) / TI, nty = (nj + TJ - 1) / TJ, ntiles = ntx * nty;
-    const long nblocks = (long)((ntiles + 7) / 8) * 8 * g.nk;
-    if (nblocks >= (1L << 31)) return 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(NT), 0, ctx->stream, A, ntx, ntiles);
-    return 0;
-  };
-  int rc;
-  if (A.flags.bits == HV_BIH_SMAG && !meke && !ob) {
-    // the production set: one block per (tile, chunk of HV_KCH layers), the chunks of a tile back to back on one XCD
-    constexpr int TI = HV_CW - 4, TJ = HV_CH - 4;
-    const int ntx = (ni + TI - 1) / TI, nty = (nj + TJ - 1) / TJ, ntiles = ntx * nty, nch = (g.nk + HV_KCH - 1) / HV_KCH;
-    const long nblocks = (long)((ntiles + 7) / 8) * 8 * nch;
-    rc = nblocks >= (1L << 31);
-    if (!rc) hipLaunchKernelGGL((hv_chunk_kernel<HV_CW, HV_CH>), dim3((unsigned)nblocks), dim3(HV_CW * HV_CH), 0, ctx->stream, A, ntx, ntiles, nch);
-  } else {
-    // everything else (OBC maps, MEKE Ku / Au and str_*_out, the Laplacian, options at run time) one layer per block
-    // (tiles of 64x8, 64x12, 32x16, 128x8 points and blocks of 256 / 1024 threads all ran within 5% of this one: the kernel is
-    // bound by the L2 -> L1 traffic of the metric planes, which every block reads for its tile -- profiles/r02_hor_visc.txt)
-    rc = launch(hv_fused_kernel<HV_GENERIC, 64, 16, 512, 4>, 64, 16, 512);
-  }
-  M6_REQUIRE(rc == 0, "horizontal_viscosity: the grid is too large for one launch");
+  // the production set goes to hv_chunk_kernel: one block per (tile, chunk of HV_KCH layers), the chunks of a tile back to back on one
+  // XCD.  Everything else (OBC maps, MEKE Ku / Au and str_*_out, the Laplacian, options at run time) to hv_fused_kernel, one layer per
+  // block (tiles of 64x8, 64x12, 32x16, 128x8 points and blocks of 256 / 1024 threads all ran within 5% of this one: the kernel is
+  // bound by the L2 -> L1 traffic of the metric planes, which every block reads for its tile -- profiles/r02_hor_visc.txt)
+  const bool chunked = A.flags.bits == HV_BIH_SMAG && !(A.Ku || A.Au || cs->MEKE_mom_src) && !ob;
+  const int TI = chunked ? HV_CW - 4 : HV_TI, TJ = chunked ? HV_CH - 4 : HV_TJ, nper = chunked ? (g.nk + HV_KCH - 1) / HV_KCH : g.nk;
+  const int ntx = (ni + TI - 1) / TI, nty = (nj + TJ - 1) / TJ, ntiles = ntx * nty;
+  const long nblocks = (long)((ntiles + 7) / 8) * 8 * nper;
+  M6_REQUIRE(nblocks < (1L << 31), "horizontal_viscosity: the grid is too large for one launch");
+  if (chunked) hipLaunchKernelGGL((hv_chunk_kernel<HV_CW, HV_CH>), dim3((unsigned)nblocks), dim3(HV_CW * HV_CH), 0, ctx->stream, A, ntx, ntiles, nper);
+  else hipLaunchKernelGGL(hv_fused_kernel, dim3((unsigned)nblocks), dim3(HV_NT), 0, ctx->stream, A, ntx, ntiles);
   if (cs->MEKE_mom_src)
     hipLaunchKernelGGL(hv_frictwork_kernel, dim3((ni + 255) / 256, nj), dim3(256), 0, ctx->stream, g, u, v, A.str_xx_out, A.str_xy_out,
                        cs->MEKE_mom_src);
@@ -1142,16 +1122,13 @@ extern "C" int mom6hip_horizontal_viscosity_obc(mom6hip_ctx_t *ctx, const mom6hi
   M6_REQUIRE(cs && u && v && h && diffu && diffv, "horizontal_viscosity: null argument");
   M6_REQUIRE(memspace == MOM6HIP_MEM_HOST || memspace == MOM6HIP_MEM_DEVICE, "horizontal_viscosity: bad memspace");
   M6_REQUIRE(cs->initialized, "MOM_hor_visc: Module must be initialized before it is used.");
-  if (check_cs(cs, "horizontal_viscosity")) return 1;
+  if (hv_check(ctx, cs, "horizontal_viscosity")) return 1;
   const m6::GridDev g = ctx->g;
-  M6_REQUIRE(g.isc - g.isd >= 2 && g.jsc - g.jsd >= 2, "horizontal_viscosity: the halo must be at least 2 points wide");
-  const size_t bH2 = sizeof(double) * (size_t)g.nih * g.njh, bQ2 = sizeof(double) * (size_t)(g.nih + 1) * (g.njh + 1);
+  const size_t bH2 = sizeof(double) * (size_t)g.nih * g.njh;
   const size_t bH = sizeof(double) * (size_t)g.nh3(), bU = sizeof(double) * (size_t)g.nu3(), bV = sizeof(double) * (size_t)g.nv3();
   m6::Stager st(ctx, memspace);
   mom6hip_hor_visc_cs_t dcs = *cs;
-  double *const *src = &cs->Kh_bg_xx;
-  double **dst = &dcs.Kh_bg_xx;
-  for (int n = 0; n < 16; n++) dst[n] = (double *)st.in(src[n], n < 8 ? bH2 : bQ2);
+  for (int n = 0; n < HV_NARRAYS; n++) hv_array(dcs, n) = (double *)st.in(hv_array(*cs, n), hv_array_bytes(g, n));
   const double *du = st.in(u, bU), *dv = st.in(v, bV), *dh = st.in(h, bH);
   const double *dhu = st.in(hu_cont, bU), *dhv = st.in(hv_cont, bV);
   double *ddu = st.inout(diffu, bU), *ddv = st.inout(diffv, bV);      // (only the compute ranges are written)

@@ -150,7 +150,7 @@ def test_gpu_parity_with_meke(name):
     from mom6_amd.tracer_advect import DeviceGrid
     kw, members = MEKE_VARIANTS[name]
     for (ni, nj, nk, topo, land) in [(70, 21, 3, (True, False), 0.25), (44, 40, 2, (True, True), 0.3), (10, 8, 8, (False, False), 0.2),
-                                     (300, 9, 5, (True, False), 0.25)]:
+                                     (300, 9, 5, (True, False), 0.25), (61, 13, 17, (True, False), 0.25), (65, 17, 2, (False, False), 0.2)]:
         g = xs.make_grid(ni, nj, nk, land_frac=land, reentrant_x=topo[0], reentrant_y=topo[1])
         d = xs.make_state(g, umax=0.3)
         Ku, Au, src0 = meke_fields(g)
@@ -185,7 +185,7 @@ def test_gpu_parity(name):
     from mom6_amd.tracer_advect import DeviceGrid
     kw = VARIANTS[name]
     for (ni, nj, nk, topo, land) in [(70, 21, 3, (True, False), 0.25), (44, 40, 2, (True, True), 0.3), (10, 8, 8, (False, False), 0.2),
-                                     (300, 9, 2, (True, False), 0.25)]:
+                                     (300, 9, 2, (True, False), 0.25), (61, 13, 17, (True, False), 0.25), (65, 17, 2, (False, False), 0.2)]:
         g = xs.make_grid(ni, nj, nk, land_frac=land, reentrant_x=topo[0], reentrant_y=topo[1])
         d = xs.make_state(g, umax=0.3)
         hu_c = np.ascontiguousarray(0.5 * (d["h"][:, :, :-1] + d["h"][:, :, 1:]) * 1.01)
