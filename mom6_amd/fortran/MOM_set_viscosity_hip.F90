@@ -281,7 +281,7 @@ subroutine set_visc_init(Time, G, GV, US, param_file, diag, visc, CS, restart_CS
   call get_param(param_file, mdl, "KV", Kv_background, "The background kinematic viscosity in the interior.", units="m2 s-1", &
                  fail_if_missing=.true., scale=US%m_to_Z**2*US%T_to_s)
   call get_param(param_file, mdl, "KV_BBL_MIN", CS%st%Kv_BBL_min, "The minimum viscosities in the bottom boundary layer.", &
-                 units="m2 s-1", default=US%Z_to_m**2*US%s_to_T*Kv_background, scale=US%m_to_Z**2*US%T_to_s)
+                 units="m2 s-1", default=US%Z_to_m**2*US%s_to_T*Kv_background, scale=GV%m2_s_to_HZ_T)      ! [H Z T-1] (:3081-3083)
   call get_param(param_file, mdl, "CORRECT_BBL_BOUNDS", flag, &
                  "If true, uses the correct bounds on the BBL thickness and viscosity so that the bottom layer feels the intended drag.", &
                  default=.false.)

@@ -297,14 +297,14 @@ subroutine vertvisc_init(MIS, Time, G, GV, US, param_file, diag, ADp, dirs, ntru
   if (CS%st%direct_stress /= 0 .and. CS%st%Hmix_stress <= 0.0) call MOM_error(FATAL, "vertvisc_init: " // &
        "HMIX_STRESS must be set to a positive value if DIRECT_STRESS is true.")
   call get_param(param_file, mdl, "KV", CS%st%Kv, "The background kinematic viscosity in the interior.", units="m2 s-1", &
-                 fail_if_missing=.true., scale=US%m_to_Z**2*US%T_to_s)
+                 fail_if_missing=.true., scale=GV%m2_s_to_HZ_T)      ! [H Z T-1] (:2606)
   CS%st%Kvml_invZ2 = 0.0
   if (GV%nkml < 1) call get_param(param_file, mdl, "KV_ML_INVZ2", CS%st%Kvml_invZ2, &      ! (:2672-2690)
                  "An extra kinematic viscosity in a mixed layer of thickness HMIX_FIXED, with the actual viscosity scaling as 1/(z*HMIX_FIXED)^2.", &
-                 units="m2 s-1", default=0.0, scale=US%m_to_Z**2*US%T_to_s)
+                 units="m2 s-1", default=0.0, scale=GV%m2_s_to_HZ_T)      ! (:2682-2689)
   call get_param(param_file, mdl, "KV_EXTRA_BBL", CS%st%Kv_extra_bbl, &
                  "An extra kinematic viscosity in the benthic boundary layer. KV_EXTRA_BBL is not used if BOTTOMDRAGLAW is true.", &
-                 units="m2 s-1", default=0.0, scale=US%m_to_Z**2*US%T_to_s)
+                 units="m2 s-1", default=0.0, scale=GV%m2_s_to_HZ_T)      ! (:2696)
   call get_param(param_file, mdl, "HBBL", CS%st%Hbbl, "The thickness of a bottom boundary layer with a viscosity increased by KV_EXTRA_BBL.", &
                  units="m", fail_if_missing=.true., scale=US%m_to_Z)
   call get_param(param_file, mdl, "MAXVEL", CS%st%maxvel, "The maximum velocity allowed before the velocity components are truncated.", &

@@ -35,8 +35,8 @@ class Grid:
     metrics: dict = field(default_factory=dict)
 
     def __post_init__(self):
-        # GV%H_subroundoff = 1e-20 * max(GV%Angstrom_H, GV%m_to_H*1e-17)   (MOM_verticalGrid.F90:165)
-        self.H_subroundoff = 1.0e-20 * max(self.Angstrom_H, 1.0e-17)
+        # GV%H_subroundoff = 1e-20 * max(GV%Angstrom_H, GV%m_to_H*1e-17)   (MOM_verticalGrid.F90:215; GV%m_to_H is Z_to_H, US%Z_to_m = 1)
+        self.H_subroundoff = 1.0e-20 * max(self.Angstrom_H, self.Z_to_H * 1.0e-17)
         self.dZ_subroundoff = 1.0e-20 * max(self.Angstrom_H * self.H_to_Z, 1.0e-17)
         # hor_index_type: local numbering with isd = 1 (MOM_hor_index.F90)
         self.isd, self.jsd = 1, 1

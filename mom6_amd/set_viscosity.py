@@ -56,7 +56,7 @@ class set_visc_CS:
         st.cdrag, st.drag_bg_vel, st.dz_bbl = float(CDRAG), float(DRAG_BG_VEL), float(HBBL)
         st.Hbbl = float(HBBL) * g.Z_to_H      # :3127
         st.BBL_thick_min = float(BBL_THICK_MIN)
-        st.Kv_BBL_min = float(KV if KV_BBL_MIN is None else KV_BBL_MIN)
+        st.Kv_BBL_min = float(KV if KV_BBL_MIN is None else KV_BBL_MIN) * g.Z_to_H      # scale=GV%m2_s_to_HZ_T [H Z T-1] :3081-3083
         st.BBL_thick_max = 6.378e6            # G%Rad_Earth_L * US%L_to_Z
         st.H_to_RZ = g.Rho0 * g.H_to_Z
         st.bottomdraglaw, st.linear_drag, st.BBL_use_EOS = int(bool(BOTTOMDRAGLAW)), int(bool(LINEAR_DRAG)), int(bool(BBL_USE_EOS))

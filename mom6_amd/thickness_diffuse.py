@@ -35,7 +35,12 @@ class thickness_diffuse_CS:
         st = self.st = _abi.ThicknessDiffuseCS()
         st.thickness_diffuse = int(bool(THICKNESSDIFFUSE))
         st.Khth, st.Khth_Min, st.Khth_Max, st.max_Khth_CFL, st.slope_max = float(KHTH), float(KHTH_MIN), float(KHTH_MAX), float(KHTH_MAX_CFL), float(KHTH_SLOPE_MAX)
-        st.kappa_smooth, st.KHTH_Slope_Cff, st.KhTh_fac = float(KD_SMOOTH), float(KHTH_SLOPE_CFF), float(MEKE_KHTH_FAC)
+        # KD_SMOOTH: scale=GV%m2_s_to_HZ_T [H Z T-1] (:2304).  G = None gives a record to look at, with KD_SMOOTH as it came: without the
+        # grid's Z_to_H it cannot be converted, and thickness_diffuse refuses such a record
+        g = G.grid if isinstance(G, DeviceGrid) else G
+        self.has_grid = g is not None
+        Z_to_H = g.Z_to_H if self.has_grid else 1.0
+        st.kappa_smooth, st.KHTH_Slope_Cff, st.KhTh_fac = float(KD_SMOOTH) * Z_to_H, float(KHTH_SLOPE_CFF), float(MEKE_KHTH_FAC)
         st.use_GM_work_bug, st.nkml = int(bool(USE_GM_WORK_BUG)), int(NKML)
         # KHTH_USE_FGNV_STREAMFUNCTION (:2305-2337): the streamfunction of Ferrari et al. (2010); N2_floor = (FGNV_STRAT_FLOOR * OMEGA)**2
         st.use_FGNV_streamfn, st.FGNV_scale = int(bool(KHTH_USE_FGNV_STREAMFUNCTION)), float(FGNV_FILTER_SCALE)
@@ -67,7 +72,8 @@ class thickness_diffuse_CS:
 
 
 def thickness_diffuse_init(G: DeviceGrid, **params) -> thickness_diffuse_CS:
-    """thickness_diffuse_init(Time, G, GV, US, param_file, diag, CDp, CS) -- :2169."""
+    """thickness_diffuse_init(Time, G, GV, US, param_file, diag, CDp, CS) -- :2169.  G: the DeviceGrid (or Grid) whose Z_to_H converts
+    KD_SMOOTH; with G = None the record can be inspected but thickness_diffuse does not take it."""
     return thickness_diffuse_CS(G, **params)
 
 
@@ -79,6 +85,8 @@ def thickness_diffuse(h, uhtr, vhtr, tv, dt, G: DeviceGrid, MEKE, VarMix, CDp, C
     read by MEKE_GEOMETRIC too) -- its presence is VarMix%use_variable_mixing; CDp: None or a dict with uhGM, vhGM (outputs)."""
     if CS is None or not CS.st.initialized:
         raise Mom6HipError("MOM_thickness_diffuse: Module must be initialized before it is used.")
+    if not getattr(CS, "has_grid", True):
+        raise Mom6HipError("thickness_diffuse: thickness_diffuse_init was given no grid, so KD_SMOOTH is not in thickness units (GV%m2_s_to_HZ_T)")
     if STOCH is not None:
         raise Mom6HipError("thickness_diffuse (HIP): stochastic parameterizations are not supported on this path")
     T, S, EOS = tv if tv is not None else (None, None, None)

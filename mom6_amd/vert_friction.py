@@ -70,12 +70,13 @@ class vertvisc_CS:
             if n not in _abi.VERTVISC_UNSUPPORTED:
                 raise Mom6HipError(f"vertvisc_init: unknown parameter {n}")
             st.unsupported[_abi.VERTVISC_UNSUPPORTED.index(n)] = int(val)
-        st.Kv, st.Hbbl, st.Hmix = float(KV), float(HBBL), float(HMIX_FIXED)
+        # KV, KV_ML_INVZ2, KV_EXTRA_BBL: scale=GV%m2_s_to_HZ_T [H Z T-1] (:2606, :2682-2689, :2696); HBBL, HMIX_FIXED: [Z] (:2586, :2718)
+        st.Kv, st.Hbbl, st.Hmix = float(KV) * g.Z_to_H, float(HBBL), float(HMIX_FIXED)
         st.bottomdraglaw, st.harmonic_visc, st.direct_stress = int(bool(BOTTOMDRAGLAW)), int(bool(HARMONIC_VISC)), int(bool(DIRECT_STRESS))
         st.harm_BL_val = float(HARMONIC_BL_SCALE)
         # HMIX_STRESS defaults to HMIX_FIXED (:2591-2593), in thickness units
         st.Hmix_stress = float(HMIX_STRESS if HMIX_STRESS is not None else HMIX_FIXED) * g.Z_to_H
-        st.Kvml_invZ2, st.Kv_extra_bbl = float(KV_ML_INVZ2), float(KV_EXTRA_BBL)
+        st.Kvml_invZ2, st.Kv_extra_bbl = float(KV_ML_INVZ2) * g.Z_to_H, float(KV_EXTRA_BBL) * g.Z_to_H
         st.maxvel, st.CFL_based_trunc, st.CFL_trunc = float(MAXVEL), int(bool(CFL_BASED_TRUNCATIONS)), float(CFL_TRUNCATE)
         st.vel_underflow, st.answer_date = float(VEL_UNDERFLOW), int(VERT_FRICTION_ANSWER_DATE)
         st.H_to_RZ = g.Rho0 * g.H_to_Z      # GV%H_to_RZ (Boussinesq, unscaled units)

@@ -792,11 +792,12 @@ def vertvisc_cs(grid, Kv, Hbbl, Hmix=0.0, bottomdraglaw=True, harmonic_visc=Fals
     """mom6hip_vertvisc_cs_t with numpy arrays behind a_u, a_v, h_u, h_v (kept on the struct as ._arrs)."""
     cs = _abi.VertviscCS()
     cs.dynamic_viscous_ML, cs.nkml, cs.vonKar = int(dynamic_viscous_ML), int(nkml), float(vonKar)
-    cs.Kv, cs.Hbbl, cs.Hmix = Kv, Hbbl, Hmix
+    # KV, KV_ML_INVZ2 and KV_EXTRA_BBL are read with scale=GV%m2_s_to_HZ_T [H Z T-1] (MOM_vert_friction.F90:2606, :2682-2689, :2696); HBBL, HMIX_FIXED in Z
+    cs.Kv, cs.Hbbl, cs.Hmix = Kv * grid.Z_to_H, Hbbl, Hmix
     cs.bottomdraglaw, cs.harmonic_visc, cs.direct_stress = int(bottomdraglaw), int(harmonic_visc), int(direct_stress)
     cs.harm_BL_val = harm_BL_val
     cs.Hmix_stress = (Hmix_stress if Hmix_stress is not None else Hmix) * grid.Z_to_H
-    cs.Kvml_invZ2, cs.Kv_extra_bbl = Kvml_invZ2, Kv_extra_bbl
+    cs.Kvml_invZ2, cs.Kv_extra_bbl = Kvml_invZ2 * grid.Z_to_H, Kv_extra_bbl * grid.Z_to_H
     cs.maxvel, cs.CFL_based_trunc, cs.CFL_trunc, cs.vel_underflow, cs.answer_date = maxvel, int(CFL_based_trunc), CFL_trunc, vel_underflow, answer_date
     cs.H_to_RZ = grid.Rho0 * grid.H_to_Z
     cs._arrs = {}
@@ -859,7 +860,8 @@ def set_visc_cs(grid, Hbbl, Kv, cdrag=0.003, drag_bg_vel=0.0, BBL_thick_min=0.0,
     cs.Channel_drag, cs.c_Smag, cs.Chan_drag_max_vol, cs.concave_trigonometric_L, cs.Z_ref = (int(Channel_drag), c_Smag, Chan_drag_max_vol,
                                                                                             int(concave_trigonometric_L), Z_ref)
     cs.cdrag, cs.drag_bg_vel, cs.dz_bbl, cs.Hbbl = cdrag, drag_bg_vel, Hbbl, Hbbl * grid.Z_to_H
-    cs.BBL_thick_min, cs.Kv_BBL_min, cs.BBL_thick_max = BBL_thick_min, (Kv if Kv_BBL_min is None else Kv_BBL_min), 6.378e6
+    # KV_BBL_MIN is read with scale=GV%m2_s_to_HZ_T [H Z T-1] (MOM_set_viscosity.F90:3081-3083)
+    cs.BBL_thick_min, cs.Kv_BBL_min, cs.BBL_thick_max = BBL_thick_min, (Kv if Kv_BBL_min is None else Kv_BBL_min) * grid.Z_to_H, 6.378e6
     cs.H_to_RZ = grid.Rho0 * grid.H_to_Z
     cs.bottomdraglaw, cs.linear_drag, cs.BBL_use_EOS = int(bottomdraglaw), int(linear_drag), int(BBL_use_EOS)
     cs.correct_BBL_bounds, cs.body_force_drag, cs.RiNo_mix, cs.initialized = int(correct_BBL_bounds), int(body_force_drag), int(RiNo_mix), 1
@@ -1012,7 +1014,8 @@ def thickness_diffuse_cs(grid, Khth=0.0, Khth_Min=0.0, Khth_Max=0.0, max_Khth_CF
     _abi.THICKNESS_DIFFUSE_UNSUPPORTED set to True"""
     cs = _abi.ThicknessDiffuseCS()
     cs.Khth, cs.Khth_Min, cs.Khth_Max, cs.max_Khth_CFL, cs.slope_max = Khth, Khth_Min, Khth_Max, max_Khth_CFL, slope_max
-    cs.kappa_smooth, cs.KHTH_Slope_Cff, cs.KhTh_fac = kappa_smooth, KHTH_Slope_Cff, KhTh_fac
+    # KD_SMOOTH is read with scale=GV%m2_s_to_HZ_T [H Z T-1] (MOM_thickness_diffuse.F90:2304)
+    cs.kappa_smooth, cs.KHTH_Slope_Cff, cs.KhTh_fac = kappa_smooth * grid.Z_to_H, KHTH_Slope_Cff, KhTh_fac
     cs.thickness_diffuse, cs.use_GM_work_bug, cs.nkml, cs.use_variable_mixing = int(thickness_diffuse), int(use_GM_work_bug), int(nkml), int(use_variable_mixing)
     cs.use_FGNV_streamfn, cs.FGNV_scale = int(use_FGNV_streamfn), float(FGNV_scale)
     cs.N2_floor = (FGNV_strat_floor * omega) ** 2 if use_FGNV_streamfn else 0.0      # :2337

@@ -34,11 +34,15 @@ def bits_equal(a, b):
 
 
 def barotropic_case(orc, ni=22, nj=18, nk=4, seed=5, reentrant_x=True, reentrant_y=False, land_frac=0.2, dt=900.0,
-                    use_bt_cont=True, hvel_scheme=None, rest=False, nstep_min=13, **cs_kw):
+                    use_bt_cont=True, hvel_scheme=None, rest=False, nstep_min=13, H_power=0, **cs_kw):
     """Inputs of btstep built the way step_MOM_dyn_split_RK2 builds them (src/core/MOM_dynamics_split_RK2.F90:586-658),
-    with the oracle's continuity / PressureForce providing BT_cont, uh0/vh0, pbce and eta_PF."""
+    with the oracle's continuity / PressureForce providing BT_cont, uh0/vh0, pbce and eta_PF.  H_power = c: the same ocean with
+    thicknesses in units of 2^-c of the thickness unit (tests/rescaling.py)."""
     g = synth.make_grid(ni, nj, nk, land_frac=land_frac, seed=seed + 200, reentrant_x=reentrant_x, reentrant_y=reentrant_y)
     d = {k: v.numpy() for k, v in synth.make_dynamics_state(g, seed=seed, umax=0.0 if rest else 0.3).items()}
+    if H_power:
+        from rescaling import rescale_grid
+        g = rescale_grid(g, H_power); d["h"] = d["h"] * 2.0 ** H_power
     rng = np.random.default_rng(seed)
     kk = (np.arange(nk) + 0.5) / nk
     vru = np.clip(1.0 - 0.8 * kk[:, None, None] ** 2 + 0 * d["u"], 0.0, 1.0) * (g.mask2dCu[None] > 0)
@@ -68,7 +72,7 @@ def barotropic_case(orc, ni=22, nj=18, nk=4, seed=5, reentrant_x=True, reentrant
         orc.btcalc(g, cs, d["h"])
     eta = np.ascontiguousarray(d["h"].sum(0) - g.bathyT * g.Z_to_H)
     if not rest:   # the free surface the barotropic solver carries drifts a little from the layer sum
-        eta = eta + 0.01 * rng.standard_normal(eta.shape) * g.mask2dT
+        eta = eta + (0.01 * g.Z_to_H) * rng.standard_normal(eta.shape) * g.mask2dT
     orc.halo_update(g, eta, _abi.POS_H)
     orc.bt_mass_source(g, cs, d["h"], eta, True)
     orc.set_dtbt(g, cs, pbce=pbce, bt_cont=bt if use_bt_cont else None, gtot_est=g.g_Earth, SSH_add=10.0)

@@ -113,7 +113,7 @@ def thickness_diffuse(g, h, uhtr, vhtr, T, S, eos, dt, Khth=0.0, Khth_Min=0.0, K
         rsum[k + 1] = avail[0] if k == 0 else rsum[k] + avail[k]
         pres[k + 1] = pres[k] + gH * h[k]
     if use_EOS:
-        Tf, Sf = _vert_fill_TS(g, h, T, S, kappa_smooth * dt)
+        Tf, Sf = _vert_fill_TS(g, h, T, S, (kappa_smooth * g.Z_to_H) * dt)      # KD_SMOOTH in m2 s-1; CS%kappa_smooth [H Z T-1] :2304
 
     I_slope_max2 = 1.0 / (slope_max * slope_max)
     h_neglect = g.H_subroundoff; h_neglect2 = h_neglect * h_neglect

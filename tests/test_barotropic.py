@@ -191,13 +191,18 @@ BT_CASES = [
 @pytest.mark.parametrize("space", ["device", "host"])
 @pytest.mark.parametrize("kw", BT_CASES, ids=[",".join(f"{k}={v}" for k, v in c.items()) or "default" for c in BT_CASES])
 def test_btstep_matches_oracle_bitwise(kw, space):
+    if space == "host" and kw not in (dict(), dict(use_bt_cont=False)):
+        pytest.skip("the staged path is covered on two cases")
+    btstep_against_the_oracle(kw, "cuda" if space == "device" else "cpu")
+
+
+def btstep_against_the_oracle(kw, device="cuda"):
+    """barotropic_init, btcalc, bt_mass_source, set_dtbt and btstep of the library on barotropic_case(**kw), each against the oracle, bit for
+    bit; returns the grid, the case and the results of both (the oracle's dict and the library's, with nstep, dtbt and dtbt_max)"""
     import torch
     from mom6_amd.barotropic import barotropic_init, bt_mass_source, btcalc, btstep, set_dtbt
     from mom6_amd.continuity import BT_cont_type
     from mom6_amd.tracer_advect import DeviceGrid
-    if space == "host" and kw not in (dict(), dict(use_bt_cont=False)):
-        pytest.skip("the staged path is covered on two cases")
-    device = "cuda" if space == "device" else "cpu"
     g, cs_o, case, keep = barotropic_case(orc, **kw)
     dg = DeviceGrid(g)
     T = lambda a: _to(device, a)
@@ -245,7 +250,10 @@ def test_btstep_matches_oracle_bitwise(kw, space):
         a, b = _np(out[n]), ref[n]
         assert bits_equal(a, b), (n, float(np.abs(a - b).max()), int((a != b).sum()))
     assert bits_equal(_np(CS.ubtav), keep["cs_arrs"]["ubtav"]) and bits_equal(_np(CS.vbtav), keep["cs_arrs"]["vbtav"])
+    got = dict({n: _np(a) for n, a in out.items()}, ubtav=_np(CS.ubtav), vbtav=_np(CS.vbtav), frhatu=_np(CS.frhatu), frhatv=_np(CS.frhatv),
+               eta_cor=_np(CS.eta_cor), nstep=int(CS.st.nstep_last), dtbt=float(CS.st.dtbt), dtbt_max=float(CS.st.dtbt_max))
     dg.close()
+    return g, case, ref, got
 
 
 @pytest.mark.gpu

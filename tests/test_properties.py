@@ -137,10 +137,11 @@ VV = dict(Kv=1.0e-4, Hbbl=10.0, Hmix=20.0, Kvml_invZ2=1.0e-2)
 HV = dict(biharmonic=1, Smagorinsky_Ah=1, Smag_bi_const=0.06, Ah_vel_scale=0.01)
 
 
-def oracle_steps(g, d, taux, tauy, dt, nsteps, viscous, rk2b=False):
-    kw = dict(rk2b=rk2b)
+def oracle_steps(g, d, taux, tauy, dt, nsteps, viscous, rk2b=False, Kv_bbl=1.0e-3, **dyn_kw):
+    """Kv_bbl: visc%Kv_bbl_u, _v [H Z T-1 ~> m2 s-1]; dyn_kw: further arguments of orc.DynState (bound_coriolis = False is hip_steps' choice)"""
+    kw = dict(dyn_kw, rk2b=rk2b)
     if viscous:
-        visc = orc.vertvisc_type(Kv_bbl_u=1.0e-3 * g.mask2dCu, Kv_bbl_v=1.0e-3 * g.mask2dCv, bbl_thick_u=5.0 * g.mask2dCu,
+        visc = orc.vertvisc_type(Kv_bbl_u=Kv_bbl * g.mask2dCu, Kv_bbl_v=Kv_bbl * g.mask2dCv, bbl_thick_u=5.0 * g.mask2dCu,
                                  bbl_thick_v=5.0 * g.mask2dCv)
         kw.update(vertvisc=orc.vertvisc_cs(g, **VV), visc=visc, hor_visc=orc.hor_visc_cs(g, dt, **HV))
     st = orc.DynState(g, d["u"], d["v"], d["h"], d["T"], d["S"], dt, **kw)
@@ -169,7 +170,7 @@ def test_oracle_rk2_step_turns_with_the_grid(viscous, rk2b):
     assert same(interior(g, uhb, _abi.POS_U), interior(g, a.uhtr, _abi.POS_U)), "uhtr"
 
 
-def hip_steps(g, d, taux, tauy, dt, nsteps, viscous, restart_after=None, rk2b=False):
+def hip_steps(g, d, taux, tauy, dt, nsteps, viscous, restart_after=None, rk2b=False, Kv_bbl=1.0e-3):
     """nsteps of the library's step; restart_after = n: after step n the restart fields are saved and a NEW control
     structure is initialised from them (and from u, v, h as they are) for the remaining steps"""
     import torch
@@ -191,7 +192,7 @@ def hip_steps(g, d, taux, tauy, dt, nsteps, viscous, restart_after=None, rk2b=Fa
     if viscous:
         kw.update(vertvisc=dict(KV=VV["Kv"], HBBL=VV["Hbbl"], HMIX_FIXED=VV["Hmix"], KV_ML_INVZ2=VV["Kvml_invZ2"]),
                   hor_visc=dict(BIHARMONIC=True, SMAGORINSKY_AH=True, SMAG_BI_CONST=HV["Smag_bi_const"], AH_VEL_SCALE=HV["Ah_vel_scale"]))
-        visc = vertvisc_type(Kv_bbl_u=T(1.0e-3 * g.mask2dCu), Kv_bbl_v=T(1.0e-3 * g.mask2dCv), bbl_thick_u=T(5.0 * g.mask2dCu),
+        visc = vertvisc_type(Kv_bbl_u=T(Kv_bbl * g.mask2dCu), Kv_bbl_v=T(Kv_bbl * g.mask2dCv), bbl_thick_u=T(5.0 * g.mask2dCu),
                              bbl_thick_v=T(5.0 * g.mask2dCv))
     CS = initialize_dyn_split_RK2(u, v, h, uh, vh, dt, dg, **kw)
     tx, ty = T(taux), T(tauy)
