@@ -326,6 +326,29 @@ int mom6hip_advect_tracer_obc(mom6hip_ctx_t *ctx, const double *h_end, const dou
                               int32_t x_first_in, double *vol_prev, int32_t max_iter_in, int32_t update_vol_prev, double *uhr_out,
                               double *vhr_out, const struct mom6hip_obc *obc, int32_t memspace, mom6hip_advect_stats_t *stats);
 
+/* The flux diagnostics of one registered tracer (tracer_type, src/tracer/MOM_tracer_registry.F90): NULL = not associated.  The arrays are
+ * in the memory space of the call and whole (data domain): ad_x, df_x at u points and ad_y, df_y at v points with nk layers, advection_xy
+ * at h points with nk layers, ad2d_x, df2d_x at u points and ad2d_y, df2d_y at v points, one plane. */
+typedef struct mom6hip_tracer_flux_diag {
+  double *ad_x, *ad_y;            /* advective fluxes [conc H L2 T-1], MOM_tracer_advect.F90:665-667, :1070-1076 */
+  double *ad2d_x, *ad2d_y;        /* their sums over the layers, in layer order, pass after pass (:689-698, :1078-1084) */
+  double *advection_xy;           /* the convergence of the advective fluxes [conc H T-1] (:671-676, :1051-1054) */
+  double *df_x, *df_y;            /* along-layer diffusive fluxes [conc H L2 T-1], MOM_tracer_hor_diff.F90:576-583 */
+  double *df2d_x, *df2d_y;        /* their sums over the layers, in layer order, iteration after iteration (:584-591) */
+} mom6hip_tracer_flux_diag_t;
+
+/* mom6hip_advect_tracer_obc with the advective flux diagnostics: diag is NULL (the call above) or an array of ntr records, of which the
+ * five advective pointers are read.  The arrays asked for are zeroed whole (:193-197) and then take, iteration after iteration and pass
+ * after pass, what the reference adds, bit for bit (Idt = 1.0/dt; (flux*Idt) for the fluxes, ((fx - fxm)*Idt)*IareaT for the convergence;
+ * the 2-D sums by a march over k = 1..nz of one thread a face, never by atomics).  The do_i flag of a cell outside the range of a pass,
+ * which the reference reads without having set it, counts as false.  The diagnostics are provided by the marching kernels only: on the
+ * general path (a tracer registry on an OBC segment, MOM6HIP_ADV_GENERIC=1) a diagnostic asked for is refused by name. */
+int mom6hip_advect_tracer_diag(mom6hip_ctx_t *ctx, const double *h_end, const double *uhtr, const double *vhtr, double dt,
+                               const mom6hip_tracer_advect_cs_t *cs, double *const *tr, const double *conc_underflow, int32_t ntr,
+                               int32_t x_first_in, double *vol_prev, int32_t max_iter_in, int32_t update_vol_prev, double *uhr_out,
+                               double *vhr_out, const struct mom6hip_obc *obc, int32_t memspace, mom6hip_advect_stats_t *stats,
+                               const mom6hip_tracer_flux_diag_t *diag);
+
 /* Per-kernel device time of the last advect_tracer call, from HIP events on the context's stream:
  * ms_x / ms_y are the summed durations of the advect_x / advect_y kernels, n_x / n_y their launch
  * counts, ms_total the whole call.  Only filled when timing was enabled before the call. */
@@ -1040,7 +1063,9 @@ int mom6hip_set_viscous_ml(mom6hip_ctx_t *ctx, const mom6hip_set_visc_cs_t *cs, 
  * the interface coefficients of the neutral and the boundary-diffusion branch decay with fields->ebt_struct (:428-462, :503-518), with
  * FULL_DEPTH_KHTR_MIN (full_depth_khtr_min) floored by KHTR_MIN in the boundary-diffusion branch.  The along-layer and the epipycnal
  * branch read level 1 only: they accept the switch and ignore the field.  Refused: the switch with fields->ebt_struct NULL.
- * Not provided (refused by name, any nonzero `unsupported`): offline khdt arrays, the df_x / df_y flux diagnostics.
+ * The df_x / df_y / df2d_x / df2d_y flux diagnostics of the along-layer branch come through mom6hip_tracer_hordiff_diag.
+ * Not provided (refused by name, any nonzero `unsupported`): offline khdt arrays; the flux diagnostics asked for by unsupported[7], which
+ * carries no arrays (the epipycnal contribution to df2d_x / df2d_y, :1405 and :1526, is not provided either).
  */
 typedef struct mom6hip_tracer_hor_diff_cs {
   double KhTr;             /* KHTR [L2 T-1] (0: tracer_hordiff returns at once unless use_variable_mixing) */
@@ -1090,6 +1115,14 @@ int mom6hip_tracer_hordiff(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_
 int mom6hip_tracer_hordiff_varmix(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hordiff_fields_t *fields,
                                   const double *h, double dt, double *const *tr, const double *conc_underflow, int32_t ntr,
                                   int32_t memspace, mom6hip_hordiff_stats_t *stats);
+/* the same with the diffusive flux diagnostics: diag is NULL (the call above) or an array of ntr records, of which the four diffusive
+ * pointers are read.  The arrays asked for are zeroed over the ranges of :389-406 and take, in each of the num_itts iterations of the
+ * along-layer loop, Coef_x(I,j,1) * (t(i,j,k) - t(i+1,j,k)) * Idt with the tracer of before the iteration's update, and the y twin
+ * (:576-591), bit for bit; df2d_x / df2d_y are summed over k in order by one thread a face.  Returned early (:197), the call leaves them
+ * as they are, as the reference does. */
+int mom6hip_tracer_hordiff_diag(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hordiff_fields_t *fields,
+                                const double *h, double dt, double *const *tr, const double *conc_underflow, int32_t ntr,
+                                int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_tracer_flux_diag_t *diag);
 
 /*
  * neutral_diffusion_CS, src/tracer/MOM_neutral_diffusion.F90:38-120, as set by neutral_diffusion_init (:138-330).
@@ -1156,6 +1189,12 @@ int mom6hip_tracer_hordiff_epipycnal(mom6hip_ctx_t *ctx, const mom6hip_tracer_ho
                                      const mom6hip_hordiff_fields_t *fields, const double *h, const mom6hip_eos_t *eos, double dt,
                                      double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S,
                                      int32_t memspace, mom6hip_hordiff_stats_t *stats);
+/* the same with the diffusive flux diagnostics (diag as mom6hip_tracer_hordiff_diag takes it): df_x / df_y stay zero in the layers the
+ * along-layer loop leaves out (:544-550); df2d_x / df2d_y, which would need the epipycnal contribution (:1405, :1526), are refused by name */
+int mom6hip_tracer_hordiff_epipycnal_diag(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_epipycnal_cs_t *epi,
+                                          const mom6hip_hordiff_fields_t *fields, const double *h, const mom6hip_eos_t *eos, double dt,
+                                          double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S,
+                                          int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_tracer_flux_diag_t *diag);
 
 /*
  * hbd_CS, src/tracer/MOM_hor_bnd_diffusion.F90:40-70, as set by hor_bnd_diffusion_init (:79-158): horizontal boundary diffusion of the

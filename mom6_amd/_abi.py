@@ -242,6 +242,16 @@ class Obc(C.Structure):
                [(n, C.c_void_p) for n in ("rx_oblique_u", "ry_oblique_u", "cff_normal_u", "rx_oblique_v", "ry_oblique_v", "cff_normal_v")]
 
 
+# the flux diagnostics of a tracer (mom6hip_tracer_flux_diag_t): advection, then diffusion
+ADV_DIAGS = ("ad_x", "ad_y", "ad2d_x", "ad2d_y", "advection_xy")
+DIFF_DIAGS = ("df_x", "df_y", "df2d_x", "df2d_y")
+
+
+class TracerFluxDiag(C.Structure):
+    """mom6hip_tracer_flux_diag_t (include/mom6hip.h): null = not associated."""
+    _fields_ = [(n, C.c_void_p) for n in ADV_DIAGS + DIFF_DIAGS]
+
+
 class HorDiffStats(C.Structure):
     _fields_ = [("num_itts", C.c_int32), ("halo_updates", C.c_int32), ("max_CFL", C.c_double)]
 

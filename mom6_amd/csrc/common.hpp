@@ -172,6 +172,7 @@ struct mom6hip_ctx {
   m6::DevBuf adv_gen;           // the general path of advect_tracer: the transports and fluxes of a pass, the segments' tables (tracer_advect.hip)
   m6::DevBuf adv_obc[64];       // device copies of the segments' tracer reservoirs handed over as host arrays
   int adv_obc_n = 0;
+  m6::DevBuf adv_diag;          // the flux diagnostics of advect_tracer: the scratch of a pass, and the staged copies of the arrays asked for
   m6::HostTable tables[m6::TABLE_COUNT];      // cached device copies of short host tables (m6::HostTable)
   uint64_t xfer[4] = {0, 0, 0, 0};            // calls and bytes of mom6hip_sync_to_device, then of mom6hip_sync_to_host / stage_to_host
   m6::DevBuf ale_sub;           // sub-cell structure of the two grids, handed from ale_sub_cells_kernel to the remap kernel

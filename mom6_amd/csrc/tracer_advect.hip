@@ -22,12 +22,14 @@
 //    scheme) into template arguments.  mom6hip_advect_tracer_obc is a sequence of phases on one AdvCall: adv_check, adv_stage_in,
 //    adv_work_space, adv_registries, adv_setup; an iteration adv_group_pass, adv_sweep (adv_pass x and y), adv_count_remaining; adv_outputs.
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
 
 #include "common.hpp"
+#include "flux_diag_march.hpp"
 
 namespace m6 { int halo_update_field(mom6hip_ctx_t *ctx, double *f, int pos, int nk); }      // (group_pass etc.: common.hpp)
 
@@ -52,6 +54,19 @@ struct AdvArgs {
   int write_mass;            // 1: this tracer group also updates hprev / uhr|vhr / domore flags
   int any_cu;                // any conc_underflow > 0 in this group
 };
+
+// The flux diagnostics of a tracer group, handed to the DIAG instantiations of the marching kernels only (AdvNoDiag otherwise, so that the
+// instantiations without diagnostics are what they were).  A null pointer: that tracer did not ask.
+//   face[m]  scratch, face-shaped: the pass's flux of tracer m through every face it worked on, times Idt (zeroed before the pass)
+//   axy[m]   Tr(m)%advection_xy, updated in place by the lane that owns the cell (:671-676, :1051-1054)
+//   doi      scratch, h-shaped: do_i of the pass (zeroed before the pass: a cell outside its range counts as false)
+struct AdvDiag {
+  double *face[MAXG], *axy[MAXG];
+  int *doi;
+  double Idt;
+};
+struct AdvNoDiag {};
+template <bool DIAG> using AdvDiagArg = std::conditional_t<DIAG, AdvDiag, AdvNoDiag>;
 
 // Orders this wave's LDS traffic: the hardware executes one wave's LDS instructions in order, so
 // all that is needed is to stop the compiler from moving loads/stores across this point.
@@ -328,8 +343,8 @@ __global__ void adv_vflags_prep_kernel(m6::GridDev g, const int *in, int *out, c
 
 // ---------------------------------------------------------------------------------------------
 // advect_x: one wavefront per (j,k) row.
-template <int NT, int SCHEME>
-__global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
+template <int NT, int SCHEME, bool DIAG = false>
+__global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p, AdvDiagArg<DIAG> d) {
   const m6::GridDev &g = p.g;
   __shared__ double s_T[4][NT][XTW];
   __shared__ double s_h[4][XTW];
@@ -430,6 +445,10 @@ __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
         face_slopes<SCHEME>(sT[m][Pu - 2], Tm, Tc, Tp, sT[m][Pu + 2], mk_m, mk_c, mk_p, sm, sc, sp);
         flux[m] = face_flux<SCHEME>(Tp, Tc, Tm, sm, sc, sp, mk_c, hh, CFL);
       }
+      if constexpr (DIAG) {      // flux_x(I,j,m)*Idt of :665-667 / :694-696; flux_diag_march_kernel (adv_diag_apply) adds it where do_i allows
+#pragma unroll
+        for (int m = 0; m < NT; m++) if (d.face[m]) d.face[m][rowU + (i - g.isd)] = flux[m] * d.Idt;
+      }
     }
     // west-face values from the neighbouring lane (lane 0: carried from the previous chunk)
     double hh_w = __shfl_up(hh, 1);
@@ -460,6 +479,17 @@ __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
         double t_new = cell_tracer(do_i && Ihnew > 0.0, t_old, hlst, flux[m], fl_w[m], Ihnew);
         if (underflows(t_new, p.cu[m])) t_new = 0.0;
         if (changed(t_new, t_old)) p.tr[m][rowH + (i - g.isd)] = t_new;
+      }
+      if constexpr (DIAG) {
+        if (d.doi) d.doi[rowH + (i - g.isd)] = do_i ? 1 : 0;
+        if (do_i) {      // :671-676
+          const double IaT = g.IareaT[row2H + (i - g.isd)];
+#pragma unroll
+          for (int m = 0; m < NT; m++) if (d.axy[m]) {
+            double *a = &d.axy[m][rowH + (i - g.isd)];
+            *a = *a - ((flux[m] - fl_w[m]) * d.Idt) * IaT;
+          }
+        }
       }
     }
     wave_sync();
@@ -500,11 +530,11 @@ __global__ __launch_bounds__(256) void adv_x_kernel(AdvArgs p) {
 constexpr int YSEG_MAX = 8;      // the waves a block may have: sizes the kernel's LDS and its launch bounds
 constexpr int YSEG = 4;          // the waves a block is given: measured best on MI355X (8: one block per CU; 1-2: too few waves)
 
-template <int NT, int SCHEME>
+template <int NT, int SCHEME, bool DIAG = false>
 #ifndef ADVY_OCC
 #define ADVY_OCC 2      // waves per SIMD the register allocation aims at (tools/build_variant.sh for experiments)
 #endif
-__global__ __launch_bounds__(64 * YSEG_MAX, ADVY_OCC) void adv_y_kernel(AdvArgs p, int seglen) {
+__global__ __launch_bounds__(64 * YSEG_MAX, ADVY_OCC) void adv_y_kernel(AdvArgs p, int seglen, AdvDiagArg<DIAG> d) {
   const m6::GridDev &g = p.g;
   constexpr int NHR = (SCHEME == CW) ? 3 : 2;        // foreign T rows needed above the segment's last face
   __shared__ double s_halo[YSEG_MAX][NHR * NT + 2][64];
@@ -641,6 +671,12 @@ __global__ __launch_bounds__(64 * YSEG_MAX, ADVY_OCC) void adv_y_kernel(AdvArgs 
       const double v_new = remaining_transport(v_c, hh, g.vh_neglect[col2V + (long)sH * (J - g.jsd)]);
       if (changed(v_new, v_c)) p.vhr[colV + (long)sH * (J - g.jsd)] = v_new;
     }
+    if constexpr (DIAG) {      // flux_y(i,m,J)*Idt of :1072-1074 / :1080-1082 (zero on a face that is not active)
+      if (own && lane_ok) {
+#pragma unroll
+        for (int m = 0; m < NT; m++) if (d.face[m]) d.face[m][colV + (long)sH * (J - g.jsd)] = flux[m] * d.Idt;
+      }
+    }
     // cell j = J, :1028-1059, and underflow :1062-1066
     if (own && J >= p.js && lane_ok) {
       double h_new, hlst, Ihnew;
@@ -652,6 +688,17 @@ __global__ __launch_bounds__(64 * YSEG_MAX, ADVY_OCC) void adv_y_kernel(AdvArgs 
         double t_new = cell_tracer(do_i, t_old, hlst, flux[m], fl_prev[m], Ihnew);
         if (underflows(t_new, p.cu[m])) t_new = 0.0;
         if (changed(t_new, t_old)) p.tr[m][colH + (long)sH * (j - g.jsd)] = t_new;
+      }
+      if constexpr (DIAG) {
+        if (d.doi) d.doi[colH + (long)sH * (j - g.jsd)] = do_i ? 1 : 0;
+        if (do_i) {      // :1051-1054
+          const double IaT = g.IareaT[col2H + (long)sH * (j - g.jsd)];
+#pragma unroll
+          for (int m = 0; m < NT; m++) if (d.axy[m]) {
+            double *a = &d.axy[m][colH + (long)sH * (j - g.jsd)];
+            *a = *a - ((flux[m] - fl_prev[m]) * d.Idt) * IaT;
+          }
+        }
       }
     }
     // advance the rings
@@ -899,6 +946,11 @@ struct AdvCall {
   // the general path: the segments with a registry by direction, their registries, the scratch of a pass (hh, then the fluxes)
   std::vector<GenSeg> gsegs[2]; std::vector<GenReg> gregs;
   GenSeg *d_gsegs[2]; GenReg *d_gregs; double *gen_scratch; size_t fmax_el; int *gen_flags;
+  // the flux diagnostics (null: none asked for): the caller's records; per tracer the device views of its five arrays (ad_x, ad_y, ad2d_x,
+  // ad2d_y, advection_xy) and its slot of face scratch (-1: no face diagnostic); the scratch of a pass (the slots, then doi)
+  const mom6hip_tracer_flux_diag_t *diag; double Idt;
+  std::vector<std::array<double *, 5>> d_diag; std::vector<int> diag_slot;
+  double *diag_face; int *diag_doi; size_t diag_scratch_bytes; int diag_nslots;
   // the iteration (:203): its number, the range still valid, what the statistics report
   int itt, isv, iev, jsv, jev, halo_updates, remaining;
   Timer *t_k; mom6hip_advect_timing_t tm;
@@ -1029,6 +1081,74 @@ int adv_registries(AdvCall &c) {
   return 0;
 }
 
+// The flux diagnostics asked for: device views of the arrays (staged copies with host arrays), zeroed whole (:193-197), and the scratch of
+// a pass.  One block of the context holds the scratch and then the staged copies.
+int adv_diag_setup(AdvCall &c) {
+  if (!c.diag) return 0;
+  const m6::GridDev &g = c.g; hipStream_t s = c.s;
+  const size_t b2U = c.bU / c.nz, b2V = c.bV / c.nz, bytes[5] = {c.bU, c.bV, b2U, b2V, c.bH};
+  c.d_diag.assign(c.ntr, std::array<double *, 5>{});
+  c.diag_slot.assign(c.ntr, -1);
+  bool any = false;
+  size_t staged = 0;
+  for (int m = 0; m < c.ntr; m++) {
+    const mom6hip_tracer_flux_diag_t &D = c.diag[m];
+    double *const src[5] = {D.ad_x, D.ad_y, D.ad2d_x, D.ad2d_y, D.advection_xy};
+    for (int q = 0; q < 5; q++) if (src[q]) { any = true; staged += bytes[q]; }
+    if (D.ad_x || D.ad_y || D.ad2d_x || D.ad2d_y) c.diag_slot[m] = c.diag_nslots++;
+  }
+  if (!any) { c.diag = nullptr; return 0; }
+  M6_REQUIRE(!c.generic, "advect_tracer: the flux diagnostics (ad_x, ad_y, ad2d_x, ad2d_y, advection_xy) are not provided on the general "
+                         "path (a tracer registry on an OBC segment, or MOM6HIP_ADV_GENERIC=1)");
+  const bool host = (c.memspace == MOM6HIP_MEM_HOST);
+  c.diag_scratch_bytes = (size_t)c.diag_nslots * c.fmax_el * 8 + (c.diag_nslots ? (size_t)g.nh3() * sizeof(int) : 0);
+  if (c.ctx->adv_diag.reserve(c.diag_scratch_bytes + (host ? staged : 0) + 64)) return 1;
+  char *q = (char *)c.ctx->adv_diag.p;
+  c.diag_face = (double *)q; c.diag_doi = c.diag_nslots ? (int *)(q + (size_t)c.diag_nslots * c.fmax_el * 8) : nullptr;
+  q += (c.diag_scratch_bytes + 7) & ~(size_t)7;
+  for (int m = 0; m < c.ntr; m++) {
+    const mom6hip_tracer_flux_diag_t &D = c.diag[m];
+    double *const src[5] = {D.ad_x, D.ad_y, D.ad2d_x, D.ad2d_y, D.advection_xy};
+    for (int n = 0; n < 5; n++) if (src[n]) {
+      c.d_diag[m][n] = host ? (double *)q : src[n];
+      if (host) q += bytes[n];
+      M6_HIP(hipMemsetAsync(c.d_diag[m][n], 0, bytes[n], s));
+    }
+  }
+  return 0;
+}
+
+// the diagnostics of tracer group grp for the pass in direction dir; false: none of its tracers asked for any
+bool group_diag(const AdvCall &c, int grp, int dir, AdvDiag &d) {
+  bool any = false;
+  d.Idt = c.Idt; d.doi = nullptr;
+  for (int m = 0; m < MAXG; m++) {
+    const int t = grp * MAXG + m;
+    d.face[m] = nullptr; d.axy[m] = nullptr;
+    if (t >= c.ntr) continue;
+    if (c.diag_slot[t] >= 0 && (c.d_diag[t][dir] || c.d_diag[t][2 + dir])) {
+      d.face[m] = c.diag_face + (size_t)c.diag_slot[t] * c.fmax_el; d.doi = c.diag_doi; any = true;
+    }
+    if (c.d_diag[t][4]) { d.axy[m] = c.d_diag[t][4]; any = true; }
+  }
+  return any;
+}
+
+// after the marching kernels of a pass: the march over k (flux_diag_march.hpp) of every tracer that has a face diagnostic of this direction:
+// ad_x | ad_y take the pass's flux*Idt where do_i holds on either side of the face (:665-667, :1070-1076), ad2d_x | ad2d_y the same in the
+// order of k (:689-698, :1078-1084).  A row or layer the pass did not work on has zeros in the scratch and in doi.
+int adv_diag_apply(AdvCall &c, int dir, int is, int ie, int js, int je) {
+  m6::FluxDiagMarch a; a.g = c.g; a.doi = c.diag_doi; a.skip0 = a.skip1 = 0; a.zero = 0; a.is = is; a.ie = ie; a.js = js; a.je = je; a.n = 0;
+  for (int t = 0; t < c.ntr; t++) {
+    if (c.diag_slot[t] < 0 || !(c.d_diag[t][dir] || c.d_diag[t][2 + dir])) continue;
+    a.face[a.n] = c.diag_face + (size_t)c.diag_slot[t] * c.fmax_el; a.a3[a.n] = c.d_diag[t][dir]; a.a2[a.n] = c.d_diag[t][2 + dir];
+    if (++a.n == m6::FLUX_DIAG_MAXD) { m6::flux_diag_march(dir, a, c.s); a.n = 0; }
+  }
+  if (a.n) m6::flux_diag_march(dir, a, c.s);
+  M6_HIP(hipGetLastError());
+  return 0;
+}
+
 // uhr, vhr, hprev :152-178
 int adv_setup(AdvCall &c) {
   const m6::GridDev &g = c.g;
@@ -1104,18 +1224,28 @@ int adv_pass(AdvCall &c, int dir, int is, int ie, int js, int je) {
       grid = dim3((ie - is + 1 + 63) / 64, nz); block = dim3(64 * nseg);
     }
     const int ngroups = (c.ntr + MAXG - 1) / MAXG;
+    if (c.diag && c.diag_scratch_bytes) M6_HIP(hipMemsetAsync(c.diag_face, 0, c.diag_scratch_bytes, s));
     for (int grp = 0; grp < ngroups; grp++) {
       AdvArgs a; const int n = group_args(c, grp, ngroups, a);
       a.is = is; a.ie = ie; a.js = js; a.je = je;
       a.domore_v_in = c.domore_v; a.domore_v_out = dir ? c.domore_v2 : c.domore_v;
+      AdvDiag d;
+      const bool diag = c.diag && group_diag(c, grp, dir, d);
       with_group(n, scheme, [&](auto nt, auto sc) {
         constexpr int NT = decltype(nt)::value, SCHEME = decltype(sc)::value;
-        if (dir) hipLaunchKernelGGL((adv_y_kernel<NT, SCHEME>), grid, block, 0, s, a, seglen);
-        else     hipLaunchKernelGGL((adv_x_kernel<NT, SCHEME>), grid, block, 0, s, a);
+        if (diag) {
+          if (dir) hipLaunchKernelGGL((adv_y_kernel<NT, SCHEME, true>), grid, block, 0, s, a, seglen, d);
+          else     hipLaunchKernelGGL((adv_x_kernel<NT, SCHEME, true>), grid, block, 0, s, a, d);
+        } else {
+          if (dir) hipLaunchKernelGGL((adv_y_kernel<NT, SCHEME>), grid, block, 0, s, a, seglen, AdvNoDiag{});
+          else     hipLaunchKernelGGL((adv_x_kernel<NT, SCHEME>), grid, block, 0, s, a, AdvNoDiag{});
+        }
       });
       M6_HIP(hipGetLastError());
       n_pass++;
     }
+    if (c.diag && c.diag_nslots)
+      if (int rc = adv_diag_apply(c, dir, is, ie, js, je)) return rc;
   }
   if (dir) std::swap(c.domore_v, c.domore_v2);
   const double ms = c.t_k->stop();
@@ -1201,6 +1331,13 @@ int adv_outputs(AdvCall &c, mom6hip_advect_stats_t *stats) {
   if (c.uhr_out) M6_HIP(hipMemcpyAsync(c.uhr_out, c.uhr, c.bU, kind, s));
   if (c.vhr_out) M6_HIP(hipMemcpyAsync(c.vhr_out, c.vhr, c.bV, kind, s));
   if (c.vol_prev && c.update_vol_prev) M6_HIP(hipMemcpyAsync(c.vol_prev, c.hprev, c.bH, kind, s));
+  if (c.diag && c.memspace == MOM6HIP_MEM_HOST) {
+    const size_t bytes[5] = {c.bU, c.bV, c.bU / c.nz, c.bV / c.nz, c.bH};
+    for (int m = 0; m < c.ntr; m++) {
+      double *const dst[5] = {c.diag[m].ad_x, c.diag[m].ad_y, c.diag[m].ad2d_x, c.diag[m].ad2d_y, c.diag[m].advection_xy};
+      for (int q = 0; q < 5; q++) if (dst[q]) M6_HIP(hipMemcpyAsync(dst[q], c.d_diag[m][q], bytes[q], kind, s));
+    }
+  }
   if (stats || c.memspace == MOM6HIP_MEM_HOST)      // (the copies are complete behind it)
     if (int rc = adv_count_remaining(c, false)) return rc;
   if (stats) { stats->iterations = c.itt; stats->halo_updates = c.halo_updates; stats->domore_remaining = c.remaining; }
@@ -1229,6 +1366,16 @@ extern "C" int mom6hip_advect_tracer_obc(mom6hip_ctx_t *ctx, const double *h_end
                                          const mom6hip_tracer_advect_cs_t *cs, double *const *tr, const double *conc_underflow, int32_t ntr,
                                          int32_t x_first_in, double *vol_prev, int32_t max_iter_in, int32_t update_vol_prev, double *uhr_out,
                                          double *vhr_out, const mom6hip_obc_t *obc, int32_t memspace, mom6hip_advect_stats_t *stats) {
+  return mom6hip_advect_tracer_diag(ctx, h_end, uhtr, vhtr, dt, cs, tr, conc_underflow, ntr, x_first_in, vol_prev, max_iter_in, update_vol_prev,
+                                    uhr_out, vhr_out, obc, memspace, stats, nullptr);
+}
+
+// the same with the flux diagnostics of the tracers (diag: null, or a record a tracer; adv_diag_setup, group_diag, adv_diag_apply)
+extern "C" int mom6hip_advect_tracer_diag(mom6hip_ctx_t *ctx, const double *h_end, const double *uhtr, const double *vhtr, double dt,
+                                          const mom6hip_tracer_advect_cs_t *cs, double *const *tr, const double *conc_underflow, int32_t ntr,
+                                          int32_t x_first_in, double *vol_prev, int32_t max_iter_in, int32_t update_vol_prev, double *uhr_out,
+                                          double *vhr_out, const mom6hip_obc_t *obc, int32_t memspace, mom6hip_advect_stats_t *stats,
+                                          const mom6hip_tracer_flux_diag_t *diag) {
   M6_REQUIRE(ctx != nullptr, "advect_tracer: null context (tracer_advect_init must be called before advect_tracer)");
   if (stats) memset(stats, 0, sizeof(*stats));
   M6_REQUIRE(ntr >= 0, "advect_tracer: ntr < 0");
@@ -1237,6 +1384,7 @@ extern "C" int mom6hip_advect_tracer_obc(mom6hip_ctx_t *ctx, const double *h_end
   c.ctx = ctx; c.cs = cs; c.obc = obc; c.s = ctx->stream; c.g = ctx->g;
   c.h_end = h_end; c.uhtr = uhtr; c.vhtr = vhtr; c.conc_underflow = conc_underflow; c.tr = tr; c.vol_prev = vol_prev;
   c.uhr_out = uhr_out; c.vhr_out = vhr_out; c.ntr = ntr; c.memspace = memspace; c.update_vol_prev = update_vol_prev;
+  c.diag = diag; c.Idt = 1.0 / dt;      // :133
   int rc = 0;
   if ((rc = adv_check(c, dt, x_first_in, max_iter_in))) return rc;
 
@@ -1246,6 +1394,7 @@ extern "C" int mom6hip_advect_tracer_obc(mom6hip_ctx_t *ctx, const double *h_end
   if ((rc = adv_stage_in(c))) return rc;
   if ((rc = adv_work_space(c))) return rc;
   if ((rc = adv_registries(c))) return rc;
+  if ((rc = adv_diag_setup(c))) return rc;                   // :190-198
   if ((rc = adv_setup(c))) return rc;                        // :152-178
 
   c.isv = c.is; c.iev = c.ie; c.jsv = c.js; c.jev = c.je;

@@ -13,8 +13,11 @@
 // Algorithmic traffic per iteration: read h, read and write every tracer = 8 + 16 ntr B per cell (the work copy doubles the
 // tracer part).
 #include <cfloat>
+#include <array>
 #include <cmath>
+#include <type_traits>
 
+#include "flux_diag_march.hpp"
 #include "hordiff_call.hpp"
 
 namespace {
@@ -40,6 +43,13 @@ struct HDArgs {
   int nkml, nkmb;          // CS%Diffuse_ML_interior: GV%nkml, GV%nk_rho_varies (nkmb = 0: not in use)
   double ML_KhTr_scale;
 };
+
+// The diffusive flux diagnostics, handed to the DIAG instantiation of hd_step_kernel only (HDNoDiag otherwise: the instantiation without
+// diagnostics is what it was): device tables of ntr pointers to face-shaped scratch (null: the tracer did not ask), which take
+// Coef_x(I,j,1) * (t(i,j,k) - t(i+1,j,k)) * Idt of the iteration, and the y twin (:576-591); flux_diag_march_kernel adds them up.
+struct HDDiag { double *const *sx, *const *sy; double Idt; };
+struct HDNoDiag {};
+template <bool DIAG> using HDDiagArg = std::conditional_t<DIAG, HDDiag, HDNoDiag>;
 
 // the scale of layer k (0-based) :543-550; false: the layer is left out of the along-layer diffusion
 __device__ __forceinline__ bool hd_layer_scale(const HDArgs &A, int k, double &scale) {
@@ -105,8 +115,10 @@ __global__ __launch_bounds__(256) void hd_cfl_kernel(HDArgs A) {
   if ((threadIdx.x & 63) == 0) atomicMax(A.cfl_bits, b);
 }
 
-// thread (i, j, k) over the compute domain
-__global__ __launch_bounds__(256) void hd_step_kernel(HDArgs A) {
+// thread (i, j, k) over the compute domain.  DIAG: the thread stores the values of its east and north face, and of the west and south
+// face where it is the first cell of its row or column (I = IscB..IecB, j = js..je; J = JscB..JecB, i = is..ie).
+template <bool DIAG = false>
+__global__ __launch_bounds__(256) void hd_step_kernel(HDArgs A, HDDiagArg<DIAG> d) {
   const m6::GridDev &g = A.g;
   const int i = g.isc + blockIdx.x * blockDim.x + threadIdx.x, j = g.jsc + blockIdx.y, k = blockIdx.z;
   if (i > g.iec) return;
@@ -129,6 +141,17 @@ __global__ __launch_bounds__(256) void hd_step_kernel(HDArgs A) {
     const double dTr = Ihdxdy * ((CxW * (t[g.h2(i - 1, j)] - tc) - CxE * (tc - t[g.h2(i + 1, j)])) +
                                  (CyS * (t[g.h2(i, j - 1)] - tc) - CyN * (tc - t[g.h2(i, j + 1)])));
     A.work[m][kH + g.h2(i, j)] = tc + dTr;
+    if constexpr (DIAG) {
+      const long uH = (long)(g.nih + 1) * g.njh * k, vH = (long)g.nih * (g.njh + 1) * k;
+      if (d.sx[m]) {
+        d.sx[m][uH + g.u2(I, j)] = (CxE * (tc - t[g.h2(i + 1, j)])) * d.Idt;
+        if (i == g.isc) d.sx[m][uH + g.u2(I - 1, j)] = (CxW * (t[g.h2(i - 1, j)] - tc)) * d.Idt;
+      }
+      if (d.sy[m]) {
+        d.sy[m][vH + g.v2(i, J)] = (CyN * (tc - t[g.h2(i, j + 1)])) * d.Idt;
+        if (j == g.jsc) d.sy[m][vH + g.v2(i, J - 1)] = (CyS * (t[g.h2(i, j - 1)] - tc)) * d.Idt;
+      }
+    }
   }
 }
 
@@ -159,6 +182,7 @@ struct HordiffOpts {
   const double *p_surf;
   int32_t idx_T, idx_S;
   bool takes_epi, takes_hbd;
+  const mom6hip_tracer_flux_diag_t *diag = nullptr;      // the diffusive flux diagnostics of the tracers (null: none)
 };
 
 static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hordiff_fields_t *F, const double *h, double dt,
@@ -229,14 +253,39 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
     d_tr[m] = st.inout(tr[m], bH);
     d_work[m] = use_neutral ? nullptr : (double *)st.scratch(bH);
   }
+  // the diffusive flux diagnostics: device views of the arrays asked for (a host array is copied in and out: the call writes a range of
+  // it, :389-406) and a face-shaped scratch each for the x and the y increments of a tracer that has any
+  const size_t bU3 = bU2 * g.nk, bV3 = bV2 * g.nk;
+  std::vector<std::array<double *, 4>> d_df(ntr, std::array<double *, 4>{});      // df_x, df_y, df2d_x, df2d_y
+  std::vector<double *> d_sx(ntr, nullptr), d_sy(ntr, nullptr);
+  bool any_df = false;
+  if (o.diag) for (int m = 0; m < ntr; m++) {
+    const mom6hip_tracer_flux_diag_t &D = o.diag[m];
+    M6_REQUIRE(!(epi && (D.df2d_x || D.df2d_y)), "tracer_hordiff: df2d_x / df2d_y together with DIFFUSE_ML_TO_INTERIOR (the epipycnal "
+               "contribution to the diffusive flux diagnostics) is not provided by libmom6hip");
+    d_df[m] = {st.inout(D.df_x, bU3), st.inout(D.df_y, bV3), st.inout(D.df2d_x, bU2), st.inout(D.df2d_y, bV2)};
+    any_df = any_df || D.df_x || D.df_y || D.df2d_x || D.df2d_y;
+  }
+  if (any_df && !use_neutral) {      // (one block: the pool of the context is short)
+    size_t nx = 0, ny = 0;
+    for (int m = 0; m < ntr; m++) { nx += (d_df[m][0] || d_df[m][2]) ? 1 : 0; ny += (d_df[m][1] || d_df[m][3]) ? 1 : 0; }
+    char *q = (char *)st.scratch(nx * bU3 + ny * bV3);
+    M6_REQUIRE(q != nullptr, "tracer_hordiff: out of device memory for the flux diagnostics");
+    for (int m = 0; m < ntr; m++) {
+      if (d_df[m][0] || d_df[m][2]) { d_sx[m] = (double *)q; q += bU3; }
+      if (d_df[m][1] || d_df[m][3]) { d_sy[m] = (double *)q; q += bV3; }
+    }
+  }
   A.khdt_x = (double *)st.scratch(bU2); A.khdt_y = (double *)st.scratch(bV2);
-  char *tab = (char *)st.scratch(2 * 24 * sizeof(double *) + 24 * sizeof(double) + 16);
+  char *tab = (char *)st.scratch(4 * 24 * sizeof(double *) + 24 * sizeof(double) + 16);
   M6_REQUIRE(!st.failed() && tab, "tracer_hordiff: staging failed");
-  double **t_tr = (double **)tab, **t_work = t_tr + 24;
-  double *t_cu = (double *)(t_work + 24);
+  double **t_tr = (double **)tab, **t_work = t_tr + 24, **t_sx = t_work + 24, **t_sy = t_sx + 24;
+  double *t_cu = (double *)(t_sy + 24);
   A.cfl_bits = (unsigned long long *)(t_cu + 24);
   M6_HIP(hipMemcpyAsync(t_tr, d_tr.data(), ntr * sizeof(double *), hipMemcpyHostToDevice, s));
   M6_HIP(hipMemcpyAsync(t_work, d_work.data(), ntr * sizeof(double *), hipMemcpyHostToDevice, s));
+  M6_HIP(hipMemcpyAsync(t_sx, d_sx.data(), ntr * sizeof(double *), hipMemcpyHostToDevice, s));
+  M6_HIP(hipMemcpyAsync(t_sy, d_sy.data(), ntr * sizeof(double *), hipMemcpyHostToDevice, s));
   std::vector<double> cu(ntr, 0.0);
   bool any_cu = false;
   if (conc_underflow) for (int m = 0; m < ntr; m++) { cu[m] = conc_underflow[m]; any_cu = any_cu || cu[m] > 0.0; }
@@ -279,6 +328,21 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   const double *d_ps = (use_neutral && o.p_surf) ? st.in(o.p_surf, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
   M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
   const m6::HordiffCall call = {ctx, st, A.h, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, o.idx_T, o.idx_S, o.eos, d_ps, d_hml, d_ebt, &halo_updates};
+  // the march over k of the diagnostics asked for, in direction dir: zero = 1 sets them to zero over their ranges (:389-406), zero = 0 adds
+  // what hd_step_kernel has just left in the scratch, but for the layers the along-layer loop leaves out (:544-550)
+  auto df_march = [&](int dir, int zero) {
+    m6::FluxDiagMarch a; a.g = g; a.doi = nullptr; a.zero = zero; a.is = g.isc; a.ie = g.iec; a.js = g.jsc; a.je = g.jec; a.n = 0;
+    a.skip0 = a.skip1 = 0;
+    if (A.nkmb > 0) { a.skip0 = (A.ML_KhTr_scale <= 0.0) ? 0 : A.nkml; a.skip1 = A.nkmb > a.skip0 ? A.nkmb : a.skip0; }
+    for (int m = 0; m < ntr; m++) {
+      if (!(d_df[m][dir] || d_df[m][2 + dir])) continue;
+      a.face[a.n] = dir ? d_sy[m] : d_sx[m]; a.a3[a.n] = d_df[m][dir]; a.a2[a.n] = d_df[m][2 + dir];
+      if (++a.n == m6::FLUX_DIAG_MAXD) { m6::flux_diag_march(dir, a, s); a.n = 0; }
+    }
+    if (a.n) m6::flux_diag_march(dir, a, s);
+  };
+  if (any_df) { df_march(0, 1); df_march(1, 1); }
+  const HDDiag hd_diag = {t_sx, t_sy, 1.0 / dt};      // Idt :204
   if (use_hbd) {      // :408-472, before the neutral or the along-layer branch
     if (int rc = m6::hbd_branch(call, hbd, cs->KhTr_min, cs->full_depth_khtr_min != 0)) return rc;
   }
@@ -288,7 +352,11 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   for (int itt = 1; itt <= num_itts; itt++) {      // :540-614
     if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;
     halo_updates++;
-    hipLaunchKernelGGL(hd_step_kernel, dim3((ni + 255) / 256, nj, g.nk), dim3(256), 0, s, A);
+    if (any_df) {
+      hipLaunchKernelGGL(hd_step_kernel<true>, dim3((ni + 255) / 256, nj, g.nk), dim3(256), 0, s, A, hd_diag);
+      df_march(0, 0); df_march(1, 0);
+    } else
+      hipLaunchKernelGGL(hd_step_kernel<false>, dim3((ni + 255) / 256, nj, g.nk), dim3(256), 0, s, A, HDNoDiag{});
     hipLaunchKernelGGL(hd_commit_kernel, dim3((ni + 255) / 256, nj, g.nk), dim3(256), 0, s, A);
   }
   M6_HIP(hipGetLastError());
@@ -314,6 +382,16 @@ extern "C" int mom6hip_tracer_hordiff_varmix(mom6hip_ctx_t *ctx, const mom6hip_t
   return mom6hip_tracer_hordiff_neutral(ctx, cs, nullptr, F, h, nullptr, nullptr, dt, tr, conc_underflow, ntr, 0, 0, memspace, stats);
 }
 
+extern "C" int mom6hip_tracer_hordiff_diag(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hordiff_fields_t *F,
+                                           const double *h, double dt, double *const *tr, const double *conc_underflow, int32_t ntr,
+                                           int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_tracer_flux_diag_t *diag) {
+  M6_REQUIRE(cs != nullptr, "tracer_hordiff: null argument");
+  M6_REQUIRE(!cs->unsupported[0], "tracer_hordiff: USE_NEUTRAL_DIFFUSION is not provided by this entry point (mom6hip_tracer_hordiff_neutral takes it)");
+  HordiffOpts o = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, false, false};
+  o.diag = diag;
+  return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
+}
+
 extern "C" int mom6hip_tracer_hordiff_neutral(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_neutral_diffusion_cs_t *nd,
                                               const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, const double *p_surf,
                                               double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
@@ -327,6 +405,17 @@ extern "C" int mom6hip_tracer_hordiff_epipycnal(mom6hip_ctx_t *ctx, const mom6hi
                                                 double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S,
                                                 int32_t memspace, mom6hip_hordiff_stats_t *stats) {
   const HordiffOpts o = {nullptr, epi, nullptr, nullptr, eos, nullptr, idx_T, idx_S, true, false};
+  return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
+}
+
+// DIFFUSE_ML_TO_INTERIOR with df_x / df_y: the layers :544-550 leave out stay zero; df2d_x / df2d_y would need the epipycnal contribution
+// (:1405, :1526) and are refused by name in hordiff_impl
+extern "C" int mom6hip_tracer_hordiff_epipycnal_diag(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_epipycnal_cs_t *epi,
+                                                     const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, double dt,
+                                                     double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S,
+                                                     int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_tracer_flux_diag_t *diag) {
+  HordiffOpts o = {nullptr, epi, nullptr, nullptr, eos, nullptr, idx_T, idx_S, true, false};
+  o.diag = diag;
   return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
 }
 

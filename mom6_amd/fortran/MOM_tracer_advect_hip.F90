@@ -12,7 +12,7 @@ module MOM_tracer_advect
 use, intrinsic :: iso_c_binding
 use mom6hip_c_api
 use mom6hip_MOM_glue,    only : mom6hip_context_create, mom6hip_read_topology
-use mom6hip_MOM_glue,     only : mom6hip_read_resident, mom6hip_resident, mom6hip_mirror, mom6hip_obc_to_c
+use mom6hip_MOM_glue,     only : mom6hip_read_resident, mom6hip_resident, mom6hip_mirror, mom6hip_obc_to_c, mom6hip_mirror_to_host
 use MOM_cpu_clock,       only : cpu_clock_id, cpu_clock_begin, cpu_clock_end, CLOCK_MODULE
 use MOM_diag_mediator,   only : diag_ctrl, time_type
 use MOM_error_handler,   only : MOM_error, FATAL, WARNING
@@ -77,7 +77,11 @@ subroutine advect_tracer(h_end, uhtr, vhtr, OBC, dt, G, GV, US, CS, Reg, x_first
   type(mom6hip_obc_segment_t), allocatable, target :: csegs(:)
   type(mom6hip_obc_segment_tracer_t), allocatable, target :: ctrs(:)
   type(c_ptr) :: p_obc
-  logical :: registries
+  logical :: registries, any_diag
+  type(mom6hip_tracer_flux_diag_t), allocatable, target :: dg(:)      ! the device (resident) or host (staged) arrays of the call
+  type(c_ptr), allocatable :: dgh(:,:)                                ! the host arrays behind them
+  type(c_ptr) :: p_dg
+  integer :: q
 
   if (.not. associated(CS)) call MOM_error(FATAL, "MOM_tracer_advect: "// &
        "tracer_advect_init must be called before advect_tracer.")
@@ -105,14 +109,21 @@ subroutine advect_tracer(h_end, uhtr, vhtr, OBC, dt, G, GV, US, CS, Reg, x_first
   if (.not. c_associated(CS%ctx)) call mom6hip_context_create(G, GV, CS%ctx, CS%reentrant)
 
   allocate(tr(Reg%ntr), cu(Reg%ntr))
+  ! the advective flux diagnostics where they are associated (:193-197, :665-698, :1051-1084): host arrays in staged mode, write-only
+  ! mirrors with GPU_RESIDENT_DYNAMICS (the call zeroes them whole), copied back before this routine returns
+  allocate(dg(Reg%ntr), dgh(5,Reg%ntr)) ; any_diag = .false. ; dgh(:,:) = c_null_ptr
   do m=1,Reg%ntr
-    if (associated(Reg%Tr(m)%ad_x) .or. associated(Reg%Tr(m)%ad_y) .or. &
-        associated(Reg%Tr(m)%advection_xy) .or. associated(Reg%Tr(m)%ad2d_x) .or. &
-        associated(Reg%Tr(m)%ad2d_y)) call MOM_error(FATAL, "MOM_tracer_advect (HIP): "// &
-        "advective flux diagnostics are not provided by the GPU tracer advection.")
+    if (associated(Reg%Tr(m)%ad_x)) dgh(1,m) = c_loc(Reg%Tr(m)%ad_x)
+    if (associated(Reg%Tr(m)%ad_y)) dgh(2,m) = c_loc(Reg%Tr(m)%ad_y)
+    if (associated(Reg%Tr(m)%ad2d_x)) dgh(3,m) = c_loc(Reg%Tr(m)%ad2d_x)
+    if (associated(Reg%Tr(m)%ad2d_y)) dgh(4,m) = c_loc(Reg%Tr(m)%ad2d_y)
+    if (associated(Reg%Tr(m)%advection_xy)) dgh(5,m) = c_loc(Reg%Tr(m)%advection_xy)
+    do q=1,5 ; if (c_associated(dgh(q,m))) any_diag = .true. ; enddo
+    dg(m)%ad_x = dgh(1,m) ; dg(m)%ad_y = dgh(2,m) ; dg(m)%ad2d_x = dgh(3,m) ; dg(m)%ad2d_y = dgh(4,m) ; dg(m)%advection_xy = dgh(5,m)
     tr(m) = c_loc(Reg%Tr(m)%t)
     cu(m) = Reg%Tr(m)%conc_underflow
   enddo
+  p_dg = c_null_ptr ; if (any_diag) p_dg = c_loc(dg)
 
   ccs%dt = CS%dt ; ccs%use_huynh_stencil_bug = merge(1, 0, CS%useHuynhStencilBug)
   ccs%scheme = MOM6HIP_ADV_PLM
@@ -131,16 +142,27 @@ subroutine advect_tracer(h_end, uhtr, vhtr, OBC, dt, G, GV, US, CS, Reg, x_first
     if (present(vol_prev)) p_vol = mom6hip_mirror(CS%ctx, p_vol, int(size(h_end), c_int64_t), .true., .true.)
     if (present(uhr_out)) p_uhr = mom6hip_mirror(CS%ctx, p_uhr, int(size(uhtr), c_int64_t), .false., .true.)
     if (present(vhr_out)) p_vhr = mom6hip_mirror(CS%ctx, p_vhr, int(size(vhtr), c_int64_t), .false., .true.)
-    rc = mom6hip_advect_tracer(CS%ctx, mom6hip_mirror(CS%ctx, c_loc(h_end), int(size(h_end), c_int64_t), .true., .false.), &
+    if (any_diag) then ; do m=1,Reg%ntr
+      if (c_associated(dgh(1,m))) dg(m)%ad_x = mom6hip_mirror(CS%ctx, dgh(1,m), int(size(uhtr), c_int64_t), .false., .true.)
+      if (c_associated(dgh(2,m))) dg(m)%ad_y = mom6hip_mirror(CS%ctx, dgh(2,m), int(size(vhtr), c_int64_t), .false., .true.)
+      if (c_associated(dgh(3,m))) dg(m)%ad2d_x = mom6hip_mirror(CS%ctx, dgh(3,m), int(size(uhtr(:,:,1)), c_int64_t), .false., .true.)
+      if (c_associated(dgh(4,m))) dg(m)%ad2d_y = mom6hip_mirror(CS%ctx, dgh(4,m), int(size(vhtr(:,:,1)), c_int64_t), .false., .true.)
+      if (c_associated(dgh(5,m))) dg(m)%advection_xy = mom6hip_mirror(CS%ctx, dgh(5,m), int(size(h_end), c_int64_t), .false., .true.)
+    enddo ; endif
+    rc = mom6hip_advect_tracer_diag(CS%ctx, mom6hip_mirror(CS%ctx, c_loc(h_end), int(size(h_end), c_int64_t), .true., .false.), &
                                mom6hip_mirror(CS%ctx, c_loc(uhtr), int(size(uhtr), c_int64_t), .true., .false.), &
                                mom6hip_mirror(CS%ctx, c_loc(vhtr), int(size(vhtr), c_int64_t), .true., .false.), dt, ccs, tr, c_loc(cu), &
-                               int(Reg%ntr, c_int32_t), xf, p_vol, mi, uv, p_uhr, p_vhr, MOM6HIP_MEM_DEVICE, stats)
+                               int(Reg%ntr, c_int32_t), xf, p_vol, mi, uv, p_uhr, p_vhr, c_null_ptr, MOM6HIP_MEM_DEVICE, stats, p_dg)
   else
-    rc = mom6hip_advect_tracer_obc(CS%ctx, c_loc(h_end), c_loc(uhtr), c_loc(vhtr), dt, ccs, tr, c_loc(cu), &
-                                   int(Reg%ntr, c_int32_t), xf, p_vol, mi, uv, p_uhr, p_vhr, p_obc, &
-                                   MOM6HIP_MEM_HOST, stats)
+    rc = mom6hip_advect_tracer_diag(CS%ctx, c_loc(h_end), c_loc(uhtr), c_loc(vhtr), dt, ccs, tr, c_loc(cu), &
+                                    int(Reg%ntr, c_int32_t), xf, p_vol, mi, uv, p_uhr, p_vhr, p_obc, &
+                                    MOM6HIP_MEM_HOST, stats, p_dg)
   endif
   if (rc /= 0) call MOM_error(FATAL, "MOM_tracer_advect (HIP): "//mom6hip_error_string())
+  ! post_tracer_transport_diagnostics reads the arrays on the host right after this call
+  if (any_diag .and. mom6hip_resident()) then
+    do m=1,Reg%ntr ; do q=1,5 ; if (c_associated(dgh(q,m))) call mom6hip_mirror_to_host(CS%ctx, dgh(q,m)) ; enddo ; enddo
+  endif
 
   call cpu_clock_end(id_clock_advect)
 end subroutine advect_tracer

@@ -13,8 +13,10 @@
 !! of a layered run (tracer_epipycnal_ML_diff :700, ML_KHTR_SCALE, HOR_DIFF_ANSWER_DATE, HOR_DIFF_LIMIT_BUG;
 !! mom6hip_tracer_hordiff_epipycnal).  NDIFF_CONTINUOUS = False goes to mom6hip_tracer_hordiff_neutral_discontinuous with the
 !! parameters of MOM_neutral_diffusion.F90:219-277 (the interface takes hbd and ndd by reference: CS%hbd stands in where HBD is off).
-!! NDIFF_USE_UNMASKED_TRANSPORT_BUG, offline khdt arrays and the
-!! df_x / df_y flux diagnostics stop with a FATAL error.
+!! The df_x / df_y / df2d_x / df2d_y flux diagnostics of the along-layer loop are passed on where they are associated
+!! (mom6hip_tracer_hordiff_diag, mom6hip_tracer_hordiff_epipycnal_diag; left zeroed with USE_NEUTRAL_DIFFUSION).
+!! NDIFF_USE_UNMASKED_TRANSPORT_BUG, offline khdt arrays, the hbd_* diagnostics, df2d_x / df2d_y with DIFFUSE_ML_TO_INTERIOR and the
+!! arrays with USE_HORIZONTAL_BOUNDARY_DIFFUSION stop with a FATAL error.
 !!
 !! Compiled INSIDE a MOM6 source tree in place of src/tracer/MOM_tracer_hor_diff.F90; here against tests/fortran/stubs.
 module MOM_tracer_hor_diff
@@ -22,7 +24,7 @@ module MOM_tracer_hor_diff
 use, intrinsic :: iso_c_binding
 use mom6hip_c_api
 use mom6hip_MOM_glue,          only : mom6hip_shared_context, mom6hip_read_topology, mom6hip_fatal_if
-use mom6hip_MOM_glue,          only : mom6hip_read_resident, mom6hip_resident, mom6hip_mirror, mom6hip_read_eos
+use mom6hip_MOM_glue,          only : mom6hip_read_resident, mom6hip_resident, mom6hip_mirror, mom6hip_read_eos, mom6hip_mirror_to_host
 use MOM_cpu_clock,             only : cpu_clock_id, cpu_clock_begin, cpu_clock_end, CLOCK_MODULE
 use MOM_CVMix_KPP,             only : KPP_CS
 use MOM_diabatic_driver,       only : diabatic_CS, extract_diabatic_member
@@ -96,7 +98,11 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   real(c_double), allocatable, target :: cu(:)
   type(c_ptr) :: p_surf
   real(c_double), allocatable, target :: Rlay(:)
-  integer :: m, rc, idx_T, idx_S
+  integer :: m, rc, idx_T, idx_S, q, k
+  logical :: any_diag
+  type(mom6hip_tracer_flux_diag_t), allocatable, target :: dg(:)      ! the device (resident) or host (staged) arrays of the call
+  type(c_ptr), allocatable :: dgh(:,:)                                ! the host arrays behind them
+  type(c_ptr) :: p_dg
 
   if (.not. associated(CS)) call MOM_error(FATAL, "MOM_tracer_hor_diff: "// &
        "register_tracer must be called before tracer_hordiff.")
@@ -115,12 +121,36 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
         Reg%Tr(m)%id_hbdxy_conc > 0 .or. Reg%Tr(m)%id_hbd_dfx > 0 .or. Reg%Tr(m)%id_hbd_dfy > 0 .or. Reg%Tr(m)%id_hbd_dfx_2d > 0 .or. &
         Reg%Tr(m)%id_hbd_dfy_2d > 0)) call MOM_error(FATAL, "tracer_hordiff (HIP): the hbd_* diagnostics of tracer "// &
         trim(Reg%Tr(m)%name)//" are not provided by the GPU path.")
-    if (associated(Reg%Tr(m)%df_x) .or. associated(Reg%Tr(m)%df_y) .or. associated(Reg%Tr(m)%df2d_x) .or. &
-        associated(Reg%Tr(m)%df2d_y)) call MOM_error(FATAL, "tracer_hordiff (HIP): the diffusive flux diagnostics of tracer "// &
-        trim(Reg%Tr(m)%name)//" are not provided by the GPU path.")
     tr(m) = c_loc(Reg%Tr(m)%t)
     cu(m) = Reg%Tr(m)%conc_underflow
   enddo
+  ! the diffusive flux diagnostics where they are associated (:389-406, :576-591)
+  allocate(dg(Reg%ntr), dgh(4,Reg%ntr)) ; any_diag = .false. ; dgh(:,:) = c_null_ptr
+  do m=1,Reg%ntr
+    if (associated(Reg%Tr(m)%df_x)) dgh(1,m) = c_loc(Reg%Tr(m)%df_x)
+    if (associated(Reg%Tr(m)%df_y)) dgh(2,m) = c_loc(Reg%Tr(m)%df_y)
+    if (associated(Reg%Tr(m)%df2d_x)) dgh(3,m) = c_loc(Reg%Tr(m)%df2d_x)
+    if (associated(Reg%Tr(m)%df2d_y)) dgh(4,m) = c_loc(Reg%Tr(m)%df2d_y)
+    do q=1,4 ; if (c_associated(dgh(q,m))) any_diag = .true. ; enddo
+    dg(m)%df_x = dgh(1,m) ; dg(m)%df_y = dgh(2,m) ; dg(m)%df2d_x = dgh(3,m) ; dg(m)%df2d_y = dgh(4,m)
+  enddo
+  if (any_diag .and. CS%use_neutral_diffusion) then
+    ! the along-layer loop does not run: the arrays stay as the reference zeroes them (:389-406), on the host where they are read
+    do m=1,Reg%ntr
+      if (associated(Reg%Tr(m)%df_x)) then ; do k=1,GV%ke
+        Reg%Tr(m)%df_x(G%isc-1:G%iec,G%jsc:G%jec,k) = 0.0
+      enddo ; endif
+      if (associated(Reg%Tr(m)%df_y)) then ; do k=1,GV%ke
+        Reg%Tr(m)%df_y(G%isc:G%iec,G%jsc-1:G%jec,k) = 0.0
+      enddo ; endif
+      if (associated(Reg%Tr(m)%df2d_x)) Reg%Tr(m)%df2d_x(G%isc-1:G%iec,G%jsc:G%jec) = 0.0
+      if (associated(Reg%Tr(m)%df2d_y)) Reg%Tr(m)%df2d_y(G%isc:G%iec,G%jsc-1:G%jec) = 0.0
+    enddo
+    any_diag = .false.
+  endif
+  if (any_diag .and. CS%use_hor_bnd_diffusion) call MOM_error(FATAL, "tracer_hordiff (HIP): the diffusive flux diagnostics (df_x, df_y, "// &
+      "df2d_x, df2d_y) together with USE_HORIZONTAL_BOUNDARY_DIFFUSION and the along-layer diffusion are not provided by the GPU path.")
+  p_dg = c_null_ptr ; if (any_diag) p_dg = c_loc(dg)
   ccs%KhTr = CS%KhTr ; ccs%max_diff_CFL = CS%max_diff_CFL
   ccs%KhTr_Slope_Cff = CS%KhTr_Slope_Cff ; ccs%KhTr_min = CS%KhTr_min ; ccs%KhTr_max = CS%KhTr_max
   ccs%KhTr_passivity_coeff = CS%KhTr_passivity_coeff ; ccs%KhTr_passivity_min = CS%KhTr_passivity_min
@@ -185,10 +215,21 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
       call to_dev(fld%L2u, size(VarMix%L2u)) ; call to_dev(fld%SN_u, size(VarMix%SN_u))
       call to_dev(fld%L2v, size(VarMix%L2v)) ; call to_dev(fld%SN_v, size(VarMix%SN_v))
     endif
+    if (any_diag) then      ! the call writes a range of each array: mirrors that are read and written
+      do m=1,Reg%ntr
+        if (c_associated(dgh(1,m))) dg(m)%df_x = mom6hip_mirror(ctx, dgh(1,m), int(size(Reg%Tr(m)%df_x), c_int64_t), .true., .true.)
+        if (c_associated(dgh(2,m))) dg(m)%df_y = mom6hip_mirror(ctx, dgh(2,m), int(size(Reg%Tr(m)%df_y), c_int64_t), .true., .true.)
+        if (c_associated(dgh(3,m))) dg(m)%df2d_x = mom6hip_mirror(ctx, dgh(3,m), int(size(Reg%Tr(m)%df2d_x), c_int64_t), .true., .true.)
+        if (c_associated(dgh(4,m))) dg(m)%df2d_y = mom6hip_mirror(ctx, dgh(4,m), int(size(Reg%Tr(m)%df2d_y), c_int64_t), .true., .true.)
+      enddo
+    endif
     if (CS%Diffuse_ML_interior) then
-      rc = mom6hip_tracer_hordiff_epipycnal(ctx, ccs, CS%epi, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
+      rc = mom6hip_tracer_hordiff_epipycnal_diag(ctx, ccs, CS%epi, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
                                             CS%eos, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
-                                            int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats)
+                                            int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats, p_dg)
+    elseif (any_diag) then
+      rc = mom6hip_tracer_hordiff_diag(ctx, ccs, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), dt, tr, &
+                                       c_loc(cu), int(Reg%ntr, c_int32_t), MOM6HIP_MEM_DEVICE, stats, p_dg)
     elseif (CS%use_neutral_diffusion .and. CS%nd%unsupported(1) /= 0) then      ! NDIFF_CONTINUOUS = False (CS%hbd is read with HBD only)
       rc = mom6hip_tracer_hordiff_neutral_discontinuous(ctx, ccs, CS%hbd, CS%nd, CS%ndd, fld, &
                                       mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
@@ -204,8 +245,11 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
                                         int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats)
     endif
   elseif (CS%Diffuse_ML_interior) then
-    rc = mom6hip_tracer_hordiff_epipycnal(mom6hip_shared_context(G, GV), ccs, CS%epi, fld, c_loc(h), CS%eos, dt, tr, c_loc(cu), &
-                                          int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats)
+    rc = mom6hip_tracer_hordiff_epipycnal_diag(mom6hip_shared_context(G, GV), ccs, CS%epi, fld, c_loc(h), CS%eos, dt, tr, c_loc(cu), &
+                                          int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats, p_dg)
+  elseif (any_diag) then
+    rc = mom6hip_tracer_hordiff_diag(mom6hip_shared_context(G, GV), ccs, fld, c_loc(h), dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), &
+                                     MOM6HIP_MEM_HOST, stats, p_dg)
   elseif (CS%use_neutral_diffusion .and. CS%nd%unsupported(1) /= 0) then
     rc = mom6hip_tracer_hordiff_neutral_discontinuous(mom6hip_shared_context(G, GV), ccs, CS%hbd, CS%nd, CS%ndd, fld, c_loc(h), CS%eos, &
                                     p_surf, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), &
@@ -219,6 +263,10 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   endif
   CS%epi%Rlay = c_null_ptr
   call mom6hip_fatal_if(rc, "tracer_hordiff")
+  ! the host posts the arrays right after this call
+  if (any_diag .and. mom6hip_resident()) then
+    do m=1,Reg%ntr ; do q=1,4 ; if (c_associated(dgh(q,m))) call mom6hip_mirror_to_host(ctx, dgh(q,m)) ; enddo ; enddo
+  endif
   call cpu_clock_end(id_clock_diffuse)
 contains
   !> a host pointer of the struct -> its device mirror (an input)

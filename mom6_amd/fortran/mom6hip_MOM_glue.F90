@@ -30,7 +30,7 @@ public :: mom6hip_context_create, mom6hip_read_topology, mom6hip_read_eos, mom6h
 ! the device mirrors of the host's arrays, shared by every module shim (GPU_RESIDENT_DYNAMICS)
 public :: mom6hip_read_resident, mom6hip_resident, mom6hip_mirror, mom6hip_mirrors_stage, mom6hip_mirrors_to_host
 public :: mom6hip_mirrors_host_was_modified, mom6hip_mirror_host_changed, mom6hip_mirror_zeroed, mom6hip_mirrors_end
-public :: mom6hip_mirror_pass_var, mom6hip_mirror_require_host_current, mom6hip_mirror_forget
+public :: mom6hip_mirror_pass_var, mom6hip_mirror_require_host_current, mom6hip_mirror_forget, mom6hip_mirror_to_host
 public :: mom6hip_obc_to_c, update_segment_tracer_reservoirs_hip
 
 integer, parameter :: MAX_MIRRORS = 160
@@ -151,6 +151,19 @@ subroutine mom6hip_mirrors_to_host(ctx)
   call mom6hip_mirrors_stage(ctx)
   rc = mom6hip_stage_wait(ctx) ; call mom6hip_fatal_if(rc, "mom6hip_mirrors_to_host")
 end subroutine mom6hip_mirrors_to_host
+
+!> The same for the one host array at hp, complete at return (the flux diagnostics of a tracer, which the host posts right after the call)
+subroutine mom6hip_mirror_to_host(ctx, hp)
+  type(c_ptr), intent(in) :: ctx, hp
+  integer :: m, rc
+  do m = 1, nmir ; if (c_associated(mir(m)%h, hp)) then
+    if (.not.mir(m)%host_current) then
+      rc = mom6hip_sync_to_host(ctx, hp, mir(m)%d, mir(m)%bytes) ; call mom6hip_fatal_if(rc, "mom6hip_mirror_to_host")
+      mir(m)%host_current = .true.
+    endif
+    return
+  endif ; enddo
+end subroutine mom6hip_mirror_to_host
 
 !> The host has changed fields (thermodynamics, ALE remapping, a new forcing ...): the next calls upload every input again
 subroutine mom6hip_mirrors_host_was_modified()

@@ -50,6 +50,13 @@ type, bind(c) :: mom6hip_advect_stats_t
   integer(c_int32_t) :: iterations, halo_updates, domore_remaining, reserved
 end type mom6hip_advect_stats_t
 
+!> mom6hip_tracer_flux_diag_t: the flux diagnostics of one registered tracer (c_loc of the array where the pointer of tracer_type is
+!! associated, c_null_ptr where it is not), in the memory space of the call
+type, bind(c) :: mom6hip_tracer_flux_diag_t
+  type(c_ptr) :: ad_x = c_null_ptr, ad_y = c_null_ptr, ad2d_x = c_null_ptr, ad2d_y = c_null_ptr, advection_xy = c_null_ptr
+  type(c_ptr) :: df_x = c_null_ptr, df_y = c_null_ptr, df2d_x = c_null_ptr, df2d_y = c_null_ptr
+end type mom6hip_tracer_flux_diag_t
+
 !> mom6hip_remapping_cs_t (remapping_CS, src/ALE/MOM_remapping.F90:25)
 type, bind(c) :: mom6hip_remapping_cs_t
   integer(c_int32_t) :: remapping_scheme, boundary_extrapolation, force_bounds_in_subcell, answer_date
@@ -400,6 +407,28 @@ interface
     integer(c_int) :: rc
   end function mom6hip_advect_tracer_obc
 
+  !> mom6hip_advect_tracer_obc with the advective flux diagnostics: diag is c_null_ptr or c_loc of an array of ntr mom6hip_tracer_flux_diag_t
+  function mom6hip_advect_tracer_diag(ctx, h_end, uhtr, vhtr, dt, cs, tr, conc_underflow, ntr, x_first_in, &
+                                      vol_prev, max_iter_in, update_vol_prev, uhr_out, vhr_out, obc, memspace, stats, diag) &
+                                      bind(c, name="mom6hip_advect_tracer_diag") result(rc)
+    import :: c_int, c_int32_t, c_double, c_ptr, mom6hip_tracer_advect_cs_t, mom6hip_advect_stats_t
+    type(c_ptr), value :: ctx
+    type(c_ptr), value :: h_end, uhtr, vhtr
+    real(c_double), value :: dt
+    type(mom6hip_tracer_advect_cs_t), intent(in) :: cs
+    type(c_ptr), intent(in) :: tr(*)
+    type(c_ptr), value :: conc_underflow
+    integer(c_int32_t), value :: ntr, x_first_in
+    type(c_ptr), value :: vol_prev
+    integer(c_int32_t), value :: max_iter_in, update_vol_prev
+    type(c_ptr), value :: uhr_out, vhr_out
+    type(c_ptr), value :: obc
+    integer(c_int32_t), value :: memspace
+    type(mom6hip_advect_stats_t), intent(out) :: stats
+    type(c_ptr), value :: diag
+    integer(c_int) :: rc
+  end function mom6hip_advect_tracer_diag
+
   function mom6hip_update_segment_tracer_reservoirs(ctx, uhr, vhr, h, obc, dt, tr, ntr, memspace) &
                                                     bind(c, name="mom6hip_update_segment_tracer_reservoirs") result(rc)
     import :: c_int, c_int32_t, c_double, c_ptr, mom6hip_obc_t
@@ -583,6 +612,21 @@ interface
     integer(c_int) :: rc
   end function mom6hip_tracer_hordiff_varmix
 
+  !> mom6hip_tracer_hordiff_varmix with the diffusive flux diagnostics: diag is c_null_ptr or c_loc of an array of ntr mom6hip_tracer_flux_diag_t
+  function mom6hip_tracer_hordiff_diag(ctx, cs, fields, h, dt, tr, conc_underflow, ntr, memspace, stats, diag) &
+                                       bind(c, name="mom6hip_tracer_hordiff_diag") result(rc)
+    import :: c_int, c_int32_t, c_double, c_ptr, mom6hip_tracer_hor_diff_cs_t, mom6hip_hordiff_stats_t, mom6hip_hordiff_fields_t
+    type(c_ptr), value :: ctx, h, conc_underflow
+    type(mom6hip_tracer_hor_diff_cs_t), intent(in) :: cs
+    type(mom6hip_hordiff_fields_t), intent(in) :: fields
+    real(c_double), value :: dt
+    type(c_ptr), intent(in) :: tr(*)
+    integer(c_int32_t), value :: ntr, memspace
+    type(mom6hip_hordiff_stats_t), intent(out) :: stats
+    type(c_ptr), value :: diag
+    integer(c_int) :: rc
+  end function mom6hip_tracer_hordiff_diag
+
   !> tracer_hordiff with CS%use_neutral_diffusion (cs%unsupported(1)); idx_T, idx_S: the 0-based places of tv%T, tv%S in tr
   function mom6hip_tracer_hordiff_neutral(ctx, cs, nd, fields, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, &
                                           stats) bind(c, name="mom6hip_tracer_hordiff_neutral") result(rc)
@@ -667,6 +711,24 @@ interface
     type(mom6hip_hordiff_stats_t), intent(out) :: stats
     integer(c_int) :: rc
   end function mom6hip_tracer_hordiff_epipycnal
+
+  !> the same with the diffusive flux diagnostics: diag is c_null_ptr or c_loc of an array of ntr mom6hip_tracer_flux_diag_t
+  function mom6hip_tracer_hordiff_epipycnal_diag(ctx, cs, epi, fields, h, eos, dt, tr, conc_underflow, ntr, idx_T, idx_S, memspace, &
+                                                 stats, diag) bind(c, name="mom6hip_tracer_hordiff_epipycnal_diag") result(rc)
+    import :: c_int, c_int32_t, c_double, c_ptr, mom6hip_tracer_hor_diff_cs_t, mom6hip_hordiff_stats_t, mom6hip_hordiff_fields_t, &
+              mom6hip_epipycnal_cs_t, mom6hip_eos_t
+    type(c_ptr), value :: ctx, h, conc_underflow
+    type(mom6hip_tracer_hor_diff_cs_t), intent(in) :: cs
+    type(mom6hip_epipycnal_cs_t), intent(in) :: epi
+    type(mom6hip_hordiff_fields_t), intent(in) :: fields
+    type(mom6hip_eos_t), intent(in) :: eos
+    real(c_double), value :: dt
+    type(c_ptr), intent(in) :: tr(*)
+    integer(c_int32_t), value :: ntr, idx_T, idx_S, memspace
+    type(mom6hip_hordiff_stats_t), intent(out) :: stats
+    type(c_ptr), value :: diag
+    integer(c_int) :: rc
+  end function mom6hip_tracer_hordiff_epipycnal_diag
 
   !> subchk / subStats of MOM_checksums (MOM_checksums.F90:1387) on a device or host field of staggering pos
   function mom6hip_chksum(ctx, field, pos, nk, di, dj, symmetric, scale, bitcount, amin, amax, memspace) &

@@ -221,13 +221,29 @@ def _ptr_space(a):
     return a.data_ptr(), _abi.MEM_DEVICE
 
 
+def flux_diag_records(diag, names, kinds, P, who):
+    """the array of mom6hip_tracer_flux_diag_t of a call: `diag` has an entry per tracer (None, or a dict of the arrays asked for);
+    P(array, kind, name) checks an array and gives its address"""
+    recs = (_abi.TracerFluxDiag * len(diag))()
+    for m, d in enumerate(diag):
+        for n, a in (d or {}).items():
+            if n not in names:
+                raise Mom6HipError(f"{who}: {n} is not a flux diagnostic of this operator ({', '.join(names)} are)")
+            if a is not None:
+                setattr(recs[m], n, P(a, kinds[n], f"Reg%Tr({m+1})%{n}"))
+    return recs
+
+
 def advect_tracer(h_end, uhtr, vhtr, OBC, dt, G: DeviceGrid, CS: TracerAdvectCS, Reg, x_first_in=None,
                   vol_prev=None, max_iter_in=None, update_vol_prev=None, uhr_out=None, vhr_out=None,
-                  conc_underflow=None):
+                  conc_underflow=None, diag=None):
     """advect_tracer(h_end, uhtr, vhtr, OBC, dt, G, GV, US, CS, Reg, x_first_in, vol_prev, max_iter_in,
     update_vol_prev, uhr_out, vhr_out)  -- MOM_tracer_advect.F90:52.
 
     `Reg` is the list of tracer arrays Reg%Tr(m)%t (updated in place); GV/US are folded into `G`.
+    `diag`: None, or one entry per tracer, each None or a dict with any of ad_x, ad_y (u / v points, nk layers), ad2d_x, ad2d_y (u / v
+    points, a plane) and advection_xy (h points, nk layers) -- Reg%Tr(m)%ad_x ... where associated: arrays in the memory space of the
+    fields, zeroed and filled as the reference does (:193-197, :665-698, :1051-1084).
     Returns the AdvectStats of the call.
     """
     if CS is None:
@@ -242,7 +258,8 @@ def advect_tracer(h_end, uhtr, vhtr, OBC, dt, G: DeviceGrid, CS: TracerAdvectCS,
         return st
     g = G.grid
     spaces = set()
-    shapes = {"h": g.shape3(_abi.POS_H), "u": g.shape3(_abi.POS_U), "v": g.shape3(_abi.POS_V)}
+    shapes = {"h": g.shape3(_abi.POS_H), "u": g.shape3(_abi.POS_U), "v": g.shape3(_abi.POS_V),
+              "u2": g.shape2(_abi.POS_U), "v2": g.shape2(_abi.POS_V)}
 
     def P(a, kind, name):
         if a is None:
@@ -256,6 +273,11 @@ def advect_tracer(h_end, uhtr, vhtr, OBC, dt, G: DeviceGrid, CS: TracerAdvectCS,
     ph, pu, pv = P(h_end, "h", "h_end"), P(uhtr, "u", "uhtr"), P(vhtr, "v", "vhtr")
     trp = (C.c_void_p * ntr)(*[P(t, "h", f"Reg%Tr({m+1})%t") for m, t in enumerate(Reg)])
     pvol, puo, pvo = P(vol_prev, "h", "vol_prev"), P(uhr_out, "u", "uhr_out"), P(vhr_out, "v", "vhr_out")
+    dg = None
+    if diag is not None:
+        if len(diag) != ntr:
+            raise Mom6HipError("advect_tracer: diag must have one entry per tracer")
+        dg = flux_diag_records(diag, _abi.ADV_DIAGS, dict(ad_x="u", ad_y="v", ad2d_x="u2", ad2d_y="v2", advection_xy="h"), P, "advect_tracer")
     if len(spaces) != 1:
         raise Mom6HipError("advect_tracer: all fields must be in the same memory space")
     cu = None
@@ -287,14 +309,17 @@ def advect_tracer(h_end, uhtr, vhtr, OBC, dt, G: DeviceGrid, CS: TracerAdvectCS,
                     if tuple(a.shape) != want:
                         raise Mom6HipError(f"advect_tracer: a tracer reservoir of an OBC segment has shape {tuple(a.shape)}, expected {want}")
     L = lib()
-    L.mom6hip_advect_tracer_obc.argtypes = ([C.c_void_p] * 4 + [C.c_double, C.c_void_p, C.c_void_p, _dp, C.c_int32, C.c_int32, C.c_void_p,
-                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])
-    rc = L.mom6hip_advect_tracer_obc(
+    # (without diagnostics the entry is the one it has always been)
+    entry = L.mom6hip_advect_tracer_obc if dg is None else L.mom6hip_advect_tracer_diag
+    entry.argtypes = ([C.c_void_p] * 4 + [C.c_double, C.c_void_p, C.c_void_p, _dp, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+                      + ([] if dg is None else [C.c_void_p]))
+    rc = entry(
         G.handle, ph, pu, pv, float(dt), C.byref(cs), trp,
         None if cu is None else cu.ctypes.data_as(_dp), ntr,
         -1 if x_first_in is None else int(bool(x_first_in)), pvol,
         0 if max_iter_in is None else int(max_iter_in), int(bool(update_vol_prev)), puo, pvo,
-        None if obc is None else C.byref(obc), space, C.byref(st))
+        None if obc is None else C.byref(obc), space, C.byref(st), *(() if dg is None else (dg,)))
     check(rc, "advect_tracer")
     return st
 

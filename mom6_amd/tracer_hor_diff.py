@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import Mom6HipError, check, lib
-from .tracer_advect import DeviceGrid, _ptr_space
+from .tracer_advect import DeviceGrid, _ptr_space, flux_diag_records
 
 _PARAMS = {"KHTR": "KhTr", "MAX_TR_DIFFUSION_CFL": "max_diff_CFL", "CHECK_DIFFUSIVE_CFL": "check_diffusive_CFL", "KHTR_SLOPE_CFF": "KhTr_Slope_Cff",
            "KHTR_MIN": "KhTr_min", "KHTR_MAX": "KhTr_max", "KHTR_PASSIVITY_COEFF": "KhTr_passivity_coeff", "KHTR_PASSIVITY_MIN": "KhTr_passivity_min"}
@@ -123,17 +123,33 @@ def tracer_hor_diff_init(Time=None, G=None, GV=None, US=None, param_file=None, d
 
 
 def tracer_hordiff(h, dt, MEKE, VarMix, visc, G: DeviceGrid, CS: tracer_hor_diff_CS, Reg, tv=None, do_online_flag=None, read_khdt_x=None,
-                   read_khdt_y=None, conc_underflow=None, GV=None):
+                   read_khdt_y=None, conc_underflow=None, GV=None, diag=None):
     """tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_online_flag, read_khdt_x, read_khdt_y) -- :119.
     Reg: the list of tracer arrays (Reg%Tr(m)%t), updated in place.  VarMix: None, or a dict (its presence is
     VarMix%use_variable_mixing) with any of L2u, L2v, SN_u, SN_v (read with KHTR_SLOPE_CFF > 0), Res_fn_h (its presence is
     VarMix%Resoln_scaled_KhTr), Rd_dx_h (KHTR_PASSIVITY_COEFF > 0); MEKE: None, or a dict with Kh (MEKE%Kh) and KhTr_fac
     (MEKE%KhTr_fac); MEKE%Kh is read with variable mixing only, as in the reference.  With KHTR_USE_EBT_STRUCT VarMix has ebt_struct
-    (VarMix%ebt_struct: h points, nk levels, a valid halo of 1) too.  Returns the iteration statistics."""
+    (VarMix%ebt_struct: h points, nk levels, a valid halo of 1) too.  diag: None, or one entry per tracer, each None or a dict with
+    any of df_x, df_y (u / v points, nk layers) and df2d_x, df2d_y (u / v points, a plane) -- Reg%Tr(m)%df_x ... where associated, arrays
+    in the memory space of the fields: the along-layer branch zeroes and fills them as the reference does (:389-406, :576-591); the other
+    branches refuse them.  Returns the iteration statistics."""
     if CS is None or Reg is None:
         raise Mom6HipError("MOM_tracer_hor_diff: register_tracer must be called before tracer_hordiff.")
     if do_online_flag is False or read_khdt_x is not None or read_khdt_y is not None:
         raise Mom6HipError("tracer_hordiff (HIP): offline khdt arrays are not supported on this path")
+    if diag is not None and not any(a is not None for d in diag for a in (d or {}).values()):
+        diag = None
+    if diag is not None and len(diag) != len(list(Reg)):
+        raise Mom6HipError("tracer_hordiff: diag must have one entry per tracer")
+    if diag is not None and CS.st.unsupported[0]:
+        # USE_NEUTRAL_DIFFUSION: the along-layer loop does not run, and the reference leaves the arrays as :389-406 zeroed them
+        if CS.st.KhTr > 0.0 or VarMix is not None:      # (:197 returns before anything is zeroed)
+            _zero_flux_diag(G.grid, diag)
+        diag = None
+    if diag is not None and CS.st.unsupported[1]:
+        # with USE_HORIZONTAL_BOUNDARY_DIFFUSION alone the reference runs the along-layer loop after the boundary diffusion (:536)
+        raise Mom6HipError("tracer_hordiff (HIP): the diffusive flux diagnostics (df_x, df_y, df2d_x, df2d_y) together with "
+                           "USE_HORIZONTAL_BOUNDARY_DIFFUSION and the along-layer diffusion are not provided by libmom6hip")
     if CS.st.unsupported[0] and CS.neutral_diffusion_CSp.unsupported[0]:
         return _tracer_hordiff_neutral_discontinuous(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow)
     if CS.st.unsupported[1]:
@@ -141,10 +157,11 @@ def tracer_hordiff(h, dt, MEKE, VarMix, visc, G: DeviceGrid, CS: tracer_hor_diff
     if CS.st.unsupported[0]:
         return _tracer_hordiff_neutral(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow)
     if CS.st.unsupported[2]:
-        return _tracer_hordiff_epipycnal(h, dt, MEKE, VarMix, G, GV, CS, Reg, tv, conc_underflow)
+        return _tracer_hordiff_epipycnal(h, dt, MEKE, VarMix, G, GV, CS, Reg, tv, conc_underflow, diag)
     L = lib()
-    L.mom6hip_tracer_hordiff_varmix.argtypes = [C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.HorDiffFields), C.c_void_p, C.c_double,
-                                                C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_abi.HorDiffStats)]
+    entry = L.mom6hip_tracer_hordiff_varmix if diag is None else L.mom6hip_tracer_hordiff_diag      # (without diagnostics: the entry as ever)
+    entry.argtypes = [C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.HorDiffFields), C.c_void_p, C.c_double,
+                      C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_abi.HorDiffStats)] + ([] if diag is None else [C.c_void_p])
     tr = list(Reg)
     spaces = set()
     hp, s0 = _ptr_space(h); spaces.add(s0)
@@ -161,14 +178,40 @@ def tracer_hordiff(h, dt, MEKE, VarMix, visc, G: DeviceGrid, CS: tracer_hor_diff
     ptrs = (C.c_void_p * max(len(tr), 1))()
     for m, t in enumerate(tr):
         p, s = _ptr_space(t); ptrs[m] = p; spaces.add(s)
+    dg = _diff_diag_records(G.grid, diag, spaces)
     if len(spaces) != 1:
-        raise Mom6HipError("tracer_hordiff: h and every tracer must be in the same memory space")
+        raise Mom6HipError("tracer_hordiff: h, every tracer and every flux diagnostic must be in the same memory space")
     cu = None if conc_underflow is None else np.ascontiguousarray(conc_underflow, dtype=np.float64)
     stats = _abi.HorDiffStats()
-    check(L.mom6hip_tracer_hordiff_varmix(G.handle, C.byref(CS.st), C.byref(F), C.c_void_p(hp), float(dt), ptrs, None if cu is None else cu.ctypes.data,
-                                          len(tr), spaces.pop(), C.byref(stats)), "tracer_hordiff")
+    check(entry(G.handle, C.byref(CS.st), C.byref(F), C.c_void_p(hp), float(dt), ptrs, None if cu is None else cu.ctypes.data,
+                len(tr), spaces.pop(), C.byref(stats), *(() if dg is None else (dg,))), "tracer_hordiff")
     CS.last = stats
     return stats
+
+
+def _diff_diag_records(g, diag, spaces):
+    """the records of the diffusive flux diagnostics of a call (None: none asked for); their memory spaces join `spaces`"""
+    if diag is None:
+        return None
+    shapes = dict(df_x=g.shape3(_abi.POS_U), df_y=g.shape3(_abi.POS_V), df2d_x=g.shape2(_abi.POS_U), df2d_y=g.shape2(_abi.POS_V))
+
+    def P(a, kind, name):
+        if tuple(a.shape) != shapes[kind]:
+            raise Mom6HipError(f"tracer_hordiff: {name} has shape {tuple(a.shape)}, expected {shapes[kind]}")
+        p, s = _ptr_space(a); spaces.add(s)
+        return p
+    return flux_diag_records(diag, _abi.DIFF_DIAGS, {n: n for n in _abi.DIFF_DIAGS}, P, "tracer_hordiff")
+
+
+def _zero_flux_diag(g, diag):
+    """:389-406: the arrays asked for are set to zero over I = is-1..ie, j = js..je and J = js-1..je, i = is..ie"""
+    for d in diag:
+        for n, a in (d or {}).items():
+            if n not in _abi.DIFF_DIAGS:
+                raise Mom6HipError(f"tracer_hordiff: {n} is not a flux diagnostic of this operator ({', '.join(_abi.DIFF_DIAGS)} are)")
+            if a is not None:
+                sj, si = g.csl(_abi.POS_U if n.endswith("x") else _abi.POS_V)
+                a[..., sj, si] = 0.0
 
 
 def _check_VarMix(VarMix, CS):
@@ -331,7 +374,7 @@ def _tracer_hordiff_neutral_discontinuous(h, dt, MEKE, VarMix, visc, G, CS, Reg,
     return stats
 
 
-def _tracer_hordiff_epipycnal(h, dt, MEKE, VarMix, G, GV, CS, Reg, tv, conc_underflow):
+def _tracer_hordiff_epipycnal(h, dt, MEKE, VarMix, G, GV, CS, Reg, tv, conc_underflow, diag=None):
     """the DIFFUSE_ML_TO_INTERIOR branches (:544-550, :613-620 and tracer_epipycnal_ML_diff :700): tv has T, S (two of the arrays of
     Reg), eqn_of_state (an _abi.EOS) and P_Ref; GV -- a dict or an object -- has Rlay (nk values), nkml and nk_rho_varies."""
     get = (lambda n: tv.get(n)) if isinstance(tv, dict) else (lambda n: getattr(tv, n, None))
@@ -346,10 +389,10 @@ def _tracer_hordiff_epipycnal(h, dt, MEKE, VarMix, G, GV, CS, Reg, tv, conc_unde
         raise Mom6HipError("tracer_hordiff: tv%T and tv%S must be registered tracers (entries of Reg)")
     _check_VarMix(VarMix, CS)
     L = lib()
-    L.mom6hip_tracer_hordiff_epipycnal.argtypes = [C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.EpipycnalCS),
-                                                   C.POINTER(_abi.HorDiffFields), C.c_void_p, C.POINTER(_abi.EOS), C.c_double,
-                                                   C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                                   C.POINTER(_abi.HorDiffStats)]
+    entry = L.mom6hip_tracer_hordiff_epipycnal if diag is None else L.mom6hip_tracer_hordiff_epipycnal_diag
+    entry.argtypes = [C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.EpipycnalCS), C.POINTER(_abi.HorDiffFields), C.c_void_p,
+                      C.POINTER(_abi.EOS), C.c_double, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                      C.POINTER(_abi.HorDiffStats)] + ([] if diag is None else [C.c_void_p])
     spaces = set()
     hp, s0 = _ptr_space(h); spaces.add(s0)
     F = _abi.HorDiffFields()
@@ -364,6 +407,7 @@ def _tracer_hordiff_epipycnal(h, dt, MEKE, VarMix, G, GV, CS, Reg, tv, conc_unde
     ptrs = (C.c_void_p * max(len(tr), 1))()
     for m, t in enumerate(tr):
         p, s = _ptr_space(t); ptrs[m] = p; spaces.add(s)
+    dg = _diff_diag_records(G.grid, diag, spaces)
     if len(spaces) != 1:
         raise Mom6HipError("tracer_hordiff: h and every tracer must be in the same memory space")
     ep = CS.epipycnal
@@ -373,8 +417,8 @@ def _tracer_hordiff_epipycnal(h, dt, MEKE, VarMix, G, GV, CS, Reg, tv, conc_unde
     ep.Rlay = Rlay.ctypes.data; ep.nkml, ep.nk_rho_varies, ep.P_Ref = int(gv("nkml")), int(gv("nk_rho_varies")), float(get("P_Ref"))
     cu = None if conc_underflow is None else np.ascontiguousarray(conc_underflow, dtype=np.float64)
     stats = _abi.HorDiffStats()
-    check(L.mom6hip_tracer_hordiff_epipycnal(G.handle, C.byref(st), C.byref(ep), C.byref(F), C.c_void_p(hp), C.byref(get("eqn_of_state")),
-                                             float(dt), ptrs, None if cu is None else cu.ctypes.data, len(tr), idx[0], idx[1],
-                                             spaces.pop(), C.byref(stats)), "tracer_hordiff")
+    check(entry(G.handle, C.byref(st), C.byref(ep), C.byref(F), C.c_void_p(hp), C.byref(get("eqn_of_state")), float(dt), ptrs,
+                None if cu is None else cu.ctypes.data, len(tr), idx[0], idx[1], spaces.pop(), C.byref(stats), *(() if dg is None else (dg,))),
+          "tracer_hordiff")
     CS.last = stats
     return stats
