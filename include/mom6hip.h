@@ -1201,7 +1201,8 @@ int mom6hip_tracer_hordiff_epipycnal_diag(mom6hip_ctx_t *ctx, const mom6hip_trac
  * tracers inside the surface boundary layer visc%h_ML (fields->h_ML).  Provided: the HBD grid of every wet face (hbd_grid, the merged
  * interfaces of both columns and both boundary-layer depths), fluxes_layer_method with HBD_LINEAR_TRANSITION, APPLY_LIMITER and
  * APPLY_LIMITER_REMAP, and HBD_REMAPPING_SCHEME PCM, PLM (the default), PPM_H4, PPM_IH4 or PPM_CW, each with or without
- * HBD_BOUNDARY_EXTRAP.  Not provided (refused by name): any other scheme, HBD_DEBUG, the hbd_* diagnostics, and more than 128 layers
+ * HBD_BOUNDARY_EXTRAP.  Not provided (refused by name): any other scheme, HBD_DEBUG, more than 128 layers, and the hbd_* diagnostics
+ * through any entry but mom6hip_tracer_hordiff_mix_diag, which provides them
  * (the reference has no such bound: a face's columns are walked from private arrays of a fixed size).
  */
 typedef struct mom6hip_hor_bnd_diffusion_cs {
@@ -1211,7 +1212,7 @@ typedef struct mom6hip_hor_bnd_diffusion_cs {
   int32_t boundary_extrap; /* HBD_BOUNDARY_EXTRAP (0) */
   int32_t remap_scheme;    /* HBD_REMAPPING_SCHEME as MOM6HIP_REMAP_* (MOM6HIP_REMAP_PLM) */
   int32_t debug;           /* HBD_DEBUG (0; refused if set) */
-  int32_t diagnostics;     /* a registered hbd_* diagnostic (0; refused if set) */
+  int32_t diagnostics;     /* a registered hbd_* diagnostic (0; refused if set, but with the records of mom6hip_tracer_hordiff_mix_diag) */
   int32_t initialized;
   int32_t reserved[8];
 } mom6hip_hor_bnd_diffusion_cs_t;
@@ -1266,6 +1267,40 @@ int mom6hip_tracer_hordiff_neutral_discontinuous(mom6hip_ctx_t *ctx, const mom6h
                                                  const double *h, const mom6hip_eos_t *eos, const double *p_surf, double dt, double *const *tr,
                                                  const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S, int32_t memspace,
                                                  mom6hip_hordiff_stats_t *stats);
+
+/* The budget diagnostics that neutral_diffusion (MOM_neutral_diffusion.F90:935-1014) and hor_bnd_diffusion
+ * (MOM_hor_bnd_diffusion.F90:292-333) post themselves, for one registered tracer: NULL = not asked for.  The arrays are in the memory
+ * space of the call and whole (data domain): u / v / h points, with nk layers or one plane. */
+typedef struct mom6hip_tracer_mix_diag {
+  double *dfx_2d, *dfy_2d;        /* trans_x_2d, trans_y_2d: -sum over the surfaces of Coef(:,:,1)*Flx, times Idt (:935-989); u / v plane */
+  double *dfxy_cont;              /* tendency = dTracer(k)*IareaT*Idt (:871-875, :916-920, :993); h points, nk */
+  double *dfxy_cont_2d;           /* its sum over k = 1..nz in layer order, from 0 (:997-1004); h plane */
+  double *dfxy_conc;              /* tendency / (h + H_subroundoff) (:1010-1014); h points, nk */
+  double *hbd_dfx, *hbd_dfy;      /* uFlx*Idt, vFlx*Idt (:292-293); u / v points, nk */
+  double *hbd_dfx_2d, *hbd_dfy_2d;/* their sums over k in layer order, from 0 (:294-308); u / v plane */
+  double *hbdxy_cont;             /* ((uFlx(I-1)-uFlx(I)) + (vFlx(J-1)-vFlx(J)))*IareaT*Idt (:268-271, :312); h points, nk */
+  double *hbdxy_cont_2d;          /* its sum over k in layer order, from 0 (:316-323); h plane */
+  double *hbdxy_conc;             /* tendency / (h + H_subroundoff) (:329-333); h points, nk */
+} mom6hip_tracer_mix_diag_t;
+uint64_t mom6hip_abi_sizeof_tracer_mix_diag(void);
+
+/* mom6hip_tracer_hordiff_neutral_discontinuous with those diagnostics: diag is NULL (that call) or an array of ntr records.  Every
+ * pairing of that entry is served: neutral diffusion on either reconstruction, both orders of NDIFF_ANSWER_DATE, NDIFF_TAPERING and
+ * KHTR_USE_EBT_STRUCT, boundary diffusion followed by the along-layer loop or by neutral diffusion.  Idt = 1.0/(I_numitts*dt).
+ * The library writes the compute range of each array asked for -- faces I = isc-1..iec, j = jsc..jec and i = isc..iec, J = jsc-1..jec,
+ * cells isc..iec x jsc..jec, every layer -- bit for bit what the reference hands to post_data there, and nothing else in the array: the
+ * reference's locals outside that range are zeros or unset, and those points are the caller's.  Land cells and dry faces inside the
+ * range get what the reference leaves there: 0.  The 2-D sums are marches over k of one thread a column or face, never atomics.
+ * The reference posts once per iteration of its itt loop and the posts are separate, so a diagnostic asked for with num_itts > 1
+ * (MAX_TR_DIFFUSION_CFL > 0, or CHECK_DIFFUSIVE_CFL finding more than one) is refused by name before any tracer has changed; so is a
+ * dfx_2d .. dfxy_conc array without USE_NEUTRAL_DIFFUSION and an hbd_* array without USE_HORIZONTAL_BOUNDARY_DIFFUSION.  With a record
+ * hbd->diagnostics and nd->unsupported[5] may be set (they say that ids are registered; the records say which); through every other
+ * entry, and with diag NULL, they stay refused. */
+int mom6hip_tracer_hordiff_mix_diag(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hor_bnd_diffusion_cs_t *hbd,
+                                    const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_ndiff_discontinuous_cs_t *ndd,
+                                    const mom6hip_hordiff_fields_t *fields, const double *h, const mom6hip_eos_t *eos, const double *p_surf,
+                                    double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T, int32_t idx_S,
+                                    int32_t memspace, mom6hip_hordiff_stats_t *stats, const mom6hip_tracer_mix_diag_t *diag);
 
 /* ---- MOM_hor_visc ----------------------------------------------------------------------------- */
 

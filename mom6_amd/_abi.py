@@ -252,6 +252,19 @@ class TracerFluxDiag(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ADV_DIAGS + DIFF_DIAGS]
 
 
+# what neutral_diffusion and hor_bnd_diffusion post themselves (mom6hip_tracer_mix_diag_t), with the position and rank of each array
+ND_MIX_DIAGS = ("dfx_2d", "dfy_2d", "dfxy_cont", "dfxy_cont_2d", "dfxy_conc")
+HBD_MIX_DIAGS = ("hbd_dfx", "hbd_dfy", "hbd_dfx_2d", "hbd_dfy_2d", "hbdxy_cont", "hbdxy_cont_2d", "hbdxy_conc")
+MIX_DIAG_KINDS = dict(dfx_2d=(POS_U, 2), dfy_2d=(POS_V, 2), dfxy_cont=(POS_H, 3), dfxy_cont_2d=(POS_H, 2), dfxy_conc=(POS_H, 3),
+                      hbd_dfx=(POS_U, 3), hbd_dfy=(POS_V, 3), hbd_dfx_2d=(POS_U, 2), hbd_dfy_2d=(POS_V, 2), hbdxy_cont=(POS_H, 3),
+                      hbdxy_cont_2d=(POS_H, 2), hbdxy_conc=(POS_H, 3))
+
+
+class TracerMixDiag(C.Structure):
+    """mom6hip_tracer_mix_diag_t (include/mom6hip.h): null = not asked for."""
+    _fields_ = [(n, C.c_void_p) for n in ND_MIX_DIAGS + HBD_MIX_DIAGS]
+
+
 class HorDiffStats(C.Structure):
     _fields_ = [("num_itts", C.c_int32), ("halo_updates", C.c_int32), ("max_CFL", C.c_double)]
 

@@ -60,4 +60,31 @@ inline void flux_diag_march(int dir, const FluxDiagMarch &a, hipStream_t s) {
   else     hipLaunchKernelGGL(flux_diag_march_kernel<0>, grid, dim3(256), 0, s, a);
 }
 
+// The same march for cell-shaped tendencies: a2(i,j) = sum over k = 1..nz of a3(i,j,k), from 0.0 in layer order, over the compute domain
+// (the depth-summed content tendencies dfxy_cont_2d, MOM_neutral_diffusion.F90:997-1004, and hbdxy_cont_2d, MOM_hor_bnd_diffusion.F90:316-323).
+// One thread a column, lanes along i; up to FLUX_DIAG_MAXD tracers a launch.
+struct CellSumMarch {
+  GridDev g;
+  const double *a3[FLUX_DIAG_MAXD];
+  double *a2[FLUX_DIAG_MAXD];
+  int n;
+};
+
+static __global__ __launch_bounds__(256) void cell_sum_march_kernel(CellSumMarch a) {
+  const GridDev &g = a.g;
+  const int i = g.isc + blockIdx.x * 256 + threadIdx.x, j = g.jsc + (int)blockIdx.y;
+  if (i > g.iec) return;
+  const long n2 = g.h2(i, j), hpl = (long)g.nih * g.njh;
+  for (int n = 0; n < a.n; n++) {
+    double acc = 0.0;
+    for (int k = 0; k < g.nk; k++) acc = acc + a.a3[n][n2 + hpl * k];
+    a.a2[n][n2] = acc;
+  }
+}
+
+inline void cell_sum_march(const CellSumMarch &a, hipStream_t s) {
+  const GridDev &g = a.g;
+  hipLaunchKernelGGL(cell_sum_march_kernel, dim3((g.iec - g.isc + 1 + 255) / 256, g.jec - g.jsc + 1), dim3(256), 0, s, a);
+}
+
 }  // namespace m6

@@ -12,6 +12,8 @@
 //   hbd_update_kernel  the update of every layer of every wet cell (:262-270) and the concentration underflow (:274-278); fluxes of
 //                      layers at or below a face's last flux layer are zero, so a layer no face reaches still gets t + 0
 //                      (which turns a -0.0 into +0.0 as the reference does)
+//   hbd_face_diag_kernel, hbd_update_kernel<HBDMixOut>  the hbd_* diagnostics (:292-333) where mom6hip_tracer_hordiff_mix_diag asks for
+//                      them: the fluxes times Idt with their sums over k in layer order, and the content / concentration tendencies
 // One lane per face walks the serial depth loops of its column pair from private arrays (sized by the template's layer bound NKM).
 // The vertical reconstructions are those of remapping_core_h (src/ALE/MOM_remapping.F90:160) for PCM, PLM, PPM_H4, PPM_IH4 and
 // PPM_CW, with and without boundary extrapolation, force_bounds_in_subcell = .false.  Their per-cell arithmetic lives in
@@ -24,6 +26,7 @@
 #include <cfloat>
 #include <cmath>
 
+#include "flux_diag_march.hpp"
 #include "neutral_common.hpp"      // boundary_k_range_surface, the layer search neutral diffusion's NDIFF_INTERIOR_ONLY shares
 #define REMAP_PIECES_SELECT 1      // m6::min2 / max2, as the oracle (remap_pieces.hpp says why there are two flavours)
 #include "remap_pieces.hpp"
@@ -435,8 +438,16 @@ __global__ __launch_bounds__(64) void hbd_flux_kernel(HBDArgs A) {
   }
 }
 
-// thread (i, j, k) over the compute domain
-__global__ __launch_bounds__(256) void hbd_update_kernel(HBDArgs A) {
+// What the diagnostic forms below take: where hbdxy_cont goes (the array, or scratch when only hbdxy_cont_2d is asked for) and hbdxy_conc
+// (null: not asked for); the arrays of the face march
+struct HBDMixOut { double *cont, *conc; double Idt; };
+struct HBDFaceOut { double *a3, *a2; double Idt; };
+
+// thread (i, j, k) over the compute domain.  D: nothing, or one HBDMixOut -- the form that also stores the tendency (:268-271) and its
+// concentration form (:329-333), 0 on land (tendency(:,:,:) = 0.0, :232)
+template <typename... D>
+__global__ __launch_bounds__(256) void hbd_update_kernel(HBDArgs A, D... d) {
+  constexpr bool DIAG = sizeof...(D) > 0;
   const m6::GridDev &g = A.g;
   const int i = g.isc + blockIdx.x * blockDim.x + threadIdx.x, j = g.jsc + blockIdx.y, k = blockIdx.z;
   if (i > g.iec) return;
@@ -450,9 +461,39 @@ __global__ __launch_bounds__(256) void hbd_update_kernel(HBDArgs A) {
     const double vS = k < A.nflx_max[1] ? A.flx[1][g.v2(i, J - 1) + vpl * k] : 0.0;
     const double vN = k < A.nflx_max[1] ? A.flx[1][g.v2(i, J) + vpl * k] : 0.0;
     x = x + (((uW - uE)) + ((vS - vN))) * g.IareaT[g.h2(i, j)] / (A.h[n] + g.H_subroundoff);
+    if constexpr (DIAG) {
+      const HBDMixOut &M = m6::nd_first(d...);
+      const double td = ((uW - uE) + (vS - vN)) * g.IareaT[g.h2(i, j)] * M.Idt;
+      if (M.cont) M.cont[n] = td;
+      if (M.conc) M.conc[n] = td / (A.h[n] + g.H_subroundoff);
+    }
+  } else if constexpr (DIAG) {
+    const HBDMixOut &M = m6::nd_first(d...);
+    if (M.cont) M.cont[n] = 0.0;
+    if (M.conc) M.conc[n] = 0.0;
   }
   if (A.cu > 0.0 && fabs(x) < A.cu) x = 0.0;
   A.t[n] = x;
+}
+
+// hbd_dfx / hbd_dfy (:292-293) and hbd_dfx_2d / hbd_dfy_2d (:294-308) of the tracer whose fluxes stand in A.flx: one thread a face of the
+// compute range marches k, stores flx*Idt (0 from nflx_max on, where no flux is kept) and the running sum from 0.0 in layer order
+template <int DIR>
+__global__ __launch_bounds__(64) void hbd_face_diag_kernel(HBDArgs A, HBDFaceOut O) {
+  const m6::GridDev &g = A.g;
+  long f = 0, cL = 0, cR = 0;
+  bool in_range;
+  hbd_face<DIR>(g, in_range, f, cL, cR);
+  if (!in_range) return;
+  const long fpl = face_plane(g, DIR);
+  const int nmax = A.nflx_max[DIR];
+  double sum = 0.0;
+  for (int k = 0; k < g.nk; k++) {
+    const double v = (k < nmax ? A.flx[DIR][f + fpl * k] : 0.0) * O.Idt;
+    if (O.a3) O.a3[f + fpl * k] = v;
+    sum = sum + v;
+  }
+  if (O.a2) O.a2[f] = sum;
 }
 
 template <int NKM>
@@ -484,7 +525,8 @@ int hbd_branch(const HordiffCall &c, const mom6hip_hor_bnd_diffusion_cs_t *hbd, 
   const std::vector<double *> &d_tr = c.d_tr;
   M6_REQUIRE(hbd->initialized, "hor_bnd_diffusion: the control structure is not initialised");
   M6_REQUIRE(!hbd->debug, "hor_bnd_diffusion: HBD_DEBUG is not provided by libmom6hip");
-  M6_REQUIRE(!hbd->diagnostics, "hor_bnd_diffusion: the hbd_* diagnostics are not provided by libmom6hip");
+  // (with the records of mom6hip_tracer_hordiff_mix_diag the hbd_* diagnostics are those the records ask for)
+  M6_REQUIRE(!hbd->diagnostics || c.mix, "hor_bnd_diffusion: the hbd_* diagnostics are not provided by libmom6hip");
   M6_REQUIRE(hbd_scheme_provided(hbd->remap_scheme), "hor_bnd_diffusion: HBD_REMAPPING_SCHEME %d is not provided by libmom6hip "
              "(PCM, PLM, PPM_H4, PPM_IH4 and PPM_CW are)", hbd->remap_scheme);
   M6_REQUIRE(c.h_ML != nullptr, "hor_bnd_diffusion requires that visc%%h_ML is associated.");
@@ -537,6 +579,17 @@ int hbd_branch(const HordiffCall &c, const mom6hip_hor_bnd_diffusion_cs_t *hbd, 
   M6_HIP(hipGetLastError());
   std::vector<double *> pf(d_tr);
   std::vector<int32_t> ppos(ntr, MOM6HIP_POS_H), pnk(ntr, nk);
+  // the diagnostics hor_bnd_diffusion posts (:292-333): where only hbdxy_cont_2d is asked for, the tendency of a tracer goes to scratch
+  const MixDiag *mix = c.mix;
+  double *cont_scr = nullptr;
+  if (mix) {
+    bool cont_to_scratch = false;
+    for (int m = 0; m < ntr; m++) cont_to_scratch = cont_to_scratch || (mix[m].a[MIX_HBDXY_CONT_2D] && !mix[m].a[MIX_HBDXY_CONT]);
+    if (cont_to_scratch) {
+      cont_scr = (double *)st.scratch(sizeof(double) * hpl * nk);
+      M6_REQUIRE(!st.failed() && cont_scr, "hor_bnd_diffusion: out of device memory for the diagnostics");
+    }
+  }
   for (int itt = 1; itt <= c.num_itts; itt++) {
     if (int rc = m6::group_pass(ctx, pf.data(), ppos.data(), pnk.data(), ntr)) return rc;      // :412, and :466 for itt > 1
     (*c.halo_updates)++;
@@ -547,7 +600,20 @@ int hbd_branch(const HordiffCall &c, const mom6hip_hor_bnd_diffusion_cs_t *hbd, 
         else if (nkm == 80) launch_flux<80>(A, nbu, nj, nbv, nj + 1, s);
         else launch_flux<128>(A, nbu, nj, nbv, nj + 1, s);
       }
-      hipLaunchKernelGGL(hbd_update_kernel, dim3((ni + 255) / 256, nj, nk), dim3(256), 0, s, A);
+      double *const *a = mix ? mix[m].a : nullptr;
+      if (a && (a[MIX_HBD_DFX] || a[MIX_HBD_DFX_2D]))      // A.flx holds this tracer's fluxes until the next tracer's launch
+        hipLaunchKernelGGL(hbd_face_diag_kernel<0>, dim3(nbu, nj), dim3(64), 0, s, A, HBDFaceOut{a[MIX_HBD_DFX], a[MIX_HBD_DFX_2D], c.Idt});
+      if (a && (a[MIX_HBD_DFY] || a[MIX_HBD_DFY_2D]))
+        hipLaunchKernelGGL(hbd_face_diag_kernel<1>, dim3(nbv, nj + 1), dim3(64), 0, s, A, HBDFaceOut{a[MIX_HBD_DFY], a[MIX_HBD_DFY_2D], c.Idt});
+      if (a && (a[MIX_HBDXY_CONT] || a[MIX_HBDXY_CONT_2D] || a[MIX_HBDXY_CONC])) {
+        HBDMixOut mo = {a[MIX_HBDXY_CONT] ? a[MIX_HBDXY_CONT] : a[MIX_HBDXY_CONT_2D] ? cont_scr : nullptr, a[MIX_HBDXY_CONC], c.Idt};
+        hipLaunchKernelGGL(hbd_update_kernel<HBDMixOut>, dim3((ni + 255) / 256, nj, nk), dim3(256), 0, s, A, mo);
+        if (a[MIX_HBDXY_CONT_2D]) {
+          CellSumMarch sum2d; sum2d.g = g; sum2d.n = 1; sum2d.a3[0] = mo.cont; sum2d.a2[0] = a[MIX_HBDXY_CONT_2D];
+          cell_sum_march(sum2d, s);
+        }
+      } else
+        hipLaunchKernelGGL(hbd_update_kernel<>, dim3((ni + 255) / 256, nj, nk), dim3(256), 0, s, A);
     }
   }
   M6_HIP(hipGetLastError());

@@ -5,6 +5,12 @@
 
 namespace m6 {
 
+// The diagnostics neutral_diffusion and hor_bnd_diffusion post themselves (mom6hip_tracer_mix_diag_t), as device views of the arrays a
+// tracer asked for (null: not asked for), in the order of the record
+enum { MIX_DFX_2D = 0, MIX_DFY_2D, MIX_DFXY_CONT, MIX_DFXY_CONT_2D, MIX_DFXY_CONC, MIX_HBD_DFX, MIX_HBD_DFY, MIX_HBD_DFX_2D, MIX_HBD_DFY_2D,
+       MIX_HBDXY_CONT, MIX_HBDXY_CONT_2D, MIX_HBDXY_CONC, MIX_COUNT };
+struct MixDiag { double *a[MIX_COUNT]; };
+
 struct HordiffCall {
   mom6hip_ctx_t *ctx;
   Stager &st;
@@ -18,6 +24,8 @@ struct HordiffCall {
   const double *p_surf, *h_ML;            // null where the call has none
   const double *ebt_struct;               // VarMix%ebt_struct with KHTR_USE_EBT_STRUCT where it is read, null without
   int *halo_updates;
+  const MixDiag *mix;                     // one per tracer, or null: no such diagnostic in this call (then num_itts == 1 is not required)
+  double Idt;                             // 1.0 / (I_numitts * dt), as neutral_diffusion and hor_bnd_diffusion form it
 };
 
 // USE_HORIZONTAL_BOUNDARY_DIFFUSION (hor_bnd_diffusion.hip)

@@ -32,6 +32,15 @@ struct NDFaces {
   int *bad;                          // a word of bits the kernels raise; the branch's table says what each means
 };
 
+// What the diagnostic forms of the kernels take beside their arguments (the forms without diagnostics take nothing: they are the code they
+// were).  NDTransOut: the flux kernels of the symmetric order, which never store the fluxes, keep one more sum per tracer of the batch --
+// trans = trans - Coef(:,:,1)*Flx(ks), the value the tendencies get -- and store trans*Idt to a plane (dfx_2d / dfy_2d; null: this
+// tracer did not ask).  NDMixOut: the update kernels store (dTracer(k)*IareaT)*Idt where dfxy_cont goes (the array, or scratch when only
+// dfxy_cont_2d is asked for) and that value / (h + H_subroundoff) to dfxy_conc, and 0 on land.
+struct NDTransOut { double *trans[ND_BATCH]; double Idt; };
+struct NDMixOut { double *cont[ND_BATCH], *conc[ND_BATCH]; double Idt; };
+template <typename T> __device__ __forceinline__ const T &nd_first(const T &t) { return t; }      // the one member of a kernel's pack
+
 // The lane's face of the direction DIR (u faces I = isc-1 .. iec, j = jsc .. jec; v faces i = isc .. iec, J = jsc-1 .. jec) in a grid of
 // nbx * rows blocks of 64 lanes: its plane offset f and plane size pl, the columns cl, cr on its two sides; has: the lane has a face
 struct NDFace { int i, j; long f, pl, hpl, cl, cr; bool has, wet; };
@@ -104,7 +113,9 @@ struct NDBranch {
   std::function<int()> surfaces;                      // neutral_diffusion_calc_coeffs :337 after the pass of CS%hbl
   std::function<int()> once;                          // (optional) what it forms once a call, after the first surfaces
   std::function<void()> tracer_cols;                  // the reconstructions of the batch's tracers
-  std::function<void(bool symmetric)> fluxes;         // neutral_surface_flux of the batch: tendencies (symmetric) or fluxes
+  // neutral_surface_flux of the batch: tendencies (symmetric) or fluxes; tx, ty: with the symmetric order, where dfx_2d / dfy_2d of the
+  // batch go (null: none of the batch asked for the direction's -- the launch without diagnostics)
+  std::function<void(bool symmetric, const NDTransOut *tx, const NDTransOut *ty)> fluxes;
   bool flux_has_coef;                                 // the fluxes carry the diffusivity (KHTR_USE_EBT_STRUCT, :834-848)
   struct Bad { int bit; const char *message; };
   std::vector<Bad> bad;                               // the bits of NDFaces::bad, in the order they are reported

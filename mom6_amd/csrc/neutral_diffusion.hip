@@ -19,6 +19,8 @@
 //   nd_taper_kernel       NDIFF_TAPERING: the four layer numbers of compute_tapering_coeffs (:1022) for one face -- boundary_k_range of
 //                         the two columns at the smaller and the larger of their boundary-layer depths; coeff_l / coeff_r are closed
 //                         forms of them
+//   nd_trans_march_kernel, and the forms of the flux and update kernels that take a record  the diagnostics neutral_diffusion posts
+//                         (:935-1014: dfx_2d, dfy_2d, dfxy_cont, dfxy_cont_2d, dfxy_conc) where mom6hip_tracer_hordiff_mix_diag asks for them
 // With either switch nd_flux_kernel forms khtr_ave (:2410-2417) from the coefficients of the interfaces klt, klb, krt, krb: a side's value
 // at klt is its value at klb of the sublayer above, so one is carried and a new one is formed only when the surface enters another cell.
 // A lane owns a column or a face and walks it: the walks are serial in the surface index and differ from lane to lane.  What a walk
@@ -32,6 +34,7 @@
 #include <type_traits>
 
 #include "neutral_common.hpp"
+#include "flux_diag_march.hpp"
 #include "eos.hpp"
 
 namespace {
@@ -357,9 +360,12 @@ __global__ __launch_bounds__(64) void nd_tracer_cols_kernel(NDArgs A, int nbx) {
 // neutral_surface_flux :2297 (continuous).  SYM: the tendencies of the two cells of the face from its fluxes, layer by layer (the order
 // of the sums of neutral_diffusion :939-954: a face at a time, its surfaces top down); otherwise the fluxes.  COEF: what coeff_l / coeff_r
 // are -- absent (khtr_ave = 1), the taper, Coef_h, or their product (:703-764); with Coef_h the fluxes carry the diffusivity (:834-878)
+// D: nothing, or (the symmetric order) one NDTransOut -- the form that also leaves trans_x_2d / trans_y_2d (:935-989) of the batch
 enum { ND_COEF_NONE = 0, ND_COEF_TAPER = 1, ND_COEF_EBT = 2, ND_COEF_BOTH = 3 };
-template <int DIR, bool SYM, int COEF = ND_COEF_NONE>
-__global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx) {
+template <int DIR, bool SYM, int COEF = ND_COEF_NONE, typename... D>
+__global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx, D... d) {
+  constexpr bool DIAG = sizeof...(D) > 0;
+  static_assert(!DIAG || SYM, "the order of 2024 and before keeps the fluxes: nd_trans_march_kernel sums them");
   const m6::GridDev &g = A.g;
   const NDFace F = nd_face<DIR>(g, nbx);
   if (!F.has) return;
@@ -369,6 +375,10 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx) {
   const int ns = A.ns, nb = A.nb, nk = g.nk;
   if (!F.wet) {
     for (int z = 0; z < nb; z++) nd_dry_fluxes<SYM>(ns, nk, Flx, tdL, tdR, A.flx_stride * z + f, pl);
+    if constexpr (DIAG) {
+      const NDTransOut &T = nd_first(d...);
+      for (int z = 0; z < nb; z++) if (T.trans[z]) T.trans[z][f] = 0.;
+    }
     return;
   }
   const double *__restrict__ PiL = A.PoL[DIR], *__restrict__ PiR = A.PoR[DIR], *__restrict__ hEff = A.hEff[DIR];
@@ -410,6 +420,11 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx) {
   double accL[ND_BATCH], accR[ND_BATCH];
 #pragma unroll
   for (int z = 0; z < ND_BATCH; z++) { accL[z] = 0.; accR[z] = 0.; }
+  [[maybe_unused]] double trn[DIAG ? ND_BATCH : 1];      // DIAG: trans_x_2d(I,j) | trans_y_2d(i,J) of the batch's tracers
+  if constexpr (DIAG) {
+#pragma unroll
+    for (int z = 0; z < ND_BATCH; z++) trn[z] = 0.;
+  }
   // COEF: coeff_l / coeff_r at the interface K (0-based: the top of the cell K), and their values at the surface above
   int kminL = 0, kmaxL = 0, kminR = 0, kmaxR = 0;
   if constexpr ((COEF & ND_COEF_TAPER) != 0) {
@@ -474,6 +489,10 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx) {
       if (SYM && (COEF & ND_COEF_EBT) != 0) { accL[z] = accL[z] + flx; accR[z] = accR[z] - flx; }
       else if (SYM) { accL[z] = accL[z] + cf * flx; accR[z] = accR[z] - cf * flx; }
       else if (z < nb) Flx[A.flx_stride * z + f + pl * ks] = flx;
+      if constexpr (DIAG) {
+        if ((COEF & ND_COEF_EBT) != 0) trn[z] = trn[z] - flx;
+        else trn[z] = trn[z] - cf * flx;
+      }
       sl.top[z] = T_left_bottom; sr.top[z] = T_right_bottom;
     }
     // the surface enters another cell: its edge values from the interface values and the mean just read; SYM: the layer it leaves is done
@@ -505,16 +524,53 @@ __global__ __launch_bounds__(64) void nd_flux_kernel(NDArgs A, int nbx) {
       nd_tend_store(tdR, A.flx_stride * z + f, pl, krt, nk, accR[z]);
     }
   }
+  if constexpr (DIAG) {
+    const NDTransOut &T = nd_first(d...);
+#pragma unroll
+    for (int z = 0; z < ND_BATCH; z++) if (z < nb && T.trans[z]) T.trans[z][f] = trn[z] * T.Idt;
+  }
   if (bad) atomicOr(A.bad, bad);
 }
 
+// trans_x_2d / trans_y_2d (:935-989) in the order of 2024 and before, where the fluxes of the batch stand in scratch: one thread a face
+// marches the surfaces, trans = trans - Coef(:,:,1)*Flx(ks) with Coef as nd_update_kernel<false> forms it, or trans - Flx(ks) where the
+// fluxes carry the coefficient (EBT); dry faces get 0
+template <int DIR, bool EBT>
+__global__ __launch_bounds__(64) void nd_trans_march_kernel(NDFaces A, int nbx, NDTransOut T) {
+  const m6::GridDev &g = A.g;
+  const NDFace F = nd_face<DIR>(g, nbx);
+  if (!F.has) return;
+  const long f = F.f, pl = F.pl;
+  const double cf = A.scale * A.khdt[DIR][f];
+  for (int z = 0; z < A.nb; z++) {
+    if (!T.trans[z]) continue;
+    double trans = 0.;
+    if (F.wet) {
+      const double *__restrict__ Flx = A.Flx[DIR] + A.flx_stride * z + f;
+      for (int ks = 0; ks < A.ns - 1; ks++) trans = EBT ? trans - Flx[pl * ks] : trans - cf * Flx[pl * ks];
+      trans = trans * T.Idt;
+    }
+    T.trans[z][f] = trans;
+  }
+}
+
 // :955-959 after the sums of :939-954 (the symmetric order): the four faces' tendencies of the layer, then the tracer
-__global__ __launch_bounds__(256) void nd_update_sym_kernel(NDFaces A) {
+// D: nothing, or one NDMixOut -- the form that also stores the tendency (:871-875, :916-920) and its concentration form (:1010-1014)
+template <typename... D>
+__global__ __launch_bounds__(256) void nd_update_sym_kernel(NDFaces A, D... d) {
+  constexpr bool DIAG = sizeof...(D) > 0;
   const m6::GridDev &g = A.g;
   const int i = g.isc + blockIdx.x * 256 + threadIdx.x, j = g.jsc + blockIdx.y, k = blockIdx.z % g.nk, z = blockIdx.z / g.nk;
   if (i > g.iec) return;
   const long n2 = g.h2(i, j), hpl = (long)g.nih * g.njh;
-  if (!(g.mask2dT[n2] > 0.)) return;
+  if (!(g.mask2dT[n2] > 0.)) {
+    if constexpr (DIAG) {      // tendency(:,:,:) = 0. (:696)
+      const NDMixOut &M = nd_first(d...);
+      if (M.cont[z]) M.cont[z][n2 + hpl * k] = 0.;
+      if (M.conc[z]) M.conc[z][n2 + hpl * k] = 0.;
+    }
+    return;
+  }
   const long upl = (long)(g.nih + 1) * g.njh, vpl = (long)g.nih * (g.njh + 1);
   const double tN = A.tend[1][0][A.flx_stride * z + g.v2(i, j) + vpl * k], tS = A.tend[1][1][A.flx_stride * z + g.v2(i, j - 1) + vpl * k];
   const double tE = A.tend[0][0][A.flx_stride * z + g.u2(i, j) + upl * k], tW = A.tend[0][1][A.flx_stride * z + g.u2(i - 1, j) + upl * k];
@@ -523,20 +579,37 @@ __global__ __launch_bounds__(256) void nd_update_sym_kernel(NDFaces A) {
   double x = t[n2 + hpl * k] + tendency * (g.IareaT[n2] / (A.h[n2 + hpl * k] + g.H_subroundoff));
   if (fabs(x) < A.cu[z]) x = 0.0;
   t[n2 + hpl * k] = x;
+  if constexpr (DIAG) {
+    const NDMixOut &M = nd_first(d...);
+    const double td = (tendency * g.IareaT[n2]) * M.Idt;
+    if (M.cont[z]) M.cont[z][n2 + hpl * k] = td;
+    if (M.conc[z]) M.conc[z][n2 + hpl * k] = td / (A.h[n2 + hpl * k] + g.H_subroundoff);
+  }
 }
 
 // :921-938, :955-959 (the order of 2024 and before): the cell's tendency from the fluxes of its four faces, surface by surface round the
 // faces E, W, N, S, accumulated per layer in LDS (the layer index is data: KoL / KoR), then the tracer.  (A thread per layer that walks
 // the runs of its four faces -- no LDS, full occupancy -- reads the fluxes as gathers and is slower: profiles/r04_experiments.txt.)
 // EBT: the fluxes carry the diffusivity (:834-848); otherwise they are multiplied by Coef_x(I,j,1), Coef_y(i,J,1) (:880-893)
-template <bool EBT>
-__global__ __launch_bounds__(64) void nd_update_kernel(NDFaces A) {
+// D: as nd_update_sym_kernel takes it
+template <bool EBT, typename... D>
+__global__ __launch_bounds__(64) void nd_update_kernel(NDFaces A, D... d) {
+  constexpr bool DIAG = sizeof...(D) > 0;
   extern __shared__ double acc[];      // [nk][64]
   const m6::GridDev &g = A.g;
   const int lane = threadIdx.x, i = g.isc + blockIdx.x * 64 + lane, j = g.jsc + blockIdx.y, nk = g.nk, z = blockIdx.z;
   if (i > g.iec) return;
   const long n2 = g.h2(i, j), hpl = (long)g.nih * g.njh;
-  if (!(g.mask2dT[n2] > 0.)) return;
+  if (!(g.mask2dT[n2] > 0.)) {
+    if constexpr (DIAG) {      // tendency(:,:,:) = 0. (:696)
+      const NDMixOut &M = nd_first(d...);
+      for (int k = 0; k < nk; k++) {
+        if (M.cont[z]) M.cont[z][n2 + hpl * k] = 0.;
+        if (M.conc[z]) M.conc[z][n2 + hpl * k] = 0.;
+      }
+    }
+    return;
+  }
   double *__restrict__ t = A.t[z];
   const long upl = (long)(g.nih + 1) * g.njh, vpl = (long)g.nih * (g.njh + 1);
   const long uE = g.u2(i, j), uW = g.u2(i - 1, j), vN = g.v2(i, j), vS = g.v2(i, j - 1);
@@ -583,6 +656,12 @@ __global__ __launch_bounds__(64) void nd_update_kernel(NDFaces A) {
     double x = t[n2 + hpl * k] + ACC(k) * (IareaT / (A.h[n2 + hpl * k] + g.H_subroundoff));
     if (fabs(x) < A.cu[z]) x = 0.0;
     t[n2 + hpl * k] = x;
+    if constexpr (DIAG) {
+      const NDMixOut &M = nd_first(d...);
+      const double td = (ACC(k) * IareaT) * M.Idt;
+      if (M.cont[z]) M.cont[z][n2 + hpl * k] = td;
+      if (M.conc[z]) M.conc[z][n2 + hpl * k] = td / (A.h[n2 + hpl * k] + g.H_subroundoff);
+    }
   }
 #undef ACC
 }
@@ -630,6 +709,18 @@ int neutral_drive(const HordiffCall &c, const mom6hip_neutral_diffusion_cs_t *nd
   }
   S.flx_stride = (long)per_tracer;
   M6_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+  // the diagnostics neutral_diffusion posts (:935-1014): where only dfxy_cont_2d is asked for, the tendency of a batch goes to scratch
+  const MixDiag *mix = c.mix;
+  bool any_mix = false, cont_to_scratch = false;
+  if (mix) for (int m = 0; m < ntr; m++) {
+    for (int q = MIX_DFX_2D; q <= MIX_DFXY_CONC; q++) any_mix = any_mix || mix[m].a[q];
+    cont_to_scratch = cont_to_scratch || (mix[m].a[MIX_DFXY_CONT_2D] && !mix[m].a[MIX_DFXY_CONT]);
+  }
+  double *cont_scr = nullptr;
+  if (cont_to_scratch) {
+    cont_scr = (double *)c.st.scratch(sizeof(double) * hpl * nk * (size_t)nbmax);
+    M6_REQUIRE(!c.st.failed() && cont_scr, "neutral_diffusion: out of device memory for the diagnostics");
+  }
 
   const int ni = g.iec - g.isc + 1, nj = g.jec - g.jsc + 1;
   std::vector<double *> pf(d_tr);
@@ -655,11 +746,39 @@ int neutral_drive(const HordiffCall &c, const mom6hip_neutral_diffusion_cs_t *nd
     for (int m0 = 0; m0 < ntr; m0 += nbmax) {      // neutral_diffusion :605: the tracers are independent of each other, a batch at a time
       S.nb = (ntr - m0 < nbmax) ? ntr - m0 : nbmax;
       for (int z = 0; z < ND_BATCH; z++) { S.t[z] = z < S.nb ? d_tr[m0 + z] : nullptr; S.cu[z] = z < S.nb ? c.cu[m0 + z] : 0.; }
+      // what the batch asked for: the launches without diagnostics are taken where it asked for nothing
+      NDTransOut tx = {}, ty = {};
+      NDMixOut mo = {};
+      CellSumMarch sum2d; sum2d.g = g; sum2d.n = 0;
+      bool has_tx = false, has_ty = false, has_mo = false;
+      tx.Idt = ty.Idt = mo.Idt = c.Idt;
+      if (any_mix) for (int z = 0; z < S.nb; z++) {
+        double *const *a = mix[m0 + z].a;
+        tx.trans[z] = a[MIX_DFX_2D]; ty.trans[z] = a[MIX_DFY_2D]; mo.conc[z] = a[MIX_DFXY_CONC];
+        mo.cont[z] = a[MIX_DFXY_CONT] ? a[MIX_DFXY_CONT] : a[MIX_DFXY_CONT_2D] ? cont_scr + hpl * nk * z : nullptr;
+        if (a[MIX_DFXY_CONT_2D]) { sum2d.a3[sum2d.n] = mo.cont[z]; sum2d.a2[sum2d.n] = a[MIX_DFXY_CONT_2D]; sum2d.n++; }
+        has_tx = has_tx || tx.trans[z]; has_ty = has_ty || ty.trans[z]; has_mo = has_mo || mo.cont[z] || mo.conc[z];
+      }
       b.tracer_cols();
-      b.fluxes(symmetric);
-      if (symmetric) hipLaunchKernelGGL(nd_update_sym_kernel, dim3((ni + 255) / 256, nj, nk * S.nb), dim3(256), 0, s, S);
-      else if (b.flux_has_coef) hipLaunchKernelGGL(nd_update_kernel<true>, dim3((ni + 63) / 64, nj, S.nb), dim3(64), sizeof(double) * 64 * nk, s, S);
-      else hipLaunchKernelGGL(nd_update_kernel<false>, dim3((ni + 63) / 64, nj, S.nb), dim3(64), sizeof(double) * 64 * nk, s, S);
+      b.fluxes(symmetric, symmetric && has_tx ? &tx : nullptr, symmetric && has_ty ? &ty : nullptr);
+      if (!symmetric && (has_tx || has_ty)) {      // the fluxes stand in scratch until the next batch
+        const int nbu = (ni + 1 + 63) / 64, nbv = (ni + 63) / 64;
+        if (has_tx && b.flux_has_coef) hipLaunchKernelGGL((nd_trans_march_kernel<0, true>), dim3(nbu * nj), dim3(64), 0, s, S, nbu, tx);
+        else if (has_tx) hipLaunchKernelGGL((nd_trans_march_kernel<0, false>), dim3(nbu * nj), dim3(64), 0, s, S, nbu, tx);
+        if (has_ty && b.flux_has_coef) hipLaunchKernelGGL((nd_trans_march_kernel<1, true>), dim3(nbv * (nj + 1)), dim3(64), 0, s, S, nbv, ty);
+        else if (has_ty) hipLaunchKernelGGL((nd_trans_march_kernel<1, false>), dim3(nbv * (nj + 1)), dim3(64), 0, s, S, nbv, ty);
+      }
+      const dim3 gsym((ni + 255) / 256, nj, nk * S.nb), gupd((ni + 63) / 64, nj, S.nb);
+      const size_t lds = sizeof(double) * 64 * nk;
+      if (has_mo) {
+        if (symmetric) hipLaunchKernelGGL((nd_update_sym_kernel<NDMixOut>), gsym, dim3(256), 0, s, S, mo);
+        else if (b.flux_has_coef) hipLaunchKernelGGL((nd_update_kernel<true, NDMixOut>), gupd, dim3(64), lds, s, S, mo);
+        else hipLaunchKernelGGL((nd_update_kernel<false, NDMixOut>), gupd, dim3(64), lds, s, S, mo);
+        if (sum2d.n) cell_sum_march(sum2d, s);
+      }
+      else if (symmetric) hipLaunchKernelGGL(nd_update_sym_kernel<>, gsym, dim3(256), 0, s, S);
+      else if (b.flux_has_coef) hipLaunchKernelGGL(nd_update_kernel<true>, gupd, dim3(64), lds, s, S);
+      else hipLaunchKernelGGL(nd_update_kernel<false>, gupd, dim3(64), lds, s, S);
     }
   }
   M6_HIP(hipGetLastError());
@@ -679,11 +798,13 @@ int neutral_branch(const HordiffCall &c, const mom6hip_neutral_diffusion_cs_t *n
   M6_REQUIRE(nd != nullptr && eos != nullptr, "tracer_hordiff: USE_NEUTRAL_DIFFUSION needs the neutral_diffusion control structure and tv%%eqn_of_state");
   M6_REQUIRE(nd->initialized, "neutral_diffusion: the control structure is not initialised");
   if (nd->unsupported[0] && ndd) {      // NDIFF_CONTINUOUS = False with its parameters: neutral_diffusion_disc.hip
-    for (int q = 4; q < 8; q++) M6_REQUIRE(!nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
+    for (int q = 4; q < 8; q++) M6_REQUIRE((q == 5 && c.mix) || !nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
     return neutral_disc_branch(c, nd, ndd);
   }
   // unsupported[2] (tapering) and [3] (KhTh_use_ebt_struct) are the switches of the two modes of the fluxes
-  for (int q = 0; q < 8; q++) M6_REQUIRE(q == 2 || q == 3 || !nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
+  // ([5], the diagnostics, is taken with the records of mom6hip_tracer_hordiff_mix_diag: neutral_drive)
+  for (int q = 0; q < 8; q++)
+    M6_REQUIRE(q == 2 || q == 3 || (q == 5 && c.mix) || !nd->unsupported[q], "neutral_diffusion: %s is not provided by libmom6hip", names[q]);
   const bool taper = nd->unsupported[2] != 0, ebt = c.ebt_struct != nullptr;
   M6_REQUIRE(!taper || nd->interior_only, "neutral_diffusion: NDIFF_TAPERING is read with NDIFF_INTERIOR_ONLY only (the reference never reads it "
              "otherwise): it is refused without");
@@ -734,17 +855,29 @@ int neutral_branch(const HordiffCall &c, const mom6hip_neutral_diffusion_cs_t *n
   };
   b.tracer_cols = [&]() { hipLaunchKernelGGL(nd_tracer_cols_kernel, gc, b64, 0, s, A, nbc); };
   // the two flux kernels of a batch in the coefficient mode of the call
-  auto launch_flux = [&](auto sym, auto mode) {
-    hipLaunchKernelGGL((nd_flux_kernel<0, decltype(sym)::value, decltype(mode)::value>), gu, b64, 0, s, A, nbu);
-    hipLaunchKernelGGL((nd_flux_kernel<1, decltype(sym)::value, decltype(mode)::value>), gv, b64, 0, s, A, nbv);
+  // (tx, ty: the form that also leaves dfx_2d / dfy_2d, in the symmetric order only)
+  auto launch_flux = [&](auto sym, auto mode, const NDTransOut *tx, const NDTransOut *ty) {
+    constexpr bool SYM = decltype(sym)::value;
+    constexpr int MODE = decltype(mode)::value;
+    if constexpr (SYM) {
+      if (tx) hipLaunchKernelGGL((nd_flux_kernel<0, true, MODE, NDTransOut>), gu, b64, 0, s, A, nbu, *tx);
+      else hipLaunchKernelGGL((nd_flux_kernel<0, true, MODE>), gu, b64, 0, s, A, nbu);
+      if (ty) hipLaunchKernelGGL((nd_flux_kernel<1, true, MODE, NDTransOut>), gv, b64, 0, s, A, nbv, *ty);
+      else hipLaunchKernelGGL((nd_flux_kernel<1, true, MODE>), gv, b64, 0, s, A, nbv);
+    } else {
+      hipLaunchKernelGGL((nd_flux_kernel<0, false, MODE>), gu, b64, 0, s, A, nbu);
+      hipLaunchKernelGGL((nd_flux_kernel<1, false, MODE>), gv, b64, 0, s, A, nbv);
+    }
   };
-  auto launch_fluxes = [&](auto sym) {
-    if (coef == ND_COEF_NONE) launch_flux(sym, std::integral_constant<int, ND_COEF_NONE>());
-    else if (coef == ND_COEF_TAPER) launch_flux(sym, std::integral_constant<int, ND_COEF_TAPER>());
-    else if (coef == ND_COEF_EBT) launch_flux(sym, std::integral_constant<int, ND_COEF_EBT>());
-    else launch_flux(sym, std::integral_constant<int, ND_COEF_BOTH>());
+  auto launch_fluxes = [&](auto sym, const NDTransOut *tx, const NDTransOut *ty) {
+    if (coef == ND_COEF_NONE) launch_flux(sym, std::integral_constant<int, ND_COEF_NONE>(), tx, ty);
+    else if (coef == ND_COEF_TAPER) launch_flux(sym, std::integral_constant<int, ND_COEF_TAPER>(), tx, ty);
+    else if (coef == ND_COEF_EBT) launch_flux(sym, std::integral_constant<int, ND_COEF_EBT>(), tx, ty);
+    else launch_flux(sym, std::integral_constant<int, ND_COEF_BOTH>(), tx, ty);
   };
-  b.fluxes = [&](bool symmetric) { if (symmetric) launch_fluxes(std::true_type()); else launch_fluxes(std::false_type()); };
+  b.fluxes = [&](bool symmetric, const NDTransOut *tx, const NDTransOut *ty) {
+    if (symmetric) launch_fluxes(std::true_type(), tx, ty); else launch_fluxes(std::false_type(), tx, ty);
+  };
   return neutral_drive(c, nd, A, b);
 }
 }  // namespace m6

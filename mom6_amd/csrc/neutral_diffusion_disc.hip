@@ -429,8 +429,12 @@ __device__ __forceinline__ TEval t_eval(const NDDArgs &A, int z, long c, int k, 
   return r;
 }
 
-template <int DIR, bool SYM>
-__global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx) {
+// D: nothing, or (the symmetric order) one NDTransOut -- the form that also leaves trans_x_2d / trans_y_2d (:935-989).  The tracers of the
+// batch are walked one after the other, each down the 4 nk surfaces, so the sum is one register
+template <int DIR, bool SYM, typename... D>
+__global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx, D... d) {
+  constexpr bool DIAG = sizeof...(D) > 0;
+  static_assert(!DIAG || SYM, "the order of 2024 and before keeps the fluxes: nd_trans_march_kernel sums them");
   const m6::GridDev &g = A.g;
   const NDFace F = nd_face<DIR>(g, nbx);
   if (!F.has) return;
@@ -439,6 +443,10 @@ __global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx) {
   if (!F.wet) {
     for (int z = 0; z < nb; z++)
       nd_dry_fluxes<SYM>(ns, nk, A.Flx[DIR] + A.flx_stride * z, A.tend[DIR][0] + A.flx_stride * z, A.tend[DIR][1] + A.flx_stride * z, f, pl);
+    if constexpr (DIAG) {
+      const NDTransOut &T = nd_first(d...);
+      for (int z = 0; z < nb; z++) if (T.trans[z]) T.trans[z][f] = 0.;
+    }
     return;
   }
   const double *__restrict__ PiL = A.PoL[DIR], *__restrict__ PiR = A.PoR[DIR], *__restrict__ hEff = A.hEff[DIR];
@@ -451,6 +459,7 @@ __global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx) {
     double pLt = PiL[f], pRt = PiR[f];
     int klt = KoL[f] - 1, krt = KoR[f] - 1;
     double accL = 0., accR = 0.;
+    [[maybe_unused]] double trans = 0.;
     if (SYM) { nd_tend_store(tdL, f, pl, -1, klt, 0.); nd_tend_store(tdR, f, pl, -1, krt, 0.); }
     for (int ks = 0; ks < ns - 1; ks++) {
       const double pLb = PiL[f + pl * (ks + 1)], pRb = PiR[f + pl * (ks + 1)];
@@ -471,6 +480,7 @@ __global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx) {
       }
       if (SYM) { accL = accL + cf * flx; accR = accR - cf * flx; }
       else Flx[f + pl * ks] = flx;
+      if constexpr (DIAG) trans = trans - cf * flx;
       if (SYM && klb > klt) { nd_tend_store(tdL, f, pl, klt, klb, accL); accL = 0.; }
       if (SYM && krb > krt) { nd_tend_store(tdR, f, pl, krt, krb, accR); accR = 0.; }
       pLt = pLb; pRt = pRb;
@@ -478,6 +488,10 @@ __global__ __launch_bounds__(64) void ndd_flux_kernel(NDDArgs A, int nbx) {
       if (krb > krt) krt = krb;
     }
     if (SYM) { nd_tend_store(tdL, f, pl, klt, nk, accL); nd_tend_store(tdR, f, pl, krt, nk, accR); }
+    if constexpr (DIAG) {
+      const NDTransOut &T = nd_first(d...);
+      if (T.trans[z]) T.trans[z][f] = trans * T.Idt;
+    }
   }
   if (bad) atomicOr(A.bad, bad);
 }
@@ -551,10 +565,12 @@ int neutral_disc_branch(const HordiffCall &c, const mom6hip_neutral_diffusion_cs
     return 0;
   };
   b.tracer_cols = [&]() { columns(true); };
-  b.fluxes = [&](bool symmetric) {
+  b.fluxes = [&](bool symmetric, const NDTransOut *tx, const NDTransOut *ty) {
     if (symmetric) {
-      hipLaunchKernelGGL((ndd_flux_kernel<0, true>), gu, b64, 0, s, A, nbu);
-      hipLaunchKernelGGL((ndd_flux_kernel<1, true>), gv, b64, 0, s, A, nbv);
+      if (tx) hipLaunchKernelGGL((ndd_flux_kernel<0, true, NDTransOut>), gu, b64, 0, s, A, nbu, *tx);
+      else hipLaunchKernelGGL((ndd_flux_kernel<0, true>), gu, b64, 0, s, A, nbu);
+      if (ty) hipLaunchKernelGGL((ndd_flux_kernel<1, true, NDTransOut>), gv, b64, 0, s, A, nbv, *ty);
+      else hipLaunchKernelGGL((ndd_flux_kernel<1, true>), gv, b64, 0, s, A, nbv);
     } else {
       hipLaunchKernelGGL((ndd_flux_kernel<0, false>), gu, b64, 0, s, A, nbu);
       hipLaunchKernelGGL((ndd_flux_kernel<1, false>), gv, b64, 0, s, A, nbv);

@@ -183,6 +183,7 @@ struct HordiffOpts {
   int32_t idx_T, idx_S;
   bool takes_epi, takes_hbd;
   const mom6hip_tracer_flux_diag_t *diag = nullptr;      // the diffusive flux diagnostics of the tracers (null: none)
+  const mom6hip_tracer_mix_diag_t *mix = nullptr;        // what neutral_diffusion and hor_bnd_diffusion post themselves (null: none)
 };
 
 static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hordiff_fields_t *F, const double *h, double dt,
@@ -276,6 +277,36 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
       if (d_df[m][1] || d_df[m][3]) { d_sy[m] = (double *)q; q += bV3; }
     }
   }
+  // the diagnostics of neutral_diffusion and hor_bnd_diffusion: device views of the arrays asked for.  Host arrays are staged through one
+  // block (the pool of the context is short) once the iteration count has been accepted, copied in whole -- the call writes their compute
+  // range only -- and copied back at the end
+  static const char *mix_names[m6::MIX_COUNT] = {"dfx_2d", "dfy_2d", "dfxy_cont", "dfxy_cont_2d", "dfxy_conc", "hbd_dfx", "hbd_dfy", "hbd_dfx_2d",
+                                                 "hbd_dfy_2d", "hbdxy_cont", "hbdxy_cont_2d", "hbdxy_conc"};
+  const size_t mix_bytes[m6::MIX_COUNT] = {bU2, bV2, bH, bH / g.nk, bH, bU3, bV3, bU2, bV2, bH, bH / g.nk, bH};
+  std::vector<m6::MixDiag> d_mix;
+  struct MixBack { double *host, *dev; size_t bytes; };
+  std::vector<MixBack> mix_back;
+  bool any_mix = false;
+  size_t mix_total = 0;
+  if (o.mix) {
+    d_mix.assign(ntr, m6::MixDiag{});
+    size_t &total = mix_total;
+    for (int m = 0; m < ntr; m++) {
+      double *const p[m6::MIX_COUNT] = {o.mix[m].dfx_2d, o.mix[m].dfy_2d, o.mix[m].dfxy_cont, o.mix[m].dfxy_cont_2d, o.mix[m].dfxy_conc,
+                                        o.mix[m].hbd_dfx, o.mix[m].hbd_dfy, o.mix[m].hbd_dfx_2d, o.mix[m].hbd_dfy_2d, o.mix[m].hbdxy_cont,
+                                        o.mix[m].hbdxy_cont_2d, o.mix[m].hbdxy_conc};
+      for (int q = 0; q < m6::MIX_COUNT; q++) {
+        if (!p[q]) continue;
+        any_mix = true;
+        M6_REQUIRE(q >= m6::MIX_HBD_DFX || use_neutral, "tracer_hordiff: %s of tracer %d is a diagnostic of neutral_diffusion: it is refused "
+                   "without USE_NEUTRAL_DIFFUSION", mix_names[q], m + 1);
+        M6_REQUIRE(q < m6::MIX_HBD_DFX || use_hbd, "tracer_hordiff: %s of tracer %d is a diagnostic of hor_bnd_diffusion: it is refused "
+                   "without USE_HORIZONTAL_BOUNDARY_DIFFUSION", mix_names[q], m + 1);
+        d_mix[m].a[q] = p[q];
+        if (memspace == MOM6HIP_MEM_HOST) { mix_back.push_back({p[q], nullptr, mix_bytes[q]}); total += mix_bytes[q]; }
+      }
+    }
+  }
   A.khdt_x = (double *)st.scratch(bU2); A.khdt_y = (double *)st.scratch(bV2);
   char *tab = (char *)st.scratch(4 * 24 * sizeof(double *) + 24 * sizeof(double) + 16);
   M6_REQUIRE(!st.failed() && tab, "tracer_hordiff: staging failed");
@@ -317,6 +348,20 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   }
   A.scale = 1.0 / ((double)num_itts);      // I_numitts
   M6_HIP(hipGetLastError());
+  // neutral_diffusion and hor_bnd_diffusion post once an iteration of the itt loop, and the posts are separate
+  M6_REQUIRE(!(any_mix && num_itts > 1), "tracer_hordiff: the diagnostics of neutral_diffusion and hor_bnd_diffusion (dfx_2d .. dfxy_conc, "
+             "hbd_*) are posted once an iteration by the reference: with num_itts = %d iterations (MAX_TR_DIFFUSION_CFL, CHECK_DIFFUSIVE_CFL) "
+             "they are not provided by libmom6hip", num_itts);
+  if (mix_total) {      // (staged only after the refusal above: a call that is refused copies nothing)
+    char *q = (char *)st.scratch(mix_total);
+    M6_REQUIRE(!st.failed() && q, "tracer_hordiff: out of device memory for the diagnostics");
+    size_t at = 0;
+    for (int m = 0; m < ntr; m++) for (int w = 0; w < m6::MIX_COUNT; w++) if (d_mix[m].a[w]) {
+      MixBack &e = mix_back[at++];
+      e.dev = (double *)q; q += e.bytes; d_mix[m].a[w] = e.dev;
+      M6_HIP(hipMemcpyAsync(e.dev, e.host, e.bytes, hipMemcpyHostToDevice, s));
+    }
+  }
 
   std::vector<double *> pf(d_tr);
   std::vector<int32_t> ppos(ntr, MOM6HIP_POS_H), pnk(ntr, g.nk);
@@ -327,7 +372,8 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
   const double *d_hml = reads_h_ML ? st.in(F->h_ML, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
   const double *d_ps = (use_neutral && o.p_surf) ? st.in(o.p_surf, sizeof(double) * (size_t)g.nih * g.njh) : nullptr;
   M6_REQUIRE(!st.failed(), "tracer_hordiff: staging failed");
-  const m6::HordiffCall call = {ctx, st, A.h, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, o.idx_T, o.idx_S, o.eos, d_ps, d_hml, d_ebt, &halo_updates};
+  const m6::HordiffCall call = {ctx, st, A.h, A.khdt_x, A.khdt_y, num_itts, A.scale, d_tr, cu, o.idx_T, o.idx_S, o.eos, d_ps, d_hml, d_ebt, &halo_updates,
+                                  any_mix ? d_mix.data() : nullptr, 1.0 / (A.scale * dt)};
   // the march over k of the diagnostics asked for, in direction dir: zero = 1 sets them to zero over their ranges (:389-406), zero = 0 adds
   // what hd_step_kernel has just left in the scratch, but for the layers the along-layer loop leaves out (:544-550)
   auto df_march = [&](int dir, int zero) {
@@ -364,6 +410,7 @@ static int hordiff_impl(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *
     if (int rc = m6::epipycnal_branch(call, epi)) return rc;
   }
   if (stats) { stats->num_itts = num_itts; stats->halo_updates = halo_updates; stats->max_CFL = max_CFL; }
+  for (const MixBack &e : mix_back) M6_HIP(hipMemcpyAsync(e.host, e.dev, e.bytes, hipMemcpyDeviceToHost, s));      // (finish synchronises)
   return st.finish();
 }
 
@@ -439,6 +486,19 @@ extern "C" int mom6hip_tracer_hordiff_neutral_discontinuous(mom6hip_ctx_t *ctx, 
   return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
 }
 
+// the same with the diagnostics neutral_diffusion and hor_bnd_diffusion post themselves; diag == NULL: the call above
+extern "C" int mom6hip_tracer_hordiff_mix_diag(mom6hip_ctx_t *ctx, const mom6hip_tracer_hor_diff_cs_t *cs, const mom6hip_hor_bnd_diffusion_cs_t *hbd,
+                                               const mom6hip_neutral_diffusion_cs_t *nd, const mom6hip_ndiff_discontinuous_cs_t *ndd,
+                                               const mom6hip_hordiff_fields_t *F, const double *h, const mom6hip_eos_t *eos, const double *p_surf,
+                                               double dt, double *const *tr, const double *conc_underflow, int32_t ntr, int32_t idx_T,
+                                               int32_t idx_S, int32_t memspace, mom6hip_hordiff_stats_t *stats,
+                                               const mom6hip_tracer_mix_diag_t *diag) {
+  HordiffOpts o = {nd, nullptr, hbd, ndd, eos, p_surf, idx_T, idx_S, false, true};
+  o.mix = diag;
+  return hordiff_impl(ctx, cs, F, h, dt, tr, conc_underflow, ntr, memspace, stats, o);
+}
+
+extern "C" uint64_t mom6hip_abi_sizeof_tracer_mix_diag(void) { return sizeof(mom6hip_tracer_mix_diag_t); }
 extern "C" uint64_t mom6hip_abi_sizeof_tracer_hor_diff_cs(void) { return sizeof(mom6hip_tracer_hor_diff_cs_t); }
 extern "C" uint64_t mom6hip_abi_sizeof_epipycnal_cs(void) { return sizeof(mom6hip_epipycnal_cs_t); }
 extern "C" uint64_t mom6hip_abi_sizeof_hordiff_stats(void) { return sizeof(mom6hip_hordiff_stats_t); }

@@ -17,6 +17,13 @@
 !! (mom6hip_tracer_hordiff_diag, mom6hip_tracer_hordiff_epipycnal_diag; left zeroed with USE_NEUTRAL_DIFFUSION).
 !! NDIFF_USE_UNMASKED_TRANSPORT_BUG, offline khdt arrays, the hbd_* diagnostics, df2d_x / df2d_y with DIFFUSE_ML_TO_INTERIOR and the
 !! arrays with USE_HORIZONTAL_BOUNDARY_DIFFUSION stop with a FATAL error.
+!! What neutral_diffusion and hor_bnd_diffusion post themselves is posted here: with USE_NEUTRAL_DIFFUSION a tracer's id_dfx_2d, id_dfy_2d,
+!! id_dfxy_cont, id_dfxy_cont_2d and id_dfxy_conc, and, where USE_NEUTRAL_DIFFUSION follows USE_HORIZONTAL_BOUNDARY_DIFFUSION, its
+!! id_hbd_dfx, id_hbd_dfy, id_hbd_dfx_2d, id_hbd_dfy_2d, id_hbdxy_cont, id_hbdxy_cont_2d and id_hbdxy_conc get a zero-filled work array
+!! each (the reference's posted arrays are zero outside the compute range), mom6hip_tracer_hordiff_mix_diag fills their compute ranges,
+!! and post_data is called in the reference's order (the boundary diffusion's posts tracer after tracer, then neutral diffusion's).
+!! Still refused: an hbd_* id with the boundary diffusion followed by the along-layer loop (FATAL here), and any of these ids with
+!! more than one iteration (MAX_TR_DIFFUSION_CFL, CHECK_DIFFUSIVE_CFL): the library's refusal is passed on as FATAL.
 !!
 !! Compiled INSIDE a MOM6 source tree in place of src/tracer/MOM_tracer_hor_diff.F90; here against tests/fortran/stubs.
 module MOM_tracer_hor_diff
@@ -29,7 +36,7 @@ use MOM_cpu_clock,             only : cpu_clock_id, cpu_clock_begin, cpu_clock_e
 use MOM_CVMix_KPP,             only : KPP_CS
 use MOM_diabatic_driver,       only : diabatic_CS, extract_diabatic_member
 use MOM_energetic_PBL,         only : energetic_PBL_CS
-use MOM_diag_mediator,         only : diag_ctrl, time_type
+use MOM_diag_mediator,         only : diag_ctrl, time_type, post_data
 use MOM_EOS,                   only : EOS_type
 use MOM_error_handler,         only : MOM_error, FATAL, WARNING
 use MOM_file_parser,           only : get_param, log_version, param_file_type
@@ -103,6 +110,15 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   type(mom6hip_tracer_flux_diag_t), allocatable, target :: dg(:)      ! the device (resident) or host (staged) arrays of the call
   type(c_ptr), allocatable :: dgh(:,:)                                ! the host arrays behind them
   type(c_ptr) :: p_dg
+  ! what neutral_diffusion and hor_bnd_diffusion post themselves (mom6hip_tracer_mix_diag_t): the work arrays of the call are slices of
+  ! one zero-filled host block (and, resident, of one zeroed device block that is copied back before the posts)
+  type(mom6hip_tracer_mix_diag_t), allocatable, target :: mx(:)
+  real(c_double), allocatable, target :: pool(:)
+  integer(c_int64_t), allocatable :: mix_off(:,:)      ! (12, ntr): the offset of an array in the block, -1: not asked for
+  integer(c_int64_t) :: mix_n(12), mix_tot, nu2, nv2, nh2
+  integer :: mix_id(12)
+  logical :: any_mix
+  type(c_ptr) :: d_pool, p_ndd
 
   if (.not. associated(CS)) call MOM_error(FATAL, "MOM_tracer_hor_diff: "// &
        "register_tracer must be called before tracer_hordiff.")
@@ -117,7 +133,7 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
 
   allocate(tr(Reg%ntr), cu(Reg%ntr))
   do m=1,Reg%ntr
-    if (CS%use_hor_bnd_diffusion .and. (Reg%Tr(m)%id_hbdxy_cont > 0 .or. Reg%Tr(m)%id_hbdxy_cont_2d > 0 .or. &
+    if (CS%use_hor_bnd_diffusion .and. .not.CS%use_neutral_diffusion .and. (Reg%Tr(m)%id_hbdxy_cont > 0 .or. Reg%Tr(m)%id_hbdxy_cont_2d > 0 .or. &
         Reg%Tr(m)%id_hbdxy_conc > 0 .or. Reg%Tr(m)%id_hbd_dfx > 0 .or. Reg%Tr(m)%id_hbd_dfy > 0 .or. Reg%Tr(m)%id_hbd_dfx_2d > 0 .or. &
         Reg%Tr(m)%id_hbd_dfy_2d > 0)) call MOM_error(FATAL, "tracer_hordiff (HIP): the hbd_* diagnostics of tracer "// &
         trim(Reg%Tr(m)%name)//" are not provided by the GPU path.")
@@ -151,6 +167,24 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   if (any_diag .and. CS%use_hor_bnd_diffusion) call MOM_error(FATAL, "tracer_hordiff (HIP): the diffusive flux diagnostics (df_x, df_y, "// &
       "df2d_x, df2d_y) together with USE_HORIZONTAL_BOUNDARY_DIFFUSION and the along-layer diffusion are not provided by the GPU path.")
   p_dg = c_null_ptr ; if (any_diag) p_dg = c_loc(dg)
+  ! the ids of the posts of neutral_diffusion (MOM_neutral_diffusion.F90:935-1014) and, where it follows the boundary diffusion, of
+  ! hor_bnd_diffusion (MOM_hor_bnd_diffusion.F90:292-333), in the order of the record
+  nu2 = int(size(h,1)+1, c_int64_t) * size(h,2) ; nv2 = int(size(h,1), c_int64_t) * (size(h,2)+1) ; nh2 = int(size(h,1), c_int64_t) * size(h,2)
+  mix_n(:) = (/ nu2, nv2, nh2*GV%ke, nh2, nh2*GV%ke, nu2*GV%ke, nv2*GV%ke, nu2, nv2, nh2*GV%ke, nh2, nh2*GV%ke /)
+  allocate(mix_off(12,Reg%ntr), mx(Reg%ntr)) ; mix_off(:,:) = -1 ; mix_tot = 0 ; any_mix = .false.
+  if (CS%use_neutral_diffusion) then ; do m=1,Reg%ntr
+    call mix_ids(m)
+    do q=1,12 ; if (mix_id(q) > 0 .and. (q <= 5 .or. CS%use_hor_bnd_diffusion)) then
+      mix_off(q,m) = mix_tot ; mix_tot = mix_tot + mix_n(q) ; any_mix = .true.
+    endif ; enddo
+  enddo ; endif
+  if (any_mix) then
+    allocate(pool(mix_tot)) ; pool(:) = 0.0
+    if (.not.mom6hip_resident()) then
+      do m=1,Reg%ntr ; do q=1,12 ; if (mix_off(q,m) >= 0) call mix_set(mx(m), q, c_loc(pool(mix_off(q,m)+1))) ; enddo ; enddo
+    endif
+    p_ndd = c_null_ptr ; if (CS%nd%unsupported(1) /= 0) p_ndd = c_loc(CS%ndd)
+  endif
   ccs%KhTr = CS%KhTr ; ccs%max_diff_CFL = CS%max_diff_CFL
   ccs%KhTr_Slope_Cff = CS%KhTr_Slope_Cff ; ccs%KhTr_min = CS%KhTr_min ; ccs%KhTr_max = CS%KhTr_max
   ccs%KhTr_passivity_coeff = CS%KhTr_passivity_coeff ; ccs%KhTr_passivity_min = CS%KhTr_passivity_min
@@ -223,7 +257,18 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
         if (c_associated(dgh(4,m))) dg(m)%df2d_y = mom6hip_mirror(ctx, dgh(4,m), int(size(Reg%Tr(m)%df2d_y), c_int64_t), .true., .true.)
       enddo
     endif
-    if (CS%Diffuse_ML_interior) then
+    if (any_mix) then
+      rc = mom6hip_malloc(d_pool, 8_c_int64_t*mix_tot) ; call mom6hip_fatal_if(rc, "tracer_hordiff")
+      rc = mom6hip_memset_zero(ctx, d_pool, 8_c_int64_t*mix_tot) ; call mom6hip_fatal_if(rc, "tracer_hordiff")
+      do m=1,Reg%ntr ; do q=1,12 ; if (mix_off(q,m) >= 0) &
+        call mix_set(mx(m), q, transfer(transfer(d_pool, 0_c_intptr_t) + 8_c_intptr_t*mix_off(q,m), d_pool)) ; enddo ; enddo
+      rc = mom6hip_tracer_hordiff_mix_diag(ctx, ccs, merge(c_loc(CS%hbd), c_null_ptr, CS%use_hor_bnd_diffusion), c_loc(CS%nd), p_ndd, fld, &
+                                      mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), c_loc(CS%eos), p_surf, dt, tr, &
+                                      c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, &
+                                      stats, c_loc(mx))
+      if (rc == 0) rc = mom6hip_sync_to_host(ctx, c_loc(pool), d_pool, 8_c_int64_t*mix_tot)
+      q = mom6hip_free(d_pool)
+    elseif (CS%Diffuse_ML_interior) then
       rc = mom6hip_tracer_hordiff_epipycnal_diag(ctx, ccs, CS%epi, fld, mom6hip_mirror(ctx, c_loc(h), int(size(h), c_int64_t), .true., .false.), &
                                             CS%eos, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
                                             int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats, p_dg)
@@ -244,6 +289,10 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
                                         CS%eos, p_surf, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), &
                                         int(idx_S, c_int32_t), MOM6HIP_MEM_DEVICE, stats)
     endif
+  elseif (any_mix) then
+    rc = mom6hip_tracer_hordiff_mix_diag(mom6hip_shared_context(G, GV), ccs, merge(c_loc(CS%hbd), c_null_ptr, CS%use_hor_bnd_diffusion), &
+                                    c_loc(CS%nd), p_ndd, fld, c_loc(h), c_loc(CS%eos), p_surf, dt, tr, c_loc(cu), int(Reg%ntr, c_int32_t), &
+                                    int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats, c_loc(mx))
   elseif (CS%Diffuse_ML_interior) then
     rc = mom6hip_tracer_hordiff_epipycnal_diag(mom6hip_shared_context(G, GV), ccs, CS%epi, fld, c_loc(h), CS%eos, dt, tr, c_loc(cu), &
                                           int(Reg%ntr, c_int32_t), int(idx_T, c_int32_t), int(idx_S, c_int32_t), MOM6HIP_MEM_HOST, stats, p_dg)
@@ -267,8 +316,49 @@ subroutine tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_
   if (any_diag .and. mom6hip_resident()) then
     do m=1,Reg%ntr ; do q=1,4 ; if (c_associated(dgh(q,m))) call mom6hip_mirror_to_host(ctx, dgh(q,m)) ; enddo ; enddo
   endif
+  ! the posts, in the reference's order: hor_bnd_diffusion's tracer after tracer (it runs first), then neutral_diffusion's
+  if (any_mix) then
+    do m=1,Reg%ntr ; call mix_ids(m) ; do q=6,12 ; if (mix_off(q,m) >= 0) call mix_post(q, mix_id(q), mix_off(q,m)) ; enddo ; enddo
+    do m=1,Reg%ntr ; call mix_ids(m) ; do q=1,5 ; if (mix_off(q,m) >= 0) call mix_post(q, mix_id(q), mix_off(q,m)) ; enddo ; enddo
+  endif
   call cpu_clock_end(id_clock_diffuse)
 contains
+  !> the twelve diagnostic ids of tracer m, in the order of mom6hip_tracer_mix_diag_t
+  subroutine mix_ids(m)
+    integer, intent(in) :: m
+    mix_id(:) = (/ Reg%Tr(m)%id_dfx_2d, Reg%Tr(m)%id_dfy_2d, Reg%Tr(m)%id_dfxy_cont, Reg%Tr(m)%id_dfxy_cont_2d, Reg%Tr(m)%id_dfxy_conc, &
+                   Reg%Tr(m)%id_hbd_dfx, Reg%Tr(m)%id_hbd_dfy, Reg%Tr(m)%id_hbd_dfx_2d, Reg%Tr(m)%id_hbd_dfy_2d, Reg%Tr(m)%id_hbdxy_cont, &
+                   Reg%Tr(m)%id_hbdxy_cont_2d, Reg%Tr(m)%id_hbdxy_conc /)
+  end subroutine mix_ids
+  !> member q of a record
+  subroutine mix_set(r, q, p)
+    type(mom6hip_tracer_mix_diag_t), intent(inout) :: r
+    integer,     intent(in) :: q
+    type(c_ptr), intent(in) :: p
+    select case (q)
+      case (1) ; r%dfx_2d = p ; case (2) ; r%dfy_2d = p ; case (3) ; r%dfxy_cont = p ; case (4) ; r%dfxy_cont_2d = p
+      case (5) ; r%dfxy_conc = p ; case (6) ; r%hbd_dfx = p ; case (7) ; r%hbd_dfy = p ; case (8) ; r%hbd_dfx_2d = p
+      case (9) ; r%hbd_dfy_2d = p ; case (10) ; r%hbdxy_cont = p ; case (11) ; r%hbdxy_cont_2d = p ; case (12) ; r%hbdxy_conc = p
+    end select
+  end subroutine mix_set
+  !> post_data of the array q at offset off of the host block, with the bounds of the reference's local array
+  subroutine mix_post(q, id, off)
+    integer,            intent(in) :: q, id
+    integer(c_int64_t), intent(in) :: off
+    real, pointer :: a2(:,:), a3(:,:,:)
+    select case (q)
+      case (1, 8) ; a2(G%IsdB:G%IedB,G%jsd:G%jed) => pool(off+1:off+mix_n(q))
+      case (2, 9) ; a2(G%isd:G%ied,G%JsdB:G%JedB) => pool(off+1:off+mix_n(q))
+      case (4, 11) ; a2(G%isd:G%ied,G%jsd:G%jed) => pool(off+1:off+mix_n(q))
+      case (6) ; a3(G%IsdB:G%IedB,G%jsd:G%jed,1:GV%ke) => pool(off+1:off+mix_n(q))
+      case (7) ; a3(G%isd:G%ied,G%JsdB:G%JedB,1:GV%ke) => pool(off+1:off+mix_n(q))
+      case default ; a3(G%isd:G%ied,G%jsd:G%jed,1:GV%ke) => pool(off+1:off+mix_n(q))
+    end select
+    select case (q)
+      case (1, 2, 4, 8, 9, 11) ; call post_data(id, a2, CS%diag)
+      case default ; call post_data(id, a3, CS%diag)
+    end select
+  end subroutine mix_post
   !> a host pointer of the struct -> its device mirror (an input)
   subroutine to_dev(p, n)
     type(c_ptr), intent(inout) :: p

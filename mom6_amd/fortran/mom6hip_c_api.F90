@@ -57,6 +57,14 @@ type, bind(c) :: mom6hip_tracer_flux_diag_t
   type(c_ptr) :: df_x = c_null_ptr, df_y = c_null_ptr, df2d_x = c_null_ptr, df2d_y = c_null_ptr
 end type mom6hip_tracer_flux_diag_t
 
+!> mom6hip_tracer_mix_diag_t: what neutral_diffusion and hor_bnd_diffusion post themselves for one registered tracer (c_loc of a whole
+!! work array where the id is set, c_null_ptr where it is not), in the memory space of the call
+type, bind(c) :: mom6hip_tracer_mix_diag_t
+  type(c_ptr) :: dfx_2d = c_null_ptr, dfy_2d = c_null_ptr, dfxy_cont = c_null_ptr, dfxy_cont_2d = c_null_ptr, dfxy_conc = c_null_ptr
+  type(c_ptr) :: hbd_dfx = c_null_ptr, hbd_dfy = c_null_ptr, hbd_dfx_2d = c_null_ptr, hbd_dfy_2d = c_null_ptr
+  type(c_ptr) :: hbdxy_cont = c_null_ptr, hbdxy_cont_2d = c_null_ptr, hbdxy_conc = c_null_ptr
+end type mom6hip_tracer_mix_diag_t
+
 !> mom6hip_remapping_cs_t (remapping_CS, src/ALE/MOM_remapping.F90:25)
 type, bind(c) :: mom6hip_remapping_cs_t
   integer(c_int32_t) :: remapping_scheme, boundary_extrapolation, force_bounds_in_subcell, answer_date
@@ -682,6 +690,27 @@ interface
     type(mom6hip_hordiff_stats_t), intent(out) :: stats
     integer(c_int) :: rc
   end function mom6hip_tracer_hordiff_neutral_discontinuous
+
+  !> mom6hip_tracer_hordiff_neutral_discontinuous with the diagnostics neutral_diffusion and hor_bnd_diffusion post themselves: diag is
+  !! c_null_ptr or c_loc of an array of ntr mom6hip_tracer_mix_diag_t; hbd, nd, ndd and eos are c_loc of the records or c_null_ptr
+  function mom6hip_tracer_hordiff_mix_diag(ctx, cs, hbd, nd, ndd, fields, h, eos, p_surf, dt, tr, conc_underflow, ntr, idx_T, idx_S, &
+                                           memspace, stats, diag) bind(c, name="mom6hip_tracer_hordiff_mix_diag") result(rc)
+    import :: c_int, c_int32_t, c_double, c_ptr, mom6hip_tracer_hor_diff_cs_t, mom6hip_hordiff_stats_t, mom6hip_hordiff_fields_t
+    type(c_ptr), value :: ctx, hbd, nd, ndd, h, eos, p_surf, conc_underflow, diag
+    type(mom6hip_tracer_hor_diff_cs_t), intent(in) :: cs
+    type(mom6hip_hordiff_fields_t), intent(in) :: fields
+    real(c_double), value :: dt
+    type(c_ptr), intent(in) :: tr(*)
+    integer(c_int32_t), value :: ntr, idx_T, idx_S, memspace
+    type(mom6hip_hordiff_stats_t), intent(out) :: stats
+    integer(c_int) :: rc
+  end function mom6hip_tracer_hordiff_mix_diag
+
+  !> sizeof(mom6hip_tracer_mix_diag_t) as the library was compiled
+  function mom6hip_abi_sizeof_tracer_mix_diag() bind(c, name="mom6hip_abi_sizeof_tracer_mix_diag") result(n)
+    import :: c_int64_t
+    integer(c_int64_t) :: n
+  end function mom6hip_abi_sizeof_tracer_mix_diag
 
   !> sizeof(mom6hip_ndiff_discontinuous_cs_t) as the library was compiled
   function mom6hip_abi_sizeof_ndiff_discontinuous_cs() bind(c, name="mom6hip_abi_sizeof_ndiff_discontinuous_cs") result(n)

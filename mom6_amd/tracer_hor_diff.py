@@ -123,7 +123,7 @@ def tracer_hor_diff_init(Time=None, G=None, GV=None, US=None, param_file=None, d
 
 
 def tracer_hordiff(h, dt, MEKE, VarMix, visc, G: DeviceGrid, CS: tracer_hor_diff_CS, Reg, tv=None, do_online_flag=None, read_khdt_x=None,
-                   read_khdt_y=None, conc_underflow=None, GV=None, diag=None):
+                   read_khdt_y=None, conc_underflow=None, GV=None, diag=None, mix_diag=None):
     """tracer_hordiff(h, dt, MEKE, VarMix, visc, G, GV, US, CS, Reg, tv, do_online_flag, read_khdt_x, read_khdt_y) -- :119.
     Reg: the list of tracer arrays (Reg%Tr(m)%t), updated in place.  VarMix: None, or a dict (its presence is
     VarMix%use_variable_mixing) with any of L2u, L2v, SN_u, SN_v (read with KHTR_SLOPE_CFF > 0), Res_fn_h (its presence is
@@ -132,7 +132,12 @@ def tracer_hordiff(h, dt, MEKE, VarMix, visc, G: DeviceGrid, CS: tracer_hor_diff
     (VarMix%ebt_struct: h points, nk levels, a valid halo of 1) too.  diag: None, or one entry per tracer, each None or a dict with
     any of df_x, df_y (u / v points, nk layers) and df2d_x, df2d_y (u / v points, a plane) -- Reg%Tr(m)%df_x ... where associated, arrays
     in the memory space of the fields: the along-layer branch zeroes and fills them as the reference does (:389-406, :576-591); the other
-    branches refuse them.  Returns the iteration statistics."""
+    branches refuse them.  mix_diag: None, or one entry per tracer, each None or a dict with any of what neutral_diffusion posts (dfx_2d,
+    dfy_2d: u / v points, a plane; dfxy_cont, dfxy_conc: h points, nk layers; dfxy_cont_2d: h points, a plane -- with USE_NEUTRAL_DIFFUSION)
+    and of what hor_bnd_diffusion posts (hbd_dfx, hbd_dfy, hbd_dfx_2d, hbd_dfy_2d, hbdxy_cont, hbdxy_cont_2d, hbdxy_conc -- with
+    USE_HORIZONTAL_BOUNDARY_DIFFUSION): arrays in the memory space of the fields, of which the call writes the compute range and nothing
+    else (mom6hip_tracer_hordiff_mix_diag); with more than one iteration they are refused.  diag and mix_diag are independent of each
+    other.  Returns the iteration statistics."""
     if CS is None or Reg is None:
         raise Mom6HipError("MOM_tracer_hor_diff: register_tracer must be called before tracer_hordiff.")
     if do_online_flag is False or read_khdt_x is not None or read_khdt_y is not None:
@@ -150,6 +155,15 @@ def tracer_hordiff(h, dt, MEKE, VarMix, visc, G: DeviceGrid, CS: tracer_hor_diff
         # with USE_HORIZONTAL_BOUNDARY_DIFFUSION alone the reference runs the along-layer loop after the boundary diffusion (:536)
         raise Mom6HipError("tracer_hordiff (HIP): the diffusive flux diagnostics (df_x, df_y, df2d_x, df2d_y) together with "
                            "USE_HORIZONTAL_BOUNDARY_DIFFUSION and the along-layer diffusion are not provided by libmom6hip")
+    if mix_diag is not None and not any(a is not None for d in mix_diag for a in (d or {}).values()):
+        mix_diag = None
+    if mix_diag is not None:
+        if len(mix_diag) != len(list(Reg)):
+            raise Mom6HipError("tracer_hordiff: mix_diag must have one entry per tracer")
+        if not (CS.st.unsupported[0] or CS.st.unsupported[1]):
+            raise Mom6HipError("tracer_hordiff: mix_diag holds the diagnostics of neutral_diffusion and hor_bnd_diffusion: it is refused without "
+                               "USE_NEUTRAL_DIFFUSION or USE_HORIZONTAL_BOUNDARY_DIFFUSION")
+        return _tracer_hordiff_mix(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow, mix_diag)
     if CS.st.unsupported[0] and CS.neutral_diffusion_CSp.unsupported[0]:
         return _tracer_hordiff_neutral_discontinuous(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow)
     if CS.st.unsupported[1]:
@@ -370,6 +384,56 @@ def _tracer_hordiff_neutral_discontinuous(h, dt, MEKE, VarMix, visc, G, CS, Reg,
         if CS.discontinuous or "NDIFF_CONTINUOUS" not in str(e):
             raise
         raise Mom6HipError(f"{e} (NDIFF_REMAPPING_SCHEME -- {', '.join(_abi.NDIFF_REMAPPING_SCHEMES)} -- has to be named with it)") from None
+    CS.last = stats
+    return stats
+
+
+def _tracer_hordiff_mix(h, dt, MEKE, VarMix, visc, G, CS, Reg, tv, conc_underflow, mix_diag):
+    """any pairing of USE_HORIZONTAL_BOUNDARY_DIFFUSION and USE_NEUTRAL_DIFFUSION (either reconstruction) with the diagnostics the two
+    modules post themselves (mom6hip_tracer_hordiff_mix_diag); tv and visc as the branches take them"""
+    tr = list(Reg)
+    st, nd = CS.st, CS.neutral_diffusion_CSp
+    hbd, neutral = bool(st.unsupported[1]), bool(st.unsupported[0])
+    idx, eos, p_surf = [0, 0], None, None
+    if neutral:
+        get, idx = _tv_TS(tv, tr, "USE_NEUTRAL_DIFFUSION")
+        eos, p_surf = get("eqn_of_state"), get("p_surf")
+    L = lib()
+    L.mom6hip_tracer_hordiff_mix_diag.argtypes = [
+        C.c_void_p, C.POINTER(_abi.TracerHorDiffCS), C.POINTER(_abi.HorBndDiffusionCS), C.POINTER(_abi.NeutralDiffusionCS),
+        C.POINTER(_abi.NdiffDiscontinuousCS), C.POINTER(_abi.HorDiffFields), C.c_void_p, C.POINTER(_abi.EOS), C.c_void_p, C.c_double,
+        C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_abi.HorDiffStats), C.c_void_p]
+    hp, F, ptrs, spaces = _marshal(h, MEKE, VarMix, CS, tr)
+    if hbd or (neutral and nd.interior_only):
+        p, s = _ptr_space(_h_ML(visc)); spaces.add(s); F.h_ML = p
+    ps = None
+    if p_surf is not None:
+        ps, s = _ptr_space(p_surf); spaces.add(s)
+    g = G.grid
+    recs = (_abi.TracerMixDiag * len(tr))()
+    names = _abi.ND_MIX_DIAGS + _abi.HBD_MIX_DIAGS
+    for m, d in enumerate(mix_diag):
+        for n, a in (d or {}).items():
+            if n not in names:
+                raise Mom6HipError(f"tracer_hordiff: {n} is not a diagnostic of neutral_diffusion or hor_bnd_diffusion ({', '.join(names)} are)")
+            if a is None:
+                continue
+            pos, rank = _abi.MIX_DIAG_KINDS[n]
+            want = g.shape2(pos) if rank == 2 else g.shape3(pos)
+            if tuple(a.shape) != want:
+                raise Mom6HipError(f"tracer_hordiff: {n} of tracer {m + 1} has shape {tuple(a.shape)}, expected {want}")
+            p, s = _ptr_space(a); spaces.add(s); setattr(recs[m], n, p)
+    if len(spaces) != 1:
+        raise Mom6HipError("tracer_hordiff: h, visc%h_ML, p_surf, every tracer and every diagnostic must be in the same memory space")
+    if neutral and nd.H_to_RZ == 0.0:
+        nd.H_to_RZ = float(G.grid.Rho0 * G.grid.H_to_Z)      # GV%H_to_RZ, Boussinesq
+    cu = None if conc_underflow is None else np.ascontiguousarray(conc_underflow, dtype=np.float64)
+    stats = _abi.HorDiffStats()
+    check(L.mom6hip_tracer_hordiff_mix_diag(
+        G.handle, C.byref(st), C.byref(CS.hor_bnd_diffusion_CSp) if hbd else None, C.byref(nd) if neutral else None,
+        C.byref(CS.ndiff_discontinuous) if (neutral and CS.discontinuous) else None, C.byref(F), C.c_void_p(hp),
+        C.byref(eos) if neutral else None, None if ps is None else C.c_void_p(ps), float(dt), ptrs, None if cu is None else cu.ctypes.data,
+        len(tr), idx[0], idx[1], spaces.pop(), C.byref(stats), recs), "tracer_hordiff")
     CS.last = stats
     return stats
 
